@@ -25,6 +25,7 @@ Extra objects on the JSON line:
                FLOPs per launch / average launch duration; peak = 2500 TFLOP/s dense fp16 MFMA.
   cpu_baseline the reference's CPU-eager semantics (the oracle's graphs on PyTorch's CPU kernels,
                fp32) timed on this box's host cores on a bounded sample, rank 0 at N=1 only.
+  dump_outputs with --dump-outputs DIR: the files written there (the last timed step's RGB48 frame, rank 0).
 """
 import argparse
 import ctypes as C
@@ -89,7 +90,39 @@ def parse():
     ap.add_argument("--sim-fps", type=float, nargs="*", help="with --dispatcher-sim: offered rates to run (default: 100 per worker)")
     ap.add_argument("--sim-numa", action="store_true", help="with --dispatcher-sim: workers pin themselves as they would to their GPU's NUMA node")
     ap.add_argument("--layers", action="store_true", help="print the per-layer profile to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed region, write what its last step delivered (rank 0's RGB48 frame from the pinned host ring) "
+                         "as DIR/*.npy in float32 / float64 (dump_outputs below): two builds compared output for output on the same inputs")
     return ap.parse_args()
+
+
+# --dump-outputs: frames up to this many values are written whole as float32; larger ones as a fixed seeded sample
+DUMP_FULL_MAX_VALUES = 1 << 23          # 32 MB of float32: 1920x1080x3 fits, 3840x2160x3 is sampled
+DUMP_SAMPLE_VALUES = 1 << 21            # 8 MB of values + 16 MB of float64 indices
+DUMP_SAMPLE_SEED = 20240917
+
+
+def dump_outputs(out_dir, rgb48, frame_index):
+    """Write the RGB48 frame ([H][W][3] uint16) a timed step delivered as .npy files in out_dir, at most ~33 MB in all:
+    rgb48.npy (float32 [H,W,3]) when it holds at most DUMP_FULL_MAX_VALUES values, otherwise rgb48_sample.npy (float32) at the
+    flat indices rgb48_sample_index.npy (float64, sorted; the same for every run at this size); always rgb48_row_mean.npy
+    ([H,3]) and rgb48_col_mean.npy ([W,3]) in float64, which cover every pixel.  Returns what was written."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = rgb48.reshape(-1)
+    files = {}
+    if flat.size <= DUMP_FULL_MAX_VALUES:
+        files["rgb48"] = rgb48.astype(np.float32)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.size, size=DUMP_SAMPLE_VALUES, replace=False))
+        files["rgb48_sample"] = flat[idx].astype(np.float32)
+        files["rgb48_sample_index"] = idx.astype(np.float64)
+    files["rgb48_row_mean"] = rgb48.mean(axis=1, dtype=np.float64)
+    files["rgb48_col_mean"] = rgb48.mean(axis=0, dtype=np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in files), "frame_index": frame_index,
+            "bytes": int(sum(a.nbytes for a in files.values())),
+            "what": "the RGB48 frame ([H][W][3] uint16, as float) the last timed step delivered into the pinned host ring"}
 
 
 def physical_cores():
@@ -572,6 +605,7 @@ def main():
             s0 = pending.pop(0)
             lib.hdrtv_ring_wait(ctx, s0)
             lib.hdrtv_ring_release(ctx, s0)
+        return hp.value                                         # the slot's pinned host frame (valid once waited for)
 
     def ring_drain():
         while pending:
@@ -590,12 +624,18 @@ def main():
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        ring_step(i, ev=evs[i])
+        last_host = ring_step(i, ev=evs[i])
     ring_drain()
     torch.cuda.synchronize(dev)
     elapsed_own = time.perf_counter() - t0          # this rank's own K frames (per_rank_frames_per_s)
     barrier()
     elapsed = time.perf_counter() - t0
+    # the last timed frame, copied out of its (waited-for, released) ring slot before any later leg can reuse the slot
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last_frame = np.ctypeslib.as_array((C.c_uint16 * (H * Wd * 3)).from_address(last_host)).reshape(H, Wd, 3).copy()
+        dumped = dump_outputs(args.dump_outputs, last_frame, args.steps - 1)
+        del last_frame
     per_frame_ms = sorted(a.elapsed_time(b) for a, b in evs)
     p50 = per_frame_ms[len(per_frame_ms) // 2]
     p99 = per_frame_ms[min(len(per_frame_ms) - 1, int(len(per_frame_ms) * 0.99))]
@@ -860,6 +900,8 @@ def main():
             "roofline": roof,
             "roofline_next": roof_next,
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if world == 1 and use_hg and not args.int8 and not args.no_int8_extra:
             line["config4_int8"] = int8_extra(args, dev, dev_frames)
             # the reference's default preset is the mixed recipe (gui_config.py: DEFAULT_PRECISION_KEY = "INT8 Mixed (QAT)")
