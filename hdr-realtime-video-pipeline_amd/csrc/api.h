@@ -238,9 +238,9 @@ struct hdrtv_ctx {
     size_t hgf_wfrag = 0, hg_w10a = 0;        // fused HG tail: conv1 + conv10(second half) fragments, conv10 first half
     // workspace
     int H = 0, W = 0;
-    hdrtv_host::Arena ws;                 // ws.dev: the workspace of the lane being launched (lane 0 outside hdrtv_infer_lane)
+    hdrtv_host::Arena ws;                 // the layout of one lane's workspace (ws.dev unused: the buffers are lane_ws)
     int lanes = 1;                        // hdrtv_set_lanes: one activation workspace per frame in flight
-    std::vector<unsigned char *> lane_ws; // [lanes] after hdrtv_reserve; lane_ws[0] == ws.dev
+    std::vector<unsigned char *> lane_ws; // [lanes] after hdrtv_reserve, empty before; lane 0 holds the taps and the resize tables
     std::map<std::string, hdrtv_host::Tensor> t;
     int launches = 0;
     double macs = 0.0;
@@ -297,20 +297,58 @@ Shapes shapes_for(int H, int W);
 Tensor &ws_add(hdrtv_ctx *c, const std::string &name, int C, int H, int W, int layout);
 int do_reserve(hdrtv_ctx *c, int H, int W);
 void free_workspaces(hdrtv_ctx *c);            // every lane's; leaves no reserved size behind
+// a workspace tensor inside one lane's buffer (base: c->lane_ws[lane])
 template <typename T>
-T *wsp(hdrtv_ctx *c, const std::string &name)
+T *wsp(hdrtv_ctx *c, unsigned char *base, const std::string &name)
 {
     auto it = c->t.find(name);
     if (it == c->t.end()) { fprintf(stderr, "hdrtv: internal error, no workspace tensor %s\n", name.c_str()); abort(); }
-    return reinterpret_cast<T *>(c->ws.dev + it->second.off);
+    return reinterpret_cast<T *>(base + it->second.off);
 }
 template <typename T>
 const T *wtp(hdrtv_ctx *c, size_t off) { return reinterpret_cast<const T *>(c->wts.dev + off); }
+
+// ---- the Hallucination Generator after conv1 (Hallucination_arch.py): conv2 .. Up_conv5 in launch order.  build_weights packs
+// these rows (fp16 or W8A8), do_reserve registers their tensors (hg.<t> NHWC f16, or hg8.<t> int8 codes) and run_hg launches them.
+struct HgLayer {
+    const char *name;               // packed as hg.<name>; weights <name>.0 (3x3 blocks) or <name> (1x1 fuse convs)
+    int cout, cin, skip_cin;        // cin includes the skip input's channels, concatenated behind the input's
+    int ks, ps;                     // ps: channels after the Up blocks' pixel shuffle, else 0
+    int mode, act;                  // epilogue (ST_*); activation (the W8A8 layers: ReLU where the fp16 layer has it)
+    int level;                      // input resolution: (Hp, Wp) >> level
+    const char *in, *skip, *out;    // workspace tensors; out null: Up_conv5's sums go to hg.part
+    const char *bn;                 // BatchNorm2d of the conv blocks, "" none
+    const char *consumer, *shares;  // W8A8: the layer whose quantiser codes the output, and a second reader that must share it
+    int out_c() const { return ps ? ps : cout; }
+    int out_level() const { return level + (mode == ST_POOL ? 1 : 0) - (ps ? 1 : 0); }
+};
+inline constexpr HgLayer hg_layers[] = {
+    {"conv2", 128, 64, 0, 3, 0, ST_NHWC, ACT_RELU, 1, "p1", nullptr, "conv2", "conv2.1", "conv3_1.0", "conv9"},
+    {"conv3_1", 256, 128, 0, 3, 0, ST_POOL, ACT_RELU, 1, "conv2", nullptr, "p3", "conv3_1.1", "conv3_2.0", nullptr},
+    {"conv3_2", 256, 256, 0, 3, 0, ST_NHWC, ACT_RELU, 2, "p3", nullptr, "conv3_2", "conv3_2.1", "conv4_1.0", "conv8"},
+    {"conv4_1", 512, 256, 0, 3, 0, ST_POOL, ACT_RELU, 2, "conv3_2", nullptr, "p4", "conv4_1.1", "conv4_2.0", nullptr},
+    {"conv4_2", 512, 512, 0, 3, 0, ST_NHWC, ACT_RELU, 3, "p4", nullptr, "conv4_2", "conv4_2.1", "conv5_1.0", "conv7"},
+    {"conv5_1", 512, 512, 0, 3, 0, ST_POOL, ACT_RELU, 3, "conv4_2", nullptr, "p5", "conv5_1.1", "conv5_2.0", nullptr},
+    {"conv5_2", 512, 512, 0, 3, 0, ST_NHWC, ACT_RELU, 4, "p5", nullptr, "conv5_2", "conv5_2.1", "conv_code1.0", "conv6"},
+    {"conv_code1", 512, 512, 0, 3, 0, ST_POOL, ACT_RELU, 4, "conv5_2", nullptr, "pc", "conv_code1.1", "conv_code2.0", nullptr},
+    {"conv_code2", 512, 512, 0, 3, 0, ST_NHWC, ACT_RELU, 5, "pc", nullptr, "conv_code2", "conv_code2.1", "Up_conv1.0", nullptr},
+    {"Up_conv1", 2048, 512, 0, 3, 512, ST_PS, ACT_RELU, 5, "conv_code2", nullptr, "up1", "", "conv6", nullptr},
+    {"conv6", 512, 1024, 512, 1, 0, ST_NHWC, ACT_NONE, 4, "up1", "conv5_2", "conv6", "", "Up_conv2.0", nullptr},
+    {"Up_conv2", 2048, 512, 0, 3, 512, ST_PS, ACT_RELU, 4, "conv6", nullptr, "up2", "", "conv7", nullptr},
+    {"conv7", 256, 1024, 512, 1, 0, ST_NHWC, ACT_NONE, 3, "up2", "conv4_2", "conv7", "", "Up_conv3.0", nullptr},
+    {"Up_conv3", 1024, 256, 0, 3, 256, ST_PS, ACT_RELU, 3, "conv7", nullptr, "up3", "", "conv8", nullptr},
+    {"conv8", 128, 512, 256, 1, 0, ST_NHWC, ACT_NONE, 2, "up3", "conv3_2", "conv8", "", "Up_conv4.0", nullptr},
+    {"Up_conv4", 512, 128, 0, 3, 128, ST_PS, ACT_RELU, 2, "conv8", nullptr, "up4", "", "conv9", nullptr},
+    {"conv9", 64, 256, 128, 1, 0, ST_NHWC, ACT_NONE, 1, "up4", "conv2", "conv9", "", "Up_conv5.0", nullptr},
+    // Up_conv5 -> pixel shuffle -> ReLU -> first half of conv10, fused: 3 partial sums per pixel leave the kernel
+    {"Up_conv5", 256, 64, 0, 3, 64, ST_PS_DOT3, ACT_RELU, 1, "conv9", nullptr, nullptr, "", nullptr, nullptr},
+};
 
 // ---- api_graph.hip: launch sequencing of one hdrtv_infer (AGCM, LE, HG); fp32_graph.hip: the fp32 preset's graph
 struct Seq {
     hdrtv_ctx *c;
     hipStream_t s;
+    unsigned char *ws;              // the lane's workspace (c->lane_ws[lane]): every tensor this sequence names lies in it
     int rc = HDRTV_OK;
     // conv3x3s2_preg<192> only, consumed by the next conv(): CondNet2's 1x1 tail fused behind its first 64 output channels
     const f16 *tail_w = nullptr;
@@ -349,15 +387,35 @@ struct Seq {
     void c3(const std::string &key, const f16 *in, int H, int W, int act, f16 *out, f16 *out_pool, float pool_q_inv = 0.f, float pool_q_zero = 0.f, const f16 *w2frag = nullptr, float *part2 = nullptr);
     // persistent 32-channel 3x3 conv, optionally with the SFT layer `sft_key` fused in front (conv32p.hip)
     void conv32(const std::string &key, const f16 *src, const f16 *cond, const std::string &sft_key, int H, int W, int act, int mode, f16 *dst, int dstC, int Hd, int Wd, const f16 *res1 = nullptr, const f16 *res2 = nullptr, f16 *dst_planar = nullptr, const f16 *res_planar = nullptr, const f16 *c3_img = nullptr, const std::string &c3_key = "");
+    // the lane's copy of workspace tensor `name`
+    template <typename T>
+    T *wsp(const std::string &name) const { return hdrtv_host::wsp<T>(c, ws, name); }
     // diagnostic builds (make STAMP=1) write per-phase cycle sums of launch number HDRTV_STAMP_LAUNCH (read once) here
     void *stamp_buf() const
     {
 #ifdef HDRTV_STAMP
         static const int stamp_launch = [] { const char *e = getenv("HDRTV_STAMP_LAUNCH"); return e ? atoi(e) : -1; }();
-        return (stamp_launch >= 0 && c->launches == stamp_launch) ? (void *)wsp<f16>(c, "dbg.stamps") : nullptr;
+        return (stamp_launch >= 0 && c->launches == stamp_launch) ? (void *)wsp<f16>("dbg.stamps") : nullptr;
 #else
         return nullptr;
 #endif
+    }
+    // the 3x3 private-weight schedule (conv3x3_prw.hip, conv3x3_prw_i8.hip) for a layer it can run, Cout a multiple of 256:
+    // its tile height, 16 or 8 rows, or 0 for conv_pglds.  Variant "prw": 0 = never, 1 (default) = the cheapest shape per
+    // layer, 2 / 3 = 16-row / 8-row tiles wherever it applies
+    static int prw_rows(int prw_mode, int Ho, int Wo, int cout, int n_cu)
+    {
+        if (prw_mode != 1) return prw_mode == 0 ? 0 : (prw_mode == 3 ? 8 : 16);
+        // Its tiles cover 256 output channels (conv_pglds: 128).  Pick the shape whose tile count wastes least of the last
+        // round on n_cu workgroups: relative cost per unit of work 1.0 (16-row tiles), 1.09 (8-row tiles: twice the weight
+        // bytes per MAC, 1.11x the halo), 1.15 - 1.22 (conv_pglds) -- measured on full rounds, profiles/r03_prw_ab.txt
+        const long tx = (Wo + 15) / 16, n = n_cu;
+        auto cost = [&](long tiles, double rel) { return (double)(((tiles + n - 1) / n) * n) / (double)tiles * rel; };
+        const double c16 = cost(tx * ((Ho + 15) / 16) * (cout / 256), 1.0);
+        const double c8 = cost(tx * ((Ho + 7) / 8) * (cout / 256), 1.09);
+        const double cp = cost(tx * ((Ho + 15) / 16) * (cout / 128), 1.22);
+        if (cp <= c16 && cp <= c8) return 0;
+        return c8 < c16 ? 8 : 16;
     }
     // a conv inside a fused row kernel: its fp16 pack, or (W8A8 layer, variant le_rows_fq) the dequantised pack + its activation quantiser
     static FqParam fqp(const ActQf &q) { return FqParam{q.inv(), q.zoff(), q.scale, q.asym ? q.zero : -128.f * q.scale}; }
@@ -385,12 +443,23 @@ struct Seq {
         for (int i = 0; i < 4; ++i) fq[i] = fqp(S.fq[i]);
         return true;
     }
-    // the row-streaming kernels (le_rows.hip) cut a map into 60-column strips x row segments, one workgroup each: worth it
-    // when a segment is long against its 4 .. 6 warm-up rows
-    bool rows_fit(int H, int W) const
+    // the row-streaming kernels (le_rows.hip) run (variant le_rows) on maps they cut into 60-column strips x row segments, one
+    // workgroup each: worth it when a segment is long against its 4 .. 6 warm-up rows.  even: the head / tail kernels, which
+    // also need even H and W
+    bool rows_on(int H, int W, bool even) const
     {
+        if (!c->var.at("le_rows") || (even && ((H | W) & 1))) return false;
         const int nstrips = (W + 59) / 60, nseg = std::max(1, c->n_cu / nstrips);
         return W >= 60 && (H + nseg - 1) / nseg >= c->var.at("le_rows_min");
+    }
+    // the operands of a W8A8 conv / SFT layer in the int8 row kernels (le_rows_i8.hip)
+    RowsConvI8 rows_i8(const QLayer &Q) const
+    {
+        return RowsConvI8{wtp<int8_t>(c, Q.wpk8), wtp<float>(c, Q.scale), wtp<float>(c, Q.shift), Q.q.inv(), Q.q.zoff()};
+    }
+    RowsSftI8 rows_i8(const SftLayer &S) const
+    {
+        return RowsSftI8{wtp<int8_t>(c, S.qfrag), wtp<float>(c, S.qconst), {S.inv[0], S.inv[1]}, {S.zoff[0], S.zoff[1]}, {S.hzoff[0], S.hzoff[1]}};
     }
     // ResBlock_with_SFT (arch_util.py:89-95): y = x + conv2(sft2(relu(conv1(sft1(x,c))),c))  [+ extra]; 2 launches
     void resblock(const std::string &base, const f16 *x, const f16 *cond, int H, int W, f16 *tb, f16 *y, const f16 *extra = nullptr);

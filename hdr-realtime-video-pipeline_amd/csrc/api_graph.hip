@@ -27,51 +27,50 @@ void Seq::conv(const std::string &key, const f16 *src0, int c0, const f16 *src1,
     p.zeros = wtp<f16>(c, c->zeros_off);
     p.tail_w = tail_w; p.tail_b = tail_b; p.tail_s = tail_s; p.tail_out = tail_out;
     tail_w = nullptr; tail_b = nullptr; tail_s = nullptr; tail_out = nullptr;
-    const bool g64 = L.stride == 1 && L.cin_t == 64 && L.bn == 128 && !res1 && !res2 && !dst_full && mode != ST_PLANAR3;
-    const bool pglds = g64 && L.ks == 3 && L.cout == L.coutPad;      // HG 3x3 convs: persistent LDS-DMA kernel
-    const bool glds1 = g64 && L.ks == 1 && mode == ST_NHWC && (c0 + c1) >= 128 && L.coutPad <= 512 && (act == ACT_RELU || act == ACT_NONE);   // HG 1x1 fuse convs
     p.trash = const_cast<char *>(wtp<char>(c, c->dump_off));
     const int nt_slow = c->var.at("pglds_nt_slow");
     // default: the Up convs (Cout = 4 Cin: 4 .. 16 Cout-tiles per pixel tile) walk Cout-tile slowest -- an XCD then shares one
     // weight slab instead of re-fetching up to 16 (-17 % L2 misses, profiles/r02_pmc_traffic_tile_order.json); the other
     // layers walk it fastest so that the blocks of an XCD share halo tiles (+45 .. +75 % misses the other way round)
     p.nt_slow = nt_slow == 3 ? (mode == ST_PS) : (nt_slow == 2 ? (L.coutPad >= 512) : nt_slow);
-    const bool s2g = L.ks == 3 && L.stride == 2 && L.cin_t == 64 && L.bn == L.coutPad && (L.coutPad == 64 || L.coutPad == 192);
-    // a fused 1x1 tail (run_le sets it and then skips the tail's own launch) exists in conv3x3s2_preg's epilogue only
-    if (p.tail_w && !s2g) { rc = fail(c, HDRTV_ESTATE, "conv %s: a fused CondNet tail was requested but the layer does not run on conv3x3s2_preg", key.c_str()); return; }
+    // the kernel, chosen once: the tag and the launch below both follow `route`
+    enum { T16, S2G, PRW, PGLDS, GLDS1, IGEMM } route = IGEMM;
+    int prw_th = 0;
+    const bool g64 = L.stride == 1 && L.cin_t == 64 && L.bn == 128 && !res1 && !res2 && !dst_full && mode != ST_PLANAR3;
     const bool no_t16 = c->var.at("no_t16") != 0;                         // developer A/B: the generic implicit-GEMM kernel
-    const bool t16 = !no_t16 && L.ks == 3 && L.stride == 2 && L.cin == 32 && L.coutPad == 32 && !src1 && mode == ST_NHWC && !res1 && !res2;
-    // HG 3x3 convs with Cout a multiple of 256: the private-weight schedule (conv3x3_prw.hip); variant prw = 0: conv_pglds
-    // variant "prw": 0 = never, 1 (default) = the cheapest shape per layer, 2 / 3 = 16-row / 8-row tiles wherever it applies
-    const int use_prw_mode = c->var.at("prw");
-    const bool use_prw = use_prw_mode != 0;
-    const bool prw_dot3 = mode == ST_PS_DOT3 && L.coutPad == 256;                // Up_conv5: always the 16-row shape
-    bool prw = pglds && use_prw && (L.coutPad % 256) == 0 && (mode != ST_PS_DOT3 || prw_dot3);
-    int prw_th = 16;
-    if (prw && prw_dot3) {
-    } else if (prw && use_prw_mode == 1) {
-        // Its tiles cover 256 output channels (conv_pglds: 128).  Pick the shape whose tile count wastes least of the last
-        // round on n_cu workgroups: relative cost per unit of work 1.0 (16-row tiles), 1.09 (8-row tiles: twice the weight
-        // bytes per MAC, 1.11x the halo), 1.15 - 1.22 (conv_pglds) -- measured on full rounds, profiles/r03_prw_ab.txt
-        const long tx = (p.Wo + 15) / 16, n = c->n_cu;
-        auto cost = [&](long tiles, double rel) { return (double)(((tiles + n - 1) / n) * n) / (double)tiles * rel; };
-        const double c16 = cost(tx * ((p.Ho + 15) / 16) * (L.coutPad / 256), 1.0);
-        const double c8 = cost(tx * ((p.Ho + 7) / 8) * (L.coutPad / 256), 1.09);
-        const double c0 = cost(tx * ((p.Ho + 15) / 16) * (L.coutPad / 128), 1.22);
-        if (c0 <= c16 && c0 <= c8) prw = false;
-        else prw_th = c8 < c16 ? 8 : 16;
-    } else if (prw && use_prw_mode == 3) {
-        prw_th = 8;
-    }
+    if (!no_t16 && L.ks == 3 && L.stride == 2 && L.cin == 32 && L.coutPad == 32 && !src1 && mode == ST_NHWC && !res1 && !res2)
+        route = T16;
+    else if (L.ks == 3 && L.stride == 2 && L.cin_t == 64 && L.bn == L.coutPad && (L.coutPad == 64 || L.coutPad == 192))
+        route = S2G;
+    else if (g64 && L.ks == 3 && L.cout == L.coutPad) {                   // HG 3x3 convs: persistent LDS-DMA kernel
+        // Cout a multiple of 256: the private-weight schedule (conv3x3_prw.hip); Up_conv5 (ST_PS_DOT3) only at 256, always 16 rows
+        const int prw_mode = c->var.at("prw");
+        if (prw_mode != 0 && (L.coutPad % 256) == 0 && mode != ST_PS_DOT3) prw_th = prw_rows(prw_mode, p.Ho, p.Wo, L.coutPad, c->n_cu);
+        else if (prw_mode != 0 && mode == ST_PS_DOT3 && L.coutPad == 256) prw_th = 16;
+        route = prw_th ? PRW : PGLDS;
+    } else if (g64 && L.ks == 1 && mode == ST_NHWC && (c0 + c1) >= 128 && L.coutPad <= 512 && (act == ACT_RELU || act == ACT_NONE))
+        route = GLDS1;                                                     // HG 1x1 fuse convs
+    // a fused 1x1 tail (run_le sets it and then skips the tail's own launch) exists in conv3x3s2_preg's epilogue only
+    if (p.tail_w && route != S2G) { rc = fail(c, HDRTV_ESTATE, "conv %s: a fused CondNet tail was requested but the layer does not run on conv3x3s2_preg", key.c_str()); return; }
+    const char *epi = mode == ST_POOL ? "pool" : (mode == ST_PS ? "ps" : (mode == ST_PS_DOT3 ? "ps_dot3" : "nhwc"));
     char tag[64];
-    if (t16) snprintf(tag, sizeof tag, "conv_t16<32,3,2>");
-    else if (s2g) snprintf(tag, sizeof tag, p.tail_w ? "conv3x3s2_preg<%d>+tail" : "conv3x3s2_preg<%d>", L.coutPad);
-    else if (pglds) snprintf(tag, sizeof tag, "%s<%s>", prw ? (prw_th == 8 ? "conv_prw8" : "conv_prw") : "conv_pglds", mode == ST_POOL ? "pool" : (mode == ST_PS ? "ps" : (mode == ST_PS_DOT3 ? "ps_dot3" : "nhwc")));
-    else if (glds1) snprintf(tag, sizeof tag, "conv_glds1");
-    else snprintf(tag, sizeof tag, "conv_igemm<%d,%d,%d,%d>", L.cin_t, L.bn, L.ks, L.stride);
+    hipError_t e;
+    switch (route) {
+    case T16: snprintf(tag, sizeof tag, "conv_t16<32,3,2>"); e = conv_t16_launch(p, s, c->n_cu); break;
+    case S2G:
+        snprintf(tag, sizeof tag, p.tail_w ? "conv3x3s2_preg<%d>+tail" : "conv3x3s2_preg<%d>", L.coutPad);
+        e = conv3x3s2_preg_launch(p, c->n_cu, s);
+        break;
+    case PRW: snprintf(tag, sizeof tag, "%s<%s>", prw_th == 8 ? "conv_prw8" : "conv_prw", epi); e = conv_prw_launch(p, prw_th, c->n_cu, s); break;
+    case PGLDS: snprintf(tag, sizeof tag, "conv_pglds<%s>", epi); e = conv_pglds_launch(p, c->n_cu, s); break;
+    case GLDS1: snprintf(tag, sizeof tag, "conv_glds1"); e = conv_glds1_launch(p, s, c->n_cu, c->var.at("glds1_old") != 0); break;
+    default:
+        snprintf(tag, sizeof tag, "conv_igemm<%d,%d,%d,%d>", L.cin_t, L.bn, L.ks, L.stride);
+        e = conv_igemm_launch(p, L.cin_t, L.bn, L.ks, L.stride, s);
+    }
     double macs = (double)p.Ho * p.Wo * L.cin * L.ks * L.ks * L.cout;
     double bytes = 2.0 * Hi * Wi * L.cin + 2.0 * L.ks * L.ks * L.cin * L.coutPad;
-    if (s2g && p.tail_w) {          // a fused 1x1 tail: + its MACs, 16 channels out instead of the 64 it consumes
+    if (p.tail_w) {                 // a fused 1x1 tail: + its MACs, 16 channels out instead of the 64 it consumes
         macs += (double)p.Ho * p.Wo * (p.tail_s ? 64 * 16 : 64 * 64 + 64 * 16);
         bytes -= 2.0 * p.Ho * p.Wo * (64 - 16);
     }
@@ -79,10 +78,7 @@ void Seq::conv(const std::string &key, const f16 *src0, int c0, const f16 *src1,
                                           : (mode == ST_PLANAR3 ? 3.0 * Hd * Wd
                                                                 : (mode == ST_PS_DOT3 ? 8.0 * Hd * Wd : (double)p.Ho * p.Wo * L.cout));
     bytes += 2.0 * outel * (1 + (res1 ? 1 : 0) + (res2 ? 1 : 0) + (res_planar ? 1 : 0));
-    chk(t16 ? conv_t16_launch(p, s, c->n_cu) : s2g ? conv3x3s2_preg_launch(p, c->n_cu, s)
-            : (pglds ? (prw ? conv_prw_launch(p, prw_th, c->n_cu, s) : conv_pglds_launch(p, c->n_cu, s))
-                     : (glds1 ? conv_glds1_launch(p, s, c->n_cu, c->var.at("glds1_old") != 0) : conv_igemm_launch(p, L.cin_t, L.bn, L.ks, L.stride, s))),
-        key.c_str(), tag, macs, bytes);
+    chk(e, key.c_str(), tag, macs, bytes);
 }
 
 
@@ -113,21 +109,12 @@ void Seq::conv8(const std::string &key, const int8_t *src0, int c0, const int8_t
                          (mode == ST_PS_DOT3 ? 16.0 * Hd * Wd : outel * (L.out_f16 ? 2.0 : 1.0));
     // the private-weight schedule (conv3x3_prw_i8.hip) and its tile shape, picked as for the fp16 layers (Seq::conv)
     const int prw_mode = c->var.at("prw");
-    bool prw = prw_mode != 0 && L.ks == 3 && c0 != 64 && (L.cout % 256) == 0 && mode != ST_PS_DOT3 && !L.out_f16;
-    int prw_th = 16;
-    if (prw && prw_mode == 1) {
-        const long tx = (Wi + 15) / 16, n = c->n_cu;
-        auto cost = [&](long tiles, double rel) { return (double)(((tiles + n - 1) / n) * n) / (double)tiles * rel; };
-        const double c16 = cost(tx * ((Hi + 15) / 16) * (L.cout / 256), 1.0), c8 = cost(tx * ((Hi + 7) / 8) * (L.cout / 256), 1.09);
-        const double c0c = cost(tx * ((Hi + 15) / 16) * (L.cout / 128), 1.22);
-        if (c0c <= c16 && c0c <= c8) prw = false;
-        else prw_th = c8 < c16 ? 8 : 16;
-    } else if (prw && prw_mode == 3) {
-        prw_th = 8;
-    }
+    int prw_th = prw_mode != 0 && L.ks == 3 && c0 != 64 && (L.cout % 256) == 0 && mode != ST_PS_DOT3 && !L.out_f16
+                     ? prw_rows(prw_mode, Hi, Wi, L.cout, c->n_cu) : 0;
     // variant "prw_i8": 0 = never, 1 = only where the 8-row tiles win (the low-resolution layers), 2 = wherever "prw" selects it
     const int i8_mode = c->var.at("prw_i8");
-    if (i8_mode == 0 || (i8_mode == 1 && prw_th != 8)) prw = false;
+    if (i8_mode == 0 || (i8_mode == 1 && prw_th != 8)) prw_th = 0;
+    const bool prw = prw_th != 0;
     if (prw) snprintf(tag, sizeof tag, "conv_prw%s_i8<%s>", prw_th == 8 ? "8" : "", mode == ST_POOL ? "pool" : (mode == ST_PS ? "ps" : "nhwc"));
     chk(L.ks == 3 ? (prw ? conv_prw_i8_launch(p, prw_th, c->n_cu, s) : conv_pglds_i8_launch(p, c->n_cu, s)) : conv1x1_i8_launch(p, s),
         key.c_str(), tag, macs, bytes);
@@ -226,21 +213,19 @@ void Seq::conv32(const std::string &key, const f16 *src, const f16 *cond, const 
 
 void Seq::resblock(const std::string &base, const f16 *x, const f16 *cond, int H, int W, f16 *tb, f16 *y, const f16 *extra)
 {
+    // no second residual, enough rows per segment to amortise the 4-row warm-up: ONE row-streaming launch, the intermediate
+    // never leaves LDS
+    const bool rows = ok() && !extra && rows_on(H, W, false);
     // every layer of the block W8A8 (the full-QAT recipe): the row-streaming kernel on int8 MFMA (le_rows_i8.hip), the rings hold
     // the layers' int8 codes; bit-identical to the two conv32s<sft-i8, i8> launches at the bottom (variant le_rows_i8 = 0: the
     // fake-quant form below, or those launches)
-    if (ok() && c->var.at("le_rows") && c->var.at("le_rows_i8") && !extra && rows_fit(H, W)) {
+    if (rows && c->var.at("le_rows_i8")) {
         auto q1 = c->q32.find(base + ".conv1"), q2 = c->q32.find(base + ".conv2");
         const SftLayer &S1 = c->sft.at(base + ".sft1"), &S2 = c->sft.at(base + ".sft2");
         if (q1 != c->q32.end() && q2 != c->q32.end() && S1.q && S2.q && q1->second.coutPad == 32 && q2->second.coutPad == 32) {
             RowsRbI8Params p;
             memset(&p, 0, sizeof p);
-            auto cv = [&](const QLayer &Q) { return RowsConvI8{wtp<int8_t>(c, Q.wpk8), wtp<float>(c, Q.scale), wtp<float>(c, Q.shift), Q.q.inv(), Q.q.zoff()}; };
-            auto sv = [&](const SftLayer &S) {
-                RowsSftI8 r{wtp<int8_t>(c, S.qfrag), wtp<float>(c, S.qconst), {S.inv[0], S.inv[1]}, {S.zoff[0], S.zoff[1]}, {S.hzoff[0], S.hzoff[1]}};
-                return r;
-            };
-            p.x = x; p.cond = cond; p.c1 = cv(q1->second); p.c2 = cv(q2->second); p.s1 = sv(S1); p.s2 = sv(S2);
+            p.x = x; p.cond = cond; p.c1 = rows_i8(q1->second); p.c2 = rows_i8(q2->second); p.s1 = rows_i8(S1); p.s2 = rows_i8(S2);
             p.slope1 = act_slope(ACT_RELU);
             p.dst = y; p.trash = const_cast<char *>(wtp<char>(c, c->dump_off)); p.H = H; p.W = W;
             const double npx = (double)H * W;
@@ -249,9 +234,8 @@ void Seq::resblock(const std::string &base, const f16 *x, const f16 *cond, int H
             return;
         }
     }
-    // fp16 block without a second residual, enough rows per segment to amortise the 4-row warm-up: ONE row-streaming
-    // launch (le_rows.hip), the intermediate never leaves LDS; bit-identical to the two launches below
-    if (ok() && c->var.at("le_rows") && !extra && rows_fit(H, W)) {
+    // fp16 block (le_rows.hip), W8A8 layers as fake-quant (variant le_rows_fq); bit-identical to the two launches below
+    if (rows) {
         RowsRbParams p;
         memset(&p, 0, sizeof p);
         bool q1, q2, qs1, qs2;
@@ -278,7 +262,7 @@ void Seq::resblock(const std::string &base, const f16 *x, const f16 *cond, int H
 
 int f32_plan(hdrtv_ctx *c, int H, int W)
 {
-    Seq q{c, nullptr};
+    Seq q{c, nullptr, nullptr};
     return run_f32(c, q, true, H, W, nullptr, nullptr, nullptr, nullptr);
 }
 
@@ -289,14 +273,14 @@ int run_agcm(hdrtv_ctx *c, Seq &q, const f16 *rgb, const f16 *cond, f16 *agcm_ou
     char a[64], b[64];
     for (int i = 0; i < 5; ++i) {
         snprintf(a, sizeof a, "agcm.u%d", i + 1);
-        float *out = wsp<float>(c, a);
+        float *out = q.wsp<float>(a);
         const void *in = cond;
         const float *nm = nullptr, *nr = nullptr, *ng = nullptr, *nb = nullptr;
         if (i > 0) {
             snprintf(b, sizeof b, "agcm.u%d", i);
-            in = wsp<float>(c, b);
-            snprintf(b, sizeof b, "agcm.mean%d", i); nm = wsp<float>(c, b);
-            snprintf(b, sizeof b, "agcm.rstd%d", i); nr = wsp<float>(c, b);
+            in = q.wsp<float>(b);
+            snprintf(b, sizeof b, "agcm.mean%d", i); nm = q.wsp<float>(b);
+            snprintf(b, sizeof b, "agcm.rstd%d", i); nr = q.wsp<float>(b);
             snprintf(b, sizeof b, "cls%d.g", i - 1); ng = wtp<float>(c, c->f32v.at(b));
             snprintf(b, sizeof b, "cls%d.be", i - 1); nb = wtp<float>(c, c->f32v.at(b));
         }
@@ -306,17 +290,17 @@ int run_agcm(hdrtv_ctx *c, Seq &q, const f16 *rgb, const f16 *cond, f16 *agcm_ou
         const float *bias = wtp<float>(c, c->f32v.at(b));
         int nblk = 0;
         q.chk(cls_block_launch(in, i == 0, cls_ci[i], s.ch[i], s.cw[i], nm, nr, ng, nb, w, bias, cls_co[i], out, s.ch[i + 1],
-                               s.cw[i + 1], wsp<float>(c, "agcm.part"), q.s, c->cls_q[i].on ? &c->cls_q[i] : nullptr,
+                               s.cw[i + 1], q.wsp<float>("agcm.part"), q.s, c->cls_q[i].on ? &c->cls_q[i] : nullptr,
                                (i == 4 && c->cls_q[5].on) ? &c->cls_q[5] : nullptr, &nblk),
               "cls_block", c->cls_q[i].on ? "cls_block<fq>" : "cls_block", (double)s.ch[i] * s.cw[i] * cls_ci[i] * cls_co[i]);
         snprintf(a, sizeof a, "agcm.mean%d", i + 1);
         snprintf(b, sizeof b, "agcm.rstd%d", i + 1);
-        q.chk(cls_stats_launch(wsp<float>(c, "agcm.part"), cls_co[i], nblk, s.ch[i + 1] * s.cw[i + 1], 1e-5f, wsp<float>(c, a),
-                               wsp<float>(c, b), q.s),
+        q.chk(cls_stats_launch(q.wsp<float>("agcm.part"), cls_co[i], nblk, s.ch[i + 1] * s.cw[i + 1], 1e-5f, q.wsp<float>(a),
+                               q.wsp<float>(b), q.s),
               "cls_stats", "cls_stats");
     }
     AgcmFoldArgs fa;
-    fa.mean5 = wsp<float>(c, "agcm.mean5");
+    fa.mean5 = q.wsp<float>("agcm.mean5");
     fa.w20 = wtp<float>(c, c->f32v.at("cls20.w")); fa.b20 = wtp<float>(c, c->f32v.at("cls20.b"));
     for (int st = 0; st < 3; ++st) {
         snprintf(a, sizeof a, "gfm.s%d.w", st); fa.ws[st] = wtp<float>(c, c->f32v.at(a));
@@ -333,16 +317,16 @@ int run_agcm(hdrtv_ctx *c, Seq &q, const f16 *rgb, const f16 *cond, f16 *agcm_ou
         for (int i = 0; i < 6; ++i) qa.qlin[i] = c->lin_q[i];
         qa.P = wtp<float>(c, c->ag_P); qa.Q = wtp<float>(c, c->ag_Q);
         qa.inv2 = c->ag_q[1].inv(); qa.inv3 = c->ag_q[2].inv();
-        qa.consts = wsp<float>(c, "agcm.qconst");
-        q.chk(agcm_fold_q8_launch(fa, qa, wsp<float>(c, "agcm.bias"), q.s), "agcm_fold", "agcm_fold<q8>", 128.0 * 6 + 6.0 * (64 + 64 + 3) * 2);
+        qa.consts = q.wsp<float>("agcm.qconst");
+        q.chk(agcm_fold_q8_launch(fa, qa, q.wsp<float>("agcm.bias"), q.s), "agcm_fold", "agcm_fold<q8>", 128.0 * 6 + 6.0 * (64 + 64 + 3) * 2);
         q.chk(agcm_mlp_q8_launch(rgb, agcm_out, (size_t)c->H * c->W, wtp<int8_t>(c, c->ag_frag), qa.consts, c->ag_q[0].inv(), c->ag_q[0].zoff(),
                                  c->ag_q[1].zoff(), c->ag_q[2].zoff(), q.s),
               "agcm_mlp", "agcm_mlp<q8>", (double)c->H * c->W * (3 * 64 + 64 * 64 + 64 * 3), 12.0 * c->H * c->W);
         return q.rc;
     }
-    q.chk(agcm_fold_launch(fa, wsp<f16>(c, "agcm.frags"), wsp<float>(c, "agcm.bias"), q.s), "agcm_fold", "agcm_fold",
+    q.chk(agcm_fold_launch(fa, q.wsp<f16>("agcm.frags"), q.wsp<float>("agcm.bias"), q.s), "agcm_fold", "agcm_fold",
           128.0 * 6 + 6.0 * (64 + 64 + 3) * 2);
-    q.chk(agcm_mlp_launch(rgb, agcm_out, (size_t)c->H * c->W, wsp<f16>(c, "agcm.frags"), wsp<float>(c, "agcm.bias"), q.s),
+    q.chk(agcm_mlp_launch(rgb, agcm_out, (size_t)c->H * c->W, q.wsp<f16>("agcm.frags"), q.wsp<float>("agcm.bias"), q.s),
           "agcm_mlp", "agcm_mlp", (double)c->H * c->W * (3 * 64 + 64 * 64 + 64 * 3), 12.0 * c->H * c->W);
     return q.rc;
 }
@@ -352,10 +336,10 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
 {
     const Shapes s = shapes_for(c->H, c->W);
     const int H = s.H, W = s.W;
-    f16 *cond = wsp<f16>(c, "le.cond");
-    f16 *cond1 = wsp<f16>(c, "le.cond1"), *cond2 = wsp<f16>(c, "le.cond2"), *cond3 = wsp<f16>(c, "le.cond3"),
-        *cond4 = wsp<f16>(c, "le.cond4");
-    f16 *h2a = wsp<f16>(c, "le.h2a");
+    f16 *cond = q.wsp<f16>("le.cond");
+    f16 *cond1 = q.wsp<f16>("le.cond1"), *cond2 = q.wsp<f16>("le.cond2"), *cond3 = q.wsp<f16>("le.cond3"),
+        *cond4 = q.wsp<f16>("le.cond4");
+    f16 *h2a = q.wsp<f16>("le.h2a");
     // condition trunk
     // cond_first (3 layers) + CondNet1 (3 layers) in one launch: img -> cond (64 ch) and cond1 (16 ch)
     auto qlast = [&](const QLastLayer &Q, QLastArgs &a) -> const QLastArgs * {
@@ -377,7 +361,7 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
               "LE.cond_trunk", c->q_trunk6.on ? "le_cond_trunk<q6>" : "le_cond_trunk", (double)H * W * (27 * 64 + 4 * 64 * 64 + 64 * 16), (double)H * W * (6 + 128 + 32));
     auto isq8 = [&](const char *L) { return c->q8.find(L) != c->q8.end(); };
     auto qof = [&](const char *L) -> const ActQf * { auto it = c->q8.find(L); return it == c->q8.end() ? nullptr : &it->second.q; };
-    f16 *h2b = wsp<f16>(c, "le.h2b");
+    f16 *h2b = q.wsp<f16>("le.h2b");
     // CondNet{2,3,4}.0 (3x3 / stride 2 from the 64-channel condition map).  All-fp16 recipes read `cond` once (one launch,
     // 192 channels); a W8A8 layer among them quantises `cond` with its own x_scale / x_zero and runs alone, writing the int8
     // codes of the layer that reads it when that one is W8A8 too.
@@ -386,7 +370,7 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
     int astride = 64;
     bool cond2_fused = false;
     if (c->conv.find("LE.CondNet234.0") != c->conv.end()) {
-        f16 *x192 = wsp<f16>(c, "le.x192");
+        f16 *x192 = q.wsp<f16>("le.x192");
         // CondNet2.2 + .4 ride in that launch's epilogue (variant cond2_fused; a W8A8 CondNet2.4 keeps its own kernel): the first 64 of
         // the 192 channels then never reach HBM
         cond2_fused = c->var.at("cond2_fused") != 0 && !c->tail_q8 && !c->q_tail2.on;
@@ -394,8 +378,8 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
         q.conv("LE.CondNet234.0", cond, 64, nullptr, 0, H, W, ACT_LRELU01, ST_NHWC, x192, 192, s.H1, s.W1);
         a2 = x192; a3 = x192 + 64; a4 = x192 + 128; astride = 192;
     } else {
-        f16 *ca[3] = {wsp<f16>(c, "le.c2a"), wsp<f16>(c, "le.c3a"), wsp<f16>(c, "le.c4a")};
-        int8_t *ca8[3] = {wsp<int8_t>(c, "le8.c2a"), wsp<int8_t>(c, "le8.c3a"), wsp<int8_t>(c, "le8.c4a")};
+        f16 *ca[3] = {q.wsp<f16>("le.c2a"), q.wsp<f16>("le.c3a"), q.wsp<f16>("le.c4a")};
+        int8_t *ca8[3] = {q.wsp<int8_t>("le8.c2a"), q.wsp<int8_t>("le8.c3a"), q.wsp<int8_t>("le8.c4a")};
         const char *l0[3] = {"LE.CondNet2.0", "LE.CondNet3.0", "LE.CondNet4.0"}, *l2[3] = {nullptr, "LE.CondNet3.2", "LE.CondNet4.2"};
         const f16 **af[3] = {&a2, &a3, &a4};
         const int8_t **aq[3] = {&a2q, &a3q, &a4q};
@@ -452,7 +436,7 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
             bool h_i8 = false;
             if (isq8(l2[i])) {
                 const ActQf *oq = qof(l4[i]);
-                int8_t *h8 = oq ? wsp<int8_t>(c, i ? "le8.h2b" : "le8.h2a") : nullptr;
+                int8_t *h8 = oq ? q.wsp<int8_t>(i ? "le8.h2b" : "le8.h2a") : nullptr;
                 q.convq8(l2[i], aq[i] ? (const void *)aq[i] : (const void *)af[i], aq[i] != nullptr, aq[i] ? 64 : astride, s.H1, s.W1,
                          ACT_LRELU01, oq ? (void *)h8 : (void *)h2[i], 64, oq);
                 if (oq) { h = h8; h_i8 = true; }
@@ -474,23 +458,23 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
         }
     }
     // main branch: every SFT is fused into the 3x3 conv that follows it
-    f16 *f0a = wsp<f16>(c, "le.f0a"), *f0b = wsp<f16>(c, "le.f0b"), *fea0 = wsp<f16>(c, "le.fea0"), *up3 = wsp<f16>(c, "le.up3");
+    f16 *f0a = q.wsp<f16>("le.f0a"), *f0b = q.wsp<f16>("le.f0b"), *fea0 = q.wsp<f16>("le.fea0"), *up3 = q.wsp<f16>("le.up3");
     bool head_fused = false;
-    // conv_first .. down_conv1 in one row-streaming launch (le_rows.hip) when the shapes are even and every layer is fp16 or a W8A8
-    // layer the kernel runs as fake-quant (variant le_rows_fq)
+    // the full-resolution head and tail each as one row-streaming launch: even shapes, enough rows per segment
+    const bool rows = q.rows_on(H, W, true);
+    // conv_first .. down_conv1 in one row-streaming launch (le_rows.hip) when every layer is fp16 or a W8A8 layer the kernel runs
+    // as fake-quant (variant le_rows_fq)
     // every layer of the head W8A8 (the full-QAT recipe): the row kernel on int8 MFMA (le_rows_i8.hip), bit-identical to conv_c3_q8 +
     // conv32s<sft-i8, i8> + conv_q8<32,3,2>
-    if (q.ok() && c->var.at("le_rows") && c->var.at("le_rows_i8") && !c->var.at("no_c3q8") && !(H & 1) && !(W & 1) && q.rows_fit(H, W)) {
+    if (q.ok() && rows && c->var.at("le_rows_i8") && !c->var.at("no_c3q8")) {
         auto qc = c->q8.find("LE.conv_first#c3");
         auto qh = c->q32.find("LE.HR_conv1"), qd = c->q32.find("LE.down_conv1#rows8");
         const SftLayer &S1 = c->sft.at("LE.SFT_layer1");
         if (qc != c->q8.end() && qh != c->q32.end() && qd != c->q32.end() && S1.q && qh->second.coutPad == 32 && qd->second.coutPad == 32) {
             RowsHeadI8Params p;
             memset(&p, 0, sizeof p);
-            auto cv = [&](const QLayer &Q) { return RowsConvI8{wtp<int8_t>(c, Q.wpk8), wtp<float>(c, Q.scale), wtp<float>(c, Q.shift), Q.q.inv(), Q.q.zoff()}; };
-            p.img = img; p.cond = cond1; p.fea0 = fea0; p.fea1 = wsp<f16>(c, "le.fea1a"); p.H = H; p.W = W;
-            p.cf = cv(qc->second); p.hr = cv(qh->second); p.dn = cv(qd->second);
-            p.s = RowsSftI8{wtp<int8_t>(c, S1.qfrag), wtp<float>(c, S1.qconst), {S1.inv[0], S1.inv[1]}, {S1.zoff[0], S1.zoff[1]}, {S1.hzoff[0], S1.hzoff[1]}};
+            p.img = img; p.cond = cond1; p.fea0 = fea0; p.fea1 = q.wsp<f16>("le.fea1a"); p.H = H; p.W = W;
+            p.cf = q.rows_i8(qc->second); p.hr = q.rows_i8(qh->second); p.dn = q.rows_i8(qd->second); p.s = q.rows_i8(S1);
             p.slope_relu = act_slope(ACT_RELU);
             p.trash = const_cast<char *>(wtp<char>(c, c->dump_off));
             const double npx = (double)H * W;
@@ -499,7 +483,7 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
             head_fused = true;
         }
     }
-    if (!head_fused && q.ok() && c->var.at("le_rows") && !c->var.at("no_c3fuse") && !c->var.at("conv32_old") && !(H & 1) && !(W & 1) && q.rows_fit(H, W)) {
+    if (!head_fused && q.ok() && rows && !c->var.at("no_c3fuse") && !c->var.at("conv32_old")) {
         RowsHeadParams p;
         memset(&p, 0, sizeof p);
         bool qh, qd, qs, qi = isq8("LE.conv_first");
@@ -509,7 +493,7 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
         if (Lh && Ld && q.rows_sft(S1, p.fq_s, qs) && i3 != c->c3.end() && (!qi || c->var.at("le_rows_fq"))) {
             if (qi) p.fq_img = Seq::fqp(c->q8.at("LE.conv_first").q);
             p.fq = (qi ? 1 : 0) | (qh ? 2 : 0) | (qd ? 4 : 0) | (qs ? 8 : 0);
-            p.img = img; p.cond = cond1; p.H = H; p.W = W; p.fea0 = fea0; p.fea1 = wsp<f16>(c, "le.fea1a");
+            p.img = img; p.cond = cond1; p.H = H; p.W = W; p.fea0 = fea0; p.fea1 = q.wsp<f16>("le.fea1a");
             p.c3_wfrag = wtp<f16>(c, i3->second.wfrag);
             p.sft_wfrag = wtp<f16>(c, S1.wfrag); p.sft_bias = wtp<float>(c, S1.bias);
             p.w_hr = wtp<f16>(c, Lh->wpk); p.b_hr = wtp<float>(c, Lh->shift); p.w_down = wtp<f16>(c, Ld->wpk); p.b_down = wtp<float>(c, Ld->shift);
@@ -524,7 +508,7 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
     if (!head_fused) {
         if (isq8("LE.conv_first")) {
             if (c->var.at("no_c3q8")) {                  // developer A/B switch: the generic two-launch form     // the 3 planes as NHWC int8 codes (3 of 32 bytes real), then the generic int8 conv
-                int8_t *img32 = wsp<int8_t>(c, "le8.img32");
+                int8_t *img32 = q.wsp<int8_t>("le8.img32");
                 const QLayer &Lq = c->q8.at("LE.conv_first");
                 if (q.ok()) q.chk(planar3_to_q8_launch(img, (size_t)H * W, Lq.q.inv(), Lq.q.zoff(), img32, q.s), "le.conv_first.pack", "planar3_to_q8", 0.0, 38.0 * H * W);
                 q.convq8("LE.conv_first", img32, true, 32, H, W, ACT_RELU, f0a, 32, nullptr);
@@ -549,32 +533,32 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
             }
         }
     }
-    f16 *fea1a = wsp<f16>(c, "le.fea1a"), *fea1 = wsp<f16>(c, "le.fea1"), *l1b = wsp<f16>(c, "le.l1b");
+    f16 *fea1a = q.wsp<f16>("le.fea1a"), *fea1 = q.wsp<f16>("le.fea1"), *l1b = q.wsp<f16>("le.l1b");
     auto down = [&](const char *key, const f16 *src, int Hi, int Wi, f16 *dst, int Ho, int Wo) {
         if (isq8(key)) q.convq8(key, src, false, 32, Hi, Wi, ACT_RELU, dst, 32, nullptr);
         else q.conv(key, src, 32, nullptr, 0, Hi, Wi, ACT_RELU, ST_NHWC, dst, 32, Ho, Wo);
     };
     if (!head_fused) down("LE.down_conv1", fea0, H, W, fea1a, s.H1, s.W1);
     q.resblock("LE.recon_trunk1.0", fea1a, cond2, s.H1, s.W1, l1b, fea1);
-    f16 *fea2a = wsp<f16>(c, "le.fea2a"), *fea2 = wsp<f16>(c, "le.fea2"), *l2b = wsp<f16>(c, "le.l2b");
+    f16 *fea2a = q.wsp<f16>("le.fea2a"), *fea2 = q.wsp<f16>("le.fea2"), *l2b = q.wsp<f16>("le.l2b");
     down("LE.down_conv2", fea1, s.H1, s.W1, fea2a, s.H2, s.W2);
     q.resblock("LE.recon_trunk2.0", fea2a, cond3, s.H2, s.W2, l2b, fea2);
-    f16 *fea3 = wsp<f16>(c, "le.fea3"), *l3b = wsp<f16>(c, "le.l3b"), *t3x = wsp<f16>(c, "le.t3x"), *t3y = wsp<f16>(c, "le.t3y");
+    f16 *fea3 = q.wsp<f16>("le.fea3"), *l3b = q.wsp<f16>("le.l3b"), *t3x = q.wsp<f16>("le.t3x"), *t3y = q.wsp<f16>("le.t3y");
     down("LE.down_conv3", fea2, s.H2, s.W2, fea3, s.H3, s.W3);
     q.resblock("LE.recon_trunk3.0", fea3, cond4, s.H3, s.W3, l3b, t3x);
     q.resblock("LE.recon_trunk3.1", t3x, cond4, s.H3, s.W3, l3b, t3y);
     q.resblock("LE.recon_trunk3.2", t3y, cond4, s.H3, s.W3, l3b, t3x);
     q.resblock("LE.recon_trunk3.3", t3x, cond4, s.H3, s.W3, l3b, t3y, fea3);   // "+ fea3" (line 180) fused as 2nd residual
     // up path: relu(shuffle(conv)) + skip, cropped to the skip's size (_align_to)
-    f16 *up1 = wsp<f16>(c, "le.up1"), *t4 = wsp<f16>(c, "le.t4");
+    f16 *up1 = q.wsp<f16>("le.up1"), *t4 = q.wsp<f16>("le.t4");
     q.conv32("LE.up_conv1.0", t3y, nullptr, "", s.H3, s.W3, ACT_RELU, ST_PS, up1, 32, s.H2, s.W2, fea2);
     q.resblock("LE.recon_trunk4.0", up1, cond3, s.H2, s.W2, l2b, t4);
-    f16 *up2 = wsp<f16>(c, "le.up2"), *t5 = wsp<f16>(c, "le.t5");
+    f16 *up2 = q.wsp<f16>("le.up2"), *t5 = q.wsp<f16>("le.t5");
     q.conv32("LE.up_conv2.0", t4, nullptr, "", s.H2, s.W2, ACT_RELU, ST_PS, up2, 32, s.H1, s.W1, fea1);
     q.resblock("LE.recon_trunk5.0", up2, cond2, s.H1, s.W1, l1b, t5);
-    // the full-resolution tail: one row-streaming launch (le_rows.hip) when the shapes are even and every layer is fp16 or a W8A8
-    // layer the kernel runs as fake-quant, else per layer
-    if (q.ok() && c->var.at("le_rows") && c->var.at("le_rows_i8") && !(H & 1) && !(W & 1) && s.H1 * 2 == H && s.W1 * 2 == W && q.rows_fit(H, W)) {
+    // the full-resolution tail: one row-streaming launch (le_rows.hip) when every layer is fp16 or a W8A8 layer the kernel runs as
+    // fake-quant, else per layer
+    if (q.ok() && rows && c->var.at("le_rows_i8")) {
         // every layer of the tail W8A8 (the full-QAT recipe): the row kernel on int8 MFMA (le_rows_i8.hip), bit-identical to the three
         // per-layer int8 launches at the bottom
         auto qu = c->q32.find("LE.up_conv3.0"), qh = c->q32.find("LE.HR_conv2"), ql = c->q32.find("LE.conv_last");
@@ -583,10 +567,8 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
             qh->second.coutPad == 32 && ql->second.coutPad == 32) {
             RowsTailI8Params p;
             memset(&p, 0, sizeof p);
-            auto cv = [&](const QLayer &Q) { return RowsConvI8{wtp<int8_t>(c, Q.wpk8), wtp<float>(c, Q.scale), wtp<float>(c, Q.shift), Q.q.inv(), Q.q.zoff()}; };
             p.u = t5; p.fea0 = fea0; p.cond = cond1; p.res_planar = img; p.dst_planar = out_planar; p.H = H; p.W = W;
-            p.up = cv(qu->second); p.hr = cv(qh->second); p.last = cv(ql->second);
-            p.s = RowsSftI8{wtp<int8_t>(c, S2.qfrag), wtp<float>(c, S2.qconst), {S2.inv[0], S2.inv[1]}, {S2.zoff[0], S2.zoff[1]}, {S2.hzoff[0], S2.hzoff[1]}};
+            p.up = q.rows_i8(qu->second); p.hr = q.rows_i8(qh->second); p.last = q.rows_i8(ql->second); p.s = q.rows_i8(S2);
             p.slope_relu = act_slope(ACT_RELU);
             p.trash = const_cast<char *>(wtp<char>(c, c->dump_off));
             const double npx = (double)H * W;
@@ -595,7 +577,7 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
             return q.rc;
         }
     }
-    if (q.ok() && c->var.at("le_rows") && !(H & 1) && !(W & 1) && s.H1 * 2 == H && s.W1 * 2 == W && q.rows_fit(H, W)) {
+    if (q.ok() && rows) {
         RowsTailParams p;
         memset(&p, 0, sizeof p);
         bool qu, qh, ql, qs;
@@ -627,73 +609,47 @@ int run_hg(hdrtv_ctx *c, Seq &q, const f16 *base, void *out, int out_f32)
 {
     const Shapes s = shapes_for(c->H, c->W);
     const int Hp = s.Hp, Wp = s.Wp;
-    f16 *img = wsp<f16>(c, "hg.img");
-    uint8_t *mask = wsp<uint8_t>(c, "hg.mask");
+    f16 *img = q.wsp<f16>("hg.img");
+    uint8_t *mask = q.wsp<uint8_t>("hg.mask");
     q.chk(hg_prep_launch(base, s.H, s.W, Hp, Wp, img, mask, c->mask_r, 0.1f, q.s), "hg_prep", "hg_prep", 0.0, 13.0 * Hp * Wp);
-    float *part = wsp<float>(c, "hg.part");
+    float *part = q.wsp<float>("hg.part");
     // conv1: only the pooled map is kept; its kernel also leaves conv10's second half (the 64 -> 3 sums over conv1's channels) per
     // pixel, so the tail is a per-pixel kernel.  Variant final_recompute (developer A/B switch): the tail recomputes conv1
     // instead (hg_final_fused) -- same arithmetic, same results.
     const bool light = !c->var.at("final_recompute");
-    float *part2 = light ? wsp<float>(c, "hg.part2") : nullptr;
+    float *part2 = light ? q.wsp<float>("hg.part2") : nullptr;
     const f16 *w2frag = light ? wtp<f16>(c, c->hgf_wfrag) + 6 * 64 * 8 : nullptr;      // fragments 6..9 of the tail's set
-    if (c->hg_i8) {
-        int8_t *p1q = wsp<int8_t>(c, "hg8.p1");
-        // the fp16 -> int8 boundary costs no pass of its own: conv1 stores the codes its reader conv2 wants
-        q.c3("hg.conv1", img, Hp, Wp, ACT_RELU, nullptr, reinterpret_cast<f16 *>(p1q), c->hg_q0_inv, c->hg_q0_zero, w2frag, part2);
-        // W8A8 checkpoint: conv2 .. conv9 on int8 MFMA, every activation between conv1 and conv9 one int8 tensor
-        int8_t *c2q = wsp<int8_t>(c, "hg8.conv2"), *p3 = wsp<int8_t>(c, "hg8.p3"), *c3 = wsp<int8_t>(c, "hg8.conv3_2"),
-               *p4 = wsp<int8_t>(c, "hg8.p4"), *c4 = wsp<int8_t>(c, "hg8.conv4_2"), *p5 = wsp<int8_t>(c, "hg8.p5"),
-               *c5 = wsp<int8_t>(c, "hg8.conv5_2"), *pc = wsp<int8_t>(c, "hg8.pc"), *code = wsp<int8_t>(c, "hg8.conv_code2"),
-               *u1 = wsp<int8_t>(c, "hg8.up1"), *c6 = wsp<int8_t>(c, "hg8.conv6"), *u2 = wsp<int8_t>(c, "hg8.up2"),
-               *c7 = wsp<int8_t>(c, "hg8.conv7"), *u3 = wsp<int8_t>(c, "hg8.up3"), *c8 = wsp<int8_t>(c, "hg8.conv8"),
-               *u4q = wsp<int8_t>(c, "hg8.up4"), *c9q = wsp<int8_t>(c, "hg8.conv9");
-        q.conv8("hg.conv2", p1q, 64, nullptr, 0, Hp / 2, Wp / 2, ST_NHWC, c2q, 128, Hp / 2, Wp / 2);
-        q.conv8("hg.conv3_1", c2q, 128, nullptr, 0, Hp / 2, Wp / 2, ST_POOL, p3, 256, Hp / 4, Wp / 4);
-        q.conv8("hg.conv3_2", p3, 256, nullptr, 0, Hp / 4, Wp / 4, ST_NHWC, c3, 256, Hp / 4, Wp / 4);
-        q.conv8("hg.conv4_1", c3, 256, nullptr, 0, Hp / 4, Wp / 4, ST_POOL, p4, 512, Hp / 8, Wp / 8);
-        q.conv8("hg.conv4_2", p4, 512, nullptr, 0, Hp / 8, Wp / 8, ST_NHWC, c4, 512, Hp / 8, Wp / 8);
-        q.conv8("hg.conv5_1", c4, 512, nullptr, 0, Hp / 8, Wp / 8, ST_POOL, p5, 512, Hp / 16, Wp / 16);
-        q.conv8("hg.conv5_2", p5, 512, nullptr, 0, Hp / 16, Wp / 16, ST_NHWC, c5, 512, Hp / 16, Wp / 16);
-        q.conv8("hg.conv_code1", c5, 512, nullptr, 0, Hp / 16, Wp / 16, ST_POOL, pc, 512, Hp / 32, Wp / 32);
-        q.conv8("hg.conv_code2", pc, 512, nullptr, 0, Hp / 32, Wp / 32, ST_NHWC, code, 512, Hp / 32, Wp / 32);
-        q.conv8("hg.Up_conv1", code, 512, nullptr, 0, Hp / 32, Wp / 32, ST_PS, u1, 512, Hp / 16, Wp / 16);
-        q.conv8("hg.conv6", u1, 512, c5, 512, Hp / 16, Wp / 16, ST_NHWC, c6, 512, Hp / 16, Wp / 16);
-        q.conv8("hg.Up_conv2", c6, 512, nullptr, 0, Hp / 16, Wp / 16, ST_PS, u2, 512, Hp / 8, Wp / 8);
-        q.conv8("hg.conv7", u2, 512, c4, 512, Hp / 8, Wp / 8, ST_NHWC, c7, 256, Hp / 8, Wp / 8);
-        q.conv8("hg.Up_conv3", c7, 256, nullptr, 0, Hp / 8, Wp / 8, ST_PS, u3, 256, Hp / 4, Wp / 4);
-        q.conv8("hg.conv8", u3, 256, c3, 256, Hp / 4, Wp / 4, ST_NHWC, c8, 128, Hp / 4, Wp / 4);
-        q.conv8("hg.Up_conv4", c8, 128, nullptr, 0, Hp / 4, Wp / 4, ST_PS, u4q, 128, Hp / 2, Wp / 2);
-        q.conv8("hg.conv9", u4q, 128, c2q, 128, Hp / 2, Wp / 2, ST_NHWC, c9q, 64, Hp / 2, Wp / 2);
-        // Up_conv5 -> pixel shuffle -> ReLU -> first half of conv10, fused: 3 partial sums per pixel leave the kernel
-        q.conv8("hg.Up_conv5", c9q, 64, nullptr, 0, Hp / 2, Wp / 2, ST_PS_DOT3, nullptr, 64, Hp, Wp, wtp<float>(c, c->hg_w10a), part);
-    } else {
-        f16 *p1 = wsp<f16>(c, "hg.p1"), *c2 = wsp<f16>(c, "hg.conv2"), *u4 = wsp<f16>(c, "hg.up4"), *c9 = wsp<f16>(c, "hg.conv9");
-        q.c3("hg.conv1", img, Hp, Wp, ACT_RELU, nullptr, p1, 0.f, 0.f, w2frag, part2);
-        q.conv("hg.conv2", p1, 64, nullptr, 0, Hp / 2, Wp / 2, ACT_RELU, ST_NHWC, c2, 128, Hp / 2, Wp / 2);
-        f16 *p3 = wsp<f16>(c, "hg.p3"), *c3 = wsp<f16>(c, "hg.conv3_2"), *p4 = wsp<f16>(c, "hg.p4"), *c4 = wsp<f16>(c, "hg.conv4_2"),
-            *p5 = wsp<f16>(c, "hg.p5"), *c5 = wsp<f16>(c, "hg.conv5_2"), *pc = wsp<f16>(c, "hg.pc"), *code = wsp<f16>(c, "hg.conv_code2");
-        f16 *u1 = wsp<f16>(c, "hg.up1"), *c6 = wsp<f16>(c, "hg.conv6"), *u2 = wsp<f16>(c, "hg.up2"), *c7 = wsp<f16>(c, "hg.conv7"),
-            *u3 = wsp<f16>(c, "hg.up3"), *c8 = wsp<f16>(c, "hg.conv8");
-        q.conv("hg.conv3_1", c2, 128, nullptr, 0, Hp / 2, Wp / 2, ACT_RELU, ST_POOL, p3, 256, Hp / 4, Wp / 4);
-        q.conv("hg.conv3_2", p3, 256, nullptr, 0, Hp / 4, Wp / 4, ACT_RELU, ST_NHWC, c3, 256, Hp / 4, Wp / 4);
-        q.conv("hg.conv4_1", c3, 256, nullptr, 0, Hp / 4, Wp / 4, ACT_RELU, ST_POOL, p4, 512, Hp / 8, Wp / 8);
-        q.conv("hg.conv4_2", p4, 512, nullptr, 0, Hp / 8, Wp / 8, ACT_RELU, ST_NHWC, c4, 512, Hp / 8, Wp / 8);
-        q.conv("hg.conv5_1", c4, 512, nullptr, 0, Hp / 8, Wp / 8, ACT_RELU, ST_POOL, p5, 512, Hp / 16, Wp / 16);
-        q.conv("hg.conv5_2", p5, 512, nullptr, 0, Hp / 16, Wp / 16, ACT_RELU, ST_NHWC, c5, 512, Hp / 16, Wp / 16);
-        q.conv("hg.conv_code1", c5, 512, nullptr, 0, Hp / 16, Wp / 16, ACT_RELU, ST_POOL, pc, 512, Hp / 32, Wp / 32);
-        q.conv("hg.conv_code2", pc, 512, nullptr, 0, Hp / 32, Wp / 32, ACT_RELU, ST_NHWC, code, 512, Hp / 32, Wp / 32);
-        q.conv("hg.Up_conv1", code, 512, nullptr, 0, Hp / 32, Wp / 32, ACT_RELU, ST_PS, u1, 512, Hp / 16, Wp / 16);
-        q.conv("hg.conv6", u1, 512, c5, 512, Hp / 16, Wp / 16, ACT_NONE, ST_NHWC, c6, 512, Hp / 16, Wp / 16);
-        q.conv("hg.Up_conv2", c6, 512, nullptr, 0, Hp / 16, Wp / 16, ACT_RELU, ST_PS, u2, 512, Hp / 8, Wp / 8);
-        q.conv("hg.conv7", u2, 512, c4, 512, Hp / 8, Wp / 8, ACT_NONE, ST_NHWC, c7, 256, Hp / 8, Wp / 8);
-        q.conv("hg.Up_conv3", c7, 256, nullptr, 0, Hp / 8, Wp / 8, ACT_RELU, ST_PS, u3, 256, Hp / 4, Wp / 4);
-        q.conv("hg.conv8", u3, 256, c3, 256, Hp / 4, Wp / 4, ACT_NONE, ST_NHWC, c8, 128, Hp / 4, Wp / 4);
-        q.conv("hg.Up_conv4", c8, 128, nullptr, 0, Hp / 4, Wp / 4, ACT_RELU, ST_PS, u4, 128, Hp / 2, Wp / 2);
-        q.conv("hg.conv9", u4, 128, c2, 128, Hp / 2, Wp / 2, ACT_NONE, ST_NHWC, c9, 64, Hp / 2, Wp / 2);
-        // Up_conv5 -> pixel shuffle -> ReLU -> first half of conv10, fused: 3 partial sums per pixel leave the kernel
-        q.conv("hg.Up_conv5", c9, 64, nullptr, 0, Hp / 2, Wp / 2, ACT_RELU, ST_PS_DOT3, nullptr, 64, Hp, Wp, nullptr, nullptr, nullptr,
-               nullptr, nullptr, wtp<float>(c, c->hg_w10a), part);
+    // the table's tensors, each looked up once: hg.<t>, or (W8A8 checkpoint: conv2 .. conv9 on int8 MFMA) the int8 codes hg8.<t>
+    constexpr int n_layers = (int)(sizeof hg_layers / sizeof hg_layers[0]);
+    const char *tn[3 * n_layers];
+    void *tp[3 * n_layers];
+    int nt = 0;
+    auto tensor = [&](const char *name) -> void * {
+        if (!name) return nullptr;
+        for (int i = 0; i < nt; ++i)
+            if (!strcmp(tn[i], name)) return tp[i];
+        char key[32];
+        snprintf(key, sizeof key, "%s%s", c->hg_i8 ? "hg8." : "hg.", name);
+        tn[nt] = name;
+        tp[nt] = q.wsp<void>(key);
+        return tp[nt++];
+    };
+    // conv1 keeps only its pooled map, conv2's input.  W8A8: the fp16 -> int8 boundary costs no pass of its own, conv1 stores the
+    // codes conv2 wants (hg_q0_inv = 0 for an fp16 HG: no quantiser)
+    q.c3("hg.conv1", img, Hp, Wp, ACT_RELU, nullptr, (f16 *)tensor(hg_layers[0].in), c->hg_q0_inv, c->hg_q0_zero, w2frag, part2);
+    char key[32];
+    for (const HgLayer &L : hg_layers) {
+        snprintf(key, sizeof key, "hg.%s", L.name);
+        const int c1 = L.skip_cin, c0 = L.cin - c1, Hi = Hp >> L.level, Wi = Wp >> L.level;
+        const int Ho = Hp >> L.out_level(), Wo = Wp >> L.out_level();
+        const bool dot3 = L.mode == ST_PS_DOT3;
+        const float *dotw = dot3 ? wtp<float>(c, c->hg_w10a) : nullptr;
+        float *dst_dot = dot3 ? part : nullptr;
+        if (c->hg_i8)
+            q.conv8(key, (const int8_t *)tensor(L.in), c0, (const int8_t *)tensor(L.skip), c1, Hi, Wi, L.mode, tensor(L.out), L.out_c(), Ho, Wo, dotw, dst_dot);
+        else
+            q.conv(key, (const f16 *)tensor(L.in), c0, (const f16 *)tensor(L.skip), c1, Hi, Wi, L.act, L.mode, (f16 *)tensor(L.out), L.out_c(), Ho, Wo,
+                   nullptr, nullptr, nullptr, nullptr, nullptr, dotw, dst_dot);
     }
     if (!q.ok()) return q.rc;
     const C3Layer &L1 = c->c3.at("hg.conv1");

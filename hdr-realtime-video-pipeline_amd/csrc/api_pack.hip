@@ -821,55 +821,30 @@ bool build_weights(hdrtv_ctx *c, const Pack &hr, const Pack *hg)
     if (hg) {
         if (!pack_c3(c, *hg, "hg.conv1", "conv1.0", 64, "conv1.1")) return false;
         c->hg_i8 = hg->has("conv3_1.0.weight_int8");
-        if (!c->hg_i8) {
-            const Spec blocks[] = {{"conv2", 128, 64, 3, 1, 0}, {"conv3_1", 256, 128, 3, 1, 0}, {"conv3_2", 256, 256, 3, 1, 0},
-                                   {"conv4_1", 512, 256, 3, 1, 0}, {"conv4_2", 512, 512, 3, 1, 0}, {"conv5_1", 512, 512, 3, 1, 0},
-                                   {"conv5_2", 512, 512, 3, 1, 0}, {"conv_code1", 512, 512, 3, 1, 0}, {"conv_code2", 512, 512, 3, 1, 0}};
-            for (const Spec &s : blocks)
-                if (!pack_conv(c, *hg, std::string("hg.") + s.name, std::string(s.name) + ".0", s.co, s.ci, 3, 1,
-                               std::string(s.name) + ".1", 0))
-                    return false;
-            const Spec ups[] = {{"Up_conv1", 2048, 512, 3, 1, 512}, {"Up_conv2", 2048, 512, 3, 1, 512}, {"Up_conv3", 1024, 256, 3, 1, 256},
-                                {"Up_conv4", 512, 128, 3, 1, 128}, {"Up_conv5", 256, 64, 3, 1, 64}};
-            for (const Spec &s : ups)
-                if (!pack_conv(c, *hg, std::string("hg.") + s.name, std::string(s.name) + ".0", s.co, s.ci, 3, 1, "", s.ps)) return false;
-            const Spec fuses[] = {{"conv6", 512, 1024, 1, 1, 0}, {"conv7", 256, 1024, 1, 1, 0}, {"conv8", 128, 512, 1, 1, 0},
-                                  {"conv9", 64, 256, 1, 1, 0}};
-            for (const Spec &s : fuses)
-                if (!pack_conv(c, *hg, std::string("hg.") + s.name, s.name, s.co, s.ci, 1, 1, "", 0)) return false;
-        } else {
-            // W8A8 checkpoint (weights.HG_W8A8_GROUPS): conv2 .. Up_conv5 and the fuse convs conv6..9 on int8 MFMA; conv1,
-            // conv10, conv_last stay fp16 (conv1 writes int8 codes of its pooled output, Up_conv5 real-valued partial sums).  A layer's epilogue writes the codes of the layer that
-            // reads its output; tensors read by two layers (encoder skip) or concatenated must share one quantiser.
-            struct Q8 { const char *name; int co, ci, ks, ps; const char *bn; const char *consumer; const char *shares; };
-            const Q8 q8[] = {
-                {"conv2", 128, 64, 3, 0, "conv2.1", "conv3_1.0", "conv9"},
-                {"conv3_1", 256, 128, 3, 0, "conv3_1.1", "conv3_2.0", nullptr}, {"conv3_2", 256, 256, 3, 0, "conv3_2.1", "conv4_1.0", "conv8"},
-                {"conv4_1", 512, 256, 3, 0, "conv4_1.1", "conv4_2.0", nullptr}, {"conv4_2", 512, 512, 3, 0, "conv4_2.1", "conv5_1.0", "conv7"},
-                {"conv5_1", 512, 512, 3, 0, "conv5_1.1", "conv5_2.0", nullptr}, {"conv5_2", 512, 512, 3, 0, "conv5_2.1", "conv_code1.0", "conv6"},
-                {"conv_code1", 512, 512, 3, 0, "conv_code1.1", "conv_code2.0", nullptr},
-                {"conv_code2", 512, 512, 3, 0, "conv_code2.1", "Up_conv1.0", nullptr},
-                {"Up_conv1", 2048, 512, 3, 512, "", "conv6", nullptr}, {"conv6", 512, 1024, 1, 0, "", "Up_conv2.0", nullptr},
-                {"Up_conv2", 2048, 512, 3, 512, "", "conv7", nullptr}, {"conv7", 256, 1024, 1, 0, "", "Up_conv3.0", nullptr},
-                {"Up_conv3", 1024, 256, 3, 256, "", "conv8", nullptr}, {"conv8", 128, 512, 1, 0, "", "Up_conv4.0", nullptr},
-                {"Up_conv4", 512, 128, 3, 128, "", "conv9", nullptr}, {"conv9", 64, 256, 1, 0, "", "Up_conv5.0", nullptr},
-                {"Up_conv5", 256, 64, 3, 64, "", nullptr, nullptr}};
-            for (const Q8 &L : q8) {
-                ActQ out;
-                if (L.consumer && !read_actq(c, *hg, L.consumer, out)) return false;
-                if (L.shares) {
-                    ActQ o2;
-                    if (!read_actq(c, *hg, L.shares, o2)) return false;
-                    if (o2.scale != out.scale || o2.kf != out.kf) {
-                        c->err = std::string("W8A8 HG: ") + L.consumer + " and " + L.shares + " read one tensor and must share x_scale / x_zero";
-                        return false;
-                    }
-                }
-                const bool relu = L.ks == 3;       // conv blocks and Up blocks end in ReLU
-                const std::string wname = L.ks == 3 ? std::string(L.name) + ".0" : std::string(L.name);
-                if (!pack_conv_i8(c, *hg, std::string("hg.") + L.name, wname, L.co, L.ci, L.ks, L.bn, L.ps, out, relu)) return false;
+        // W8A8 checkpoint (weights.HG_W8A8_GROUPS): conv2 .. Up_conv5 and the fuse convs conv6..9 on int8 MFMA; conv1, conv10,
+        // conv_last stay fp16 (conv1 writes int8 codes of its pooled output, Up_conv5 real-valued partial sums).  A layer's epilogue
+        // writes the codes of the layer that reads its output; tensors read by two layers (encoder skip) or concatenated must share
+        // one quantiser.
+        for (const HgLayer &L : hg_layers) {
+            const std::string key = std::string("hg.") + L.name, wname = L.ks == 3 ? std::string(L.name) + ".0" : std::string(L.name);
+            if (!c->hg_i8) {
+                if (!pack_conv(c, *hg, key, wname, L.cout, L.cin, L.ks, 1, L.bn, L.ps)) return false;
+                continue;
             }
-            ActQ q0;                       // the fp16 -> int8 boundary: conv1's pooled output, read by conv2
+            ActQ out;
+            if (L.consumer && !read_actq(c, *hg, L.consumer, out)) return false;
+            if (L.shares) {
+                ActQ o2;
+                if (!read_actq(c, *hg, L.shares, o2)) return false;
+                if (o2.scale != out.scale || o2.kf != out.kf) {
+                    c->err = std::string("W8A8 HG: ") + L.consumer + " and " + L.shares + " read one tensor and must share x_scale / x_zero";
+                    return false;
+                }
+            }
+            if (!pack_conv_i8(c, *hg, key, wname, L.cout, L.cin, L.ks, L.bn, L.ps, out, L.act == ACT_RELU)) return false;
+        }
+        if (c->hg_i8) {
+            ActQ q0;                   // the fp16 -> int8 boundary: conv1's pooled output, read by conv2
             if (!read_actq(c, *hg, "conv2.0", q0)) return false;
             c->hg_q0_inv = 1.f / q0.scale;
             c->hg_q0_zero = (float)(q0.kf - 128.0);

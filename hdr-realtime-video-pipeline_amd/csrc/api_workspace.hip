@@ -73,13 +73,12 @@ void free_workspaces(hdrtv_ctx *c)
     for (unsigned char *p : c->lane_ws)
         if (p) (void)hipFree(p);
     c->lane_ws.clear();
-    c->ws.dev = nullptr;
     c->H = c->W = 0;
 }
 
 int do_reserve(hdrtv_ctx *c, int H, int W)
 {
-    if (c->H == H && c->W == W && c->ws.dev) return HDRTV_OK;
+    if (c->H == H && c->W == W && !c->lane_ws.empty()) return HDRTV_OK;
     if (H < 8 || W < 8 || H > 16384 || W > 16384) return fail(c, HDRTV_EINVAL, "unsupported frame size %dx%d", W, H);
     const Shapes s = shapes_for(H, W);
     // InstanceNorm2d needs more than one spatial element at the 4th classifier block (the reference raises
@@ -152,29 +151,13 @@ int do_reserve(hdrtv_ctx *c, int H, int W)
         ws_add(c, "hg.img", 3, Hp, Wp, 1); ws_add(c, "hg.mask", 1, Hp, Wp, 4);
         ws_add(c, "hg.part", 4, Hp, Wp, 3);
         ws_add(c, "hg.part2", 4, Hp, Wp, 3);        // conv10's second half (over conv1), left by conv1's kernel
-        if (!c->hg_i8) {
-            ws_add(c, "hg.p1", 64, Hp / 2, Wp / 2, 0);
-            ws_add(c, "hg.conv2", 128, Hp / 2, Wp / 2, 0); ws_add(c, "hg.up4", 128, Hp / 2, Wp / 2, 0);
-            ws_add(c, "hg.p3", 256, Hp / 4, Wp / 4, 0); ws_add(c, "hg.conv3_2", 256, Hp / 4, Wp / 4, 0);
-            ws_add(c, "hg.p4", 512, Hp / 8, Wp / 8, 0); ws_add(c, "hg.conv4_2", 512, Hp / 8, Wp / 8, 0);
-            ws_add(c, "hg.p5", 512, Hp / 16, Wp / 16, 0); ws_add(c, "hg.conv5_2", 512, Hp / 16, Wp / 16, 0);
-            ws_add(c, "hg.pc", 512, Hp / 32, Wp / 32, 0); ws_add(c, "hg.conv_code2", 512, Hp / 32, Wp / 32, 0);
-            ws_add(c, "hg.up1", 512, Hp / 16, Wp / 16, 0); ws_add(c, "hg.conv6", 512, Hp / 16, Wp / 16, 0);
-            ws_add(c, "hg.up2", 512, Hp / 8, Wp / 8, 0); ws_add(c, "hg.conv7", 256, Hp / 8, Wp / 8, 0);
-            ws_add(c, "hg.up3", 256, Hp / 4, Wp / 4, 0); ws_add(c, "hg.conv8", 128, Hp / 4, Wp / 4, 0);
-        } else {            // W8A8: the same tensors as int8 codes (q - 128), each once
-            ws_add(c, "hg8.p1", 64, Hp / 2, Wp / 2, 5);
-            ws_add(c, "hg8.conv2", 128, Hp / 2, Wp / 2, 5); ws_add(c, "hg8.up4", 128, Hp / 2, Wp / 2, 5);
-            ws_add(c, "hg8.conv9", 64, Hp / 2, Wp / 2, 5);
-            ws_add(c, "hg8.p3", 256, Hp / 4, Wp / 4, 5); ws_add(c, "hg8.conv3_2", 256, Hp / 4, Wp / 4, 5);
-            ws_add(c, "hg8.p4", 512, Hp / 8, Wp / 8, 5); ws_add(c, "hg8.conv4_2", 512, Hp / 8, Wp / 8, 5);
-            ws_add(c, "hg8.p5", 512, Hp / 16, Wp / 16, 5); ws_add(c, "hg8.conv5_2", 512, Hp / 16, Wp / 16, 5);
-            ws_add(c, "hg8.pc", 512, Hp / 32, Wp / 32, 5); ws_add(c, "hg8.conv_code2", 512, Hp / 32, Wp / 32, 5);
-            ws_add(c, "hg8.up1", 512, Hp / 16, Wp / 16, 5); ws_add(c, "hg8.conv6", 512, Hp / 16, Wp / 16, 5);
-            ws_add(c, "hg8.up2", 512, Hp / 8, Wp / 8, 5); ws_add(c, "hg8.conv7", 256, Hp / 8, Wp / 8, 5);
-            ws_add(c, "hg8.up3", 256, Hp / 4, Wp / 4, 5); ws_add(c, "hg8.conv8", 128, Hp / 4, Wp / 4, 5);
-        }
-        if (!c->hg_i8) ws_add(c, "hg.conv9", 64, Hp / 2, Wp / 2, 0);
+        // conv2's input (conv1's pooled map) and every layer's output: NHWC f16, or (W8A8) the same tensors as int8 codes (q - 128)
+        const char *pre = c->hg_i8 ? "hg8." : "hg.";
+        const int layout = c->hg_i8 ? 5 : 0;
+        const HgLayer &L0 = hg_layers[0];
+        ws_add(c, pre + std::string(L0.in), L0.cin - L0.skip_cin, Hp >> L0.level, Wp >> L0.level, layout);
+        for (const HgLayer &L : hg_layers)
+            if (L.out) ws_add(c, pre + std::string(L.out), L.out_c(), Hp >> L.out_level(), Wp >> L.out_level(), layout);
     }
     }
     // one workspace per lane (hdrtv_set_lanes): lane 0 is initialised, the others start as copies of it
@@ -185,15 +168,14 @@ int do_reserve(hdrtv_ctx *c, int H, int W)
             free_workspaces(c);
             return fail(c, HDRTV_ENOMEM, "workspace allocation of %d x %zu bytes failed", c->lanes, c->ws.size);
         }
-    c->ws.dev = c->lane_ws[0];
-    hipError_t e = hipMemset(c->ws.dev, 0, c->ws.size + 4096);
+    hipError_t e = hipMemset(c->lane_ws[0], 0, c->ws.size + 4096);
     auto up = [&](const char *name, const void *src, size_t bytes) {
-        if (e == hipSuccess) e = hipMemcpy(wsp<char>(c, name), src, bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(wsp<char>(c, c->lane_ws[0], name), src, bytes, hipMemcpyHostToDevice);
     };
     up("aa.wx", wx.data(), wx.size() * 4); up("aa.wy", wy.data(), wy.size() * 4);
     up("aa.xmn", xmn.data(), xmn.size() * 4); up("aa.xns", xns.data(), xns.size() * 4);
     up("aa.ymn", ymn.data(), ymn.size() * 4); up("aa.yns", yns.data(), yns.size() * 4);
-    for (int l = 1; l < c->lanes && e == hipSuccess; ++l) e = hipMemcpy(c->lane_ws[l], c->ws.dev, c->ws.size + 4096, hipMemcpyDeviceToDevice);
+    for (int l = 1; l < c->lanes && e == hipSuccess; ++l) e = hipMemcpy(c->lane_ws[l], c->lane_ws[0], c->ws.size + 4096, hipMemcpyDeviceToDevice);
     if (e != hipSuccess) {                 // leave no half-initialised workspace behind a size that looks reserved
         free_workspaces(c);
         return fail(c, HDRTV_EHIP, "workspace initialisation failed: %s", hipGetErrorString(e));

@@ -108,7 +108,7 @@ struct F32Run {
             else if (it->second.C != C || it->second.H != H || it->second.W != W) { fprintf(stderr, "hdrtv: fp32 plan: %s re-declared with another shape\n", name.c_str()); abort(); }
             return t;
         }
-        t.p = wsp<float>(c, name);
+        t.p = q->wsp<float>(name);
         return t;
     }
     // scratch shared by every use of the same shape (the stream orders them)

@@ -128,27 +128,27 @@ int hdrtv_reserve(hdrtv_ctx *c, int H, int W)
 int hdrtv_preprocess(hdrtv_ctx *c, void *stream, const uint8_t *bgr, int H, int W, void *rgb, void *cond)
 {
     if (!c || !bgr || !rgb || !cond) return fail(c, HDRTV_EINVAL, "null argument");
-    if (c->H != H || c->W != W || !c->ws.dev) return fail(c, HDRTV_ESTATE, "call hdrtv_reserve(%d,%d) first", H, W);
+    if (c->H != H || c->W != W || c->lane_ws.empty()) return fail(c, HDRTV_ESTATE, "call hdrtv_reserve(%d,%d) first", H, W);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    Seq q{c, s};
+    Seq q{c, s, c->lane_ws[0]};          // the resize tables: do_reserve uploads them to lane 0 only
     const Shapes sh = shapes_for(H, W);
     if (c->fp32) {                       // precision="fp32": rgb / cond are fp32 tensors
-        q.chk(pre_f32_launch(bgr, (float *)rgb, (float *)cond, H, W, sh.h4, sh.w4, wsp<float>(c, "aa.wx"), wsp<int>(c, "aa.xmn"),
-                             wsp<int>(c, "aa.xns"), wsp<float>(c, "aa.wy"), wsp<int>(c, "aa.ymn"), wsp<int>(c, "aa.yns"),
+        q.chk(pre_f32_launch(bgr, (float *)rgb, (float *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
+                             q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"),
                              c->cond_mode, s), "pre_f32");
         return q.rc;
     }
     const bool split = c->var.at("pre_split") != 0;                       // developer A/B: the two-kernel form
     if (H / 4 >= 1 && W / 4 >= 1 && !(split && c->cond_mode == 0)) {
-        q.chk(pre_fused_launch(bgr, (f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, wsp<float>(c, "aa.wx"), wsp<int>(c, "aa.xmn"),
-                               wsp<int>(c, "aa.xns"), wsp<float>(c, "aa.wy"), wsp<int>(c, "aa.ymn"), wsp<int>(c, "aa.yns"), c->cond_mode, s),
+        q.chk(pre_fused_launch(bgr, (f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
+                               q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"), c->cond_mode, s),
               "pre_fused");
         return q.rc;
     }
     q.chk(pre_unpack_launch(bgr, (f16 *)rgb, H, W, s), "pre_unpack");
-    q.chk(cond_resize_launch((const f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, wsp<float>(c, "aa.wx"), wsp<int>(c, "aa.xmn"),
-                             wsp<int>(c, "aa.xns"), wsp<float>(c, "aa.wy"), wsp<int>(c, "aa.ymn"), wsp<int>(c, "aa.yns"), s),
+    q.chk(cond_resize_launch((const f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
+                             q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"), s),
           "cond_resize");
     return q.rc;
 }
@@ -168,7 +168,7 @@ int hdrtv_set_lanes(hdrtv_ctx *c, int lanes)
     if (lanes < 1 || lanes > (lifted ? 4 : 2)) return fail(c, HDRTV_EINVAL, "lanes must be 1 or 2");
     if (lanes > 1 && c->fp32 && !lifted) return fail(c, HDRTV_EINVAL, "the fp32 preset runs one frame at a time (one lane)");
     if (lanes == c->lanes) return HDRTV_OK;
-    if (c->ws.dev) {                      // the reservation goes with the old lane count
+    if (!c->lane_ws.empty()) {            // the reservation goes with the old lane count
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, hipDeviceSynchronize());
         free_workspaces(c);
@@ -189,27 +189,21 @@ int hdrtv_infer_lane(hdrtv_ctx *c, int lane, void *stream, const void *rgb, cons
                      void *agcm_out)
 {
     if (!c || !rgb || !cond || !out) return fail(c, HDRTV_EINVAL, "null argument");
-    if (c->H != H || c->W != W || !c->ws.dev) return fail(c, HDRTV_ESTATE, "call hdrtv_reserve(%d,%d) first", H, W);
+    if (c->H != H || c->W != W || c->lane_ws.empty()) return fail(c, HDRTV_ESTATE, "call hdrtv_reserve(%d,%d) first", H, W);
     if (lane < 0 || lane >= c->lanes) return fail(c, HDRTV_EINVAL, "lane %d of %d (hdrtv_set_lanes)", lane, c->lanes);
-    // every workspace tensor of this call resolves inside the lane's buffer; taps and hdrtv_preprocess's tables stay on lane 0
-    struct LaneScope {
-        hdrtv_ctx *c;
-        LaneScope(hdrtv_ctx *c_, int l) : c(c_) { c->ws.dev = c->lane_ws[(size_t)l]; }
-        ~LaneScope() { c->ws.dev = c->lane_ws[0]; }
-    } lane_scope(c, lane);
     if (out_dtype != HDRTV_F16 && out_dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "bad out_dtype");
     if (c->fp32 && out_dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "an fp32 context takes and returns f32 tensors");
     if (!c->fp32 && !c->has_hg && out_dtype != HDRTV_F16) return fail(c, HDRTV_EINVAL, "the no-HG model returns f16");
     HIPCHK(c, hipSetDevice(c->device));
-    Seq q{c, (hipStream_t)stream};
+    Seq q{c, (hipStream_t)stream, c->lane_ws[(size_t)lane]};   // every workspace tensor of this call lies in the lane's buffer
     c->launches = 0;
     c->macs = 0.0;
     c->prof.clear();
     q.mark();
     if (c->fp32) return run_f32(c, q, false, H, W, (const float *)rgb, (const float *)cond, (float *)out, (float *)agcm_out);
-    f16 *agcm = agcm_out ? (f16 *)agcm_out : wsp<f16>(c, "agcm.out");
+    f16 *agcm = agcm_out ? (f16 *)agcm_out : q.wsp<f16>("agcm.out");
     if (run_agcm(c, q, (const f16 *)rgb, (const f16 *)cond, agcm) != HDRTV_OK) return q.rc;
-    f16 *le_out = c->has_hg ? wsp<f16>(c, "le.out") : (f16 *)out;
+    f16 *le_out = c->has_hg ? q.wsp<f16>("le.out") : (f16 *)out;
     if (run_le(c, q, agcm, le_out) != HDRTV_OK) return q.rc;
     if (c->has_hg && run_hg(c, q, le_out, out, out_dtype == HDRTV_F32) != HDRTV_OK) return q.rc;
     return q.rc;
@@ -568,8 +562,8 @@ int hdrtv_get_tap(hdrtv_ctx *c, const char *name, void **dev_ptr, int *C, int *H
 {
     if (!c || !name) return HDRTV_EINVAL;
     auto it = c->t.find(name);
-    if (it == c->t.end() || !c->ws.dev) return fail(c, HDRTV_EINVAL, "no tap named %s", name);
-    if (dev_ptr) *dev_ptr = c->ws.dev + it->second.off;
+    if (it == c->t.end() || c->lane_ws.empty()) return fail(c, HDRTV_EINVAL, "no tap named %s", name);
+    if (dev_ptr) *dev_ptr = c->lane_ws[0] + it->second.off;      // taps read lane 0
     if (C) *C = it->second.C;
     if (H) *H = it->second.H;
     if (W) *W = it->second.W;
