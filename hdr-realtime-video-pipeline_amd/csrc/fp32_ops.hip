@@ -12,6 +12,7 @@
 // Both accumulate in the order (input channel, tap) from zero and add the bias behind the sum.
 #include "common.h"
 #include "launchers.h"
+#include "yuv420.h"
 
 namespace {
 
@@ -520,6 +521,15 @@ hipError_t pre_f32_launch(const uint8_t *bgr, float *rgb, float *cond, int H, in
                           const int *xmn, const int *xns, const float *wy, const int *ymn, const int *yns, int mode, hipStream_t s)
 {
     hipLaunchKernelGGL(pre_unpack_f32_kernel, ew_grid_f32((size_t)H * W), dim3(256), 0, s, bgr, rgb, (size_t)H * W);
+    hipLaunchKernelGGL(cond_resize_f32_kernel, ew_grid_f32((size_t)3 * Ho * Wo), dim3(256), 0, s, rgb, cond, H, W, Ho, Wo, wx, xmn,
+                       xns, wy, ymn, yns, mode);
+    return hipGetLastError();
+}
+
+// the condition-map half of pre_f32_launch on its own: the fp32 preset's YUV route (yuv420.h) unpacks with its own kernel
+hipError_t cond_resize_f32_launch(const float *rgb, float *cond, int H, int W, int Ho, int Wo, const float *wx, const int *xmn,
+                                  const int *xns, const float *wy, const int *ymn, const int *yns, int mode, hipStream_t s)
+{
     hipLaunchKernelGGL(cond_resize_f32_kernel, ew_grid_f32((size_t)3 * Ho * Wo), dim3(256), 0, s, rgb, cond, H, W, Ho, Wo, wx, xmn,
                        xns, wy, ymn, yns, mode);
     return hipGetLastError();

@@ -2,6 +2,7 @@
 // the RGB48 ring, letterbox / metrics / PQ tables.  Packing, workspace and launch sequencing are their own translation units
 // (api.h).  No kernel lives in this file.
 #include "api.h"
+#include "yuv420.h"
 
 using namespace hdrtv_host;
 // =========================================================================== exported C ABI
@@ -150,6 +151,61 @@ int hdrtv_preprocess(hdrtv_ctx *c, void *stream, const uint8_t *bgr, int H, int 
     q.chk(cond_resize_launch((const f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
                              q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"), s),
           "cond_resize");
+    return q.rc;
+}
+
+// The argument rule of both YUV entry points (include/hdrtv_mi355x.h); fills `src` on success.
+static int yuv_args(hdrtv_ctx *c, const uint8_t *y, int y_pitch, const uint8_t *u, const uint8_t *v, int c_pitch, int layout,
+                    int matrix, int full_range, int H, int W, Yuv420Src *src)
+{
+    if (!y || !u) return fail(c, HDRTV_EINVAL, "yuv420: null plane");
+    if (layout != HDRTV_YUV_I420 && layout != HDRTV_YUV_NV12) return fail(c, HDRTV_EINVAL, "yuv420: unknown layout %d", layout);
+    if (layout == HDRTV_YUV_I420 && !v) return fail(c, HDRTV_EINVAL, "yuv420: I420 needs the Cr plane");
+    if (layout == HDRTV_YUV_NV12 && v) return fail(c, HDRTV_EINVAL, "yuv420: NV12 takes dev_v = NULL (CbCr interleaved in dev_u)");
+    if (H <= 0 || W <= 0 || (H & 1) || (W & 1)) return fail(c, HDRTV_EINVAL, "yuv420: frame %dx%d is not even-sized", W, H);
+    if (y_pitch < W) return fail(c, HDRTV_EINVAL, "yuv420: luma pitch %d < width %d", y_pitch, W);
+    const int cw = layout == HDRTV_YUV_NV12 ? W : W / 2;
+    if (c_pitch < cw) return fail(c, HDRTV_EINVAL, "yuv420: chroma pitch %d < %d", c_pitch, cw);
+    YuvCoef k;
+    if (!yuv_coef(matrix, full_range, &k)) return fail(c, HDRTV_EINVAL, "yuv420: matrix %d / range %d (601, 709, 2020; 0 or 1)", matrix, full_range);
+    *src = Yuv420Src{y, u, v, y_pitch, c_pitch, layout, k};
+    return HDRTV_OK;
+}
+
+int hdrtv_yuv420_to_bgr_u8(hdrtv_ctx *c, void *stream, const uint8_t *y, int y_pitch, const uint8_t *u, const uint8_t *v, int c_pitch,
+                           int layout, int matrix, int full_range, int H, int W, uint8_t *bgr)
+{
+    if (!c || !bgr) return fail(c, HDRTV_EINVAL, "null argument");
+    Yuv420Src src;
+    if (const int rc = yuv_args(c, y, y_pitch, u, v, c_pitch, layout, matrix, full_range, H, W, &src)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const hipError_t e = yuv420_to_bgr_launch(src, H, W, bgr, (hipStream_t)stream);
+    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "yuv420_to_bgr: %s", hipGetErrorString(e));
+}
+
+int hdrtv_preprocess_yuv420(hdrtv_ctx *c, void *stream, const uint8_t *y, int y_pitch, const uint8_t *u, const uint8_t *v, int c_pitch,
+                            int layout, int matrix, int full_range, int H, int W, void *rgb, void *cond)
+{
+    if (!c || !rgb || !cond) return fail(c, HDRTV_EINVAL, "null argument");
+    Yuv420Src src;
+    if (const int rc = yuv_args(c, y, y_pitch, u, v, c_pitch, layout, matrix, full_range, H, W, &src)) return rc;
+    if (c->H != H || c->W != W || c->lane_ws.empty()) return fail(c, HDRTV_ESTATE, "call hdrtv_reserve(%d,%d) first", H, W);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    Seq q{c, s, c->lane_ws[0]};          // lane 0's resize tables, as hdrtv_preprocess
+    const Shapes sh = shapes_for(H, W);
+    if (c->fp32) {                       // pre_f32_launch's two steps, the unpack reading the planes
+        q.chk(pre_unpack_yuv_f32_launch(src, H, W, (float *)rgb, s), "pre_unpack_yuv_f32");
+        q.chk(cond_resize_f32_launch((const float *)rgb, (float *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
+                                     q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"),
+                                     c->cond_mode, s), "cond_resize_f32");
+        return q.rc;
+    }
+    // hdrtv_reserve's 8 x 8 minimum puts every reserved size on the fused kernel's ground (H / 4, W / 4 >= 1); the pre_split
+    // developer variant (the two-kernel BGR form, bit-identical to pre_fused) has no YUV counterpart
+    q.chk(pre_fused_yuv_launch(src, (f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
+                               q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"), c->cond_mode, s),
+          "pre_fused_yuv");
     return q.rc;
 }
 

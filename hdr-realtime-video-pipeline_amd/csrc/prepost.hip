@@ -10,6 +10,9 @@
 // accesses, so every wave instruction moves whole cache lines.  Quantisers use __fmul_rn /
 // __fadd_rn: the reference rounds the multiply and the add separately.
 #include "launchers.h"
+#include "yuv420.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -115,11 +118,100 @@ __global__ __launch_bounds__(256) void cond_resize_kernel(const f16 *__restrict_
 constexpr int PF_OW = 32, PF_OH = 8, PF_IW = 140, PF_IH = 44, PF_ROWDW = 107;   // 107 dwords cover 420 B at any alignment
 constexpr int PF_PITCH = 144;
 
-__global__ __launch_bounds__(256) void pre_fused_kernel(const uint8_t *__restrict__ bgr, f16 *__restrict__ out, f16 *__restrict__ cond,
-                                                        int H, int W, int Ho, int Wo, const float *__restrict__ wx,
-                                                        const int *__restrict__ xmn, const int *__restrict__ xns,
-                                                        const float *__restrict__ wy, const int *__restrict__ ymn,
-                                                        const int *__restrict__ yns, int mode)
+// The staging step of pre_fused is its template argument: it fills s_in[c][r][q] (c = R, G, B) with fp16(float(u8) * fp32(1/255))
+// of patch pixel (ix0 + q, iy0 + r), for every r with iy0 + r < H and q with ix0 + q < W.  Everything after it is shared.
+//  PfBgr      u8 HWC BGR, the staging written out in the kernel body (its instruction sequence is that of the kernel before the
+//             template: an inlined helper let hipcc pick another division sequence for e / PF_ROWDW)
+//  Yuv420Src  I420 / NV12 planes: pf_stage below, the conversion rule of yuv420.h
+typedef const uint8_t *__restrict__ PfBgr;
+
+// YUV staging.  Byte staging area: the horizontal pass's s_h (17.4 KB, unused until the barrier after staging), so the kernel's LDS
+// and occupancy are those of the BGR form.  It holds the luma patch (44 rows x 140 bytes, pitch 144) and the chroma rows and columns
+// that cover it with a one-sample halo, clamped at the frame edge: up to 25 rows x 72 samples per plane (I420: Cb at bytes 0..71 of
+// a 144-byte row, Cr at 72..143; NV12: the CbCr pairs as they lie in memory).  Loads are whole aligned dwords that hold at least one
+// byte of the segment (never a dword past a segment's last byte, whatever the plane's alignment and pitch); bytes outside it are
+// dropped.  Then each patch pixel is converted once, two horizontally adjacent pixels (one chroma column) per item.
+constexpr int PFY_PITCH = 144, PFY_DW = 36;              // 36 dwords cover 140 B at any alignment
+constexpr int PFC_ROWS = 25, PFC_PITCH = 144, PFC_W = 72; // chroma rows / samples a patch needs at most (odd iy0 / ix0)
+constexpr int PFC_DW1 = 19, PFC_DW2 = 37;                // dwords covering 72 B (an I420 plane row) / 144 B (an NV12 row)
+
+__device__ __forceinline__ void pf_stage(const Yuv420Src &src, f16 (*s_in)[PF_IH][PF_PITCH], uint8_t *scratch, int tid, int H, int W,
+                                         int ix0, int iy0)
+{
+    uint8_t *s_y = scratch, *s_c = scratch + PF_IH * PFY_PITCH;
+    const bool nv12 = src.layout == YUV_NV12;
+    const int Hc = H >> 1, Wc = W >> 1;
+    const int ylast = min(iy0 + PF_IH, H) - 1, xlast = min(ix0 + PF_IW, W) - 1;
+    const int jlo = max((iy0 >> 1) - 1, 0), jhi = min((ylast >> 1) + 1, Hc - 1);
+    const int ilo = ix0 >> 1, ihi = min((xlast >> 1) + 1, Wc - 1);
+    const int ylen = xlast - ix0 + 1, clen = (ihi - ilo + 1) << (nv12 ? 1 : 0);
+    const int cdw = nv12 ? PFC_DW2 : PFC_DW1, nc = nv12 ? PFC_ROWS * PFC_DW2 : 2 * PFC_ROWS * PFC_DW1;
+    constexpr int NY = PF_IH * PFY_DW;
+    constexpr int NLD = (NY + 2 * PFC_ROWS * PFC_DW1 + 255) / 256;      // >= the NV12 count (25 x 37 < 2 x 25 x 19)
+    uint32_t word[NLD];
+    int rel[NLD], dst[NLD];                              // rel: byte offset of the dword from its segment's start (< -3: skip)
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+        const int e = tid + 256 * i;
+        const uint8_t *seg = nullptr;
+        int len = 0, d = 0;
+        dst[i] = 0;
+        if (e < NY) {
+            const int r = e / PFY_DW;
+            d = e - r * PFY_DW;
+            if (iy0 + r < H) { seg = src.y + (size_t)(iy0 + r) * src.y_pitch + ix0; len = ylen; dst[i] = r * PFY_PITCH; }
+        } else if (e < NY + nc) {
+            const int e2 = e - NY, plane = e2 / (PFC_ROWS * cdw), e3 = e2 - plane * (PFC_ROWS * cdw), rr = e3 / cdw;
+            d = e3 - rr * cdw;
+            if (jlo + rr <= jhi) {
+                seg = (plane ? src.v : src.u) + (size_t)(jlo + rr) * src.c_pitch + (ilo << (nv12 ? 1 : 0));
+                len = clen;
+                dst[i] = PF_IH * PFY_PITCH + rr * PFC_PITCH + plane * PFC_W;
+            }
+        }
+        const uintptr_t a = ((uintptr_t)seg & ~(uintptr_t)3) + 4 * (uintptr_t)d;
+        const bool ok = seg != nullptr && a < (uintptr_t)seg + len;
+        rel[i] = ok ? (int)(a - (uintptr_t)seg) : -1000;
+        word[i] = ok ? *reinterpret_cast<const uint32_t *>(a) : 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int b = rel[i] + k;
+            if (b >= 0 && b < (tid + 256 * i < NY ? ylen : clen)) scratch[dst[i] + b] = (uint8_t)(word[i] >> (8 * k));
+        }
+    }
+    __syncthreads();
+    const int cs = nv12 ? 2 : 1, co = nv12 ? 1 : PFC_W;
+    const float k255 = (float)(1.0 / 255.0);
+    for (int e = tid; e < PF_IH * PFC_W; e += 256) {
+        const int r = e / PFC_W, p = e - r * PFC_W;
+        const int y = iy0 + r, i = ilo + p, q0 = 2 * i - ix0;
+        if (y >= H || i > ihi) continue;          // (i <= ihi: a chroma column the patch uses)
+        const int j = y >> 1, n = (y & 1) ? min(j + 1, Hc - 1) : max(j - 1, 0), i2 = min(i + 1, Wc - 1);
+        const uint8_t *cj = s_c + (j - jlo) * PFC_PITCH, *cn = s_c + (n - jlo) * PFC_PITCH;
+        const int k1 = cs * p, k2 = cs * (i2 - ilo);
+        const int u4a = 3 * cj[k1] + cn[k1], u4b = 3 * cj[k2] + cn[k2];
+        const int v4a = 3 * cj[k1 + co] + cn[k1 + co], v4b = 3 * cj[k2 + co] + cn[k2 + co];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int q = q0 + h;
+            if (q < 0 || q >= PF_IW || ix0 + q >= W) continue;
+            uint32_t R, G, B;
+            yuv_rule(s_y[r * PFY_PITCH + q], h ? u4a + u4b : 2 * u4a, h ? v4a + v4b : 2 * v4a, src.k, R, G, B);
+            s_in[0][r][q] = (f16)__fmul_rn((float)R, k255);
+            s_in[1][r][q] = (f16)__fmul_rn((float)G, k255);
+            s_in[2][r][q] = (f16)__fmul_rn((float)B, k255);
+        }
+    }
+}
+
+template <typename Src>
+__global__ __launch_bounds__(256) void pre_fused_kernel(const Src src, f16 *__restrict__ out, f16 *__restrict__ cond, int H, int W,
+                                                        int Ho, int Wo, const float *__restrict__ wx, const int *__restrict__ xmn,
+                                                        const int *__restrict__ xns, const float *__restrict__ wy,
+                                                        const int *__restrict__ ymn, const int *__restrict__ yns, int mode)
 {
     __shared__ __attribute__((aligned(16))) f16 s_in[3][PF_IH][PF_PITCH];     // 288-byte rows: 16-byte reads at columns 8k
     __shared__ float s_h[3][PF_IH][PF_OW + 1];
@@ -138,43 +230,47 @@ __global__ __launch_bounds__(256) void pre_fused_kernel(const uint8_t *__restric
     }
     if (tid < PF_OW) { const bool in = ox0 + tid < Wo; s_xb[tid] = in ? xmn[ox0 + tid] - ix0 : 0; s_xn[tid] = in ? xns[ox0 + tid] : 0; }
     if (tid >= 64 && tid < 64 + PF_OH) { const int o = tid - 64; const bool in = oy0 + o < Ho; s_yb[o] = in ? ymn[oy0 + o] - iy0 : 0; s_yn[o] = in ? yns[oy0 + o] : 0; }
-    const size_t total = (size_t)H * W * 3;
-    const float k255 = (float)(1.0 / 255.0);
-    // all of this thread's dword loads first (19 independent loads in flight), then the byte unpacking: a loop that loads and
-    // unpacks one dword at a time pays one HBM round trip per dword
-    constexpr int NLD = (PF_IH * PF_ROWDW + 255) / 256;
-    uint32_t word[NLD];
-    long rel[NLD];                                     // byte offset of the dword's first byte from its row segment's start; < -3: skip
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-        const int e = tid + 256 * i;
-        const int r = e / PF_ROWDW, d = e - r * PF_ROWDW;
-        const int iy = iy0 + r;
-        const size_t row0 = ((size_t)(iy < H ? iy : 0) * W + ix0) * 3;
-        const size_t addr = (row0 & ~(size_t)3) + 4 * (size_t)d;
-        const bool ok = e < PF_IH * PF_ROWDW && iy < H && addr < total;
-        rel[i] = ok ? (long)addr - (long)row0 : -1000;
-        word[i] = 0;
-        if (ok) {
-            if (addr + 4 <= total) {
-                word[i] = *reinterpret_cast<const uint32_t *>(bgr + addr);
-            } else {
-                for (size_t k = 0; addr + k < total; ++k) word[i] |= (uint32_t)bgr[addr + k] << (8 * k);
+    if constexpr (std::is_same<Src, PfBgr>::value) {
+        const size_t total = (size_t)H * W * 3;
+        const float k255 = (float)(1.0 / 255.0);
+        // all of this thread's dword loads first (19 independent loads in flight), then the byte unpacking: a loop that loads and
+        // unpacks one dword at a time pays one HBM round trip per dword
+        constexpr int NLD = (PF_IH * PF_ROWDW + 255) / 256;
+        uint32_t word[NLD];
+        long rel[NLD];                                     // byte offset of the dword's first byte from its row segment's start; < -3: skip
+    #pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int e = tid + 256 * i;
+            const int r = e / PF_ROWDW, d = e - r * PF_ROWDW;
+            const int iy = iy0 + r;
+            const size_t row0 = ((size_t)(iy < H ? iy : 0) * W + ix0) * 3;
+            const size_t addr = (row0 & ~(size_t)3) + 4 * (size_t)d;
+            const bool ok = e < PF_IH * PF_ROWDW && iy < H && addr < total;
+            rel[i] = ok ? (long)addr - (long)row0 : -1000;
+            word[i] = 0;
+            if (ok) {
+                if (addr + 4 <= total) {
+                    word[i] = *reinterpret_cast<const uint32_t *>(src + addr);
+                } else {
+                    for (size_t k = 0; addr + k < total; ++k) word[i] |= (uint32_t)src[addr + k] << (8 * k);
+                }
             }
         }
-    }
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-        const int e = tid + 256 * i;
-        const int r = e / PF_ROWDW;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int b = (int)rel[i] + k;
-            if (b >= 0 && b < PF_IW * 3) {
-                const int q = (b * 683) >> 11, ch = b - 3 * q;             // b / 3 for b < 600
-                if (ix0 + q < W) s_in[2 - ch][r][q] = (f16)__fmul_rn((float)((word[i] >> (8 * k)) & 0xff), k255);
+    #pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int e = tid + 256 * i;
+            const int r = e / PF_ROWDW;
+    #pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int b = (int)rel[i] + k;
+                if (b >= 0 && b < PF_IW * 3) {
+                    const int q = (b * 683) >> 11, ch = b - 3 * q;             // b / 3 for b < 600
+                    if (ix0 + q < W) s_in[2 - ch][r][q] = (f16)__fmul_rn((float)((word[i] >> (8 * k)) & 0xff), k255);
+                }
             }
         }
+    } else {
+        pf_stage(src, s_in, reinterpret_cast<uint8_t *>(&s_h[0][0][0]), tid, H, W, ix0, iy0);
     }
     __syncthreads();
     // ---- the pixels this tile owns -> f16 planes.  The last tile of a row / column also owns the W % 4 (H % 4) remainder.
@@ -498,7 +594,18 @@ hipError_t pre_fused_launch(const uint8_t *bgr, f16 *out, f16 *cond, int H, int 
 {
     if (Ho != H / 4 || Wo != W / 4 || Ho < 1 || Wo < 1) return hipErrorInvalidValue;
     dim3 grid((Wo + PF_OW - 1) / PF_OW, (Ho + PF_OH - 1) / PF_OH, 1);
-    hipLaunchKernelGGL(pre_fused_kernel, grid, dim3(256), 0, s, bgr, out, cond, H, W, Ho, Wo, wx, xmn, xns, wy, ymn, yns, mode);
+    hipLaunchKernelGGL(pre_fused_kernel<PfBgr>, grid, dim3(256), 0, s, bgr, out, cond, H, W, Ho, Wo, wx, xmn, xns, wy, ymn, yns, mode);
+    return hipGetLastError();
+}
+
+hipError_t pre_fused_yuv_launch(const Yuv420Src &src, f16 *out, f16 *cond, int H, int W, int Ho, int Wo, const float *wx,
+                                const int *xmn, const int *xns, const float *wy, const int *ymn, const int *yns, int mode,
+                                hipStream_t s)
+{
+    if (Ho != H / 4 || Wo != W / 4 || Ho < 1 || Wo < 1 || (H & 1) || (W & 1)) return hipErrorInvalidValue;
+    dim3 grid((Wo + PF_OW - 1) / PF_OW, (Ho + PF_OH - 1) / PF_OH, 1);
+    hipLaunchKernelGGL(pre_fused_kernel<Yuv420Src>, grid, dim3(256), 0, s, src, out, cond, H, W, Ho, Wo, wx, xmn, xns, wy, ymn, yns,
+                       mode);
     return hipGetLastError();
 }
 

@@ -56,6 +56,7 @@ class _Mi355xWorker:
     stream (and activation workspace: a lane) per frame in flight."""
 
     depth = 2
+    input_format = ("bgr24", 709, False)     # (pix_fmt, matrix, full_range); _worker_main sets the dispatcher's
 
     def __init__(self, rank, device_index, init_args):
         import ctypes as C
@@ -99,21 +100,21 @@ class _Mi355xWorker:
                                "pageable transfers")
         self._registered = ptr
 
-    def _buffers(self, h, w):
+    def _buffers(self, h, w, in_shape):
         torch = self._torch
-        if self._hw != (h, w):
+        if self._hw != (h, w, in_shape):
             self.proc._ensure_buffers(h, w)
-            self._raw = [torch.empty((h, w, 3), dtype=torch.uint8, device=self.dev) for _ in range(self.depth)]
+            self._raw = [torch.empty(in_shape, dtype=torch.uint8, device=self.dev) for _ in range(self.depth)]
             self._u16 = [torch.empty((h, w, 3), dtype=torch.uint16, device=self.dev) for _ in range(self.depth)]
             self._up_ev = [torch.cuda.Event() for _ in range(self.depth)]
             self._comp_ev = [None] * self.depth
             self._dn_ev = [None] * self.depth
-            self._hw = (h, w)
+            self._hw = (h, w, in_shape)
 
     def begin(self, frame, out):
         torch, p = self._torch, self.proc
-        h, w = frame.shape[:2]
-        self._buffers(h, w)
+        h, w = out.shape[:2]                  # a 4:2:0 input slot is (h*3//2, w)
+        self._buffers(h, w, frame.shape)
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
         # frame's kernels with the next frame's (processor.enqueue_frame); one lane = the single compute stream of before
@@ -129,7 +130,12 @@ class _Mi355xWorker:
         main.wait_event(self._up_ev[k])
         if self._dn_ev[k] is not None:
             main.wait_event(self._dn_ev[k])                    # u16[k]'s previous frame has left the device
-        p.enqueue_frame(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), stream=main)
+        if self.input_format[0] == "bgr24":
+            p.enqueue_frame(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), stream=main)
+        else:
+            fmt, matrix, full = self.input_format
+            p.enqueue_frame_yuv420(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), layout=fmt, matrix=matrix,
+                                   full_range=full, stream=main)
         self._comp_ev[k] = torch.cuda.Event()
         self._comp_ev[k].record(main)
         self._dn.wait_event(self._comp_ev[k])
@@ -181,7 +187,7 @@ class _HostSimWorker:
             self._result = np.empty(out.shape, out.dtype)
             self._result[...] = 257 * (self.rank + 1)
         np.copyto(self._staged, frame)                     # "H2D": the slot's 24.9 MB (4K) leave host memory
-        self._result[0, 0, 0] = int(frame[0, 0, 0]) * 257  # (so that a test can tell the frames apart)
+        self._result[0, 0, 0] = int(frame.flat[0]) * 257   # (so that a test can tell the frames apart; 3-D BGR or 2-D 4:2:0)
         self._result[0, 0, 1] = self.rank
         start = max(time.perf_counter(), self._busy_until)
         self._busy_until = start + self.device_ms * 1e-3   # the device works on one frame at a time
@@ -222,12 +228,14 @@ class _SyncBody:
         return None
 
 
-def _worker_main(rank, device_index, make_worker, init_args, geom, task_q, done_q, use_numa, shm_name=None):
+def _worker_main(rank, device_index, make_worker, init_args, geom, task_q, done_q, use_numa, shm_name=None, input_format=None):
     shm, ins, outs, body = None, None, None, None
     code = 0
     try:
         h, w, slots = geom
-        in_b, out_b = h * w * 3, h * w * 6
+        input_format = tuple(input_format or ("bgr24", 709, False))
+        in_shape = _in_shape(h, w, input_format[0])
+        in_b, out_b = int(np.prod(in_shape)), h * w * 6
         # placement first: affinity, then the slots (created and first-touched HERE, on the GPU's node), then the GPU
         from . import numa
         info = numa.pin_to_gpu_node(device_index, apply=bool(use_numa)) if use_numa is not None else {"device": device_index, "numa_node": -1, "cpus": [], "pinned": False}
@@ -245,9 +253,11 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, task_q, done_
         body = make_worker(rank, device_index, init_args)
         if not hasattr(body, "begin"):
             body = _SyncBody(body)
+        if input_format[0] != "bgr24" and hasattr(body, "input_format"):
+            body.input_format = input_format
         if hasattr(body, "pin"):
             body.pin(shm.buf)
-        ins = [np.ndarray((h, w, 3), np.uint8, shm.buf, offset=s * in_b) for s in range(slots)]
+        ins = [np.ndarray(in_shape, np.uint8, shm.buf, offset=s * in_b) for s in range(slots)]
         outs = [np.ndarray((h, w, 3), np.uint16, shm.buf, offset=slots * in_b + s * out_b) for s in range(slots)]
         depth = max(1, int(getattr(body, "depth", 1)))
         free_out = list(range(slots))
@@ -321,18 +331,35 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, task_q, done_
         raise SystemExit(code)
 
 
+def _in_shape(h, w, pix_fmt):
+    """An input slot's frame: u8 BGR (h, w, 3), or the planes of a 4:2:0 frame back to back (h*3//2, w)."""
+    return (h, w, 3) if pix_fmt == "bgr24" else (h * 3 // 2, w)
+
+
 class FrameDispatcher:
     def __init__(self, n_workers, height, width, sink, make_worker=mi355x_worker, init_args=None, devices=None, slots=3,
-                 start_timeout=600.0, numa=True):
+                 start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False):
         """``sink(index, rgb48_view)`` is called in index order from the reorder thread; the view is only valid during the
         call (the slot goes back to its worker afterwards).  ``numa``: workers pin themselves to their GPU's NUMA node
-        (False: report only)."""
+        (False: report only).  ``pix_fmt``: ``bgr24`` input frames are u8 (H, W, 3); ``yuv420p`` / ``nv12`` frames are u8
+        (H*3//2, W), the planes back to back (half the slot bytes and copies), which the product's worker converts on the device
+        with ``yuv_matrix`` / ``yuv_full_range`` (``HDRTVNetMI355X.enqueue_frame_yuv420``); stand-in workers receive them as they
+        are.  Output slots, order and sink do not depend on it."""
         if n_workers < 1 or slots < 2:
             raise ValueError("n_workers >= 1 and slots >= 2")
+        if pix_fmt not in ("bgr24", "yuv420p", "nv12"):
+            raise ValueError("pix_fmt must be bgr24, yuv420p or nv12")
+        if pix_fmt != "bgr24" and (int(height) % 2 or int(width) % 2):
+            raise ValueError(f"{pix_fmt} frames have even sizes")
+        if int(yuv_matrix) not in (601, 709, 2020):
+            raise ValueError("yuv_matrix must be 601, 709 or 2020")
         self.n, self.h, self.w, self.slots = int(n_workers), int(height), int(width), int(slots)
+        self.pix_fmt = pix_fmt
+        self._in_shape = _in_shape(self.h, self.w, pix_fmt)
+        fmt = (pix_fmt, int(yuv_matrix), bool(yuv_full_range))
         self._sink = sink
         ctx = mp.get_context("spawn")           # fresh interpreters: nothing GPU-related is inherited
-        self._in_b, self._out_b = self.h * self.w * 3, self.h * self.w * 6
+        self._in_b, self._out_b = int(np.prod(self._in_shape)), self.h * self.w * 6
         self._shm = [None] * self.n             # created by the workers (first touch on their GPU's node), attached below
         # ... under names chosen HERE, so that close() can unlink a segment whose worker died between creating it and saying so
         self._shm_names = [f"hdrtv_{os.getpid()}_{uuid.uuid4().hex[:12]}_{r}" for r in range(self.n)]
@@ -343,7 +370,7 @@ class FrameDispatcher:
         self._stop = False
         self._procs = [ctx.Process(target=_worker_main, daemon=True,
                                    args=(r, devices[r], make_worker, dict(init_args or {}),
-                                         (self.h, self.w, self.slots), self._task[r], self._done, bool(numa), self._shm_names[r]))
+                                         (self.h, self.w, self.slots), self._task[r], self._done, bool(numa), self._shm_names[r], fmt))
                        for r in range(self.n)]
         for p in self._procs:
             p.start()
@@ -381,7 +408,7 @@ class FrameDispatcher:
                 self._shm[rank] = shared_memory.SharedMemory(name=name)
                 self.placement[rank] = payload
                 buf = self._shm[rank].buf
-                self._ins[rank] = [np.ndarray((self.h, self.w, 3), np.uint8, buf, offset=s * self._in_b) for s in range(self.slots)]
+                self._ins[rank] = [np.ndarray(self._in_shape, np.uint8, buf, offset=s * self._in_b) for s in range(self.slots)]
                 self._outs[rank] = [np.ndarray((self.h, self.w, 3), np.uint16, buf, offset=self.slots * self._in_b + s * self._out_b)
                                     for s in range(self.slots)]
                 continue

@@ -17,6 +17,7 @@ LIB_PATH_AB = os.path.join(os.path.dirname(_PKG), "lib", "libhdrtv_mi355x_ab.so"
 OK, EINVAL, EWEIGHTS, EHIP, ENOMEM, ESTATE = 0, -1, -2, -3, -4, -5
 F16, F32 = 0, 1
 PREC_F16, PREC_F32 = 0, 1
+YUV_I420, YUV_NV12 = 0, 1                  # hdrtv_yuv420_to_bgr_u8 / hdrtv_preprocess_yuv420 layouts
 
 # every symbol include/hdrtv_mi355x.h declares: (name, restype, argtypes)
 _VP, _I, _SZ = C.c_void_p, C.c_int, C.c_size_t
@@ -38,6 +39,8 @@ SYMBOLS = [
     ("hdrtv_post_rgb48", _I, [_VP, _VP, _VP, _I, _I, _I, _VP]),
     ("hdrtv_post_pq_rgb48", _I, [_VP, _VP, _VP, _I, _I, _I, C.c_float, _VP]),
     ("hdrtv_letterbox_u8", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I]),
+    ("hdrtv_yuv420_to_bgr_u8", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
+    ("hdrtv_preprocess_yuv420", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP]),
     ("hdrtv_metrics", _I, [_VP, _VP, _VP, _VP, _I, _I, _I, C.c_float, C.POINTER(C.c_double)]),
     ("hdrtv_ring_create", _I, [_VP, _I, _I, _I]),
     ("hdrtv_ring_acquire", _I, [_VP, _I, C.POINTER(_VP), C.POINTER(_VP)]),

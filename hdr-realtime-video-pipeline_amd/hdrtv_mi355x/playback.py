@@ -59,7 +59,7 @@ class SyntheticSource:
 
 
 class PinnedFrame(np.ndarray):
-    """A u8 BGR frame that lives in page-locked memory; ``pinned_tensor`` is the torch tensor sharing it
+    """A u8 BGR (or 4:2:0, ``(H*3//2, W)``) frame that lives in page-locked memory; ``pinned_tensor`` is the torch tensor sharing it
     (HDRTVNetMI355X.preprocess uploads such a frame without the host-side copy into its own pinned slot).  When the
     prefetcher has already uploaded it, ``device_tensor`` is the device copy and ``ready_event`` the event recorded
     behind that upload on the prefetcher's stream."""
@@ -84,6 +84,8 @@ class PinnedPrefetch:
         self._error = None
         self.width, self.height, self.fps = source.width, source.height, source.fps
         self.frame_count = getattr(source, "frame_count", 0)
+        self.pix_fmt = getattr(source, "pix_fmt", "bgr24")
+        self.yuv_matrix, self.yuv_full_range = getattr(source, "yuv_matrix", 709), getattr(source, "yuv_full_range", False)
         self._pool_n = max(3, int(pool))
         self._bufs = {}
         self._q = queue.Queue(maxsize=1)
@@ -133,7 +135,7 @@ class PinnedPrefetch:
         while not self._stop.is_set():
             ret, frame = self._src.read()
             item = (False, None)
-            if ret and frame is not None and frame.dtype == np.uint8 and frame.ndim == 3:
+            if ret and frame is not None and frame.dtype == np.uint8 and frame.ndim in (2, 3):      # BGR or 4:2:0 planes
                 item = (True, self._stage(frame, i))
                 i += 1
             elif ret:
@@ -165,16 +167,32 @@ class PinnedPrefetch:
 
 
 class RawVideoSource:
-    """Headerless ``bgr24`` rawvideo file (what ``ffmpeg -f rawvideo -pix_fmt bgr24`` writes), memory-mapped."""
+    """Headerless rawvideo file (what ``ffmpeg -f rawvideo -pix_fmt <pix_fmt>`` writes), memory-mapped.  ``pix_fmt``:
+    ``bgr24`` frames are u8 ``(H, W, 3)``; ``yuv420p`` (I420) and ``nv12`` frames are u8 ``(H*3//2, W)``, the planes back to back
+    (``HDRTVNetMI355X.preprocess_yuv420``), even sizes only.  ``yuv_matrix`` (601 / 709 / 2020) and ``yuv_full_range`` say how
+    the 4:2:0 frames convert to RGB (the stream's ``color_space`` / ``color_range``)."""
 
-    def __init__(self, path, width, height, fps):
+    PIX_FMTS = ("bgr24", "yuv420p", "nv12")
+
+    def __init__(self, path, width, height, fps, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False):
         self.width, self.height, self.fps = int(width), int(height), float(fps)
-        fb = self.width * self.height * 3
+        if pix_fmt not in self.PIX_FMTS:
+            raise ValueError(f"pix_fmt must be one of {self.PIX_FMTS}")
+        if int(yuv_matrix) not in (601, 709, 2020):
+            raise ValueError("yuv_matrix must be 601, 709 or 2020")
+        self.pix_fmt, self.yuv_matrix, self.yuv_full_range = pix_fmt, int(yuv_matrix), bool(yuv_full_range)
+        if pix_fmt == "bgr24":
+            shape = (self.height, self.width, 3)
+        else:
+            if self.width % 2 or self.height % 2:
+                raise ValueError(f"{pix_fmt} frames have even sizes (got {self.width}x{self.height})")
+            shape = (self.height * 3 // 2, self.width)
+        fb = int(np.prod(shape))
         size = os.path.getsize(path)
         if size < fb or size % fb:
-            raise ValueError(f"{path}: size {size} is not a whole number of {self.width}x{self.height} bgr24 frames")
+            raise ValueError(f"{path}: size {size} is not a whole number of {self.width}x{self.height} {pix_fmt} frames")
         self.frame_count = size // fb
-        self._mm = np.memmap(path, dtype=np.uint8, mode="r", shape=(self.frame_count, self.height, self.width, 3))
+        self._mm = np.memmap(path, dtype=np.uint8, mode="r", shape=(self.frame_count,) + shape)
         self._i = 0
 
     def read(self):
@@ -296,6 +314,9 @@ class RealtimePlayback:
         # optional ground-truth HDR frames ([3,H,W] or [1,3,H,W] unit-range tensors from ``gt_source.read()``): every
         # ``objective_every``-th processed frame is scored on the device (gui_pipeline_worker_objective.py role)
         self.gt_source, self.objective_every = gt_source, max(1, int(objective_every))
+        # a 4:2:0 source (RawVideoSource pix_fmt yuv420p / nv12): the worker converts its 2-D frames on the device
+        if getattr(source, "pix_fmt", "bgr24") != "bgr24" and hasattr(worker, "set_input_format"):
+            worker.set_input_format(source.pix_fmt, getattr(source, "yuv_matrix", 709), getattr(source, "yuv_full_range", False))
         self._objective = {"psnr_db": None, "sssim": None, "delta_e_itp": None}
         self._pending_precision = None
         self._pending_resolution = None
@@ -495,7 +516,7 @@ class RealtimePlayback:
 
 
 def main(argv=None):
-    """``python -m hdrtv_mi355x.playback``: synthetic (or bgr24 rawvideo) source -> worker -> rgb48le sink."""
+    """``python -m hdrtv_mi355x.playback``: synthetic (or bgr24 / yuv420p / nv12 rawvideo) source -> worker -> rgb48le sink."""
     import argparse
     import json
 
@@ -507,7 +528,10 @@ def main(argv=None):
     ap.add_argument("--size", default="3840x2160")
     ap.add_argument("--fps", type=float, default=60.0)
     ap.add_argument("--frames", type=int, default=240)
-    ap.add_argument("--input", help="bgr24 rawvideo file at --size (default: synthetic frames)")
+    ap.add_argument("--input", help="rawvideo file at --size in --pix-fmt (default: synthetic frames)")
+    ap.add_argument("--pix-fmt", choices=RawVideoSource.PIX_FMTS, default="bgr24", help="pixel format of --input")
+    ap.add_argument("--yuv-matrix", type=int, choices=(601, 709, 2020), default=709, help="Y'CbCr matrix of a yuv420p / nv12 input")
+    ap.add_argument("--yuv-range", choices=("limited", "full"), default="limited", help="Y'CbCr range of a yuv420p / nv12 input")
     ap.add_argument("--out", help="rgb48le rawvideo output (file or fifo); omit to run without a display sink")
     ap.add_argument("--no-hg", action="store_true")
     ap.add_argument("--hg-weights", default=None, help="HG weight file, or seeded:<n>")
@@ -517,7 +541,12 @@ def main(argv=None):
     ap.add_argument("--csv")
     a = ap.parse_args(argv)
     wd, ht = (int(v) for v in a.size.lower().split("x", 1))
-    src = RawVideoSource(a.input, wd, ht, a.fps) if a.input else SyntheticSource(wd, ht, a.fps, a.frames)
+    if a.input:
+        src = RawVideoSource(a.input, wd, ht, a.fps, pix_fmt=a.pix_fmt, yuv_matrix=a.yuv_matrix, yuv_full_range=a.yuv_range == "full")
+    elif a.pix_fmt != "bgr24":
+        ap.error("--pix-fmt applies to an --input file")
+    else:
+        src = SyntheticSource(wd, ht, a.fps, a.frames)
     if not a.no_prefetch:
         src = PinnedPrefetch(src)
     worker = HeadlessPipelineWorker(a.weights_dir, use_hg=not a.no_hg, proc_w=wd, proc_h=ht, hg_weights=a.hg_weights,

@@ -338,6 +338,22 @@ class HDRTVNetMI355X:
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
         self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, tout.data_ptr(), dt, h, w, dst_rgb48_ptr), "hdrtv_post_rgb48")
 
+    def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None):
+        """``enqueue_frame`` of an 8-bit 4:2:0 frame: the planes lie back to back at the device address ``src_ptr`` (the
+        ``(h*3//2, w)`` u8 array ``preprocess_yuv420`` takes) and ``hdrtv_preprocess_yuv420`` replaces ``hdrtv_preprocess``."""
+        if not 0 <= lane < self._lanes:
+            raise ValueError(f"lane {lane} of {self._lanes}")
+        planes = _yuv_planes(src_ptr, int(h), int(w), layout, matrix, full_range)
+        self._ensure_buffers(h, w)
+        st = C.c_void_p((stream if stream is not None else self._lane_streams[lane]).cuda_stream)
+        tin, tcond, tout, tagcm = self._lane_bufs[lane]
+        dt = _L.F32 if (self._use_hg or self._fp32) else _L.F16
+        self._chk(self._lib.hdrtv_preprocess_yuv420(self._ctx, st, *planes, h, w, tin.data_ptr(), tcond.data_ptr()),
+                  "hdrtv_preprocess_yuv420")
+        self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), dt,
+                                             tagcm.data_ptr()), "hdrtv_infer_lane")
+        self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, tout.data_ptr(), dt, h, w, dst_rgb48_ptr), "hdrtv_post_rgb48")
+
     # ------------------------------------------------------------------ API
     @torch.inference_mode()
     def preprocess(self, frame_bgr):
@@ -394,6 +410,63 @@ class HDRTVNetMI355X:
                                                self._gpu_raw.data_ptr(), out_h, out_w), "hdrtv_letterbox_u8")
         self._chk(self._lib.hdrtv_preprocess(self._ctx, self._stream(), self._gpu_raw.data_ptr(), out_h, out_w,
                                              self._gpu_input.data_ptr(), self._gpu_cond.data_ptr()), "hdrtv_preprocess")
+        return self._gpu_input, self._gpu_cond
+
+    def _yuv_upload(self, frame):
+        """Device pointer of an 8-bit 4:2:0 frame ``(H*3//2, W)`` u8, uploaded through a lazily allocated pinned slot (or the
+        prefetcher's own upload / pinned buffer, as ``preprocess`` uses them) -> (ptr, H, W)."""
+        h, w = _yuv_frame_hw(frame)
+        shape = (h * 3 // 2, w)
+        dev_copy, ready = getattr(frame, "device_tensor", None), getattr(frame, "ready_event", None)
+        if dev_copy is not None and ready is not None and dev_copy.device == self.device and tuple(dev_copy.shape) == shape:
+            torch.cuda.current_stream(self.device).wait_event(ready)
+            return dev_copy.data_ptr(), h, w
+        if getattr(self, "_yuv_shape", None) != shape:          # the BGR path's buffers stay as they are
+            self._yuv_pin = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
+            self._yuv_dev = torch.empty(shape, dtype=torch.uint8, device=self.device)
+            self._yuv_shape = shape
+        staged = getattr(frame, "pinned_tensor", None)
+        if staged is not None and staged.is_pinned() and tuple(staged.shape) == shape:
+            self._yuv_dev.copy_(staged, non_blocking=True)
+        else:
+            src = np.ascontiguousarray(frame)
+            C.memmove(self._yuv_pin.data_ptr(), src.ctypes.data, src.nbytes)
+            self._yuv_dev.copy_(self._yuv_pin, non_blocking=True)
+        return self._yuv_dev.data_ptr(), h, w
+
+    @torch.inference_mode()
+    def preprocess_yuv420(self, frame, *, layout="i420", matrix=709, full_range=False):
+        """``preprocess`` of an 8-bit 4:2:0 frame: ``frame`` is u8 ``(H*3//2, W)``, the planes back to back as ``ffmpeg -f
+        rawvideo -pix_fmt yuv420p`` (``layout="i420"``) or ``nv12`` writes them.  The conversion to RGB (include/hdrtv_mi355x.h:
+        ``matrix`` 601 / 709 / 2020, limited or ``full_range``) runs inside the preprocess kernel; the result equals
+        ``preprocess`` of the converted BGR frame bit for bit.  Returns the same processor-owned ``(tensor, cond)``."""
+        ptr, h, w = self._yuv_upload(frame)
+        planes = _yuv_planes(ptr, h, w, layout, matrix, full_range)
+        self._ensure_buffers(h, w)
+        self._chk(self._lib.hdrtv_preprocess_yuv420(self._ctx, self._stream(), *planes, h, w, self._gpu_input.data_ptr(),
+                                                    self._gpu_cond.data_ptr()), "hdrtv_preprocess_yuv420")
+        return self._gpu_input, self._gpu_cond
+
+    @torch.inference_mode()
+    def preprocess_yuv420_letterboxed(self, frame, out_w, out_h, *, layout="i420", matrix=709, full_range=False):
+        """``preprocess_letterboxed`` of an 8-bit 4:2:0 frame: converted to BGR on the device at the source size
+        (``hdrtv_yuv420_to_bgr_u8``), then ``hdrtv_letterbox_u8`` and ``hdrtv_preprocess``."""
+        sh, sw = _yuv_frame_hw(frame)
+        out_w, out_h = int(out_w), int(out_h)
+        if (sw, sh) == (out_w, out_h):
+            return self.preprocess_yuv420(frame, layout=layout, matrix=matrix, full_range=full_range)
+        ptr, _, _ = self._yuv_upload(frame)
+        planes = _yuv_planes(ptr, sh, sw, layout, matrix, full_range)
+        self._ensure_buffers(out_h, out_w)
+        if getattr(self, "_yuv_bgr_shape", None) != (sh, sw):
+            self._yuv_bgr = torch.empty((sh, sw, 3), dtype=torch.uint8, device=self.device)
+            self._yuv_bgr_shape = (sh, sw)
+        st = self._stream()
+        self._chk(self._lib.hdrtv_yuv420_to_bgr_u8(self._ctx, st, *planes, sh, sw, self._yuv_bgr.data_ptr()), "hdrtv_yuv420_to_bgr_u8")
+        self._chk(self._lib.hdrtv_letterbox_u8(self._ctx, st, self._yuv_bgr.data_ptr(), sh, sw, self._gpu_raw.data_ptr(), out_h, out_w),
+                  "hdrtv_letterbox_u8")
+        self._chk(self._lib.hdrtv_preprocess(self._ctx, st, self._gpu_raw.data_ptr(), out_h, out_w, self._gpu_input.data_ptr(),
+                                             self._gpu_cond.data_ptr()), "hdrtv_preprocess")
         return self._gpu_input, self._gpu_cond
 
     @torch.inference_mode()
@@ -486,6 +559,12 @@ class HDRTVNetMI355X:
     @torch.inference_mode()
     def process(self, frame_bgr):
         tensor, cond = self.preprocess(frame_bgr)
+        return self.postprocess(self.infer((tensor, cond)))
+
+    @torch.inference_mode()
+    def process_yuv420(self, frame, *, layout="i420", matrix=709, full_range=False):
+        """``process`` of an 8-bit 4:2:0 frame (``preprocess_yuv420``): u8 BGR out, as ``process``."""
+        tensor, cond = self.preprocess_yuv420(frame, layout=layout, matrix=matrix, full_range=full_range)
         return self.postprocess(self.infer((tensor, cond)))
 
     @torch.inference_mode()
@@ -635,6 +714,31 @@ def _arch_hr():
 
 
 _hip = None
+
+
+YUV_LAYOUTS = {"i420": _L.YUV_I420, "yuv420p": _L.YUV_I420, "nv12": _L.YUV_NV12}
+
+
+def _yuv_frame_hw(frame):
+    """(H, W) of an 8-bit 4:2:0 frame held as a u8 ``(H*3//2, W)`` array; H and W even."""
+    if frame.ndim != 2 or frame.dtype != np.uint8 or frame.shape[0] % 3:
+        raise ValueError("a 4:2:0 frame must be uint8 [H*3//2, W]")
+    h, w = frame.shape[0] // 3 * 2, frame.shape[1]
+    if h % 2 or w % 2 or h <= 0:
+        raise ValueError(f"4:2:0 frames have even sizes (got {w}x{h})")
+    return h, w
+
+
+def _yuv_planes(ptr, h, w, layout, matrix, full_range):
+    """The plane arguments of hdrtv_yuv420_to_bgr_u8 / hdrtv_preprocess_yuv420 for a frame whose planes lie back to back at
+    device address ``ptr``: (y, y_pitch, u, v, c_pitch, layout, matrix, full_range)."""
+    code = YUV_LAYOUTS.get(str(layout).lower())
+    if code is None:
+        raise ValueError(f"layout must be one of {sorted(YUV_LAYOUTS)}")
+    u = ptr + h * w
+    if code == _L.YUV_NV12:
+        return ptr, w, u, None, w, code, int(matrix), int(bool(full_range))
+    return ptr, w, u, u + (h // 2) * (w // 2), w // 2, code, int(matrix), int(bool(full_range))
 
 
 def _hip_memcpy_d2d(dst, src, nbytes):

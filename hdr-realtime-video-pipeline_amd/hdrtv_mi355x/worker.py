@@ -128,6 +128,14 @@ class HeadlessPipelineWorker:
         self._hdr_error = None             # exception that ended the feeder thread, re-raised by _process_frame
         self._fallback = None              # (pinned host u16 tensor, device u16 tensor) of the ring-exhaustion fallback
         self.ring_fallbacks = 0
+        self._yuv_format = dict(layout="i420", matrix=709, full_range=False)     # how 2-D (4:2:0) frames convert
+
+    def set_input_format(self, pix_fmt, yuv_matrix=709, yuv_full_range=False):
+        """How ``_process_frame`` reads a 2-D u8 frame ``(H*3//2, W)``: ``pix_fmt`` ``yuv420p`` or ``nv12``, the matrix and the
+        range of ``HDRTVNetMI355X.preprocess_yuv420``.  3-D frames are BGR whatever is set here."""
+        if pix_fmt not in ("yuv420p", "nv12"):
+            raise ValueError("pix_fmt must be yuv420p or nv12")
+        self._yuv_format = dict(layout=pix_fmt, matrix=int(yuv_matrix), full_range=bool(yuv_full_range))
 
     # ---------------------------------------------------------------- status
     def _emit(self, msg):
@@ -238,7 +246,14 @@ class HeadlessPipelineWorker:
         start.record(torch.cuda.current_stream())
         pw, ph = int(proc_w or self._proc_w), int(proc_h or self._proc_h)
         with torch.inference_mode():
-            if frame.shape[1] != pw or frame.shape[0] != ph:
+            if frame.ndim == 2:
+                # 8-bit 4:2:0 planes: converted on the device (set_input_format), letterboxed there when the sizes differ
+                fh = frame.shape[0] // 3 * 2
+                if frame.shape[1] != pw or fh != ph:
+                    tensor, cond = self._processor.preprocess_yuv420_letterboxed(frame, pw, ph, **self._yuv_format)
+                else:
+                    tensor, cond = self._processor.preprocess_yuv420(frame, **self._yuv_format)
+            elif frame.shape[1] != pw or frame.shape[0] != ph:
                 # the reference letterboxes on the host with cv2 before preprocess (gui_export.py:1080,
                 # gui_scaling.py:228-244); here the resize runs on the device
                 tensor, cond = self._processor.preprocess_letterboxed(frame, pw, ph)

@@ -135,6 +135,37 @@ int hdrtv_post_pq_rgb48(hdrtv_ctx *ctx, void *stream, const void *dev_out, int d
 int hdrtv_letterbox_u8(hdrtv_ctx *ctx, void *stream, const uint8_t *dev_src_bgr, int sh, int sw,
                        uint8_t *dev_dst_bgr, int dh, int dw);
 
+/* 8-bit 4:2:0 Y'CbCr input, the host step in front of preprocess on the device: what decoders hand out (ffmpeg yuv420p = I420,
+ * a hardware decoder's NV12), 1.5 bytes per pixel.  H and W even; chroma planes Hc = H/2 rows by Wc = W/2 samples.
+ *   I420: dev_y, dev_u (Cb), dev_v (Cr); y_pitch >= W, c_pitch >= W/2 (both planes share c_pitch).
+ *   NV12: dev_y and dev_u = the interleaved CbCr plane (Cb at byte 2i, Cr at 2i+1), dev_v = NULL; c_pitch >= W.
+ * Pitches are in bytes; no plane start or pitch needs any alignment.  matrix: 601, 709 or 2020 (BT.2020 non-constant
+ * luminance); full_range: 0 limited (Y' 16..235), 1 full.  BT.709 limited is the usual choice for HD / UHD SDR video.
+ * Parity with a decoder's own conversion (swscale behind cv2.VideoCapture) is UNPINNED; the conversion is this integer rule:
+ *  1. chroma upsampling, MPEG-2 / H.264 siting (horizontally co-sited, vertically centred), per chroma plane C:
+ *       luma row y:    j = y>>1; n = (y odd) ? min(j+1, Hc-1) : max(j-1, 0); V4[i] = 3*C[j][i] + C[n][i]
+ *       luma column x: i = x>>1; i2 = (x odd) ? min(i+1, Wc-1) : i;          C8 = V4[i] + V4[i2]   (8 x chroma)
+ *  2. offsets: y = Y - 16 (limited) or Y (full); cb = C8_U - 1024; cr = C8_V - 1024
+ *  3. matrix, int32 with arithmetic (flooring) shifts, each result clamped to [0, 255]:
+ *       R = (A*y + RV*cr + 32768) >> 16;  G = (A*y - GU*cb - GV*cr + 32768) >> 16;  B = (A*y + BU*cb + 32768) >> 16
+ *     with rnd(v) = floor(v + 0.5) in double, Kg = 1 - Kr - Kb, sY = 255/219 and sC = 255/224 (limited) or 1 and 1 (full):
+ *       A = rnd(sY*2^16), RV = rnd(2(1-Kr)*sC*2^13), GU = rnd(2(1-Kb)*Kb/Kg*sC*2^13), GV = rnd(2(1-Kr)*Kr/Kg*sC*2^13),
+ *       BU = rnd(2(1-Kb)*sC*2^13);  (Kr, Kb) = (0.299, 0.114) BT.601, (0.2126, 0.0722) BT.709, (0.2627, 0.0593) BT.2020.
+ *     BT.709 limited: A 76309, RV 14686, GU 1747, GV 4366, BU 17305.
+ * hdrtv_yuv420_to_bgr_u8 writes the result as u8 [H][W][3] B, G, R (the frame hdrtv_preprocess and hdrtv_letterbox_u8 read);
+ * needs no reservation.  hdrtv_preprocess_yuv420 equals hdrtv_preprocess of that frame bit for bit, in both outputs, for fp16
+ * and fp32 contexts and every condition mode, in one pass over the planes (fp16); same reservation rule as hdrtv_preprocess.
+ * HDRTV_EINVAL for a NULL pointer, odd H or W, a pitch below its plane's width, an unknown layout, matrix or range, or NV12
+ * with a non-NULL dev_v; HDRTV_ESTATE (preprocess) before hdrtv_reserve(H, W). */
+#define HDRTV_YUV_I420 0
+#define HDRTV_YUV_NV12 1
+int hdrtv_yuv420_to_bgr_u8(hdrtv_ctx *ctx, void *stream, const uint8_t *dev_y, int y_pitch,
+                           const uint8_t *dev_u, const uint8_t *dev_v, int c_pitch, int layout,
+                           int matrix, int full_range, int H, int W, uint8_t *dev_bgr_hwc);
+int hdrtv_preprocess_yuv420(hdrtv_ctx *ctx, void *stream, const uint8_t *dev_y, int y_pitch,
+                            const uint8_t *dev_u, const uint8_t *dev_v, int c_pitch, int layout,
+                            int matrix, int full_range, int H, int W, void *dev_rgb_chw, void *dev_cond);
+
 /* Objective metrics of the reference's metrics dict between two device images [3][H][W]
  * (R, G, B planes, unit range, f16 or f32): out3 = { PSNR dB, SSIM, dE-ITP } as _psnr_bgr / _ssim_bgr /
  * _delta_e_itp_bgr compute them (src/gui_objective_metrics.py:438-528; peak_nits = HDRTVNET_OBJECTIVE_HDR_PEAK_NITS,
