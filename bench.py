@@ -18,12 +18,17 @@ behind) -- the path BASELINE.json's north_star names.  `value` = N*K frames / ma
 time.  `value_device_only` leaves the RGB48 frame in HBM; `value_pcie_inclusive` also uploads
 every input frame from pinned host memory (never `value`: inputs are resident by contract).
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  Everything else it can measure
+or check -- the latency tail, `two_lanes` and its self-check, value_device_only, value_pcie_inclusive, roofline (and
+--layers), the INT8 / fp32 extras, the dispatcher and the CPU baseline -- runs only with --full, after the headline's
+figures are taken; the --no-* options skip single legs of a --full run.  Without --full those keys are null or absent.
+
 Extra objects on the JSON line:
-  roofline     dominant kernel (by summed time) of hdrtv_infer, timed with HIP events on the
+  roofline     (--full) dominant kernel (by summed time) of hdrtv_infer, timed with HIP events on the
                launch stream (hdrtv_profile_*), in K extra steps right after the timed region
                (kept out of it so `value` carries no event overhead): achieved = algorithmic
                FLOPs per launch / average launch duration; peak = 2500 TFLOP/s dense fp16 MFMA.
-  cpu_baseline the reference's CPU-eager semantics (the oracle's graphs on PyTorch's CPU kernels,
+  cpu_baseline (--full) the reference's CPU-eager semantics (the oracle's graphs on PyTorch's CPU kernels,
                fp32) timed on this box's host cores on a bounded sample, rank 0 at N=1 only.
   dump_outputs with --dump-outputs DIR: the files written there (the last timed step's RGB48 frame, rank 0).
 """
@@ -47,11 +52,15 @@ MFMA_F16_DENSE_PEAK_TFLOPS = 2500.0     # /opt/skills/guides/MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg: latency tail, two_lanes, value_device_only, value_pcie_inclusive, roofline, "
+                         "the INT8 / fp32 extras, the dispatcher and the CPU baseline (the --no-* options skip single legs).  Off by default: "
+                         "a plain run only sets up, warms up, times --steps, writes --dump-outputs and prints the line")
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--no-hg", action="store_true", help="debug: AGCM+LE only (not the headline config)")
@@ -93,7 +102,10 @@ def parse():
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed region, write what its last step delivered (rank 0's RGB48 frame from the pinned host ring) "
                          "as DIR/*.npy in float32 / float64 (dump_outputs below): two builds compared output for output on the same inputs")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.layers and not args.full:
+        ap.error("--layers prints the profile of the roofline leg, which runs with --full only")
+    return args
 
 
 # --dump-outputs: frames up to this many values are written whole as float32; larger ones as a fixed seeded sample
@@ -542,7 +554,9 @@ def main():
     use_hg = not args.no_hg
     H, Wd = args.height, args.width
     want_two = not args.no_two_lanes and world == 1 and args.lanes == 1
-    ctx_lanes = 2 if want_two else args.lanes           # the context holds the second workspace from the start; `value` uses args.lanes
+    # the context holds the second workspace from the start, with or without --full, so that a plain and a full run time the
+    # same context and ring; `value` uses args.lanes
+    ctx_lanes = 2 if want_two else args.lanes
     import contextlib
     with contextlib.redirect_stdout(sys.stderr):       # stdout carries exactly one JSON line
         proc = HDRTVNetMI355X(os.path.join(REPO, "tests", "golden", f"hr_int8_{args.int8_recipe}_qat.hdrw" if args.int8 else "hr_weights.hdrw"),
@@ -664,7 +678,7 @@ def main():
     # ---- latency tail over more frames than the timed region holds (never `value`): with the driver's K = 20, p99 is the slowest
     # of 20 frames and the 1 % low a single sample; the same ring-inclusive step for >= 300 more frames gives them a population
     tail_stats = None
-    if args.steps < 300 and not args.no_latency_tail:
+    if args.full and args.steps < 300 and not args.no_latency_tail:
         n_tail = 300
         tev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_tail)]
         for i in range(n_tail):
@@ -681,7 +695,7 @@ def main():
     # frame's kernels in the tails of the other's), reported beside `value` with its per-frame latency, and a self-check: 60 frames on
     # two lanes against the bytes the same frames give one at a time.  Never `value` (lanes are opt-in: DESIGN.md 7)
     two_lanes = None
-    if want_two:
+    if args.full and want_two:
         ev2 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
         for i in range(4):
             ring_step(i, lanes=2)
@@ -717,7 +731,7 @@ def main():
 
     # ---- the same K steps with the RGB48 frame left in device memory (no ring): reported at N = 1, never `value`
     device_only = None
-    if world == 1:
+    if args.full and world == 1:
         torch.cuda.synchronize(dev)
         u16 = [torch.empty((H, Wd, 3), dtype=torch.uint16, device=dev) for _ in range(args.lanes)]
         t1 = time.perf_counter()
@@ -729,7 +743,7 @@ def main():
 
     # ---- PCIe-inclusive variant (pinned H2D in, RGB48 out through the pinned host ring): reported, never `value`
     pcie = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         proc._chk(lib.hdrtv_ring_create(ctx, 2 + args.lanes, H, Wd), "ring_create")
         pin = [torch.from_numpy(f).pin_memory() for f in frames]
         torch.cuda.synchronize(dev)
@@ -779,7 +793,7 @@ def main():
 
     # ---- roofline of the dominant kernel: HIP events around every launch of hdrtv_infer
     roof, roof_next, layers = None, None, None
-    if rank == 0:
+    if args.full and rank == 0:
         proc.profile_enable(True)
         agg = {}
         nprof = max(3, min(args.steps, 10))
@@ -865,6 +879,13 @@ def main():
                 print(f"[layer] {layer:28s} {kname:26s} {lms:8.3f} ms  {2 * lmacs / max(lms, 1e-9) / 1e9:8.1f} TFLOP/s "
                       f"{lb / max(lms, 1e-9) / 1e6:8.1f} GB/s", file=sys.stderr)
 
+    if rank == 0 and args.int8 and layers is None:
+        # the INT8 metric names what ran, read from the profile of one frame behind the timed region (under --full, the roofline leg's)
+        proc.profile_enable(True)
+        step(0)
+        torch.cuda.synchronize(dev)
+        layers = proc.profile_read()
+        proc.profile_enable(False)
     launches, macs_frame = proc.infer_stats()
     ran = proc.execution_summary(layers) if (rank == 0 and args.int8) else None
     if rank == 0:
@@ -875,7 +896,7 @@ def main():
             "ms_per_step": round(elapsed / args.steps * 1e3, 3), "p50_ms": round(p50, 3), "p99_ms": round(p99, 3),
             "one_percent_low_fps": round(one_pct_low, 3), "latency_tail": tail_stats,
             "lanes": args.lanes, "two_lanes": two_lanes,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "i8+f16" if args.int8 else "f16",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "i8+f16" if args.int8 else "f16", "full": args.full,
             "world_size": dist.get_world_size() if world > 1 else 1, "backend": (backend if backend != "nccl" else "nccl (RCCL)") if world > 1 else None,
             "per_rank_frames_per_s": per_rank_fps, "per_rank_numa_node": per_rank_node,
             "data": "synthetic (seeded u8 noise + gradient/highlight frames; HR.pt weights, seeded HG weights)",
@@ -902,14 +923,14 @@ def main():
         }
         if dumped is not None:
             line["dump_outputs"] = dumped
-        if world == 1 and use_hg and not args.int8 and not args.no_int8_extra:
+        if args.full and world == 1 and use_hg and not args.int8 and not args.no_int8_extra:
             line["config4_int8"] = int8_extra(args, dev, dev_frames)
             # the reference's default preset is the mixed recipe (gui_config.py: DEFAULT_PRECISION_KEY = "INT8 Mixed (QAT)")
             line["config4_int8_mixed"] = int8_extra(args, dev, dev_frames, recipe="mixed")
             line["preset_fp32_1080p"] = fp32_extra(args, dev)
-        if world == 1 and not args.int8 and not args.no_dispatcher:
+        if args.full and world == 1 and not args.int8 and not args.no_dispatcher:
             line["dispatcher_host_fed"] = dispatcher_host_fed(args, frames, local_rank, use_hg, max(40, args.steps))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, use_hg)
         print(json.dumps(line), flush=True)
     proc.close()

@@ -1,4 +1,4 @@
-"""The bench.py output contract, checked on the lines committed under profiles/ (produced by the same bench.py on an
+"""The bench.py output contract, checked on the lines committed under profiles/ (produced by bench.py, today `--full`, on an
 MI355X; no GPU needed here): every key the driver and the judge read is present and well-formed."""
 import json
 import os
@@ -52,6 +52,16 @@ def test_bench_defaults_are_the_headline_configuration():
     assert spec is not None
     for needle in ('"--gpus", type=int, default=1', '"--height", type=int, default=2160', '"--width", type=int, default=3840'):
         assert needle in src, needle
+
+
+def test_bench_leaves_every_other_leg_to_full():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` runs only what `value` needs; `--full` (off by default) adds the other
+    legs, and `--layers`, which prints the roofline leg's profile, asks for it."""
+    import bench
+    assert bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    assert bench.parse(["--full", "--layers"]).full is True
+    with pytest.raises(SystemExit):
+        bench.parse(["--layers"])
 
 
 def test_bench_self_launches_its_ranks(tmp_path):

@@ -305,18 +305,25 @@ def test_hip_graph_follows_mask_r_and_profiling(golden_dir):
 @pytest.mark.gpu
 def test_bench_prints_exactly_one_line_on_stdout():
     """The driver parses bench.py's stdout as ONE JSON line: nothing else (processor banners of the dispatcher's worker processes,
-    warnings, progress) may land there.  Small frame, dispatcher leg included, everything else at its default."""
+    warnings, progress) may land there.  Small frame: a plain run, which leaves every other leg out, and a --full run with the
+    dispatcher leg included, everything else at its default."""
     import json
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--height", "270", "--width", "480", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-int8-extra"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    lines = r.stdout.splitlines()
-    assert len(lines) == 1, r.stdout
-    d = json.loads(lines[0])
-    assert d["n_gpus"] == 1 and d["dispatcher_host_fed"]["value"] > 0
+    for extra in ([], ["--full", "--no-cpu-baseline", "--no-int8-extra"]):
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--height", "270", "--width", "480", "--steps", "3", "--warmup", "1"]
+                           + extra, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = r.stdout.splitlines()
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["n_gpus"] == 1 and d["value"] > 0 and d["full"] == bool(extra)
+        if extra:
+            assert d["dispatcher_host_fed"]["value"] > 0 and d["roofline"] is not None and d["two_lanes"] is not None
+        else:
+            assert "dispatcher_host_fed" not in d and "cpu_baseline" not in d and "config4_int8" not in d
+            assert all(d[k] is None for k in ("latency_tail", "two_lanes", "value_device_only", "value_pcie_inclusive", "roofline"))
 
 
 def test_ring_slot_state_machine(golden_dir):

@@ -7,5 +7,5 @@ L=$1; shift
 for m in "$@"; do
   rm -rf /tmp/ablbuild && mkdir -p /tmp/ablbuild && cp -r hdr-realtime-video-pipeline_amd include tools tests oracle bench.py /tmp/ablbuild/
   (cd /tmp/ablbuild/hdr-realtime-video-pipeline_amd/csrc && touch le_rows.hip && make EXTRA=-DRB_ABL=$m -j8 > /dev/null 2>&1)
-  (cd /tmp/ablbuild && python bench.py --steps 10 --warmup 3 --layers --no-hg --no-cpu-baseline --no-dispatcher --no-int8-extra 2>&1 > /dev/null | grep "$L" | sed "s/^/ABL=$m /")
+  (cd /tmp/ablbuild && python bench.py --full --steps 10 --warmup 3 --layers --no-hg --no-cpu-baseline --no-dispatcher --no-int8-extra 2>&1 > /dev/null | grep "$L" | sed "s/^/ABL=$m /")
 done

@@ -4,20 +4,20 @@
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 B="--steps 20 --warmup 5"
-python3 $R/bench.py $B --layers > $O/r03_bench_default.json 2> $O/r03_layers.txt; echo "bench default $?"
-python3 $R/bench.py --int8 $B --layers --no-cpu-baseline --no-dispatcher > $O/r03_int8_bench.json 2> $O/r03_int8_layers.txt; echo "bench int8 full $?"
-python3 $R/bench.py --int8 --int8-recipe mixed $B --no-cpu-baseline --no-dispatcher > $O/r03_int8_mixed_bench.json 2> /dev/null; echo "bench int8 mixed $?"
-python3 $R/bench.py --int8 --int8-predequantize $B --no-cpu-baseline --no-dispatcher > $O/r03_int8_predeq_bench.json 2> /dev/null; echo "bench int8 predeq $?"
+python3 $R/bench.py --full $B --layers > $O/r03_bench_default.json 2> $O/r03_layers.txt; echo "bench default $?"
+python3 $R/bench.py --full --int8 $B --layers --no-cpu-baseline --no-dispatcher > $O/r03_int8_bench.json 2> $O/r03_int8_layers.txt; echo "bench int8 full $?"
+python3 $R/bench.py --full --int8 --int8-recipe mixed $B --no-cpu-baseline --no-dispatcher > $O/r03_int8_mixed_bench.json 2> /dev/null; echo "bench int8 mixed $?"
+python3 $R/bench.py --full --int8 --int8-predequantize $B --no-cpu-baseline --no-dispatcher > $O/r03_int8_predeq_bench.json 2> /dev/null; echo "bench int8 predeq $?"
 cd /tmp && export TMPDIR=/tmp
 Q="--no-cpu-baseline --no-int8-extra --no-dispatcher"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r03f_kt -o p -- python3 $R/bench.py $B $Q > $O/r03f_kt.json 2> $O/r03f_kt.err; echo "kt $?"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r03f_kt_i8 -o p -- python3 $R/bench.py --int8 $B $Q > $O/r03f_kt_i8.json 2> $O/r03f_kt_i8.err; echo "kt i8 $?"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r03f_kt -o p -- python3 $R/bench.py --full $B $Q > $O/r03f_kt.json 2> $O/r03f_kt.err; echo "kt $?"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r03f_kt_i8 -o p -- python3 $R/bench.py --full --int8 $B $Q > $O/r03f_kt_i8.json 2> $O/r03f_kt_i8.err; echo "kt i8 $?"
 for ctr in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $O/r03f_pmc_$ctr -o p -- python3 $R/bench.py --steps 3 --warmup 1 $Q > $O/r03f_pmc_$ctr.log 2>&1; echo "pmc $ctr $?"
-  rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $O/r03f_pmc_i8_$ctr -o p -- python3 $R/bench.py --int8 --steps 3 --warmup 1 $Q > $O/r03f_pmc_i8_$ctr.log 2>&1; echo "pmc i8 $ctr $?"
+  rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $O/r03f_pmc_$ctr -o p -- python3 $R/bench.py --full --steps 3 --warmup 1 $Q > $O/r03f_pmc_$ctr.log 2>&1; echo "pmc $ctr $?"
+  rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $O/r03f_pmc_i8_$ctr -o p -- python3 $R/bench.py --full --int8 --steps 3 --warmup 1 $Q > $O/r03f_pmc_i8_$ctr.log 2>&1; echo "pmc i8 $ctr $?"
 done
-rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/r03f_mfma -o p -- python3 $R/bench.py --steps 3 --warmup 1 $Q > $O/r03f_mfma.log 2>&1; echo "pmc mfma $?"
-rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE --output-format csv -d $O/r03f_sq -o p -- python3 $R/bench.py --steps 3 --warmup 1 $Q > $O/r03f_sq.log 2>&1; echo "pmc sq $?"
+rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/r03f_mfma -o p -- python3 $R/bench.py --full --steps 3 --warmup 1 $Q > $O/r03f_mfma.log 2>&1; echo "pmc mfma $?"
+rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE --output-format csv -d $O/r03f_sq -o p -- python3 $R/bench.py --full --steps 3 --warmup 1 $Q > $O/r03f_sq.log 2>&1; echo "pmc sq $?"
 cd $R
 f() { find $O/$1 -name "*$2" | head -1; }
 python3 tools/pmc_to_json.py $(f r03f_pmc_FETCH_SIZE counter_collection.csv) $(f r03f_pmc_WRITE_SIZE counter_collection.csv) $O/pmc_traffic.json "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of \`bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-int8-extra --no-dispatcher\`, r03 final build" > /dev/null
