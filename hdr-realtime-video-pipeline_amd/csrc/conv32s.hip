@@ -670,6 +670,9 @@ __global__ __launch_bounds__(NT) void conv32s_kernel(Conv32Params p)
             // never waited for)
             if (wave < 4) __builtin_amdgcn_s_waitcnt(waitcnt_imm(C3 ? NSTORE : 63, 0));     // C3: their condition-tile pieces are older than the stores
             else __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
+            // once more behind the join, for every wave: hipcc threads the two roles through flag-steered blocks, and an LDS-order
+            // scan of the block graph (tests/test_isa_contracts.py) must find lgkmcnt(0) on EVERY edge into the barrier
+            __builtin_amdgcn_s_waitcnt(waitcnt_imm(63, 0));
         } else {
             if (wave < 4) {
                 conv_mfma();

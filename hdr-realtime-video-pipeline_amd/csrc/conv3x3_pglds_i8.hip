@@ -34,6 +34,14 @@ template <int N> __device__ __forceinline__ void wait_vm()
 {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
+// The wait that closes a tap, in front of its barrier: the counted vmcnt AND lgkmcnt(0) as one immediate.  Behind the barrier the
+// other waves refill the ring slot (at tap NT-3 the halo buffer) this tap has read by LDS-DMA, so every LDS read of the wave must
+// have RETURNED before it arrives -- hipcc's own lgkmcnt waits sit in front of the consuming MFMAs, and those it may sink below the
+// barrier and the next tap's DMA issue (tests/test_isa_contracts.py: test_no_lds_read_is_in_flight_when_its_region_is_rewritten).
+template <int N> __device__ __forceinline__ void wait_tap()
+{
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
 
 struct Tile { int n0, oy0, ox0; };
 
@@ -204,7 +212,10 @@ __global__ __launch_bounds__(512) void conv_pglds_i8_kernel(ConvI8Params p)
                 auto ldx = [&](int ks, int j) {
                     xf[ks][j] = *reinterpret_cast<const i32x4 *>(ax + j * HW * PIXB + (((ks * 4 + kg) ^ kx) << 4));
                 };
-                // program order IS the schedule: sched_barrier(0) lets nothing cross
+                // program order IS the schedule of the LDS reads: sched_barrier(0) lets nothing cross, and the last one stands behind
+                // the last read.  The k-step-1 MFMAs behind it are left to hipcc, which sinks them below the tap's barrier and into
+                // the next tap's DMA issue (pinning them here cost 2 % of the kernel, NOTEBOOK.md); the waits for their operands
+                // must not sink with them: wait_tap
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { ldw(0, i); ldx(0, i); }
                 __builtin_amdgcn_sched_barrier(0);
@@ -228,14 +239,14 @@ __global__ __launch_bounds__(512) void conv_pglds_i8_kernel(ConvI8Params p)
                 // the halo staged at tap 6.  Allow exactly the DMAs (and, right after a tile boundary, the
                 // previous tile's stores) that are younger than those.
                 if (!pfB) {
-                    wait_vm<0>();
+                    wait_tap<0>();
                 } else if ((tap == NT - 3 || tap == NT - 2) && pfA) {
-                    if (last_chunk) wait_vm<9>();        // halo (6) + scale/shift (1) + weights(s+2) (2)
-                    else wait_vm<8>();
+                    if (last_chunk) wait_tap<9>();        // halo (6) + scale/shift (1) + weights(s+2) (2)
+                    else wait_tap<8>();
                 } else if (tap <= 1 && cc == 0 && k > 0) {
-                    wait_vm<NStores<MODE>::N + 2>();     // weights(s+1) are older than the last tile's stores
+                    wait_tap<NStores<MODE>::N + 2>();     // weights(s+1) are older than the last tile's stores
                 } else {
-                    wait_vm<2>();
+                    wait_tap<2>();
                 }
                 __builtin_amdgcn_s_barrier();
             }

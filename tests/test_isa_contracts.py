@@ -5,10 +5,12 @@ assumes every wave issued exactly NStores<MODE>::N global stores in the epilogue
 two stores (fewer than assumed) the wait would let a weight DMA be read before it landed, so the count is pinned
 here.  conv32p.hip issues its planar-residual loads as inline asm (the compiler does not know they are
 outstanding): the loaded registers must not be read before the `s_waitcnt vmcnt(0)` that precedes barrier 1."""
+import functools
 import os
 import re
 import shutil
 import subprocess
+import tempfile
 
 import pytest
 
@@ -31,6 +33,41 @@ def _asm(src, tmp_path):
     return kernels
 
 
+def _assert_every_tap_barrier_is_behind_lgkmcnt0(name, body, taps):
+    """conv_pglds / conv_pglds_i8: right behind a tap's barrier the other waves refill by LDS-DMA the weight-ring slot (and at tap
+    NT-3 the halo buffer) this wave has just read.  In front of every per-tap s_barrier -- every s_barrier behind the first MFMA of
+    the text: the prologue's stand in front of it, and the unrolled taps stay covered wherever hipcc peels or rotates them to --
+    the last wait, barrier or memory operation must be a wait with lgkmcnt(0) in it (the hand-written one, or hipcc's own behind it), on every path into the barrier
+    (hipcc turns the chain of counted waits into blocks that join in front of it, and moves ALU work and MFMAs, which touch
+    registers only, between the two): the wave's own LDS reads have RETURNED, not merely been issued, and none follows the wait.  (The general rule: test_no_lds_read_is_in_flight_when_its_region_is_rewritten.)"""
+    blocks = _basic_blocks(body)
+    preds = {}
+    for bi, (_, succ) in enumerate(blocks):
+        for sj in succ:
+            preds.setdefault(sj, []).append(bi)
+
+    def last_before(bi, ii, seen):
+        """the waits, barriers and memory operations (LDS, vector, scalar) a wave can have executed last before (bi, ii)"""
+        for s in reversed(blocks[bi][0][:ii]):
+            if s.startswith(("s_waitcnt", "s_barrier", "ds_", "buffer_", "global_", "flat_", "scratch_", "s_load", "s_buffer_load")):
+                return {s}
+        out = set() if preds.get(bi) else {"<kernel entry>"}
+        for pj in preds.get(bi, []):
+            if pj not in seen:
+                out |= last_before(pj, len(blocks[pj][0]), seen | {pj})
+        return out
+
+    seen_mfma, checked = False, 0
+    for bi, (ins, _) in enumerate(blocks):
+        for ii, s in enumerate(ins):
+            seen_mfma = seen_mfma or s.startswith("v_mfma")
+            if s.startswith("s_barrier") and seen_mfma:
+                last = last_before(bi, ii, {bi})
+                assert last and all(re.match(r"s_waitcnt\b.*\blgkmcnt\(0\)", w) for w in last), (name, "per-tap s_barrier %d" % checked, sorted(last))
+                checked += 1
+    assert checked >= taps, (name, checked)
+
+
 def test_pglds_store_counts_match_the_counted_waits(tmp_path):
     kernels = _asm("conv3x3_pglds.hip", tmp_path)
     src = open(os.path.join(CSRC, "conv3x3_pglds.hip")).read()
@@ -47,6 +84,8 @@ def test_pglds_store_counts_match_the_counted_waits(tmp_path):
         assert stores == expect[mode], (name, stores, expect[mode])
         waits = set(int(v) for v in re.findall(r"s_waitcnt vmcnt\((\d+)\)", body))
         assert expect[mode] + 2 in waits, (name, sorted(waits))
+        assert "scratch_" not in body, name
+        _assert_every_tap_barrier_is_behind_lgkmcnt0(name, _whole_bodies("conv3x3_pglds.hip")[name], 9)
         seen += 1
     assert seen == 4
 
@@ -69,6 +108,7 @@ def test_pglds_i8_store_counts_match_the_counted_waits(tmp_path):
         waits = set(int(v) for v in re.findall(r"s_waitcnt vmcnt\((\d+)\)", body))
         assert want + 2 in waits, (name, sorted(waits))
         assert "v_mfma_i32_16x16x64_i8" in body and "scratch_" not in body
+        _assert_every_tap_barrier_is_behind_lgkmcnt0(name, _whole_bodies("conv3x3_pglds_i8.hip")[name], 6)        # six taps per chunk in the <.., true> (64-channel) form
         seen += 1
     assert seen == 5
 
@@ -341,3 +381,312 @@ def test_no_packed_f32_arithmetic_in_any_kernel(tmp_path):
             assert not packed, (src, name, len(packed))
             seen += 1
     assert seen >= 50
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# LDS read / refill ordering at barriers.  The hand-scheduled kernels all rest on "by the barrier every wave has consumed its
+# fragments": a raw s_barrier carries no fence, and hipcc places the lgkmcnt wait of an LDS read in front of the read's consumer,
+# which it may sink below the barrier.  The race this leaves open loses once in thousands of frames and only beside other kernels,
+# so no numeric test sees it -- the compiled ISA is deterministic and shows it on every build.
+
+_LGKM_MAX = 15          # lgkmcnt is a 4-bit counter on gfx9: the counts saturate there, which also keeps the fixed point finite
+_NONE_BEHIND = 1 << 20
+
+_RE_BLOCK_LABEL = re.compile(r"^(\.LBB\d+_\d+):")
+_RE_BRANCH = re.compile(r"^s_(?:branch|cbranch_\w+)\s+(\.LBB\d+_\d+)")
+_RE_LDS_READ = re.compile(r"^ds_(?:read|load)")
+_RE_LDS_WRITER = re.compile(r"^(?:ds_(?:write|store|wrxchg|add|sub|rsub|inc|dec|min|max|and|or|xor|mskor|cmpst|cmpswap|wrap|pk_add)"
+                            r"|global_load_lds|buffer_load_\w+ .*\blds\b)")
+_RE_LGKM_OUT_OF_ORDER = re.compile(r"^(?:s_load|s_buffer_load|s_memtime|s_memrealtime|s_sendmsg|flat_)")
+
+
+def _lgkmcnt_allowed(wait):
+    """The lgkmcnt an s_waitcnt leaves outstanding at most; None where it does not wait on that counter."""
+    m = re.search(r"lgkmcnt\((\d+)\)", wait)
+    if m:
+        return int(m.group(1))
+    m = re.match(r"s_waitcnt\s+(0x[0-9a-fA-F]+|\d+)\s*$", wait)       # raw immediate: lgkmcnt = bits 11:8, all ones = no wait
+    if m:
+        v = (int(m.group(1), 0) >> 8) & 15
+        return None if v == 15 else v
+    return None
+
+
+def _basic_blocks(body):
+    """[(instructions, successor indices)] of a kernel body: split at .LBB labels and behind branches; s_endpgm ends a path."""
+    blocks, label, ins = [], None, []
+    for raw in body.split("\n"):
+        ln = raw.split(";")[0].strip()
+        if not ln:
+            continue
+        lm = _RE_BLOCK_LABEL.match(ln)
+        if lm:
+            if ins or label:
+                blocks.append((label, ins))
+            label, ins = lm.group(1), []
+            continue
+        if ln.startswith(".") or ln.endswith(":"):
+            continue
+        ins.append(ln)
+        if ln.startswith(("s_branch", "s_cbranch", "s_endpgm", "s_setpc", "s_swappc")):
+            blocks.append((label, ins))
+            label, ins = None, []
+    if ins or label:
+        blocks.append((label, ins))
+    index = {lab: i for i, (lab, _) in enumerate(blocks) if lab}
+    out = []
+    for i, (_, ins) in enumerate(blocks):
+        last = ins[-1] if ins else ""
+        assert not last.startswith(("s_setpc", "s_swappc")), "indirect branch: the block graph is not known"
+        succ = []
+        bm = _RE_BRANCH.match(last)
+        if bm:
+            succ.append(index[bm.group(1)])
+        if not last.startswith(("s_branch", "s_endpgm")) and i + 1 < len(blocks):
+            succ.append(i + 1)
+        out.append((ins, succ))
+    return out
+
+
+# Wave state at a program point: (cur, pre, unordered).  cur = (n, y): at most n LDS reads issued since the last barrier are
+# outstanding, and at least y LDS operations were issued behind the youngest of them.  pre = {barrier ordinal: (n, y)}: the same for
+# the reads that were outstanding when the wave passed that barrier.  unordered: an operation that counts on lgkmcnt but returns
+# out of order may be outstanding.  Joins: maximum of every n, minimum of every y, `or` of unordered -- the transfer functions are
+# monotone in that order, so the walk below converges.
+def _lds_join(a, b):
+    if a is None:
+        return b
+    (an, ay), apre, au = a
+    (bn, by), bpre, bu = b
+    pre = dict(apre)
+    for k, (n, y) in bpre.items():
+        pre[k] = (max(n, pre[k][0]), min(y, pre[k][1])) if k in pre else (n, y)
+    return ((max(an, bn), min(ay, by)), pre, au or bu)
+
+
+def _lds_retire(ny, allowed):
+    n, y = ny          # in-order return: of the `allowed` operations still outstanding, y are younger than these reads
+    return (min(n, allowed - y), y) if allowed > y else (0, _NONE_BEHIND)
+
+
+def _lds_step(state, ins, barrier, report):
+    (cn, cy), pre, unordered = state
+    if ins.startswith("s_barrier"):
+        n = cn + sum(v[0] for v in pre.values())
+        pre = {barrier: (min(n, _LGKM_MAX), min([cy] + [v[1] for v in pre.values()]))} if n else {}
+        return ((0, _NONE_BEHIND), pre, unordered)
+    if ins.startswith("s_waitcnt"):
+        allowed = _lgkmcnt_allowed(ins)
+        if allowed is None:
+            return state
+        if allowed == 0:
+            return ((0, _NONE_BEHIND), {}, False)
+        if unordered:             # the `allowed` operations left need not be the youngest: nothing is known to have returned
+            return state
+        pre = {k: v for k, v in ((k, _lds_retire(v, allowed)) for k, v in pre.items()) if v[0]}
+        return (_lds_retire((cn, cy), allowed), pre, unordered)
+    if _RE_LDS_WRITER.match(ins):
+        for b, (n, _) in pre.items():
+            report(b, n, ins)
+    if ins.startswith("ds_"):     # every DS operation takes a place in the wave's in-order LDS queue
+        pre = {k: (n, min(y + 1, _LGKM_MAX)) for k, (n, y) in pre.items()}
+        if _RE_LDS_READ.match(ins):
+            return ((min(cn + 1, _LGKM_MAX), 0), pre, unordered)
+        return ((cn, min(cy + 1, _LGKM_MAX) if cn else _NONE_BEHIND), pre, unordered)
+    if _RE_LGKM_OUT_OF_ORDER.match(ins):
+        return ((cn, cy), pre, True)
+    return state
+
+
+def lds_order_violations(name, body):
+    """Every s_barrier of a kernel that violates:
+
+        No LDS read that a wave issued before an s_barrier may still be outstanding when, after that barrier, the wave reaches an
+        instruction that writes LDS (LDS-DMA `buffer_load_* ... lds` / `global_load_lds_*`, `ds_write*` / `ds_store*`, DS atomics).
+
+    (Passing the barrier tells the other waves that this wave is done with what it read; they run the same code, so the writer this
+    wave reaches is the one they reach -- their refill may land under reads that have not returned.)
+
+    Retirement model.  The LDS operations of one wave return in order: after `s_waitcnt lgkmcnt(N)` at most N are outstanding and
+    they are the youngest N, so a read from before the barrier is retired by a wait whose N is <= the number of LDS operations
+    issued behind it (the combined form `vmcnt(a) lgkmcnt(b)` and a raw immediate count).  Scalar loads (s_load*, s_buffer_load*)
+    and FLAT accesses count on lgkmcnt too but return OUT of order: from such an instruction until the next lgkmcnt(0) a counted
+    wait is not trusted to retire anything -- conservative, it can only add findings.
+    Control flow.  The body is split at the .LBB labels and behind s_branch / s_cbranch_*; the state is propagated over the block
+    graph (branch target and fall-through; a path ends at s_endpgm) to a fixed point, so a barrier at the end of an unrolled loop
+    body is followed across the back edge.  The walk does not know which paths a wave can take: it assumes all of them.
+
+    Returns [(kernel, barrier ordinal (0 = the first s_barrier of the text), reads outstanding, writing instruction)], one entry
+    per barrier and writer reached."""
+    blocks = _basic_blocks(body)
+    ordinal = {}
+    for bi, (ins, _) in enumerate(blocks):
+        for ii, s in enumerate(ins):
+            if s.startswith("s_barrier"):
+                ordinal[(bi, ii)] = len(ordinal)
+    state_in = [None] * len(blocks)
+    state_in[0] = ((0, _NONE_BEHIND), {}, False)
+    found, work = {}, [0]
+    while work:
+        bi = work.pop()
+        st = state_in[bi]
+        ins, succ = blocks[bi]
+        for ii, s in enumerate(ins):
+            def report(b, n, w, at=(bi, ii)):
+                found[(b, at)] = (max(n, found.get((b, at), (0, w))[0]), w)
+            st = _lds_step(st, s, ordinal.get((bi, ii)), report)
+        for sj in succ:
+            new = _lds_join(state_in[sj], st)
+            if new != state_in[sj]:
+                state_in[sj] = new
+                work.append(sj)
+    return [(name, b, n, w) for (b, _), (n, w) in sorted(found.items())]
+
+
+def _flagged(asm):
+    """{barrier ordinal: reads outstanding} of a hand-written snippet."""
+    out = {}
+    for _, b, n, _ in lds_order_violations("snippet", asm):
+        out[b] = max(n, out.get(b, 0))
+    return out
+
+
+_DMA = "buffer_load_dwordx4 v1, s[4:7], s0 offen lds"
+
+
+def test_lds_order_checker_flags_a_refill_under_reads_in_flight():
+    """read / barrier / DMA / wait -- the shape conv_pglds compiled to."""
+    asm = "\n".join(["ds_read_b128 v[0:3], v9"] * 8 + ["s_waitcnt vmcnt(2)", "s_barrier", _DMA, "s_waitcnt lgkmcnt(0)", "v_mfma_f32_16x16x32_f16 v[0:3], v[4:7], v[8:11], v[0:3]", "s_endpgm"])
+    v = lds_order_violations("k", asm)
+    assert v == [("k", 0, 8, _DMA)], v
+
+
+def test_lds_order_checker_passes_reads_that_returned_before_the_barrier():
+    for wait in ("s_waitcnt lgkmcnt(0)", "s_waitcnt vmcnt(2) lgkmcnt(0)", "s_waitcnt 0x0070"):        # 0x0070: vmcnt(0) lgkmcnt(0)
+        asm = "\n".join(["ds_read_b128 v[0:3], v9"] * 8 + [wait, "s_barrier", _DMA, "s_endpgm"])
+        assert _flagged(asm) == {}, wait
+    # a wait that leaves lgkmcnt alone retires nothing (0x0f70 = vmcnt(0) only)
+    for wait in ("s_waitcnt vmcnt(0)", "s_waitcnt 0x0f70"):
+        asm = "\n".join(["ds_read_b128 v[0:3], v9"] * 8 + [wait, "s_barrier", _DMA, "s_endpgm"])
+        assert _flagged(asm) == {0: 8}, wait
+
+
+def test_lds_order_checker_counts_in_order_return():
+    """conv_prw's shape: four halo reads cross the barrier, four more follow, lgkmcnt(4) leaves only the younger four outstanding."""
+    def asm(n):
+        return "\n".join(["ds_read_b128 v[0:3], v9"] * 4 + ["s_barrier"] + ["ds_read_b128 v[4:7], v9"] * 4 + ["s_waitcnt lgkmcnt(%d)" % n, _DMA, "s_endpgm"])
+    assert _flagged(asm(4)) == {}
+    assert _flagged(asm(5)) == {0: 1}
+    assert _flagged(asm(8)) == {0: 4}
+    # a scalar load in between returns out of order: the counted wait proves nothing any more, lgkmcnt(0) still does
+    base = ["ds_read_b128 v[0:3], v9"] * 4 + ["s_barrier", "s_load_dwordx2 s[0:1], s[2:3], 0x0"] + ["ds_read_b128 v[4:7], v9"] * 4
+    assert _flagged("\n".join(base + ["s_waitcnt lgkmcnt(4)", _DMA, "s_endpgm"])) == {0: 4}
+    assert _flagged("\n".join(base + ["s_waitcnt lgkmcnt(0)", _DMA, "s_endpgm"])) == {}
+
+
+def test_lds_order_checker_follows_the_back_edge():
+    """A rotated loop whose only violation wraps around: the barrier closes the body, the DMA opens the next trip."""
+    asm = """
+        s_waitcnt vmcnt(0) lgkmcnt(0)
+        s_barrier
+    .LBB0_1:                                ; =>This Inner Loop Header: Depth=1
+        buffer_load_dwordx4 v1, s[4:7], s0 offen lds
+        s_waitcnt lgkmcnt(0)
+        v_mfma_f32_16x16x32_f16 v[0:3], v[4:7], v[8:11], v[0:3]
+        s_cbranch_scc1 .LBB0_3
+    ; %bb.2:
+        ds_read_b128 v[4:7], v9
+        ds_read_b128 v[8:11], v9 offset:16
+        s_waitcnt vmcnt(2)
+        s_barrier
+        s_branch .LBB0_1
+    .LBB0_3:
+        s_endpgm
+    """
+    assert _flagged(asm) == {1: 2}
+    # straight-line reading of the same text (branches ignored) finds nothing: the DMA stands in front of the reads
+    assert _flagged("\n".join(ln for ln in asm.split("\n") if "branch" not in ln and "LBB" not in ln)) == {}
+    assert _flagged(asm.replace("s_waitcnt vmcnt(2)", "s_waitcnt vmcnt(2) lgkmcnt(0)")) == {}
+
+
+def test_lds_order_checker_flags_plain_lds_writes_and_joins_on_the_worse_path():
+    asm = "\n".join(["ds_read_b64 v[0:1], v9", "s_barrier", "ds_write_b64 v9, v[2:3]", "s_waitcnt lgkmcnt(0)", "s_endpgm"])
+    assert _flagged(asm) == {0: 1}
+    # one arm of a branch waits, the other does not: the join keeps the reads of the arm that did not
+    asm = """
+        ds_read_b128 v[0:3], v9
+        ds_read_b128 v[4:7], v9
+        s_cbranch_vccz .LBB0_2
+    ; %bb.1:
+        s_waitcnt lgkmcnt(0)
+    .LBB0_2:
+        s_barrier
+        ds_write_b128 v9, v[0:3]
+        s_endpgm
+    """
+    assert _flagged(asm) == {0: 2}
+    assert _flagged(asm.replace("s_cbranch_vccz .LBB0_2", "s_nop 0")) == {}
+
+
+# every kernel source of the library (the host-side files hold no kernel)
+_KERNEL_SRCS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip") and not f.startswith("api_") and f not in ("hdrtv_api.hip", "fp32_graph.hip"))
+# the files that stage through LDS behind barriers today: each must be seen with barriers by the scan (a file added later is covered
+# from its first day by _KERNEL_SRCS; this list only keeps the scan from passing on an empty match)
+_BARRIER_SRCS = {"conv3x3_prw.hip", "conv3x3_pglds.hip", "conv3x3_pglds_i8.hip", "conv1x1_glds.hip", "conv_i8_misc.hip", "conv3x3s2_preg.hip",
+                 "conv32s.hip", "conv32p.hip", "conv_tile_f16.hip", "le_rows.hip", "conv3x3_prw_i8.hip", "le_rows_i8.hip", "le_fused.hip",
+                 "conv_q8.hip", "le_chain_q8.hip", "conv_igemm.hip", "agcm.hip", "le_hg_misc.hip", "prepost.hip"}
+
+
+@functools.lru_cache(maxsize=None)
+def _whole_bodies(src):
+    """{kernel: body} of one source file, compiled with _asm's flags; whole function bodies (to .Lfunc_end: _asm's end at the
+    first s_endpgm, behind which hipcc places blocks of the tap loops)."""
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, src + ".s")
+        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", "-fno-vectorize", "-DHDRTV_AB", "-S",
+                        "--cuda-device-only", os.path.join(CSRC, src), "-o", out], check=True, capture_output=True)
+        text = open(out).read()
+    return {m.group(1): m.group(2) for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M)}
+
+
+def _lds_order_scan(src):
+    """(kernels with an s_barrier, s_barriers in them, violations) of one source file."""
+    kernels = barriers = 0
+    violations = []
+    for name, body in _whole_bodies(src).items():
+        n = len(re.findall(r"^\s*s_barrier", body, re.M))
+        if n:
+            kernels += 1
+            barriers += n
+            violations += lds_order_violations(name, body)
+    return kernels, barriers, violations
+
+
+@pytest.mark.parametrize("src", _KERNEL_SRCS)
+def test_no_lds_read_is_in_flight_when_its_region_is_rewritten(src):
+    """The rule of lds_order_violations over every kernel of every kernel file that has an s_barrier in its ISA (a file without
+    one has nothing to check and passes).  Exceptions: none -- a kernel the walk flags is fixed, or listed here by its exact
+    mangled name with the LDS region its writer targets and the reason the reads in flight cannot alias it."""
+    kernels, barriers, violations = _lds_order_scan(src)
+    assert kernels > 0 or src not in _BARRIER_SRCS, (src, kernels)
+    per_kernel = {}
+    for name, b, n, w in violations:
+        per_kernel.setdefault(name, {}).setdefault(b, (n, w))
+    report = "\n".join("%s: %d barrier(s)\n" % (name, len(bs)) + "\n".join("    s_barrier %d: %d LDS read(s) outstanding -> %s" % (b, n, w) for b, (n, w) in sorted(bs.items()))
+                       for name, bs in per_kernel.items())
+    assert not violations, "%s: LDS written behind a barrier with reads from before it in flight\n%s" % (src, report)
+
+
+def test_lds_order_scan_examined_the_kernels_it_is_meant_for():
+    """An empty match must not pass: every file known to synchronise through s_barrier was seen with barriers, and the scan walked
+    at least the instances the other contracts of this file count (conv_pglds 4, conv_pglds_i8 5, conv_prw 7, conv_prw_i8 6,
+    conv32s 13, conv32p 9, le_rows 6, le_rows_i8 3 = 53) plus one kernel in each of the other eleven files, with at least nine
+    per-tap barriers in each of the nine pglds instances and one in every other kernel."""
+    assert _BARRIER_SRCS <= set(_KERNEL_SRCS), sorted(_BARRIER_SRCS - set(_KERNEL_SRCS))
+    seen = {src: _lds_order_scan(src)[:2] for src in _KERNEL_SRCS}
+    missing = sorted(src for src in _BARRIER_SRCS if seen[src][0] == 0)
+    assert not missing, missing
+    kernels, barriers = sum(v[0] for v in seen.values()), sum(v[1] for v in seen.values())
+    assert kernels >= 53 + 11, seen
+    assert barriers >= 9 * 9 + (kernels - 9), seen
+    assert seen["conv3x3_pglds.hip"][0] == 4 and seen["conv3x3_pglds_i8.hip"][0] == 5, seen
