@@ -247,7 +247,12 @@ struct hdrtv_ctx {
     // per-launch profile (hdrtv_profile_*): event i is recorded after launch i-1
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;
-    struct ProfEntry { std::string layer, kernel; double macs, bytes; float ms; };
+    // cnt != null: a launch that walks a need list of `cnt_total` tiles at most -- its executed count is read back when the entry is
+    struct ProfEntry { std::string layer, kernel; double macs, bytes; float ms; const int *cnt; int cnt_total; };
+    // lane 0's last frame ran with need lists: its hg.* tensors hold the needed tiles only until hdrtv_get_tap completes them
+    // (taps_replayable: that frame was captured into a graph, whose replays the library does not see)
+    bool taps_partial = false, taps_replayable = false;
+    hipStream_t taps_stream = nullptr;
     std::vector<ProfEntry> prof;
     // letterbox tables (hdrtv_letterbox_u8): device copy for the last geometry
     int lb_key[4] = {0, 0, 0, 0};
@@ -354,6 +359,9 @@ struct Seq {
     const f16 *tail_w = nullptr;
     const float *tail_b = nullptr, *tail_s = nullptr;       // tail_s != null: conv3x3s2_preg<64>'s single-layer tail (CondNet3.4)
     f16 *tail_out = nullptr;
+    // HG need list (hg_need.hip) of the next conv(): the list, the tile rows it is written for and the tile count of a dense launch
+    const int *need_list = nullptr;
+    int need_th = 0, need_total = 0;
     bool ok() const { return rc == HDRTV_OK; }
     void mark()
     {
@@ -367,13 +375,13 @@ struct Seq {
         (void)hipEventRecord(c->prof_ev[i], s);
     }
     // called after every launch: counts it, checks it and (profiling) closes its event interval
-    void chk(hipError_t e, const char *what, const char *kernel = "", double macs = 0.0, double bytes = 0.0)
+    void chk(hipError_t e, const char *what, const char *kernel = "", double macs = 0.0, double bytes = 0.0, const int *cnt = nullptr, int cnt_total = 0)
     {
         ++c->launches;
         c->macs += macs;
         if (e != hipSuccess && rc == HDRTV_OK) rc = fail(c, HDRTV_EHIP, "launch %s failed: %s", what, hipGetErrorString(e));
         if (c->prof_on) {
-            c->prof.push_back({what, kernel, macs, bytes, 0.f});
+            c->prof.push_back({what, kernel, macs, bytes, 0.f, cnt, cnt_total});
             mark();
         }
     }
@@ -416,6 +424,15 @@ struct Seq {
         const double cp = cost(tx * ((Ho + 15) / 16) * (cout / 128), 1.22);
         if (cp <= c16 && cp <= c8) return 0;
         return c8 < c16 ? 8 : 16;
+    }
+    // ... for a 3x3 / stride-1 layer of 64-channel chunks with epilogue `mode`: the one place that decides between conv_prw (16 / 8)
+    // and conv_pglds (0) -- conv() routes by it, hg_need_plan writes the layer's need list for the same tile height
+    static int prw_tile_rows(const hdrtv_ctx *c, int mode, int cout, int Ho, int Wo)
+    {
+        const int prw_mode = c->var.at("prw");
+        if (prw_mode == 0) return 0;
+        if (mode == ST_PS_DOT3) return cout == 256 ? 16 : 0;
+        return (cout % 256) ? 0 : prw_rows(prw_mode, Ho, Wo, cout, c->n_cu);
     }
     // a conv inside a fused row kernel: its fp16 pack, or (W8A8 layer, variant le_rows_fq) the dequantised pack + its activation quantiser
     static FqParam fqp(const ActQf &q) { return FqParam{q.inv(), q.zoff(), q.scale, q.asym ? q.zero : -128.f * q.scale}; }
@@ -467,7 +484,8 @@ struct Seq {
 
 int run_agcm(hdrtv_ctx *c, Seq &q, const f16 *rgb, const f16 *cond, f16 *agcm_out);
 int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar);
-int run_hg(hdrtv_ctx *c, Seq &q, const f16 *base, void *out, int out_f32);
+int run_hg(hdrtv_ctx *c, Seq &q, const f16 *base, void *out, int out_f32, bool complete_taps = false);
+size_t hg_need_plan(hdrtv_ctx *c, int Hp, int Wp, HgNeedParams &p);
 int run_f32(hdrtv_ctx *c, Seq &q, bool plan, int H, int W, const float *rgb, const float *cond, float *out, float *agcm_out);
 int f32_plan(hdrtv_ctx *c, int H, int W);      // registers the fp32 graph's tensors (hdrtv_reserve)
 

@@ -28,6 +28,10 @@ void Seq::conv(const std::string &key, const f16 *src0, int c0, const f16 *src1,
     p.tail_w = tail_w; p.tail_b = tail_b; p.tail_s = tail_s; p.tail_out = tail_out;
     tail_w = nullptr; tail_b = nullptr; tail_s = nullptr; tail_out = nullptr;
     p.trash = const_cast<char *>(wtp<char>(c, c->dump_off));
+    // a need list set for this launch (run_hg): consumed here; only a kernel with the list's tile geometry takes it
+    const int *const need = need_list;
+    const int need_rows = need_th, need_cells = need_total;
+    need_list = nullptr; need_th = 0; need_total = 0;
     const int nt_slow = c->var.at("pglds_nt_slow");
     // default: the Up convs (Cout = 4 Cin: 4 .. 16 Cout-tiles per pixel tile) walk Cout-tile slowest -- an XCD then shares one
     // weight slab instead of re-fetching up to 16 (-17 % L2 misses, profiles/r02_pmc_traffic_tile_order.json); the other
@@ -44,9 +48,7 @@ void Seq::conv(const std::string &key, const f16 *src0, int c0, const f16 *src1,
         route = S2G;
     else if (g64 && L.ks == 3 && L.cout == L.coutPad) {                   // HG 3x3 convs: persistent LDS-DMA kernel
         // Cout a multiple of 256: the private-weight schedule (conv3x3_prw.hip); Up_conv5 (ST_PS_DOT3) only at 256, always 16 rows
-        const int prw_mode = c->var.at("prw");
-        if (prw_mode != 0 && (L.coutPad % 256) == 0 && mode != ST_PS_DOT3) prw_th = prw_rows(prw_mode, p.Ho, p.Wo, L.coutPad, c->n_cu);
-        else if (prw_mode != 0 && mode == ST_PS_DOT3 && L.coutPad == 256) prw_th = 16;
+        prw_th = prw_tile_rows(c, mode, L.coutPad, p.Ho, p.Wo);
         route = prw_th ? PRW : PGLDS;
     } else if (g64 && L.ks == 1 && mode == ST_NHWC && (c0 + c1) >= 128 && L.coutPad <= 512 && (act == ACT_RELU || act == ACT_NONE))
         route = GLDS1;                                                     // HG 1x1 fuse convs
@@ -55,13 +57,18 @@ void Seq::conv(const std::string &key, const f16 *src0, int c0, const f16 *src1,
     const char *epi = mode == ST_POOL ? "pool" : (mode == ST_PS ? "ps" : (mode == ST_PS_DOT3 ? "ps_dot3" : "nhwc"));
     char tag[64];
     hipError_t e;
+    bool list_taken = false;        // conv_prw walked the need list (a run too long for its LDS slots runs every tile)
     switch (route) {
     case T16: snprintf(tag, sizeof tag, "conv_t16<32,3,2>"); e = conv_t16_launch(p, s, c->n_cu); break;
     case S2G:
         snprintf(tag, sizeof tag, p.tail_w ? "conv3x3s2_preg<%d>+tail" : "conv3x3s2_preg<%d>", L.coutPad);
         e = conv3x3s2_preg_launch(p, c->n_cu, s);
         break;
-    case PRW: snprintf(tag, sizeof tag, "%s<%s>", prw_th == 8 ? "conv_prw8" : "conv_prw", epi); e = conv_prw_launch(p, prw_th, c->n_cu, s); break;
+    case PRW:
+        if (need && need_rows == prw_th) p.tile_list = need;
+        snprintf(tag, sizeof tag, "%s<%s>", prw_th == 8 ? "conv_prw8" : "conv_prw", epi);
+        e = conv_prw_launch(p, prw_th, c->n_cu, s, &list_taken);
+        break;
     case PGLDS: snprintf(tag, sizeof tag, "conv_pglds<%s>", epi); e = conv_pglds_launch(p, c->n_cu, s); break;
     case GLDS1: snprintf(tag, sizeof tag, "conv_glds1"); e = conv_glds1_launch(p, s, c->n_cu, c->var.at("glds1_old") != 0); break;
     default:
@@ -78,7 +85,7 @@ void Seq::conv(const std::string &key, const f16 *src0, int c0, const f16 *src1,
                                           : (mode == ST_PLANAR3 ? 3.0 * Hd * Wd
                                                                 : (mode == ST_PS_DOT3 ? 8.0 * Hd * Wd : (double)p.Ho * p.Wo * L.cout));
     bytes += 2.0 * outel * (1 + (res1 ? 1 : 0) + (res2 ? 1 : 0) + (res_planar ? 1 : 0));
-    chk(e, key.c_str(), tag, macs, bytes);
+    chk(e, key.c_str(), tag, macs, bytes, list_taken ? p.tile_list : nullptr, need_cells);
 }
 
 
@@ -604,14 +611,73 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
     return q.rc;
 }
 
-// HG_Composite.forward tail + Hallucination_Generator.forward
-int run_hg(hdrtv_ctx *c, Seq &q, const f16 *base, void *out, int out_f32)
+// hg_need's program for a padded frame, from the layer table: the tensors' need maps, one list per layer.  Returns the bytes of
+// the buffer ("hg.need") all of it lies in; the layout does not depend on the variants, only HgNeedLayer::th does.
+size_t hg_need_plan(hdrtv_ctx *c, int Hp, int Wp, HgNeedParams &p)
+{
+    memset(&p, 0, sizeof p);
+    p.Hp = Hp; p.Wp = Wp;
+    constexpr int n_layers = (int)(sizeof hg_layers / sizeof hg_layers[0]);
+    static_assert(n_layers <= HG_NEED_MAX_LAYERS && n_layers + 2 <= HG_NEED_MAX_TENSORS, "hg_need's tables are too small");
+    auto ncell = [&](int level) { return (((Hp >> level) + 15) / 16) * (((Wp >> level) + 15) / 16); };
+    const char *names[HG_NEED_MAX_TENSORS];
+    int level[HG_NEED_MAX_TENSORS], nt = 0;
+    auto tensor = [&](const char *name, int lev) {
+        if (!name) name = "part";                    // Up_conv5's sums: their need map is hg_prep's flags
+        for (int i = 0; i < nt; ++i)
+            if (!strcmp(names[i], name)) return i;
+        names[nt] = name; level[nt] = lev;
+        return nt++;
+    };
+    for (int i = 0; i < n_layers; ++i) {
+        const HgLayer &L = hg_layers[i];
+        HgNeedLayer &N = p.L[i];
+        N.level = L.level; N.ks = L.ks;
+        N.mode = L.mode == ST_POOL ? 1 : (L.ps ? 2 : 0);
+        N.in = tensor(L.in, L.level);
+        N.skip = L.skip ? tensor(L.skip, L.level) : -1;
+        N.out = tensor(L.out, L.out_level());
+        N.th = L.ks == 3 && Seq::prw_tile_rows(c, L.mode, L.cout, Hp >> L.level, Wp >> L.level) == 8 ? 8 : 16;    // conv()'s own choice
+    }
+    p.n_layers = n_layers;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return (int)o; };
+    p.flags_off = take((size_t)ncell(0));
+    p.kmap_off = take((size_t)ncell(0));
+    p.maps_off = (int)off;
+    for (int t = 0; t < nt; ++t) p.map_off[t] = !strcmp(names[t], "part") ? p.flags_off : take((size_t)ncell(level[t]));
+    p.maps_bytes = (int)off - p.maps_off;
+    for (int i = 0; i < n_layers; ++i) p.L[i].list_off = take(4 * (2 * (size_t)ncell(p.L[i].level) + 4));
+    return off;
+}
+
+// HG_Composite.forward tail + Hallucination_Generator.forward.  complete_taps: hdrtv_get_tap's on-demand completion -- conv1 ..
+// Up_conv5 over every tile from the hg.img of the lane's last frame, no hg_prep, no blend.
+int run_hg(hdrtv_ctx *c, Seq &q, const f16 *base, void *out, int out_f32, bool complete_taps)
 {
     const Shapes s = shapes_for(c->H, c->W);
     const int Hp = s.Hp, Wp = s.Wp;
     f16 *img = q.wsp<f16>("hg.img");
     uint8_t *mask = q.wsp<uint8_t>("hg.mask");
-    q.chk(hg_prep_launch(base, s.H, s.W, Hp, Wp, img, mask, c->mask_r, 0.1f, q.s), "hg_prep", "hg_prep", 0.0, 13.0 * Hp * Wp);
+    // Need lists (variant hg_sparse; fp16 HG with the per-pixel tail): the layers on conv_prw compute only the tiles a masked
+    // output pixel depends on, the blend takes img everywhere else.  Built on the device behind hg_prep (hg_need.hip).
+    const bool sparse = !complete_taps && c->var.at("hg_sparse") != 0 && !c->hg_i8 && !c->var.at("final_recompute");
+    HgNeedParams np;
+    if (sparse) {
+        hg_need_plan(c, Hp, Wp, np);
+        np.base = q.wsp<unsigned char>("hg.need");
+    }
+    if (q.ws == c->lane_ws[0] && !complete_taps) {
+        // lane 0's hg.* tensors are partial from here on; a frame captured into a graph may be replayed any number of times later
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        c->taps_partial = sparse;
+        c->taps_replayable = sparse && hipStreamIsCapturing(q.s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+        c->taps_stream = q.s;
+    }
+    if (!complete_taps)
+        q.chk(hg_prep_launch(base, s.H, s.W, Hp, Wp, img, mask, c->mask_r, 0.1f, q.s, sparse ? np.base + np.flags_off : nullptr), "hg_prep",
+              "hg_prep", 0.0, 13.0 * Hp * Wp);
+    if (sparse) q.chk(hg_need_launch(np, q.s), "hg_need", "hg_need", 0.0, 0.0);
     float *part = q.wsp<float>("hg.part");
     // conv1: only the pooled map is kept; its kernel also leaves conv10's second half (the 64 -> 3 sums over conv1's channels) per
     // pixel, so the tail is a per-pixel kernel.  Variant final_recompute (developer A/B switch): the tail recomputes conv1
@@ -640,6 +706,12 @@ int run_hg(hdrtv_ctx *c, Seq &q, const f16 *base, void *out, int out_f32)
     char key[32];
     for (const HgLayer &L : hg_layers) {
         snprintf(key, sizeof key, "hg.%s", L.name);
+        if (sparse) {
+            const HgNeedLayer &N = np.L[&L - hg_layers];
+            q.need_list = reinterpret_cast<const int *>(np.base + N.list_off);
+            q.need_th = N.th;
+            q.need_total = (((Hp >> L.level) + N.th - 1) / N.th) * (((Wp >> L.level) + 15) / 16);
+        }
         const int c1 = L.skip_cin, c0 = L.cin - c1, Hi = Hp >> L.level, Wi = Wp >> L.level;
         const int Ho = Hp >> L.out_level(), Wo = Wp >> L.out_level();
         const bool dot3 = L.mode == ST_PS_DOT3;
@@ -651,7 +723,7 @@ int run_hg(hdrtv_ctx *c, Seq &q, const f16 *base, void *out, int out_f32)
             q.conv(key, (const f16 *)tensor(L.in), c0, (const f16 *)tensor(L.skip), c1, Hi, Wi, L.act, L.mode, (f16 *)tensor(L.out), L.out_c(), Ho, Wo,
                    nullptr, nullptr, nullptr, nullptr, nullptr, dotw, dst_dot);
     }
-    if (!q.ok()) return q.rc;
+    if (!q.ok() || complete_taps) return q.rc;
     const C3Layer &L1 = c->c3.at("hg.conv1");
     HgFinalFusedArgs fa;
     fa.img = img; fa.mask = mask; fa.part = part; fa.wfrag = wtp<f16>(c, c->hgf_wfrag);

@@ -74,6 +74,8 @@ void free_workspaces(hdrtv_ctx *c)
         if (p) (void)hipFree(p);
     c->lane_ws.clear();
     c->H = c->W = 0;
+    c->taps_partial = c->taps_replayable = false;      // no frame has run on the workspaces to come
+    c->taps_stream = nullptr;
 }
 
 int do_reserve(hdrtv_ctx *c, int H, int W)
@@ -151,6 +153,8 @@ int do_reserve(hdrtv_ctx *c, int H, int W)
         ws_add(c, "hg.img", 3, Hp, Wp, 1); ws_add(c, "hg.mask", 1, Hp, Wp, 4);
         ws_add(c, "hg.part", 4, Hp, Wp, 3);
         ws_add(c, "hg.part2", 4, Hp, Wp, 3);        // conv10's second half (over conv1), left by conv1's kernel
+        HgNeedParams np;                            // hg_need.hip: mask flags, need maps and the layers' tile lists (zeroed below)
+        ws_add(c, "hg.need", (int)hg_need_plan(c, Hp, Wp, np), 1, 1, 4);
         // conv2's input (conv1's pooled map) and every layer's output: NHWC f16, or (W8A8) the same tensors as int8 codes (q - 128)
         const char *pre = c->hg_i8 ? "hg8." : "hg.";
         const int layout = c->hg_i8 ? 5 : 0;

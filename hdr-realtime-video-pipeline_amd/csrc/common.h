@@ -133,6 +133,9 @@ struct ConvParams {
     const float *tail_b;
     const float *tail_s;
     f16 *tail_out;
+    // conv_prw only: null, or the spatial tiles to compute (hg_need.hip): [0] their count, [1 ..] tile indices ty * tiles_x + tx in
+    // the launch's tile geometry.  Device memory, read by the kernel: the launch itself does not depend on the count.
+    const int *tile_list;
 };
 
 // Parameter block of the int8 HG convolutions (conv3x3_pglds_i8.hip, conv_i8_misc.hip).  Activations are int8 codes

@@ -13,7 +13,12 @@
 //   * per MFMA: 0.56 ds_read_b128 (conv_pglds: 0.5), 0.06 LDS-DMA pieces (0.08), the same L2 -> CU weight bytes.
 // Accumulation order per output element is conv_pglds's (chunk, tap, k-step), so results are bit-identical to it.
 //
-// LDS: 2 x 41 KiB halo + 8 x 2 x 4 KiB weight rings + 2 x 2 KiB scale/shift + 1 KiB DMA trash + 1 KiB dot weights = 152 KiB.
+// LDS: 2 x 41 KiB halo + 8 x 2 x 4 KiB weight rings + 2 x 2 KiB scale/shift + 1 KiB DMA trash + 1 KiB dot weights + 2 KiB tile list = 154 KiB.
+//
+// Sparse launches (ConvParams::tile_list, the HG need lists of hg_need.hip): the spatial tiles are the list's entries instead of all
+// tiles_x * tiles_y.  The count is read once; every block copies the entries of ITS run into LDS in the prologue (in front of the
+// prologue's barrier), so the tile loop's only new operation is one LDS read per tile -- no scalar or vector memory load enters
+// the MFMA stream, whose vmcnt waits are counted by hand.
 #include "launchers.h"
 
 namespace {
@@ -32,7 +37,9 @@ constexpr int W_OFF = 2 * A_BYTES;
 constexpr int SS_OFF = W_OFF + 8 * 2 * W_SLOT;           // two slots of {scale[256], shift[256]}
 constexpr int TRASH_OFF = SS_OFF + 2 * 2048;
 constexpr int DOTW_OFF = TRASH_OFF + 1024;
-constexpr int SMEM = DOTW_OFF + 1024;                    // 155 648 B
+constexpr int LIST_OFF = DOTW_OFF + 1024;                // ConvParams::tile_list: this block's run of spatial tiles, looked up once
+constexpr int LIST_N = 512;
+constexpr int SMEM = LIST_OFF + LIST_N * 4;              // 157 696 B
 
 // LDS-DMA as a BUFFER load (buffer_load_dwordx4 ... lds), not global_load_lds: the global form is a FLAT-encoded
 // instruction that hipcc's waitcnt pass treats as "may touch LDS and memory", after which it never counts again -- every
@@ -71,7 +78,9 @@ __global__ __launch_bounds__(512) void conv_prw_kernel(ConvParams p)
 
     // ---- this block's run of tiles: XCD x owns a contiguous range, its blocks interleave in it (as conv_pglds) --
     const int ntn = p.CoutPad / BN;
-    const int total = p.tiles_x * p.tiles_y * ntn;
+    const int *const lst = p.tile_list;                      // null: every tile (dense)
+    const int nsp = lst ? lst[0] : p.tiles_x * p.tiles_y;    // spatial tiles to compute
+    const int total = nsp * ntn;
     int t_first, t_step, ntile;
     {
         const int G = gridDim.x, b = blockIdx.x, xcd = b & 7, slot = b >> 3;
@@ -84,10 +93,22 @@ __global__ __launch_bounds__(512) void conv_prw_kernel(ConvParams p)
         ntile = slot < len ? (len - slot + nslots - 1) / nslots : 0;
     }
     if (ntile == 0) return;
-    auto decode = [&](int t) {
+    // the list entries of this block's run (the launcher passes a list only when a run fits LIST_N); visible behind the prologue's barrier
+    volatile int *s_list = reinterpret_cast<volatile int *>(smem + LIST_OFF);
+    if (lst) {
+        if (tid < ntile) {
+            const int t = t_first + tid * t_step;
+            s_list[tid] = lst[1 + (p.nt_slow ? t % nsp : t / ntn)];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+    // tile number k of the run (k = 0: the prologue, in front of the barrier, reads the list itself)
+    auto decode = [&](int k) {
         Tile o;
-        const int nsp = p.tiles_x * p.tiles_y;
-        const int nt_i = p.nt_slow ? t / nsp : t % ntn, sp = p.nt_slow ? t - nt_i * nsp : t / ntn;
+        const int t = t_first + k * t_step;
+        const int nt_i = p.nt_slow ? t / nsp : t % ntn;
+        int sp = p.nt_slow ? t - nt_i * nsp : t / ntn;
+        if (lst) sp = k ? __builtin_amdgcn_readfirstlane(s_list[k]) : lst[1 + sp];
         const int ty = sp / p.tiles_x, tx = sp - ty * p.tiles_x;
         o.n0 = nt_i * BN; o.oy0 = ty * TH; o.ox0 = tx * TW;
         return o;
@@ -201,7 +222,7 @@ __global__ __launch_bounds__(512) void conv_prw_kernel(ConvParams p)
     };
 
     // ---- prologue ------------------------------------------------------------------------------
-    Tile cur = decode(t_first), nxt = cur;
+    Tile cur = decode(0), nxt = cur;
     issue_A(0, 0, cur);
     issue_SS(cur.n0, 0);
     issue_W(0, 0, cur.n0, 0);
@@ -214,7 +235,7 @@ __global__ __launch_bounds__(512) void conv_prw_kernel(ConvParams p)
     int ws = 0;                                   // taps done so far: weight slot parity
     for (int k = 0; k < ntile; ++k) {
         const bool has_next = k + 1 < ntile;
-        if (has_next) nxt = decode(t_first + (k + 1) * t_step);
+        if (has_next) nxt = decode(k + 1);
         for (int cc = 0; cc < nchunk; ++cc, ++gch) {
             const char *a = sA + (gch & 1) * A_BYTES;
             const char *a_nc = sA + ((gch + 1) & 1) * A_BYTES;
@@ -436,8 +457,9 @@ hipError_t launch_mode(const ConvParams &p, int grid, hipStream_t stream)
 // 3x3, stride 1, pad 1, Cin (src0 [+ src1 concat]) multiple of 64, Cout == CoutPad multiple of 256, no residuals;
 // store modes NHWC / PS / POOL (th = pixel rows per tile: 16 or 8) and PS_DOT3 (Cout = 256, th = 16).  One block per CU (n_cu), each walking tiles.
 // hipErrorInvalidValue otherwise.
-hipError_t conv_prw_launch(ConvParams p, int th, int n_cu, hipStream_t stream)
+hipError_t conv_prw_launch(ConvParams p, int th, int n_cu, hipStream_t stream, bool *list_taken)
 {
+    if (list_taken) *list_taken = false;
     if ((p.c0 % CT) || (p.c1 % CT) || p.c0 + p.c1 < CT || (p.CoutPad % BN) || p.Cout != p.CoutPad || p.res1 || p.res2 ||
         p.dst_full || !p.zeros || !p.trash || n_cu < 8 || (p.act != ACT_RELU && p.act != ACT_NONE) || (th != 8 && th != 16) ||
         (p.mode != ST_NHWC && p.mode != ST_PS && p.mode != ST_POOL && p.mode != ST_PS_DOT3) || (p.mode == ST_PS && (p.dstC % 64)) ||
@@ -447,6 +469,9 @@ hipError_t conv_prw_launch(ConvParams p, int th, int n_cu, hipStream_t stream)
     p.tiles_y = (p.Ho + th - 1) / th;
     const int total = p.tiles_x * p.tiles_y * (p.CoutPad / BN);
     const int grid = total < n_cu ? total : n_cu;
+    // the grid never depends on the list's count (device memory); a run too long for the LDS slots: dense
+    if (p.tile_list && (grid < 8 || (total / 8 + 1 + grid / 8 - 1) / (grid / 8) > LIST_N)) p.tile_list = nullptr;
+    if (list_taken) *list_taken = p.tile_list != nullptr;
     if (th == 16) {
         switch (p.mode) {
         case ST_NHWC: return launch_mode<ST_NHWC, 16>(p, grid, stream);

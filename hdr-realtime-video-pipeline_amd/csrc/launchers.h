@@ -14,7 +14,7 @@ struct DevOnce {
 hipError_t conv_igemm_launch(ConvParams p, int cin_t, int bn, int ks, int stride, hipStream_t stream);
 hipError_t conv_glds1_launch(ConvParams p, hipStream_t stream, int n_cu = 0, bool old_form = false);   // n_cu >= 8: the persistent form
 hipError_t conv_pglds_launch(ConvParams p, int n_cu, hipStream_t stream);
-hipError_t conv_prw_launch(ConvParams p, int th, int n_cu, hipStream_t stream);   // Cout % 256 == 0, modes NHWC / PS / POOL; th = 16 | 8
+hipError_t conv_prw_launch(ConvParams p, int th, int n_cu, hipStream_t stream, bool *list_taken = nullptr);   // Cout % 256 == 0, modes NHWC / PS / POOL; th = 16 | 8
 hipError_t conv_pglds_i8_launch(ConvI8Params p, int n_cu, hipStream_t stream);
 hipError_t conv_prw_i8_launch(ConvI8Params p, int th, int n_cu, hipStream_t stream);   // Cin % 128 == 0, Cout % 256 == 0, int8 out
 hipError_t conv1x1_i8_launch(ConvI8Params p, hipStream_t stream);
@@ -93,8 +93,26 @@ struct AgcmFoldQ8Args {
     float *consts;                 // out: 320 per-frame constants of agcm_mlp_q8
 };
 hipError_t agcm_fold_q8_launch(const AgcmFoldArgs &a, const AgcmFoldQ8Args &q, float *biasbuf, hipStream_t s);
+// flags: null, or one byte per 16x16 cell of the padded frame ([ceil(Hp/16)][ceil(Wp/16)]), set to 1 where the cell holds a masked
+// pixel inside H x W (never cleared here: hg_need consumes them)
 hipError_t hg_prep_launch(const f16 *base, int H, int W, int Hp, int Wp, f16 *img_pad, uint8_t *mask, float r, float thresh,
-                          hipStream_t s);
+                          hipStream_t s, uint8_t *flags = nullptr);
+// ---- hg_need.hip: the HG layers' need lists from hg_prep's flags.  Everything lies in one buffer (`base` + byte offsets).
+constexpr int HG_NEED_MAX_LAYERS = 24, HG_NEED_MAX_TENSORS = 32;
+struct HgNeedLayer {
+    int level, mode, ks;       // input level; 0 writes at its level, 1 pool-fused (one level down), 2 pixel shuffle (one level up)
+    int in, skip, out;         // tensor ids (skip < 0: none)
+    int th;                    // rows of the kernel tiles the list is written for: 16 or 8
+    int list_off;              // int [0] count, [1 ..] tile indices ty * ceil(W_level / 16) + tx
+};
+struct HgNeedParams {
+    unsigned char *base;
+    int Hp, Wp, n_layers;
+    int flags_off, maps_off, maps_bytes, kmap_off;
+    int map_off[HG_NEED_MAX_TENSORS];       // need map of tensor t: one byte per 16x16 cell of its level
+    HgNeedLayer L[HG_NEED_MAX_LAYERS];      // launch order
+};
+hipError_t hg_need_launch(const HgNeedParams &p, hipStream_t s);
 struct HgFinalFusedArgs {
     const f16 *img;
     const uint8_t *mask;

@@ -360,8 +360,9 @@ __global__ __launch_bounds__(256) void conv_c3_q8_kernel(const f16 *__restrict__
 // ================================================================================== hg_prep
 __global__ __launch_bounds__(256) void hg_prep_kernel(const f16 *__restrict__ base, int H, int W, int Hp, int Wp,
                                                       f16 *__restrict__ img_pad, uint8_t *__restrict__ mask, float r,
-                                                      float thresh)
+                                                      float thresh, uint8_t *__restrict__ flags)
 {
+    const int fw = (Wp + 15) >> 4;
     const size_t n = (size_t)Hp * Wp;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int yp = (int)(i / Wp), xp = (int)(i % Wp);
@@ -376,6 +377,8 @@ __global__ __launch_bounds__(256) void hg_prep_kernel(const f16 *__restrict__ ba
         m = (m - r) / (1.f - r);
         m = fminf(fmaxf(m, 0.f), 1.f);
         mask[i] = m > thresh ? 1 : 0;
+        // the cell holds a masked pixel of the cropped frame (a masked pixel of the reflect padding reaches no output)
+        if (flags && m > thresh && yp < H && xp < W) flags[(yp >> 4) * fw + (xp >> 4)] = 1;
     }
 }
 
@@ -523,13 +526,18 @@ __global__ __launch_bounds__(256) void hg_final_light_kernel(HgFinalLightParams 
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         const int y = (int)(e / nx), x0 = (int)(e - (size_t)y * nx) * 4;
         const size_t pix = (size_t)y * p.Wp + x0;          // Wp is a multiple of 32: the four pixels exist in every padded tensor
+        const uint32_t m4 = *reinterpret_cast<const uint32_t *>(p.mask + pix);
+        // The mask is 0 / 1: an unmasked pixel is img itself and its sums are not read (tiles the need lists skipped hold whatever an
+        // earlier frame left there).  A masked pixel keeps the arithmetic below to the letter, 1 * v + img.
         float4 pt[4], p2[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { pt[k] = reinterpret_cast<const float4 *>(p.part)[pix + k]; p2[k] = reinterpret_cast<const float4 *>(p.part2)[pix + k]; }
+        for (int k = 0; k < 4; ++k) {
+            pt[k] = p2[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if ((m4 >> (8 * k)) & 0xff) { pt[k] = reinterpret_cast<const float4 *>(p.part)[pix + k]; p2[k] = reinterpret_cast<const float4 *>(p.part2)[pix + k]; }
+        }
         f16x4 iv[3];
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) iv[ch] = *reinterpret_cast<const f16x4 *>(p.img + ch * plane_i + pix);
-        const uint32_t m4 = *reinterpret_cast<const uint32_t *>(p.mask + pix);
         float res[3][4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -543,7 +551,7 @@ __global__ __launch_bounds__(256) void hg_final_light_kernel(HgFinalLightParams 
 #pragma unroll
                 for (int t = 0; t < 3; ++t) v += wl[ch * 6 + t] * c10[t] + wl[ch * 6 + 3 + t] * im[t];
                 v = (float)(f16)v;
-                res[ch][k] = m * v + im[ch];
+                res[ch][k] = m != 0.f ? m * v + im[ch] : im[ch];
             }
         }
         const size_t oo = (size_t)y * p.W + x0;
@@ -620,10 +628,10 @@ hipError_t conv_c3_q8_launch(const f16 *in, int H, int W, const int8_t *wq, cons
 }
 
 hipError_t hg_prep_launch(const f16 *base, int H, int W, int Hp, int Wp, f16 *img_pad, uint8_t *mask, float r, float thresh,
-                          hipStream_t s)
+                          hipStream_t s, uint8_t *flags)
 {
     hipLaunchKernelGGL(hg_prep_kernel, dim3(grid_for((size_t)Hp * Wp, 256)), dim3(256), 0, s, base, H, W, Hp, Wp, img_pad,
-                       mask, r, thresh);
+                       mask, r, thresh, flags);
     return hipGetLastError();
 }
 

@@ -193,7 +193,11 @@ int hdrtv_ring_destroy(hdrtv_ctx *ctx);
 
 /* ---- introspection for parity tests and profiling (no reference counterpart) ----------
  * Looks up an internal activation by name after hdrtv_infer (e.g. "le.cond1", "hg.conv4_2").
- * layout: 0 = NHWC f16, 1 = planar CHW f16, 2 = planar CHW f32, 3 = f32 vector. */
+ * layout: 0 = NHWC f16, 1 = planar CHW f16, 2 = planar CHW f32, 3 = f32 vector.
+ * An hg.* tensor always comes back whole.  With variant hg_sparse (the default) a frame computes only the tiles of the HG head that
+ * its highlight mask lets reach the output; when lane 0's last frame ran that way, hdrtv_get_tap first runs the head's layers
+ * once more over every tile (from the hg.img still in the workspace, without the blend, on that frame's stream; synchronise
+ * before reading) and then returns the pointer.  Taps are a debugging surface: the frame path never takes them. */
 int hdrtv_get_tap(hdrtv_ctx *ctx, const char *name, void **dev_ptr, int *C, int *H, int *W,
                   int *layout);
 /* Number of kernel launches one hdrtv_infer issues at the reserved size, and the algorithmic
@@ -213,7 +217,11 @@ int hdrtv_profile_get(hdrtv_ctx *ctx, int i, const char **layer, const char **ke
 /* Developer / test switch with no reference counterpart: selects which of several equivalent kernels or schedules a
  * layer runs on (e.g. "le_rows": 1 = the fused row-streaming LE kernels, 0 = one launch per layer).  The table is
  * filled at hdrtv_create (defaults, then the creating process's HDRTV_VARIANTS="name=value,..."); the launch path never
- * reads the environment.  Takes effect at the next hdrtv_infer; HDRTV_EINVAL for an unknown name. */
+ * reads the environment.  Takes effect at the next hdrtv_infer; HDRTV_EINVAL for an unknown name.
+ * "hg_sparse" (default 1; fp16 HG, hdrtv_infer and hdrtv_infer_lane alike): the HG head's conv_prw layers compute only the tiles
+ * a masked output pixel depends on -- the lists are built on the device from the frame's mask (no host round trip; the launch
+ * grids do not depend on frame content) -- and the blend takes img where the mask is 0.  Output bit-identical to 0 (every
+ * tile) for finite HG values; see hdrtv_get_tap for the taps.  hdrtv_infer_stats keeps reporting the dense model's MACs. */
 int hdrtv_set_variant(hdrtv_ctx *ctx, const char *name, int value);
 int hdrtv_get_variant(hdrtv_ctx *ctx, const char *name, int *value);
 
