@@ -28,7 +28,7 @@ constexpr int BN = 128;
 constexpr int A_PIECES_PER_WAVE = 6, A_BYTES = 8 * A_PIECES_PER_WAVE * 1024;   // 324 halo px -> 48 KiB
 constexpr int B_BYTES = BN * PIXB, B_PIECES_PER_WAVE = 2;                       // 16 KiB
 constexpr int SS_OFF = 2 * A_BYTES + 3 * B_BYTES;        // two 1-KiB {scale[128], shift[128]} slots
-constexpr int DOTW_OFF = SS_OFF + 2048;                  // ST_PS_DOT3: 3 x 64 floats
+constexpr int DOTW_OFF = SS_OFF + 2048;                  // ST_PS_DOT3: 24 fragment pairs (hi, lo) of 32 B
 constexpr int SMEM = DOTW_OFF + 1024;                    // 147 KiB
 
 // stores per wave and tile, by store mode (see the epilogues)
@@ -137,8 +137,22 @@ __global__ __launch_bounds__(512) void conv_pglds_kernel(ConvParams p)
     };
 
     if constexpr (MODE == ST_PS_DOT3) {          // before any DMA is in flight (ordinary loads drain the queue)
-        float *s_w = reinterpret_cast<float *>(smem + DOTW_OFF);
-        for (int e = tid; e < 3 * 64; e += 512) s_w[e] = p.dotw[e];
+        // The 64 -> 3 dot products run as conv_prw<ps_dot3> runs them (conv3x3_prw.hip: same table, same MFMA chain, same sums), so
+        // that Up_conv5's partial sums do not depend on which of the two kernels a layer is routed to (variant prw).  Table entry
+        // ((half * 3 + o) * 4 + kg): the A-operand fragment of output o over the channels 32 half .. 32 half + 31 for the lanes
+        // of k-group kg, an fp32 weight as hi + lo * 2^-10 in two f16 values.
+        if (tid < 24) {
+            const int kgq = tid & 3, o = (tid >> 2) % 3, half = tid / 12;
+            f16x8 hi, lo;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float w = p.dotw[o * 64 + half * 32 + (e < 4 ? 4 * kgq + e : 16 + 4 * kgq + e - 4)];
+                hi[e] = (f16)w;
+                lo[e] = (f16)((w - (float)hi[e]) * 1024.f);
+            }
+            *reinterpret_cast<f16x8 *>(smem + DOTW_OFF + tid * 32) = hi;
+            *reinterpret_cast<f16x8 *>(smem + DOTW_OFF + tid * 32 + 16) = lo;
+        }
         __syncthreads();
     }
 
@@ -322,38 +336,32 @@ __global__ __launch_bounds__(512) void conv_pglds_kernel(ConvParams p)
                 *reinterpret_cast<f16x8 *>(d) = v;
             }
         } else {   // ST_PS_DOT3: pixel shuffle, then 64 -> 3 dot products; only 3 partial sums per pixel leave the CU
-            const float *s_w = reinterpret_cast<const float *>(smem + DOTW_OFF);
-            float a0[4], a1[4], a2[4];
+            // On the matrix pipe, per 32-channel half of the wave's 64 channels (= one wave of conv_prw): the f16 results of a
+            // pixel row are the B operand, output rows 4 q + o carry output o of pixel row q, so after the four rows lane (kg, l15)
+            // holds the three sums of pixel (kg, l15) in registers 0..2.  Half 0 + half 1 is the sum conv_prw's wave pair forms.
+            const int orow = l15 & 3, qrow = l15 >> 2;
+            const f16x8 zero8 = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
+            float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) a0[j] = a1[j] = a2[j] = 0.f;
+            for (int half = 0; half < 2; ++half) {
+                const char *tb = smem + DOTW_OFF + (((half * 3 + (orow < 3 ? orow : 0)) * 4 + kg) << 5);
+                f16x8 fh = *reinterpret_cast<const f16x8 *>(tb), fl = *reinterpret_cast<const f16x8 *>(tb + 16);
+                if (orow == 3) { fh = zero8; fl = zero8; }
+                f32x4 ah = {0.f, 0.f, 0.f, 0.f}, al = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float4 w0 = *reinterpret_cast<const float4 *>(s_w + i * 16 + 4 * kg);
-                const float4 w1 = *reinterpret_cast<const float4 *>(s_w + 64 + i * 16 + 4 * kg);
-                const float4 w2 = *reinterpret_cast<const float4 *>(s_w + 128 + i * 16 + 4 * kg);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float x0 = (float)o[i][j][0], x1 = (float)o[i][j][1], x2 = (float)o[i][j][2], x3 = (float)o[i][j][3];
-                    a0[j] += w0.x * x0 + w0.y * x1 + w0.z * x2 + w0.w * x3;
-                    a1[j] += w1.x * x0 + w1.y * x1 + w1.z * x2 + w1.w * x3;
-                    a2[j] += w2.x * x0 + w2.y * x1 + w2.z * x2 + w2.w * x3;
+                for (int jj = 0; jj < 4; ++jj) {
+                    const f16x4 o0 = o[2 * half][jj], o1 = o[2 * half + 1][jj];
+                    const f16x8 bq = {o0[0], o0[1], o0[2], o0[3], o1[0], o1[1], o1[2], o1[3]};
+                    const bool mine = qrow == jj;
+                    ah = __builtin_amdgcn_mfma_f32_16x16x32_f16(mine ? fh : zero8, bq, ah, 0, 0, 0);
+                    al = __builtin_amdgcn_mfma_f32_16x16x32_f16(mine ? fl : zero8, bq, al, 0, 0, 0);
                 }
+                constexpr float k = 1.f / 1024.f;
+                const float4 v = make_float4(ah[0] + al[0] * k, ah[1] + al[1] * k, ah[2] + al[2] * k, 0.f);
+                if (half == 0) r = v;
+                else { r.x += v.x; r.y += v.y; r.z += v.z; }
             }
-            // Sum the four k-groups of a pixel through the wave-private strip (ordinary LDS writes and reads), NOT with
-            // ds_bpermute: with LDS-DMA of the workgroup in flight -- the next tile's weights are -- bpermute
-            // sporadically returned wrong lanes' data on gfx950 (tests/test_gpu_parity.py:
-            // test_persistent_schedules_do_not_change_results caught ~5000 of 8.3 M pixels per frame).  Lane
-            // (kg, l15) then finishes row j = kg of the wave's four rows: one float4 store per lane, none wasted.
             const int sub = cur.n0 / 64 + wc;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                *reinterpret_cast<float4 *>(stg + j * 1024 + kg * 256 + l15 * 16) = make_float4(a0[j], a1[j], a2[j], 0.f);
-            float4 r = *reinterpret_cast<const float4 *>(stg + kg * 1024 + l15 * 16);
-#pragma unroll
-            for (int k = 1; k < 4; ++k) {
-                const float4 v = *reinterpret_cast<const float4 *>(stg + kg * 1024 + k * 256 + l15 * 16);
-                r.x += v.x; r.y += v.y; r.z += v.z;
-            }
             const int oy = cur.oy0 + wp * 4 + kg;
             const int Y = 2 * oy + (sub >> 1), X = 2 * ox + (sub & 1);
             const bool ok = oy < p.Ho && ox < p.Wo && Y < p.Hd && X < p.Wd;

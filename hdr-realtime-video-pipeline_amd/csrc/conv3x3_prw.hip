@@ -359,8 +359,8 @@ __global__ __launch_bounds__(512) void conv_prw_kernel(ConvParams p)
             // The f16 results of a pixel row (as the reference's fp16 graph holds Up_conv5's output) are the B operand of one
             // v_mfma_f32_16x16x32_f16 per weight half (hi, lo): K = the wave's 32 channels, output rows 4 q + o carry output o of
             // pixel row 4 pass + q, so after four rows lane (kg, l15) holds the three sums of pixel (4 pass + kg, l15) in
-            // registers 0..2 -- the layout the pair hand-off below expects.  fp32 accumulation as conv_pglds's, associated
-            // differently (and the weights to 22 bits): the results agree with it to rounding, not bit for bit.
+            // registers 0..2 -- the layout the pair hand-off below expects.  conv_pglds<ps_dot3> forms the same sums with the same
+            // table and MFMA chain (one wave holds both channel halves there): the two kernels agree bit for bit, keep them so.
             const int orow = l15 & 3, qrow = l15 >> 2;
             const char *tb = smem + DOTW_OFF + ((((wave & 1) * 3 + (orow < 3 ? orow : 0)) * 4 + kg) << 5);
             const f16x8 zero8 = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};

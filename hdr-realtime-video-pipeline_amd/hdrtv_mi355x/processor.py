@@ -228,6 +228,7 @@ class HDRTVNetMI355X:
         self._buf_hw = None
         self._gpu_input = self._gpu_cond = self._gpu_raw = None
         self._pin_input = self._pin_output = None
+        self._pin_uploaded = None                 # event behind the last upload out of _pin_input
         self._gpu_out = self._gpu_agcm = self._gpu_u8 = None
         print(f"MI355X device : {self.device}")
         # which arithmetic a W8A8 layer runs in depends on the kernel the launch sequence picks for it per resolution
@@ -301,6 +302,7 @@ class HDRTVNetMI355X:
             self._gpu_out = torch.empty((1, 3, h, w), dtype=torch.float32 if (self._use_hg or self._fp32) else torch.float16, device=dev)
             self._gpu_agcm = torch.empty((1, 3, h, w), dtype=self._dtype, device=dev)
             self._pin_input = torch.empty((h, w, 3), dtype=torch.uint8, pin_memory=True)
+            self._pin_uploaded = None
             self._pin_output = torch.empty((h, w, 3), dtype=torch.uint8, pin_memory=True)
             # lane l > 0: its own boundary tensors (input, cond, out, agcm) and stream; lane 0 is the set above
             self._lane_bufs = [(self._gpu_input, self._gpu_cond, self._gpu_out, self._gpu_agcm)]
@@ -380,8 +382,15 @@ class HDRTVNetMI355X:
             self._gpu_raw.copy_(staged, non_blocking=True)
         else:
             src = np.ascontiguousarray(frame_bgr)
+            # the staging buffer is reused: the last frame's upload out of it is asynchronous and must have been read before the
+            # host overwrites it (two calls without a synchronisation in between uploaded the second frame twice)
+            if self._pin_uploaded is not None:
+                self._pin_uploaded.synchronize()
             C.memmove(self._pin_input.data_ptr(), src.ctypes.data, src.nbytes)
             self._gpu_raw.copy_(self._pin_input, non_blocking=True)
+            if self._pin_uploaded is None:
+                self._pin_uploaded = torch.cuda.Event()
+            self._pin_uploaded.record(torch.cuda.current_stream(self.device))
         self._chk(self._lib.hdrtv_preprocess(self._ctx, self._stream(), self._gpu_raw.data_ptr(), h, w,
                                              self._gpu_input.data_ptr(), self._gpu_cond.data_ptr()), "hdrtv_preprocess")
         return self._gpu_input, self._gpu_cond

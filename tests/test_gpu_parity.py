@@ -545,15 +545,9 @@ def test_private_weight_conv_schedule_is_bit_identical(torch_cuda, golden_dir, m
             for other in res[1:]:
                 for name, a, b in zip(("out",) + taps + ("hg.part",), res[0], other):
                     assert torch.isfinite(a.float()).all(), (h, w, name)
-                    if name in ("out", "hg.part"):
-                        # Up_conv5's fused 64 -> 3 dot products: conv_prw adds a pixel's channels per wave (32) and then the
-                        # wave pair, conv_pglds per lane over all 64 -- the same fp32 products, associated differently
-                        # (hg.part itself moves by an fp32 rounding; behind it hg_final_fused rounds conv10 to f16 as the reference's
-                        # fp16 graph does, so isolated output values move by one f16 step, 4.9e-4, never by more)
-                        dd = (a.float() - b.float()).abs()
-                        assert dd.max().item() <= (2e-6 if name == "hg.part" else 1e-3) and dd.mean().item() <= 1e-6, (h, w, name, dd.max().item())
-                    else:
-                        assert torch.equal(a, b), (h, w, name)
+                    # Up_conv5's fused 64 -> 3 dot products included: both kernels form them per 32-channel half on the matrix
+                    # pipe from one table and add the halves (conv_prw across a wave pair, conv_pglds inside a wave)
+                    assert torch.equal(a, b), (h, w, name, int((a != b).sum()))
             assert torch.equal(res[1][0], res[2][0]) and torch.equal(res[1][-1], res[2][-1])      # both conv_prw runs agree exactly
     finally:
         p.close()
