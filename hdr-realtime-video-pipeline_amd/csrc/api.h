@@ -10,6 +10,7 @@
 #include "../../include/hdrtv_mi355x.h"
 
 #include <algorithm>
+#include <array>
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -260,6 +261,8 @@ struct hdrtv_ctx {
     void *lb_dev = nullptr;
     size_t lb_cap = 0;
     float *pq_bnd = nullptr;              // hdrtv_post_pq_rgb48: the 65536 code boundaries of the PQ quantiser (built on first use)
+    // hdrtv_post_rgb48_scaled: device tap tables per (H, W, dH, dW), xtab [dW] then ytab [dH]; built on first use of a geometry
+    std::map<std::array<int, 4>, int4 *> ps_tabs;
     // objective metrics partial sums
     double *mt_dev = nullptr;
     size_t mt_cap = 0;

@@ -383,6 +383,19 @@ struct LetterboxParams {
     const int *xc, *yc;
 };
 
+// Fused quantise + Lanczos upscale (post_scale.hip): planar [3][H][W] f16 / f32 -> u16 [dH][dW][3] RGB, dH >= H and dW >= W.
+// xtab [dW] / ytab [dH]: per destination index {first of six source taps (unclamped), q0 | q1 << 16, q2 | q3 << 16, q4 | q5 << 16},
+// the six coefficients as int16 with sum 16384 (include/hdrtv_mi355x.h states the rule).
+constexpr int PS_TW = 64, PS_TH = 32;            // output pixels per workgroup
+struct PostScaleParams {
+    const void *in;
+    uint16_t *dst;
+    const int4 *xtab, *ytab;
+    const float *pq_bnd;             // PQ variant: the code boundaries of hdrtv_post_pq_rgb48
+    float peak;
+    int H, W, dH, dW;
+};
+
 // Objective metrics (metrics.hip): two unit-range images [3][H][W], per-workgroup partial sums {squared error, SSIM, dE-ITP}
 struct MetricsParams {
     const void *a, *b;

@@ -68,6 +68,7 @@ int hdrtv_destroy(hdrtv_ctx *c)
     for (hipEvent_t ev : c->prof_ev) (void)hipEventDestroy(ev);
     if (c->pq_bnd) (void)hipFree(c->pq_bnd);
     if (c->lb_dev) (void)hipFree(c->lb_dev);
+    for (auto &kv : c->ps_tabs) (void)hipFree(kv.second);
     if (c->mt_dev) (void)hipFree(c->mt_dev);
     free_workspaces(c);
     if (c->wts.dev) (void)hipFree(c->wts.dev);
@@ -325,6 +326,75 @@ int hdrtv_post_pq_rgb48(hdrtv_ctx *c, void *stream, const void *in, int dtype, i
     }
     hipError_t e = post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, 1, peak_nits, (hipStream_t)stream, c->pq_bnd);
     return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "post_pq_rgb48: %s", hipGetErrorString(e));
+}
+
+// ------------------------------------------------------------------- RGB48 at the display size
+// Tap table of one axis of hdrtv_post_rgb48_scaled (the rule: include/hdrtv_mi355x.h), n source -> m >= n destination samples:
+// per destination index the first of six source taps (i0 - 2, unclamped) and six int16 coefficients that sum to 16384.
+static void lanczos_taps(int n, int m, int4 *out)
+{
+    const double PI = 3.14159265358979323846;
+    auto sinc = [&](double x) { return x == 0.0 ? 1.0 : std::sin(PI * x) / (PI * x); };
+    for (int d = 0; d < m; ++d) {
+        const double c = (d + 0.5) * n / m - 0.5, f = std::floor(c), t = c - f;
+        double w[6], sum = 0.0;
+        for (int k = 0; k < 6; ++k) {
+            const double x = t - (k - 2);
+            w[k] = std::fabs(x) < 3.0 ? sinc(x) * sinc(x / 3.0) : 0.0;
+            sum += w[k];
+        }
+        int q[6], tot = 0, big = 0;
+        for (int k = 0; k < 6; ++k) {
+            q[k] = (int)std::floor(w[k] / sum * 16384.0 + 0.5);
+            tot += q[k];
+            if (q[k] > q[big]) big = k;          // the lowest k on a tie
+        }
+        q[big] += 16384 - tot;
+        auto pack = [](int lo, int hi) { return (int)(((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16)); };
+        out[d] = make_int4((int)f - 2, pack(q[0], q[1]), pack(q[2], q[3]), pack(q[4], q[5]));
+    }
+}
+
+int hdrtv_post_rgb48_scaled(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
+                            uint16_t *dst, int dH, int dW)
+{
+    if (!c || !in || !dst || H <= 0 || W <= 0 || dH <= 0 || dW <= 0) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: bad argument");
+    if (dH < H || dW < W) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: %dx%d -> %dx%d shrinks (enlarging only)", W, H, dW, dH);
+    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: bad dtype %d", dtype);
+    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: pq needs peak_nits > 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (pq && !c->pq_bnd) {
+        std::vector<float> bnd;
+        pq_boundaries(bnd);
+        if (hipMalloc((void **)&c->pq_bnd, bnd.size() * 4) != hipSuccess) { c->pq_bnd = nullptr; return fail(c, HDRTV_ENOMEM, "post_rgb48_scaled: table allocation failed"); }
+        HIPCHK(c, hipMemcpy(c->pq_bnd, bnd.data(), bnd.size() * 4, hipMemcpyHostToDevice));
+    }
+    if (dH == H && dW == W) {                    // every tap table would be the identity: the unscaled kernel writes the same bytes
+        hipError_t e0 = post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd);
+        return e0 == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "post_rgb48_scaled: %s", hipGetErrorString(e0));
+    }
+    // first use of a geometry builds its tables (allocates, copies); every later call finds them and only launches
+    const std::array<int, 4> key{H, W, dH, dW};
+    auto it = c->ps_tabs.find(key);
+    if (it == c->ps_tabs.end()) {
+        if (c->ps_tabs.size() >= 16) {            // a service cycles through a handful of sizes; hipFree waits for kernels in flight
+            for (auto &kv : c->ps_tabs) (void)hipFree(kv.second);
+            c->ps_tabs.clear();
+        }
+        std::vector<int4> tab((size_t)dW + dH);
+        lanczos_taps(W, dW, tab.data());
+        lanczos_taps(H, dH, tab.data() + dW);
+        int4 *dev = nullptr;
+        if (hipMalloc((void **)&dev, tab.size() * sizeof(int4)) != hipSuccess) return fail(c, HDRTV_ENOMEM, "post_rgb48_scaled: table allocation failed");
+        if (hipMemcpy(dev, tab.data(), tab.size() * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(dev);
+            return fail(c, HDRTV_EHIP, "post_rgb48_scaled: table upload failed");
+        }
+        it = c->ps_tabs.emplace(key, dev).first;
+    }
+    PostScaleParams p{in, dst, it->second, it->second + dW, c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
+    hipError_t e = post_scale_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream);
+    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "post_rgb48_scaled: %s", hipGetErrorString(e));
 }
 
 // ------------------------------------------------------------------------------- letterbox

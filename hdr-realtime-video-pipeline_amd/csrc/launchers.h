@@ -126,6 +126,7 @@ hipError_t hg_final_fused_launch(const HgFinalFusedArgs &a, int n_cu, hipStream_
 // the same tail when conv_c3_launch(..., w2frag, part2) has left conv10's second half per pixel: a per-pixel kernel (a.wfrag, scale, shift unused)
 hipError_t hg_final_light_launch(const HgFinalFusedArgs &a, const float *part2, hipStream_t s);
 hipError_t letterbox_launch(const LetterboxParams &p, hipStream_t s);
+hipError_t post_scale_launch(const PostScaleParams &p, int is_f32, int pq, hipStream_t s);
 hipError_t metrics_launch(const MetricsParams &p, hipStream_t s);
 int metrics_blocks(int H, int W);
 

@@ -100,21 +100,23 @@ class _Mi355xWorker:
                                "pageable transfers")
         self._registered = ptr
 
-    def _buffers(self, h, w, in_shape):
+    def _buffers(self, h, w, in_shape, out_hw):
         torch = self._torch
-        if self._hw != (h, w, in_shape):
+        if self._hw != (h, w, in_shape, out_hw):
             self.proc._ensure_buffers(h, w)
             self._raw = [torch.empty(in_shape, dtype=torch.uint8, device=self.dev) for _ in range(self.depth)]
-            self._u16 = [torch.empty((h, w, 3), dtype=torch.uint16, device=self.dev) for _ in range(self.depth)]
+            self._u16 = [torch.empty(out_hw + (3,), dtype=torch.uint16, device=self.dev) for _ in range(self.depth)]
             self._up_ev = [torch.cuda.Event() for _ in range(self.depth)]
             self._comp_ev = [None] * self.depth
             self._dn_ev = [None] * self.depth
-            self._hw = (h, w, in_shape)
+            self._hw = (h, w, in_shape, out_hw)
 
     def begin(self, frame, out):
         torch, p = self._torch, self.proc
-        h, w = out.shape[:2]                  # a 4:2:0 input slot is (h*3//2, w)
-        self._buffers(h, w, frame.shape)
+        # the processing size is the input slot's (a 4:2:0 slot is (h*3//2, w)), the delivered size the output slot's
+        h, w = (frame.shape[0], frame.shape[1]) if frame.ndim == 3 else (frame.shape[0] * 2 // 3, frame.shape[1])
+        out_hw = (int(out.shape[0]), int(out.shape[1]))
+        self._buffers(h, w, tuple(frame.shape), out_hw)
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
         # frame's kernels with the next frame's (processor.enqueue_frame); one lane = the single compute stream of before
@@ -131,11 +133,11 @@ class _Mi355xWorker:
         if self._dn_ev[k] is not None:
             main.wait_event(self._dn_ev[k])                    # u16[k]'s previous frame has left the device
         if self.input_format[0] == "bgr24":
-            p.enqueue_frame(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), stream=main)
+            p.enqueue_frame(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), stream=main, out_hw=out_hw)
         else:
             fmt, matrix, full = self.input_format
             p.enqueue_frame_yuv420(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), layout=fmt, matrix=matrix,
-                                   full_range=full, stream=main)
+                                   full_range=full, stream=main, out_hw=out_hw)
         self._comp_ev[k] = torch.cuda.Event()
         self._comp_ev[k].record(main)
         self._dn.wait_event(self._comp_ev[k])
@@ -232,10 +234,11 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, task_q, done_
     shm, ins, outs, body = None, None, None, None
     code = 0
     try:
-        h, w, slots = geom
+        h, w, slots = geom[:3]
+        oh, ow = geom[3:5] if len(geom) > 3 else (h, w)        # the size of the output slots (FrameDispatcher out_height / out_width)
         input_format = tuple(input_format or ("bgr24", 709, False))
         in_shape = _in_shape(h, w, input_format[0])
-        in_b, out_b = int(np.prod(in_shape)), h * w * 6
+        in_b, out_b = int(np.prod(in_shape)), oh * ow * 6
         # placement first: affinity, then the slots (created and first-touched HERE, on the GPU's node), then the GPU
         from . import numa
         info = numa.pin_to_gpu_node(device_index, apply=bool(use_numa)) if use_numa is not None else {"device": device_index, "numa_node": -1, "cpus": [], "pinned": False}
@@ -258,7 +261,7 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, task_q, done_
         if hasattr(body, "pin"):
             body.pin(shm.buf)
         ins = [np.ndarray(in_shape, np.uint8, shm.buf, offset=s * in_b) for s in range(slots)]
-        outs = [np.ndarray((h, w, 3), np.uint16, shm.buf, offset=slots * in_b + s * out_b) for s in range(slots)]
+        outs = [np.ndarray((oh, ow, 3), np.uint16, shm.buf, offset=slots * in_b + s * out_b) for s in range(slots)]
         depth = max(1, int(getattr(body, "depth", 1)))
         free_out = list(range(slots))
         backlog = collections.deque()
@@ -338,13 +341,16 @@ def _in_shape(h, w, pix_fmt):
 
 class FrameDispatcher:
     def __init__(self, n_workers, height, width, sink, make_worker=mi355x_worker, init_args=None, devices=None, slots=3,
-                 start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False):
+                 start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False, out_height=None,
+                 out_width=None):
         """``sink(index, rgb48_view)`` is called in index order from the reorder thread; the view is only valid during the
         call (the slot goes back to its worker afterwards).  ``numa``: workers pin themselves to their GPU's NUMA node
         (False: report only).  ``pix_fmt``: ``bgr24`` input frames are u8 (H, W, 3); ``yuv420p`` / ``nv12`` frames are u8
         (H*3//2, W), the planes back to back (half the slot bytes and copies), which the product's worker converts on the device
         with ``yuv_matrix`` / ``yuv_full_range`` (``HDRTVNetMI355X.enqueue_frame_yuv420``); stand-in workers receive them as they
-        are.  Output slots, order and sink do not depend on it."""
+        are.  Output slots, order and sink do not depend on it.  ``out_height`` / ``out_width`` (default: the processing size, not
+        below it): the output slots and the sink's views are ``(out_height, out_width, 3)``; the product's worker upscales in
+        its RGB48 conversion (``enqueue_frame(..., out_hw=)``), stand-in workers fill slots of that size."""
         if n_workers < 1 or slots < 2:
             raise ValueError("n_workers >= 1 and slots >= 2")
         if pix_fmt not in ("bgr24", "yuv420p", "nv12"):
@@ -354,12 +360,15 @@ class FrameDispatcher:
         if int(yuv_matrix) not in (601, 709, 2020):
             raise ValueError("yuv_matrix must be 601, 709 or 2020")
         self.n, self.h, self.w, self.slots = int(n_workers), int(height), int(width), int(slots)
+        self.out_h, self.out_w = int(out_height or height), int(out_width or width)
+        if self.out_h < self.h or self.out_w < self.w:
+            raise ValueError(f"output size {self.out_w}x{self.out_h} is below the processing size {self.w}x{self.h} (enlarging only)")
         self.pix_fmt = pix_fmt
         self._in_shape = _in_shape(self.h, self.w, pix_fmt)
         fmt = (pix_fmt, int(yuv_matrix), bool(yuv_full_range))
         self._sink = sink
         ctx = mp.get_context("spawn")           # fresh interpreters: nothing GPU-related is inherited
-        self._in_b, self._out_b = int(np.prod(self._in_shape)), self.h * self.w * 6
+        self._in_b, self._out_b = int(np.prod(self._in_shape)), self.out_h * self.out_w * 6
         self._shm = [None] * self.n             # created by the workers (first touch on their GPU's node), attached below
         # ... under names chosen HERE, so that close() can unlink a segment whose worker died between creating it and saying so
         self._shm_names = [f"hdrtv_{os.getpid()}_{uuid.uuid4().hex[:12]}_{r}" for r in range(self.n)]
@@ -370,7 +379,7 @@ class FrameDispatcher:
         self._stop = False
         self._procs = [ctx.Process(target=_worker_main, daemon=True,
                                    args=(r, devices[r], make_worker, dict(init_args or {}),
-                                         (self.h, self.w, self.slots), self._task[r], self._done, bool(numa), self._shm_names[r], fmt))
+                                         (self.h, self.w, self.slots, self.out_h, self.out_w), self._task[r], self._done, bool(numa), self._shm_names[r], fmt))
                        for r in range(self.n)]
         for p in self._procs:
             p.start()
@@ -409,7 +418,7 @@ class FrameDispatcher:
                 self.placement[rank] = payload
                 buf = self._shm[rank].buf
                 self._ins[rank] = [np.ndarray(self._in_shape, np.uint8, buf, offset=s * self._in_b) for s in range(self.slots)]
-                self._outs[rank] = [np.ndarray((self.h, self.w, 3), np.uint16, buf, offset=self.slots * self._in_b + s * self._out_b)
+                self._outs[rank] = [np.ndarray((self.out_h, self.out_w, 3), np.uint16, buf, offset=self.slots * self._in_b + s * self._out_b)
                                     for s in range(self.slots)]
                 continue
             ready += 1

@@ -525,7 +525,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("--weights-dir", required=True, help="directory holding original/HR.pt (or .hdrw) [and original/HG.pt]")
     ap.add_argument("--precision", default="FP16")
-    ap.add_argument("--size", default="3840x2160")
+    ap.add_argument("--size", default="3840x2160", help="processing size WxH: the size the network runs at")
+    ap.add_argument("--out-size", default=None, help="size WxH the sink receives frames at (default: --size; not below it on either "
+                    "axis): the RGB48 conversion upscales on the device (hdrtv_post_rgb48_scaled)")
     ap.add_argument("--fps", type=float, default=60.0)
     ap.add_argument("--frames", type=int, default=240)
     ap.add_argument("--input", help="rawvideo file at --size in --pix-fmt (default: synthetic frames)")
@@ -541,6 +543,9 @@ def main(argv=None):
     ap.add_argument("--csv")
     a = ap.parse_args(argv)
     wd, ht = (int(v) for v in a.size.lower().split("x", 1))
+    owd, oht = (int(v) for v in a.out_size.lower().split("x", 1)) if a.out_size else (wd, ht)
+    if owd < wd or oht < ht:
+        ap.error(f"--out-size {owd}x{oht} is below --size {wd}x{ht}: the output stage only enlarges")
     if a.input:
         src = RawVideoSource(a.input, wd, ht, a.fps, pix_fmt=a.pix_fmt, yuv_matrix=a.yuv_matrix, yuv_full_range=a.yuv_range == "full")
     elif a.pix_fmt != "bgr24":
@@ -550,12 +555,12 @@ def main(argv=None):
     if not a.no_prefetch:
         src = PinnedPrefetch(src)
     worker = HeadlessPipelineWorker(a.weights_dir, use_hg=not a.no_hg, proc_w=wd, proc_h=ht, hg_weights=a.hg_weights,
-                                    status_cb=lambda m: print(m, flush=True))
+                                    status_cb=lambda m: print(m, flush=True), out_w=owd, out_h=oht)
     if not worker._load_model(a.precision):
         return 1
     sink = None
     if a.out:
-        sink = Rgb48leSink(a.out, wd, ht, a.fps)
+        sink = Rgb48leSink(a.out, owd, oht, a.fps)             # the sink, mpv_args() and ffmpeg_input_args() speak of the output size
         worker._start_hdr_feeder(sink)
     pb = RealtimePlayback(worker, src, sink=bool(sink), frame_stride=a.stride, realtime=not a.max_throughput, csv_path=a.csv)
     res = pb.run(max_frames=a.frames)
@@ -569,6 +574,8 @@ def main(argv=None):
     worker.close()
     lm = res.pop("last_metrics") or {}
     res.update({k: lm.get(k) for k in ("latency_ms", "model_latency_ms", "fps_1p_low", "proc_res", "precision")})
+    if a.out_size:
+        res["out_res"] = f"{owd}x{oht}"
     print(json.dumps(res))
     return 0
 

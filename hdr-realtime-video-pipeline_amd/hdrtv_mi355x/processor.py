@@ -323,12 +323,22 @@ class HDRTVNetMI355X:
         ``_ensure_buffers``)."""
         return self._lane_streams[lane]
 
-    def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None):
+    def _post_rgb48(self, st, tout, dt, h, w, dst_rgb48_ptr, out_hw):
+        """The tail of ``enqueue_frame*``: RGB48 at the processing size, or at ``out_hw = (out_h, out_w)`` (each >= the processing
+        size) through ``hdrtv_post_rgb48_scaled``."""
+        if out_hw is None or (int(out_hw[0]), int(out_hw[1])) == (h, w):
+            self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, tout.data_ptr(), dt, h, w, dst_rgb48_ptr), "hdrtv_post_rgb48")
+        else:
+            self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, tout.data_ptr(), dt, h, w, 0, 0.0, dst_rgb48_ptr,
+                                                        int(out_hw[0]), int(out_hw[1])), "hdrtv_post_rgb48_scaled")
+
+    def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None):
         """One frame of the hot path on lane ``lane``, stream-ordered and without any host synchronisation: u8 BGR frame in
         device memory at ``src_bgr_ptr`` -> hdrtv_preprocess -> hdrtv_infer_lane -> hdrtv_post_rgb48 -> u16 RGB48 at the device
         address ``dst_rgb48_ptr``.  ``stream``: a ``torch.cuda.Stream`` (default: the lane's own).  Frames enqueued on different
         lanes may overlap on the device; the bytes written do not depend on the lane (tests/test_gpu_lanes.py).  The caller
-        orders the use of ``src`` / ``dst`` against the stream (events), as with any asynchronous launch."""
+        orders the use of ``src`` / ``dst`` against the stream (events), as with any asynchronous launch.  ``out_hw = (out_h,
+        out_w)``: the frame is delivered at that size (``hdrtv_post_rgb48_scaled``; ``dst`` holds out_h * out_w * 3 u16)."""
         if not 0 <= lane < self._lanes:
             raise ValueError(f"lane {lane} of {self._lanes}")
         self._ensure_buffers(h, w)
@@ -338,9 +348,10 @@ class HDRTVNetMI355X:
         self._chk(self._lib.hdrtv_preprocess(self._ctx, st, src_bgr_ptr, h, w, tin.data_ptr(), tcond.data_ptr()), "hdrtv_preprocess")
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, tout.data_ptr(), dt, h, w, dst_rgb48_ptr), "hdrtv_post_rgb48")
+        self._post_rgb48(st, tout, dt, h, w, dst_rgb48_ptr, out_hw)
 
-    def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None):
+    def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None,
+                             out_hw=None):
         """``enqueue_frame`` of an 8-bit 4:2:0 frame: the planes lie back to back at the device address ``src_ptr`` (the
         ``(h*3//2, w)`` u8 array ``preprocess_yuv420`` takes) and ``hdrtv_preprocess_yuv420`` replaces ``hdrtv_preprocess``."""
         if not 0 <= lane < self._lanes:
@@ -354,7 +365,7 @@ class HDRTVNetMI355X:
                   "hdrtv_preprocess_yuv420")
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, tout.data_ptr(), dt, h, w, dst_rgb48_ptr), "hdrtv_post_rgb48")
+        self._post_rgb48(st, tout, dt, h, w, dst_rgb48_ptr, out_hw)
 
     # ------------------------------------------------------------------ API
     @torch.inference_mode()
@@ -564,6 +575,26 @@ class HDRTVNetMI355X:
         self._pin_output.copy_(self._gpu_u8, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         return self._pin_output.numpy()
+
+    @torch.inference_mode()
+    def postprocess_rgb48_scaled(self, output, out_w, out_h, pq=False, peak_nits=1000.0):
+        """RGB48 at the display size: the u16 codes of ``hdrtv_post_rgb48`` (``pq=True``: of
+        ``hdrtv_post_pq_rgb48`` at ``peak_nits``) upscaled to ``out_h`` x ``out_w`` by ``hdrtv_post_rgb48_scaled`` in one kernel.
+        Returns a new device u16 ``(out_h, out_w, 3)`` tensor; stream-ordered on the current stream, no synchronisation."""
+        if isinstance(output, (tuple, list)):
+            output = output[0]
+        if output.dtype not in (torch.float16, torch.float32):
+            raise ValueError("postprocess_rgb48_scaled expects an fp16 or fp32 tensor")
+        h, w = int(output.shape[-2]), int(output.shape[-1])
+        out_w, out_h = int(out_w), int(out_h)
+        if out_w < w or out_h < h:
+            raise ValueError(f"output size {out_w}x{out_h} is below the processing size {w}x{h} (enlarging only)")
+        output = output.contiguous()
+        dst = torch.empty((out_h, out_w, 3), dtype=torch.uint16, device=self.device)
+        self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, self._stream(), output.data_ptr(),
+                                                    _L.F32 if output.dtype == torch.float32 else _L.F16, h, w, 1 if pq else 0,
+                                                    float(peak_nits), dst.data_ptr(), out_h, out_w), "hdrtv_post_rgb48_scaled")
+        return dst
 
     @torch.inference_mode()
     def process(self, frame_bgr):

@@ -108,11 +108,14 @@ class HostFrame:
 
 class HeadlessPipelineWorker:
     def __init__(self, weights_dir, use_hg=True, proc_w=1920, proc_h=1080, hg_weights=None,
-                 status_cb=None, buffer_frames=1):
+                 status_cb=None, buffer_frames=1, out_w=None, out_h=None):
         self._weights_dir = weights_dir
         self._use_hg = bool(use_hg)
         self._hg_override = hg_weights
         self._proc_w, self._proc_h = int(proc_w), int(proc_h)
+        # the size frames are delivered at; None = the processing size.  It belongs to the sink, not to the
+        # model: a hot-swap of the processing resolution keeps it.
+        self._out_w, self._out_h = (int(out_w) if out_w else None), (int(out_h) if out_h else None)
         self._processor = None
         self._precision_key = None
         self.status_messages = []
@@ -236,7 +239,9 @@ class HeadlessPipelineWorker:
         """frame_processing.py:168-331 (SDR->HDR branch).  Returns the reference's 5-tuple
         ``(display_frame, output, prepared_out, need_hdr_cpu, model_latency_ms)``; with a sink
         attached (``mpv_w`` truthy and the HDR feeder running) the staged tensor and its ready
-        event are queued as ``(present_t, tensor, event)``."""
+        event are queued as ``(present_t, tensor, event, out_hw)``.  ``out_w`` / ``out_h`` (default: the worker's own): the size
+        the sink receives the frame at, each >= the processing size; the upscale is part of the RGB48 conversion
+        (``hdrtv_post_rgb48_scaled``) whether or not ``lower_res_processing`` is set."""
         if self._processor is None:
             raise RuntimeError("no model loaded")
         if self._hdr_error is not None:        # the feeder thread died: surface it instead of silently dropping frames
@@ -245,6 +250,9 @@ class HeadlessPipelineWorker:
         start, end = self._cuda_timing_events()
         start.record(torch.cuda.current_stream())
         pw, ph = int(proc_w or self._proc_w), int(proc_h or self._proc_h)
+        ow, oh = int(out_w or self._out_w or pw), int(out_h or self._out_h or ph)
+        if ow < pw or oh < ph:
+            raise ValueError(f"output size {ow}x{oh} is below the processing size {pw}x{ph} (enlarging only)")
         with torch.inference_mode():
             if frame.ndim == 2:
                 # 8-bit 4:2:0 planes: converted on the device (set_input_format), letterboxed there when the sizes differ
@@ -268,7 +276,7 @@ class HeadlessPipelineWorker:
             staged = self._stage_hdr_display_tensor(prepared_out, use_cuda)
             ready = torch.cuda.Event(enable_timing=False)
             ready.record(torch.cuda.current_stream())
-            self._queue_display_item(self._hdr_queue, (present_t, staged, ready))
+            self._queue_display_item(self._hdr_queue, (present_t, staged, ready, (oh, ow)))
         need_hdr_cpu = not mpv_w
         output = self._processor.postprocess(prepared_out) if need_hdr_cpu else frame
         return None, output, prepared_out, need_hdr_cpu, model_latency_ms
@@ -285,17 +293,28 @@ class HeadlessPipelineWorker:
             q.put_nowait(item)
 
     # ---------------------------------------------------------------- RGB48 ring + feeder
-    def _tensor_to_rgb48_bytes(self, tensor, stream=None):
+    def _tensor_to_rgb48_bytes(self, tensor, stream=None, out_hw=None):
         """feeders.py:193-249, GPU branch: quantise to RGB48 directly into a pinned ring slot and
         return a ``PinnedFrame`` guarded by the slot's ready event.  Ring exhaustion (no slot free
         within 250 ms, feeders.py:166-167) falls back to one blocking pinned buffer as the reference
-        does (209-235): convert, copy, synchronise the stream, hand the finished frame over."""
+        does (209-235): convert, copy, synchronise the stream, hand the finished frame over.  ``out_hw = (out_h, out_w)``: the
+        ring, the fallback buffer and the frame are at that size and the conversion is ``hdrtv_post_rgb48_scaled``."""
         p = self._processor
         t = tensor[0] if isinstance(tensor, (tuple, list)) else tensor
-        h, w = int(t.shape[-2]), int(t.shape[-1])
+        th, tw = int(t.shape[-2]), int(t.shape[-1])
+        h, w = (int(out_hw[0]), int(out_hw[1])) if out_hw is not None else (th, tw)
+        if h < th or w < tw:
+            raise ValueError(f"output size {w}x{h} is below the tensor's {tw}x{th} (enlarging only)")
         if self._ring_shape != (h, w):
             p._chk(p._lib.hdrtv_ring_create(p._ctx, _RING_FRAMES, h, w), "hdrtv_ring_create")
             self._ring_shape = (h, w)
+
+        def convert(dst):
+            if (h, w) == (th, tw):
+                p._chk(p._lib.hdrtv_post_rgb48(p._ctx, sp, t.contiguous().data_ptr(), dt, th, tw, dst), "hdrtv_post_rgb48")
+            else:
+                p._chk(p._lib.hdrtv_post_rgb48_scaled(p._ctx, sp, t.contiguous().data_ptr(), dt, th, tw, 0, 0.0, dst, h, w),
+                       "hdrtv_post_rgb48_scaled")
         host, dev = C.c_void_p(), C.c_void_p()
         st = stream or torch.cuda.current_stream(p.device)
         sp = C.c_void_p(st.cuda_stream)
@@ -307,13 +326,13 @@ class HeadlessPipelineWorker:
                 self._fallback = (torch.empty((h, w, 3), dtype=torch.uint16, pin_memory=True),
                                   torch.empty((h, w, 3), dtype=torch.uint16, device=p.device))
             fb_host, fb_dev = self._fallback
-            p._chk(p._lib.hdrtv_post_rgb48(p._ctx, sp, t.contiguous().data_ptr(), dt, h, w, fb_dev.data_ptr()), "hdrtv_post_rgb48")
+            convert(fb_dev.data_ptr())
             with torch.cuda.stream(st):
                 fb_host.copy_(fb_dev, non_blocking=True)
             st.synchronize()
             return HostFrame(fb_host.numpy().copy())       # the reference's host_np.tobytes(): a private copy
         p._chk(slot, "hdrtv_ring_acquire")
-        p._chk(p._lib.hdrtv_post_rgb48(p._ctx, sp, t.contiguous().data_ptr(), dt, h, w, dev), "hdrtv_post_rgb48")
+        convert(dev)
         p._chk(p._lib.hdrtv_ring_commit(p._ctx, slot, sp), "hdrtv_ring_commit")
         return PinnedFrame(self, slot, host.value, (h, w, 3))
 
@@ -323,11 +342,12 @@ class HeadlessPipelineWorker:
         self._stop_hdr_feeder()
         self._hdr_sink = sink
         self._hdr_error = None
-        if self._processor is not None and self._ring_shape != (self._proc_h, self._proc_w):
+        ring_hw = (self._out_h or self._proc_h, self._out_w or self._proc_w)         # the size frames are delivered at
+        if self._processor is not None and self._ring_shape != ring_hw:
             # pin the ring now (3 x 50 MB at 4K takes tens of ms) rather than inside the first frame's deadline
             p = self._processor
-            p._chk(p._lib.hdrtv_ring_create(p._ctx, _RING_FRAMES, self._proc_h, self._proc_w), "hdrtv_ring_create")
-            self._ring_shape = (self._proc_h, self._proc_w)
+            p._chk(p._lib.hdrtv_ring_create(p._ctx, _RING_FRAMES, ring_hw[0], ring_hw[1]), "hdrtv_ring_create")
+            self._ring_shape = ring_hw
         # feeders.py:634-644: queue depth = buffer_frames (1..3).  With the staging pool of buffer_frames + 2
         # (_stage_hdr_display_tensor) that is exactly enough: queued + the one in the feeder's hands + the one
         # being staged; one more queued frame and the main stream overwrites a tensor the side stream still reads.
@@ -347,10 +367,10 @@ class HeadlessPipelineWorker:
                         continue
                     if item is None:
                         break
-                    present_t, tensor, ready = item
+                    present_t, tensor, ready, out_hw = item
                     ready.synchronize()                      # cross-thread device sync (feeders.py:469-473)
                     with torch.cuda.stream(side):
-                        payload = self._tensor_to_rgb48_bytes(tensor, side)
+                        payload = self._tensor_to_rgb48_bytes(tensor, side, out_hw)
                     if present_t is not None:
                         delay = present_t - time.perf_counter()
                         if delay > 0:

@@ -127,6 +127,32 @@ int hdrtv_post_rgb48(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtyp
 int hdrtv_post_pq_rgb48(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W,
                         float peak_nits, uint16_t *dst);
 
+/* RGB48 at the display size: hdrtv_post_rgb48 (pq = 0; peak_nits ignored) or hdrtv_post_pq_rgb48 (pq != 0) and a Lanczos-3
+ * upscale of its codes to [dH][dW][3], in one kernel without a frame-sized intermediate.  The reference's "lower-resolution
+ * processing" mode leaves this resize to mpv's scalers (gui_scaling.py:13-15, 42-43, 67-162) or, on its CPU path, to
+ * cv2.resize(INTER_LANCZOS4) (gui_pipeline_worker_frame_processing.py:100-116); a headless sink has neither in front of it.
+ * Parity with mpv's or OpenCV's scalers is UNPINNED (neither is part of the reference tree, and their float paths are not
+ * reproducible); the resampling is this integer rule, restated in tests/rgb48_scale_ref.py, which the GPU tests hold this entry
+ * point to bit for bit.  Enlarging only (dH >= H, dW >= W); the whole frame maps onto the whole output (black bars of a
+ * letterboxed input are scaled with it), the axes are independent, aspect is the caller's business.  No anti-ringing, no
+ * shrinking, no crop rectangle.
+ *  1. codes: s[c][y][x] = the u16 code hdrtv_post_rgb48 / hdrtv_post_pq_rgb48 writes for that source value; the resampling sees
+ *     nothing but these integers.
+ *  2. per axis, source extent n, destination extent m, for d = 0..m-1, in double:
+ *       c = (d + 0.5) * n / m - 0.5;  i0 = floor(c);  t = c - i0;  six taps k = -2..3 at source index clamp(i0 + k, 0, n-1)
+ *       w_k = L(t - k), L(x) = sinc(x) * sinc(x/3) for |x| < 3, else 0, sinc(x) = sin(pi x)/(pi x), L(0) = 1;  w_k /= sum(w)
+ *       q_k = floor(w_k * 16384 + 0.5);  then 16384 - sum(q) is added to the largest q_k (the lowest k on a tie): sum(q) = 16384.
+ *     m == n gives q = {0, 0, 16384, 0, 0, 0}; exact 2x has the two phases {121, -1114, 4440, 14628, -2184, 493} (first tap
+ *     i0 - 2 = -3 at d = 0) and its mirror image.
+ *  3. two passes: hor[y][dx] = sum_k s[y][.] * qx_k (exact in int32: sum |q| <= 25290);
+ *     out = clamp((sum_k hor[.][dx] * qy_k + 2^27) >> 28, 0, 65535) with a flooring shift (the sum needs 46 bits).
+ * With dH == H and dW == W the bytes equal the unscaled entry point's.  Stream-ordered, needs no reservation; the tap tables are
+ * built on the host in double at the first call with a geometry (H, W, dH, dW) -- that call allocates and copies -- and kept in the
+ * context, so later calls only launch.  HDRTV_EINVAL for a NULL pointer, a non-positive size, dH < H or dW < W, an unknown dtype,
+ * or pq with peak_nits <= 0; dst is not touched then. */
+int hdrtv_post_rgb48_scaled(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W,
+                            int pq, float peak_nits, uint16_t *dst, int dH, int dW);
+
 /* The host step in front of preprocess, on the device: _letterbox_bgr
  * (src/gui_scaling.py:228-244), i.e. cv2.resize preserving the aspect ratio -- INTER_AREA when shrinking,
  * INTER_CUBIC when enlarging -- centred on a black [dh][dw] canvas.  src / dst are device u8 BGR HWC.
