@@ -396,6 +396,17 @@ struct PostScaleParams {
     int H, W, dH, dW;
 };
 
+// 10-bit limited-range BT.2020nc Y'CbCr output (post_ycbcr.hip; include/hdrtv_mi355x.h states the integer rule): a workgroup owns
+// YC_TH x YC_TW luma pixels.  fmt / siting carry the header's HDRTV_YCC_* / HDRTV_SITING_* values; pitches in u16 elements.
+constexpr int YC_TW = 128, YC_TH = 16;
+struct Ycbcr10Params {
+    const void *in;                  // planar [3][H][W] f16 / f32 (post_ycbcr10_launch) or u16 [H][W][3] RGB48 codes (rgb48_to_ycbcr10_launch)
+    uint16_t *dst_y, *dst_u, *dst_v; // P010: dst_u = the interleaved CbCr plane, dst_v unused
+    const float *pq_bnd;             // PQ variant: the code boundaries of hdrtv_post_pq_rgb48
+    float peak;
+    int H, W, y_pitch, c_pitch, fmt, siting;
+};
+
 // Objective metrics (metrics.hip): two unit-range images [3][H][W], per-workgroup partial sums {squared error, SSIM, dE-ITP}
 struct MetricsParams {
     const void *a, *b;

@@ -328,6 +328,62 @@ int hdrtv_post_pq_rgb48(hdrtv_ctx *c, void *stream, const void *in, int dtype, i
     return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "post_pq_rgb48: %s", hipGetErrorString(e));
 }
 
+// ------------------------------------------------------------------- 10-bit Y'CbCr output
+// The argument rules of include/hdrtv_mi355x.h shared by the two entry points; fills the launch parameters (pitches in u16).
+static int ycbcr10_args(hdrtv_ctx *c, const char *what, const void *src, int H, int W, int fmt, int siting, uint16_t *dst_y,
+                        int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch, Ycbcr10Params &p)
+{
+    if (!c || !src || !dst_y || !dst_u || H <= 0 || W <= 0) return fail(c, HDRTV_EINVAL, "%s: bad argument", what);
+    if (fmt != HDRTV_YCC_P010 && fmt != HDRTV_YCC_YUV420P10 && fmt != HDRTV_YCC_YUV422P10) return fail(c, HDRTV_EINVAL, "%s: unknown fmt %d", what, fmt);
+    if (siting != HDRTV_SITING_LEFT && siting != HDRTV_SITING_TOPLEFT) return fail(c, HDRTV_EINVAL, "%s: unknown siting %d", what, siting);
+    if (fmt == HDRTV_YCC_YUV422P10 && siting != HDRTV_SITING_LEFT) return fail(c, HDRTV_EINVAL, "%s: 4:2:2 chroma is co-sited (siting LEFT only)", what);
+    if ((W & 1) || (fmt != HDRTV_YCC_YUV422P10 && (H & 1))) return fail(c, HDRTV_EINVAL, "%s: %dx%d is odd for this chroma layout", what, W, H);
+    if (fmt == HDRTV_YCC_P010 ? dst_v != nullptr : dst_v == nullptr) return fail(c, HDRTV_EINVAL, "%s: dst_v must be %s for this fmt", what, fmt == HDRTV_YCC_P010 ? "NULL" : "given");
+    const int c_min = fmt == HDRTV_YCC_P010 ? 2 * W : W;
+    if ((y_pitch & 1) || (c_pitch & 1) || y_pitch < 2 * W || c_pitch < c_min)
+        return fail(c, HDRTV_EINVAL, "%s: pitches %d / %d are short or odd (need even, >= %d / %d bytes)", what, y_pitch, c_pitch, 2 * W, c_min);
+    p = Ycbcr10Params{src, dst_y, dst_u, dst_v, nullptr, 0.f, H, W, y_pitch / 2, c_pitch / 2, fmt, siting};
+    return HDRTV_OK;
+}
+
+int hdrtv_post_ycbcr10(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits, int fmt, int siting,
+                       uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch)
+{
+    Ycbcr10Params p;
+    if (int rc = ycbcr10_args(c, "post_ycbcr10", in, H, W, fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch, p)) return rc;
+    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_ycbcr10: bad dtype %d", dtype);
+    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_ycbcr10: pq needs peak_nits > 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (pq && !c->pq_bnd) {
+        std::vector<float> bnd;
+        pq_boundaries(bnd);
+        if (hipMalloc((void **)&c->pq_bnd, bnd.size() * 4) != hipSuccess) { c->pq_bnd = nullptr; return fail(c, HDRTV_ENOMEM, "post_ycbcr10: table allocation failed"); }
+        HIPCHK(c, hipMemcpy(c->pq_bnd, bnd.data(), bnd.size() * 4, hipMemcpyHostToDevice));
+    }
+    p.pq_bnd = c->pq_bnd;
+    p.peak = pq ? peak_nits : 0.f;
+    hipError_t e = post_ycbcr10_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream);
+    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "post_ycbcr10: %s", hipGetErrorString(e));
+}
+
+int hdrtv_rgb48_to_ycbcr10(hdrtv_ctx *c, void *stream, const uint16_t *src, int H, int W, int fmt, int siting, uint16_t *dst_y,
+                           int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch)
+{
+    Ycbcr10Params p;
+    if (int rc = ycbcr10_args(c, "rgb48_to_ycbcr10", src, H, W, fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch, p)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipError_t e = rgb48_to_ycbcr10_launch(p, (hipStream_t)stream);
+    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "rgb48_to_ycbcr10: %s", hipGetErrorString(e));
+}
+
+int64_t hdrtv_ycbcr10_bytes(int fmt, int H, int W)
+{
+    if (H <= 0 || W <= 0 || (W & 1)) return HDRTV_EINVAL;
+    if (fmt == HDRTV_YCC_YUV422P10) return (int64_t)H * W * 4;
+    if ((fmt != HDRTV_YCC_P010 && fmt != HDRTV_YCC_YUV420P10) || (H & 1)) return HDRTV_EINVAL;
+    return (int64_t)H * W * 3;
+}
+
 // ------------------------------------------------------------------- RGB48 at the display size
 // Tap table of one axis of hdrtv_post_rgb48_scaled (the rule: include/hdrtv_mi355x.h), n source -> m >= n destination samples:
 // per destination index the first of six source taps (i0 - 2, unclamped) and six int16 coefficients that sum to 16384.
@@ -597,7 +653,8 @@ int hdrtv_ring_acquire(hdrtv_ctx *c, int timeout_ms, uint16_t **host_ptr, uint16
 // Slot life cycle: 0 free -> (acquire) 1 acquired -> (commit) 2 committed -> (release) 0.  Every entry point looks its slot up
 // and checks its state under ring_mu (the consumer thread calls wait / release while the producer acquires and commits, and
 // hdrtv_ring_destroy may run between them): a call in the wrong state is HDRTV_ESTATE, not stale pixels.
-int hdrtv_ring_commit(hdrtv_ctx *c, int slot, void *stream)
+// whole = hdrtv_ring_commit (the slot's H * W * 6 bytes); otherwise the first `want` bytes (hdrtv_ring_commit_bytes)
+static int ring_commit_impl(hdrtv_ctx *c, int slot, void *stream, bool whole, size_t want)
 {
     if (!c) return HDRTV_EINVAL;
     uint16_t *host = nullptr, *dev = nullptr;
@@ -609,6 +666,10 @@ int hdrtv_ring_commit(hdrtv_ctx *c, int slot, void *stream)
         if (c->ring[slot].state != 1) return fail(c, HDRTV_ESTATE, "ring slot %d is not acquired (state %d)", slot, c->ring[slot].state);
         host = c->ring[slot].host; dev = c->ring[slot].dev; ev = c->ring[slot].ev;
         bytes = (size_t)c->ring_H * c->ring_W * 6;
+        if (!whole) {
+            if (want == 0 || want > bytes) return fail(c, HDRTV_EINVAL, "ring commit of %zu bytes: a slot holds %zu", want, bytes);
+            bytes = want;
+        }
         // enqueue under the lock: hdrtv_ring_destroy cannot free the buffers between the look-up and the copy (both calls
         // only enqueue; neither blocks on the device)
         hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream);
@@ -619,6 +680,10 @@ int hdrtv_ring_commit(hdrtv_ctx *c, int slot, void *stream)
     }
     return HDRTV_OK;
 }
+
+int hdrtv_ring_commit(hdrtv_ctx *c, int slot, void *stream) { return ring_commit_impl(c, slot, stream, true, 0); }
+
+int hdrtv_ring_commit_bytes(hdrtv_ctx *c, int slot, void *stream, size_t bytes) { return ring_commit_impl(c, slot, stream, false, bytes); }
 
 // Blocks on a committed slot's event OUTSIDE ring_mu.  The event stays alive meanwhile: the call is counted in ring_waiters,
 // and hdrtv_ring_destroy (also reached through hdrtv_ring_create) waits for that count to drop to zero before it frees anything.

@@ -57,6 +57,7 @@ class _Mi355xWorker:
 
     depth = 2
     input_format = ("bgr24", 709, False)     # (pix_fmt, matrix, full_range); _worker_main sets the dispatcher's
+    output_format = None                     # (out_pix_fmt, out_siting, out_h, out_w) of Y'CbCr output slots (1-D u16); None = RGB48
 
     def __init__(self, rank, device_index, init_args):
         import ctypes as C
@@ -105,7 +106,8 @@ class _Mi355xWorker:
         if self._hw != (h, w, in_shape, out_hw):
             self.proc._ensure_buffers(h, w)
             self._raw = [torch.empty(in_shape, dtype=torch.uint8, device=self.dev) for _ in range(self.depth)]
-            self._u16 = [torch.empty(out_hw + (3,), dtype=torch.uint16, device=self.dev) for _ in range(self.depth)]
+            self._u16 = [torch.empty(out_hw + (3,) if self.output_format is None else (self._out_n,), dtype=torch.uint16, device=self.dev)
+                         for _ in range(self.depth)]
             self._up_ev = [torch.cuda.Event() for _ in range(self.depth)]
             self._comp_ev = [None] * self.depth
             self._dn_ev = [None] * self.depth
@@ -115,7 +117,11 @@ class _Mi355xWorker:
         torch, p = self._torch, self.proc
         # the processing size is the input slot's (a 4:2:0 slot is (h*3//2, w)), the delivered size the output slot's
         h, w = (frame.shape[0], frame.shape[1]) if frame.ndim == 3 else (frame.shape[0] * 2 // 3, frame.shape[1])
-        out_hw = (int(out.shape[0]), int(out.shape[1]))
+        if self.output_format is None:
+            out_hw, out_fmt = (int(out.shape[0]), int(out.shape[1])), {}
+        else:                                                  # a Y'CbCr slot is the frame's planes back to back
+            out_hw, self._out_n = tuple(self.output_format[2:4]), int(out.size)
+            out_fmt = dict(out_pix_fmt=self.output_format[0], out_siting=self.output_format[1])
         self._buffers(h, w, tuple(frame.shape), out_hw)
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
@@ -133,11 +139,11 @@ class _Mi355xWorker:
         if self._dn_ev[k] is not None:
             main.wait_event(self._dn_ev[k])                    # u16[k]'s previous frame has left the device
         if self.input_format[0] == "bgr24":
-            p.enqueue_frame(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), stream=main, out_hw=out_hw)
+            p.enqueue_frame(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), stream=main, out_hw=out_hw, **out_fmt)
         else:
             fmt, matrix, full = self.input_format
             p.enqueue_frame_yuv420(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), layout=fmt, matrix=matrix,
-                                   full_range=full, stream=main, out_hw=out_hw)
+                                   full_range=full, stream=main, out_hw=out_hw, **out_fmt)
         self._comp_ev[k] = torch.cuda.Event()
         self._comp_ev[k].record(main)
         self._dn.wait_event(self._comp_ev[k])
@@ -189,12 +195,12 @@ class _HostSimWorker:
             self._result = np.empty(out.shape, out.dtype)
             self._result[...] = 257 * (self.rank + 1)
         np.copyto(self._staged, frame)                     # "H2D": the slot's 24.9 MB (4K) leave host memory
-        self._result[0, 0, 0] = int(frame.flat[0]) * 257   # (so that a test can tell the frames apart; 3-D BGR or 2-D 4:2:0)
-        self._result[0, 0, 1] = self.rank
+        self._result.flat[0] = int(frame.flat[0]) * 257    # (so that a test can tell the frames apart; 3-D BGR or 2-D 4:2:0)
+        self._result.flat[1] = self.rank
         start = max(time.perf_counter(), self._busy_until)
         self._busy_until = start + self.device_ms * 1e-3   # the device works on one frame at a time
         self.cpu_s += time.thread_time() - t0
-        return (out, self._busy_until, int(self._result[0, 0, 0]))
+        return (out, self._busy_until, int(self._result.flat[0]))
 
     def finish(self, token):
         out, t_done, tag = token
@@ -203,7 +209,7 @@ class _HostSimWorker:
             time.sleep(dt)
         t0 = time.thread_time()
         np.copyto(out, self._result)                       # "D2H": 49.8 MB (4K) land in host memory
-        out[0, 0, 0] = tag
+        out.flat[0] = tag
         self.cpu_s += time.thread_time() - t0
 
 
@@ -238,7 +244,9 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, task_q, done_
         oh, ow = geom[3:5] if len(geom) > 3 else (h, w)        # the size of the output slots (FrameDispatcher out_height / out_width)
         input_format = tuple(input_format or ("bgr24", 709, False))
         in_shape = _in_shape(h, w, input_format[0])
-        in_b, out_b = int(np.prod(in_shape)), oh * ow * 6
+        out_pix_fmt, out_siting = geom[5:7] if len(geom) > 5 else ("rgb48le", "left")
+        out_shape = _out_shape(oh, ow, out_pix_fmt)
+        in_b, out_b = int(np.prod(in_shape)), 2 * int(np.prod(out_shape))
         # placement first: affinity, then the slots (created and first-touched HERE, on the GPU's node), then the GPU
         from . import numa
         info = numa.pin_to_gpu_node(device_index, apply=bool(use_numa)) if use_numa is not None else {"device": device_index, "numa_node": -1, "cpus": [], "pinned": False}
@@ -258,10 +266,12 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, task_q, done_
             body = _SyncBody(body)
         if input_format[0] != "bgr24" and hasattr(body, "input_format"):
             body.input_format = input_format
+        if out_pix_fmt != "rgb48le" and hasattr(body, "output_format"):
+            body.output_format = (out_pix_fmt, out_siting, oh, ow)
         if hasattr(body, "pin"):
             body.pin(shm.buf)
         ins = [np.ndarray(in_shape, np.uint8, shm.buf, offset=s * in_b) for s in range(slots)]
-        outs = [np.ndarray((oh, ow, 3), np.uint16, shm.buf, offset=slots * in_b + s * out_b) for s in range(slots)]
+        outs = [np.ndarray(out_shape, np.uint16, shm.buf, offset=slots * in_b + s * out_b) for s in range(slots)]
         depth = max(1, int(getattr(body, "depth", 1)))
         free_out = list(range(slots))
         backlog = collections.deque()
@@ -339,10 +349,17 @@ def _in_shape(h, w, pix_fmt):
     return (h, w, 3) if pix_fmt == "bgr24" else (h * 3 // 2, w)
 
 
+def _out_shape(oh, ow, out_pix_fmt):
+    """An output slot's frame: u16 RGB48 (oh, ow, 3), or the 10-bit Y'CbCr planes back to back as a 1-D u16 array of
+    ``lib.out_frame_bytes`` bytes (hdrtv_ycbcr10_bytes' formula)."""
+    from . import lib as L
+    return (oh, ow, 3) if out_pix_fmt == "rgb48le" else (L.out_frame_bytes(out_pix_fmt, oh, ow) // 2,)
+
+
 class FrameDispatcher:
     def __init__(self, n_workers, height, width, sink, make_worker=mi355x_worker, init_args=None, devices=None, slots=3,
                  start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False, out_height=None,
-                 out_width=None):
+                 out_width=None, out_pix_fmt="rgb48le", out_siting="left"):
         """``sink(index, rgb48_view)`` is called in index order from the reorder thread; the view is only valid during the
         call (the slot goes back to its worker afterwards).  ``numa``: workers pin themselves to their GPU's NUMA node
         (False: report only).  ``pix_fmt``: ``bgr24`` input frames are u8 (H, W, 3); ``yuv420p`` / ``nv12`` frames are u8
@@ -350,7 +367,10 @@ class FrameDispatcher:
         with ``yuv_matrix`` / ``yuv_full_range`` (``HDRTVNetMI355X.enqueue_frame_yuv420``); stand-in workers receive them as they
         are.  Output slots, order and sink do not depend on it.  ``out_height`` / ``out_width`` (default: the processing size, not
         below it): the output slots and the sink's views are ``(out_height, out_width, 3)``; the product's worker upscales in
-        its RGB48 conversion (``enqueue_frame(..., out_hw=)``), stand-in workers fill slots of that size."""
+        its RGB48 conversion (``enqueue_frame(..., out_hw=)``), stand-in workers fill slots of that size.  ``out_pix_fmt``
+        ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` (``out_siting`` ``left`` / ``topleft``): the product's worker delivers 10-bit
+        Y'CbCr (``enqueue_frame(..., out_pix_fmt=)``); the output slots and the sink's views are then 1-D u16 arrays of
+        ``hdrtv_ycbcr10_bytes`` bytes, the planes back to back -- half the slot bytes and D2H copy of RGB48 for 4:2:0."""
         if n_workers < 1 or slots < 2:
             raise ValueError("n_workers >= 1 and slots >= 2")
         if pix_fmt not in ("bgr24", "yuv420p", "nv12"):
@@ -363,12 +383,15 @@ class FrameDispatcher:
         self.out_h, self.out_w = int(out_height or height), int(out_width or width)
         if self.out_h < self.h or self.out_w < self.w:
             raise ValueError(f"output size {self.out_w}x{self.out_h} is below the processing size {self.w}x{self.h} (enlarging only)")
+        from . import lib as _L
+        self.out_pix_fmt, self.out_siting = _L.check_out_format(out_pix_fmt, out_siting)
+        self._out_shape = _out_shape(self.out_h, self.out_w, self.out_pix_fmt)      # raises for an odd size of a Y'CbCr layout
         self.pix_fmt = pix_fmt
         self._in_shape = _in_shape(self.h, self.w, pix_fmt)
         fmt = (pix_fmt, int(yuv_matrix), bool(yuv_full_range))
         self._sink = sink
         ctx = mp.get_context("spawn")           # fresh interpreters: nothing GPU-related is inherited
-        self._in_b, self._out_b = int(np.prod(self._in_shape)), self.out_h * self.out_w * 6
+        self._in_b, self._out_b = int(np.prod(self._in_shape)), 2 * int(np.prod(self._out_shape))
         self._shm = [None] * self.n             # created by the workers (first touch on their GPU's node), attached below
         # ... under names chosen HERE, so that close() can unlink a segment whose worker died between creating it and saying so
         self._shm_names = [f"hdrtv_{os.getpid()}_{uuid.uuid4().hex[:12]}_{r}" for r in range(self.n)]
@@ -379,7 +402,7 @@ class FrameDispatcher:
         self._stop = False
         self._procs = [ctx.Process(target=_worker_main, daemon=True,
                                    args=(r, devices[r], make_worker, dict(init_args or {}),
-                                         (self.h, self.w, self.slots, self.out_h, self.out_w), self._task[r], self._done, bool(numa), self._shm_names[r], fmt))
+                                         (self.h, self.w, self.slots, self.out_h, self.out_w, self.out_pix_fmt, self.out_siting), self._task[r], self._done, bool(numa), self._shm_names[r], fmt))
                        for r in range(self.n)]
         for p in self._procs:
             p.start()
@@ -418,7 +441,7 @@ class FrameDispatcher:
                 self.placement[rank] = payload
                 buf = self._shm[rank].buf
                 self._ins[rank] = [np.ndarray(self._in_shape, np.uint8, buf, offset=s * self._in_b) for s in range(self.slots)]
-                self._outs[rank] = [np.ndarray((self.out_h, self.out_w, 3), np.uint16, buf, offset=self.slots * self._in_b + s * self._out_b)
+                self._outs[rank] = [np.ndarray(self._out_shape, np.uint16, buf, offset=self.slots * self._in_b + s * self._out_b)
                                     for s in range(self.slots)]
                 continue
             ready += 1

@@ -18,6 +18,8 @@ OK, EINVAL, EWEIGHTS, EHIP, ENOMEM, ESTATE = 0, -1, -2, -3, -4, -5
 F16, F32 = 0, 1
 PREC_F16, PREC_F32 = 0, 1
 YUV_I420, YUV_NV12 = 0, 1                  # hdrtv_yuv420_to_bgr_u8 / hdrtv_preprocess_yuv420 layouts
+YCC_P010, YCC_YUV420P10, YCC_YUV422P10 = 0, 1, 2   # hdrtv_post_ycbcr10 / hdrtv_rgb48_to_ycbcr10 layouts
+SITING_LEFT, SITING_TOPLEFT = 0, 1
 
 # every symbol include/hdrtv_mi355x.h declares: (name, restype, argtypes)
 _VP, _I, _SZ = C.c_void_p, C.c_int, C.c_size_t
@@ -39,6 +41,9 @@ SYMBOLS = [
     ("hdrtv_post_rgb48", _I, [_VP, _VP, _VP, _I, _I, _I, _VP]),
     ("hdrtv_post_pq_rgb48", _I, [_VP, _VP, _VP, _I, _I, _I, C.c_float, _VP]),
     ("hdrtv_post_rgb48_scaled", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I]),
+    ("hdrtv_post_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I]),
+    ("hdrtv_rgb48_to_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I]),
+    ("hdrtv_ycbcr10_bytes", C.c_int64, [_I, _I, _I]),
     ("hdrtv_letterbox_u8", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I]),
     ("hdrtv_yuv420_to_bgr_u8", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     ("hdrtv_preprocess_yuv420", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP]),
@@ -46,6 +51,7 @@ SYMBOLS = [
     ("hdrtv_ring_create", _I, [_VP, _I, _I, _I]),
     ("hdrtv_ring_acquire", _I, [_VP, _I, C.POINTER(_VP), C.POINTER(_VP)]),
     ("hdrtv_ring_commit", _I, [_VP, _I, _VP]),
+    ("hdrtv_ring_commit_bytes", _I, [_VP, _I, _VP, _SZ]),
     ("hdrtv_ring_wait", _I, [_VP, _I]),
     ("hdrtv_ring_release", _I, [_VP, _I]),
     ("hdrtv_ring_destroy", _I, [_VP]),
@@ -58,6 +64,49 @@ SYMBOLS = [
     ("hdrtv_get_variant", _I, [_VP, C.c_char_p, C.POINTER(_I)]),
     ("hdrtv_last_error", C.c_char_p, [_VP]),
 ]
+
+# output pixel formats of the frame path: "rgb48le" (6 bytes per pixel, the default) and the 10-bit Y'CbCr layouts
+YCC_FORMATS = {"p010le": YCC_P010, "yuv420p10le": YCC_YUV420P10, "yuv422p10le": YCC_YUV422P10}
+YCC_SITINGS = {"left": SITING_LEFT, "topleft": SITING_TOPLEFT}
+OUT_PIX_FMTS = ("rgb48le",) + tuple(YCC_FORMATS)
+
+
+def check_out_format(pix_fmt, siting="left"):
+    """Validates an output format / chroma siting pair; returns them lower-cased."""
+    pix_fmt, siting = str(pix_fmt).lower(), str(siting).lower()
+    if pix_fmt not in OUT_PIX_FMTS:
+        raise ValueError(f"out_pix_fmt must be one of {list(OUT_PIX_FMTS)}")
+    if siting not in YCC_SITINGS:
+        raise ValueError(f"out_siting must be one of {sorted(YCC_SITINGS)}")
+    if pix_fmt == "yuv422p10le" and siting != "left":
+        raise ValueError("4:2:2 chroma is horizontally co-sited: out_siting must be 'left'")
+    return pix_fmt, siting
+
+
+def out_frame_bytes(pix_fmt, h, w):
+    """Bytes of one contiguous output frame: H * W * 6 for rgb48le, hdrtv_ycbcr10_bytes' formula for the Y'CbCr layouts (3 H W for
+    the two 4:2:0 layouts, 4 H W for 4:2:2; W even, H even for 4:2:0)."""
+    h, w = int(h), int(w)
+    if pix_fmt == "rgb48le":
+        return h * w * 6
+    if pix_fmt not in YCC_FORMATS:
+        raise ValueError(f"out_pix_fmt must be one of {list(OUT_PIX_FMTS)}")
+    if h <= 0 or w <= 0 or w % 2 or (pix_fmt != "yuv422p10le" and h % 2):
+        raise ValueError(f"{pix_fmt} needs an even width{'' if pix_fmt == 'yuv422p10le' else ' and height'} (got {w}x{h})")
+    return h * w * (4 if pix_fmt == "yuv422p10le" else 3)
+
+
+def ycbcr10_planes(ptr, h, w, pix_fmt, siting="left"):
+    """The trailing arguments of hdrtv_post_ycbcr10 / hdrtv_rgb48_to_ycbcr10 for a frame whose planes lie back to back at device
+    address ``ptr`` at their minimum pitches: (fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch)."""
+    out_frame_bytes(pix_fmt, h, w)
+    fmt, sit = YCC_FORMATS[pix_fmt], YCC_SITINGS[str(siting).lower()]
+    u = ptr + h * w * 2
+    if fmt == YCC_P010:
+        return fmt, sit, ptr, 2 * w, u, None, 2 * w
+    ch = h if fmt == YCC_YUV422P10 else h // 2
+    return fmt, sit, ptr, 2 * w, u, u + ch * w, w
+
 
 _libs = {}
 

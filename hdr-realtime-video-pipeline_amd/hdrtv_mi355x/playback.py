@@ -21,6 +21,7 @@ import time
 
 import numpy as np
 
+from . import lib as _lib
 from .weights import synthetic_frame
 
 # gui_pipeline_worker.py:38-40
@@ -248,6 +249,46 @@ class Rgb48leSink:
         return ["-f", "rawvideo", "-pix_fmt", "rgb48le", "-s:v", f"{self.width}x{self.height}", "-r", f"{self.fps:.6f}",
                 "-color_range", "pc", "-colorspace", "bt2020nc", "-color_trc", "smpte2084", "-color_primaries", "bt2020",
                 "-i", "-"]
+
+
+class RawVideoSink(Rgb48leSink):
+    """``Rgb48leSink`` for any output pixel format of the worker: ``rgb48le``, or the 10-bit limited-range BT.2020nc Y'CbCr
+    layouts ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` an encoder takes, written as headerless rawvideo
+    with the planes back to back.  ``siting``: where the 4:2:0 chroma samples sit (``left``, ffmpeg's default, or ``topleft``)."""
+
+    def __init__(self, target, width, height, fps, pix_fmt="rgb48le", siting="left"):
+        super().__init__(target, width, height, fps)
+        self.pix_fmt, self.siting = _lib.check_out_format(pix_fmt, siting)
+        self.frame_bytes = _lib.out_frame_bytes(self.pix_fmt, self.height, self.width)
+
+    def __call__(self, payload):
+        try:
+            view = payload.buffer_view()
+            if len(view) != self.frame_bytes:
+                raise ValueError(f"frame of {len(view)} bytes does not match {self.width}x{self.height} {self.pix_fmt}")
+            self._f.write(view)
+            self.frames += 1
+            self.bytes += len(view)
+        finally:
+            payload.release()
+
+    def mpv_args(self):
+        if self.pix_fmt == "rgb48le":
+            return super().mpv_args()
+        return ["--demuxer=rawvideo", f"--demuxer-rawvideo-w={self.width}", f"--demuxer-rawvideo-h={self.height}",
+                f"--demuxer-rawvideo-mp-format={self.pix_fmt[:-2]}", f"--demuxer-rawvideo-fps={self.fps:g}",
+                "--vf=format=colorlevels=limited:colormatrix=bt.2020-ncl:primaries=bt.2020:gamma=pq"]
+
+    def ffmpeg_input_args(self):
+        """Input half of an encode command: limited-range BT.2020nc / PQ 10-bit Y'CbCr on stdin.  ``-chroma_sample_location`` is
+        given only where ffmpeg needs it: ``left`` is what it assumes for 4:2:0 when nothing is said, and 4:2:2 has no choice."""
+        if self.pix_fmt == "rgb48le":
+            return super().ffmpeg_input_args()
+        args = ["-f", "rawvideo", "-pix_fmt", self.pix_fmt, "-s:v", f"{self.width}x{self.height}", "-r", f"{self.fps:.6f}",
+                "-color_range", "tv", "-colorspace", "bt2020nc", "-color_trc", "smpte2084", "-color_primaries", "bt2020"]
+        if self.siting == "topleft":
+            args += ["-chroma_sample_location", "topleft"]
+        return args + ["-i", "-"]
 
 
 # ------------------------------------------------------------------------------- metrics
@@ -534,7 +575,11 @@ def main(argv=None):
     ap.add_argument("--pix-fmt", choices=RawVideoSource.PIX_FMTS, default="bgr24", help="pixel format of --input")
     ap.add_argument("--yuv-matrix", type=int, choices=(601, 709, 2020), default=709, help="Y'CbCr matrix of a yuv420p / nv12 input")
     ap.add_argument("--yuv-range", choices=("limited", "full"), default="limited", help="Y'CbCr range of a yuv420p / nv12 input")
-    ap.add_argument("--out", help="rgb48le rawvideo output (file or fifo); omit to run without a display sink")
+    ap.add_argument("--out", help="rawvideo output in --out-pix-fmt (file or fifo); omit to run without a display sink")
+    ap.add_argument("--out-pix-fmt", choices=_lib.OUT_PIX_FMTS, default="rgb48le", help="what the sink receives: full-range RGB48, or "
+                    "10-bit limited-range BT.2020nc Y'CbCr for an encoder, converted on the device (hdrtv_post_ycbcr10)")
+    ap.add_argument("--out-siting", choices=sorted(_lib.YCC_SITINGS), default="left", help="chroma siting of a 4:2:0 --out-pix-fmt: left "
+                    "(MPEG-2 / H.264, ffmpeg's default) or topleft (BT.2100 / HDR10)")
     ap.add_argument("--no-hg", action="store_true")
     ap.add_argument("--hg-weights", default=None, help="HG weight file, or seeded:<n>")
     ap.add_argument("--max-throughput", action="store_true", help="do not pace to the source clock")
@@ -555,12 +600,13 @@ def main(argv=None):
     if not a.no_prefetch:
         src = PinnedPrefetch(src)
     worker = HeadlessPipelineWorker(a.weights_dir, use_hg=not a.no_hg, proc_w=wd, proc_h=ht, hg_weights=a.hg_weights,
-                                    status_cb=lambda m: print(m, flush=True), out_w=owd, out_h=oht)
+                                    status_cb=lambda m: print(m, flush=True), out_w=owd, out_h=oht, out_pix_fmt=a.out_pix_fmt,
+                                    out_siting=a.out_siting)
     if not worker._load_model(a.precision):
         return 1
     sink = None
     if a.out:
-        sink = Rgb48leSink(a.out, owd, oht, a.fps)             # the sink, mpv_args() and ffmpeg_input_args() speak of the output size
+        sink = RawVideoSink(a.out, owd, oht, a.fps, a.out_pix_fmt, a.out_siting)      # the sink, mpv_args() and ffmpeg_input_args() speak of the output size
         worker._start_hdr_feeder(sink)
     pb = RealtimePlayback(worker, src, sink=bool(sink), frame_stride=a.stride, realtime=not a.max_throughput, csv_path=a.csv)
     res = pb.run(max_frames=a.frames)
@@ -576,6 +622,8 @@ def main(argv=None):
     res.update({k: lm.get(k) for k in ("latency_ms", "model_latency_ms", "fps_1p_low", "proc_res", "precision")})
     if a.out_size:
         res["out_res"] = f"{owd}x{oht}"
+    if a.out_pix_fmt != "rgb48le":
+        res["out_pix_fmt"] = a.out_pix_fmt
     print(json.dumps(res))
     return 0
 

@@ -223,6 +223,7 @@ class HDRTVNetMI355X:
                 self._ctx = C.c_void_p()
                 raise
         self._lane_bufs, self._lane_streams = [], []
+        self._ycc_scratch = {}                 # _post_out: RGB48 at the output size per lane / caller (the two-launch Y'CbCr path)
         if self._fast_zero_condition or self._fast_condition_resize:
             self._chk(self._lib.hdrtv_set_cond_mode(self._ctx, 2 if self._fast_zero_condition else 1), "hdrtv_set_cond_mode")
         self._buf_hw = None
@@ -332,15 +333,43 @@ class HDRTVNetMI355X:
             self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, tout.data_ptr(), dt, h, w, 0, 0.0, dst_rgb48_ptr,
                                                         int(out_hw[0]), int(out_hw[1])), "hdrtv_post_rgb48_scaled")
 
-    def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None):
+    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out_hw, pix_fmt, siting, scratch_key):
+        """The output conversion of a frame whose planar tensor lies at ``src_ptr``: ``rgb48le`` as ``_post_rgb48``; a 10-bit
+        Y'CbCr layout in one kernel at the processing size (``hdrtv_post_ycbcr10``), or, at ``out_hw``, in two launches through an
+        RGB48 scratch kept per ``scratch_key`` (``hdrtv_post_rgb48_scaled`` + ``hdrtv_rgb48_to_ycbcr10``)."""
+        oh, ow = (h, w) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        if pix_fmt == "rgb48le":
+            if (oh, ow) == (h, w):
+                self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, src_ptr, dt, h, w, dst_ptr), "hdrtv_post_rgb48")
+            else:
+                self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, dst_ptr, oh, ow),
+                          "hdrtv_post_rgb48_scaled")
+            return
+        planes = _L.ycbcr10_planes(dst_ptr, oh, ow, pix_fmt, siting)
+        if (oh, ow) == (h, w):
+            self._chk(self._lib.hdrtv_post_ycbcr10(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *planes), "hdrtv_post_ycbcr10")
+            return
+        scratch = self._ycc_scratch.get(scratch_key)
+        if scratch is None or tuple(scratch.shape) != (oh, ow, 3):
+            scratch = self._ycc_scratch[scratch_key] = torch.empty((oh, ow, 3), dtype=torch.uint16, device=self.device)
+        self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, scratch.data_ptr(), oh, ow),
+                  "hdrtv_post_rgb48_scaled")
+        self._chk(self._lib.hdrtv_rgb48_to_ycbcr10(self._ctx, st, scratch.data_ptr(), oh, ow, *planes), "hdrtv_rgb48_to_ycbcr10")
+
+    def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le",
+                      out_siting="left"):
         """One frame of the hot path on lane ``lane``, stream-ordered and without any host synchronisation: u8 BGR frame in
         device memory at ``src_bgr_ptr`` -> hdrtv_preprocess -> hdrtv_infer_lane -> hdrtv_post_rgb48 -> u16 RGB48 at the device
         address ``dst_rgb48_ptr``.  ``stream``: a ``torch.cuda.Stream`` (default: the lane's own).  Frames enqueued on different
         lanes may overlap on the device; the bytes written do not depend on the lane (tests/test_gpu_lanes.py).  The caller
         orders the use of ``src`` / ``dst`` against the stream (events), as with any asynchronous launch.  ``out_hw = (out_h,
-        out_w)``: the frame is delivered at that size (``hdrtv_post_rgb48_scaled``; ``dst`` holds out_h * out_w * 3 u16)."""
+        out_w)``: the frame is delivered at that size (``hdrtv_post_rgb48_scaled``; ``dst`` holds out_h * out_w * 3 u16).
+        ``out_pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` (``out_siting`` ``left`` / ``topleft``): ``dst`` receives the
+        10-bit Y'CbCr planes back to back instead (``lib.out_frame_bytes`` bytes) -- ``hdrtv_post_ycbcr10`` at
+        the processing size, with ``out_hw`` two launches through a per-lane RGB48 scratch."""
         if not 0 <= lane < self._lanes:
             raise ValueError(f"lane {lane} of {self._lanes}")
+        out_pix_fmt, out_siting = _L.check_out_format(out_pix_fmt, out_siting)
         self._ensure_buffers(h, w)
         st = C.c_void_p((stream if stream is not None else self._lane_streams[lane]).cuda_stream)
         tin, tcond, tout, tagcm = self._lane_bufs[lane]
@@ -348,14 +377,18 @@ class HDRTVNetMI355X:
         self._chk(self._lib.hdrtv_preprocess(self._ctx, st, src_bgr_ptr, h, w, tin.data_ptr(), tcond.data_ptr()), "hdrtv_preprocess")
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._post_rgb48(st, tout, dt, h, w, dst_rgb48_ptr, out_hw)
+        if out_pix_fmt == "rgb48le":
+            self._post_rgb48(st, tout, dt, h, w, dst_rgb48_ptr, out_hw)
+        else:
+            self._post_out(st, tout.data_ptr(), dt, h, w, dst_rgb48_ptr, out_hw, out_pix_fmt, out_siting, ("lane", lane))
 
     def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None,
-                             out_hw=None):
+                             out_hw=None, out_pix_fmt="rgb48le", out_siting="left"):
         """``enqueue_frame`` of an 8-bit 4:2:0 frame: the planes lie back to back at the device address ``src_ptr`` (the
         ``(h*3//2, w)`` u8 array ``preprocess_yuv420`` takes) and ``hdrtv_preprocess_yuv420`` replaces ``hdrtv_preprocess``."""
         if not 0 <= lane < self._lanes:
             raise ValueError(f"lane {lane} of {self._lanes}")
+        out_pix_fmt, out_siting = _L.check_out_format(out_pix_fmt, out_siting)
         planes = _yuv_planes(src_ptr, int(h), int(w), layout, matrix, full_range)
         self._ensure_buffers(h, w)
         st = C.c_void_p((stream if stream is not None else self._lane_streams[lane]).cuda_stream)
@@ -365,7 +398,10 @@ class HDRTVNetMI355X:
                   "hdrtv_preprocess_yuv420")
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._post_rgb48(st, tout, dt, h, w, dst_rgb48_ptr, out_hw)
+        if out_pix_fmt == "rgb48le":
+            self._post_rgb48(st, tout, dt, h, w, dst_rgb48_ptr, out_hw)
+        else:
+            self._post_out(st, tout.data_ptr(), dt, h, w, dst_rgb48_ptr, out_hw, out_pix_fmt, out_siting, ("lane", lane))
 
     # ------------------------------------------------------------------ API
     @torch.inference_mode()
@@ -594,6 +630,29 @@ class HDRTVNetMI355X:
         self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, self._stream(), output.data_ptr(),
                                                     _L.F32 if output.dtype == torch.float32 else _L.F16, h, w, 1 if pq else 0,
                                                     float(peak_nits), dst.data_ptr(), out_h, out_w), "hdrtv_post_rgb48_scaled")
+        return dst
+
+    @torch.inference_mode()
+    def postprocess_ycbcr10(self, output, pix_fmt="p010le", siting="left", pq=False, peak_nits=1000.0):
+        """10-bit limited-range BT.2020nc Y'CbCr for an encoder: ``hdrtv_post_ycbcr10`` converts the u16 codes
+        of ``hdrtv_post_rgb48`` (``pq=True``: of ``hdrtv_post_pq_rgb48`` at ``peak_nits``) in one kernel, without an RGB48
+        intermediate.  ``pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le``; ``siting`` of 4:2:0 chroma ``left`` (MPEG-2 /
+        H.264, ffmpeg's default) or ``topleft`` (BT.2100 / HDR10).  Returns a new contiguous 1-D device u16 tensor, the planes back
+        to back (``lib.out_frame_bytes`` bytes); stream-ordered on the current stream, no synchronisation."""
+        if isinstance(output, (tuple, list)):
+            output = output[0]
+        if output.dtype not in (torch.float16, torch.float32):
+            raise ValueError("postprocess_ycbcr10 expects an fp16 or fp32 tensor")
+        pix_fmt, siting = _L.check_out_format(pix_fmt, siting)
+        if pix_fmt == "rgb48le":
+            raise ValueError("postprocess_ycbcr10 writes p010le, yuv420p10le or yuv422p10le")
+        h, w = int(output.shape[-2]), int(output.shape[-1])
+        output = output.contiguous()
+        dst = torch.empty(_L.out_frame_bytes(pix_fmt, h, w) // 2, dtype=torch.uint16, device=self.device)
+        self._chk(self._lib.hdrtv_post_ycbcr10(self._ctx, self._stream(), output.data_ptr(),
+                                               _L.F32 if output.dtype == torch.float32 else _L.F16, h, w, 1 if pq else 0,
+                                               float(peak_nits), *_L.ycbcr10_planes(dst.data_ptr(), h, w, pix_fmt, siting)),
+                  "hdrtv_post_ycbcr10")
         return dst
 
     @torch.inference_mode()

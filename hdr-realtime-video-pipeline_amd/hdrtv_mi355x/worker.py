@@ -108,7 +108,7 @@ class HostFrame:
 
 class HeadlessPipelineWorker:
     def __init__(self, weights_dir, use_hg=True, proc_w=1920, proc_h=1080, hg_weights=None,
-                 status_cb=None, buffer_frames=1, out_w=None, out_h=None):
+                 status_cb=None, buffer_frames=1, out_w=None, out_h=None, out_pix_fmt="rgb48le", out_siting="left"):
         self._weights_dir = weights_dir
         self._use_hg = bool(use_hg)
         self._hg_override = hg_weights
@@ -116,6 +116,9 @@ class HeadlessPipelineWorker:
         # the size frames are delivered at; None = the processing size.  It belongs to the sink, not to the
         # model: a hot-swap of the processing resolution keeps it.
         self._out_w, self._out_h = (int(out_w) if out_w else None), (int(out_h) if out_h else None)
+        # what the sink receives: "rgb48le", or 10-bit Y'CbCr ("p010le", "yuv420p10le", "yuv422p10le") with the
+        # 4:2:0 chroma siting "left" / "topleft"; then a frame is a 1-D u16 view of its planes, back to back
+        self._out_pix_fmt, self._out_siting = _L.check_out_format(out_pix_fmt, out_siting)
         self._processor = None
         self._precision_key = None
         self.status_messages = []
@@ -298,7 +301,9 @@ class HeadlessPipelineWorker:
         return a ``PinnedFrame`` guarded by the slot's ready event.  Ring exhaustion (no slot free
         within 250 ms, feeders.py:166-167) falls back to one blocking pinned buffer as the reference
         does (209-235): convert, copy, synchronise the stream, hand the finished frame over.  ``out_hw = (out_h, out_w)``: the
-        ring, the fallback buffer and the frame are at that size and the conversion is ``hdrtv_post_rgb48_scaled``."""
+        ring, the fallback buffer and the frame are at that size and the conversion is ``hdrtv_post_rgb48_scaled``.  With a
+        Y'CbCr ``out_pix_fmt`` the slot (an RGB48 slot holds any of the layouts) receives the planes, only the frame's bytes are
+        committed (``hdrtv_ring_commit_bytes``) and the frame is a 1-D u16 view of them."""
         p = self._processor
         t = tensor[0] if isinstance(tensor, (tuple, list)) else tensor
         th, tw = int(t.shape[-2]), int(t.shape[-1])
@@ -309,12 +314,12 @@ class HeadlessPipelineWorker:
             p._chk(p._lib.hdrtv_ring_create(p._ctx, _RING_FRAMES, h, w), "hdrtv_ring_create")
             self._ring_shape = (h, w)
 
+        fmt = self._out_pix_fmt
+        nbytes = _L.out_frame_bytes(fmt, h, w)
+        shape = (h, w, 3) if fmt == "rgb48le" else (nbytes // 2,)
+
         def convert(dst):
-            if (h, w) == (th, tw):
-                p._chk(p._lib.hdrtv_post_rgb48(p._ctx, sp, t.contiguous().data_ptr(), dt, th, tw, dst), "hdrtv_post_rgb48")
-            else:
-                p._chk(p._lib.hdrtv_post_rgb48_scaled(p._ctx, sp, t.contiguous().data_ptr(), dt, th, tw, 0, 0.0, dst, h, w),
-                       "hdrtv_post_rgb48_scaled")
+            p._post_out(sp, t.contiguous().data_ptr(), dt, th, tw, dst, (h, w), fmt, self._out_siting, "worker")
         host, dev = C.c_void_p(), C.c_void_p()
         st = stream or torch.cuda.current_stream(p.device)
         sp = C.c_void_p(st.cuda_stream)
@@ -322,9 +327,9 @@ class HeadlessPipelineWorker:
         slot = p._lib.hdrtv_ring_acquire(p._ctx, 250, C.byref(host), C.byref(dev))
         if slot == _L.ESTATE:
             self.ring_fallbacks += 1
-            if self._fallback is None or tuple(self._fallback[0].shape) != (h, w, 3):
-                self._fallback = (torch.empty((h, w, 3), dtype=torch.uint16, pin_memory=True),
-                                  torch.empty((h, w, 3), dtype=torch.uint16, device=p.device))
+            if self._fallback is None or tuple(self._fallback[0].shape) != shape:
+                self._fallback = (torch.empty(shape, dtype=torch.uint16, pin_memory=True),
+                                  torch.empty(shape, dtype=torch.uint16, device=p.device))
             fb_host, fb_dev = self._fallback
             convert(fb_dev.data_ptr())
             with torch.cuda.stream(st):
@@ -332,9 +337,9 @@ class HeadlessPipelineWorker:
             st.synchronize()
             return HostFrame(fb_host.numpy().copy())       # the reference's host_np.tobytes(): a private copy
         p._chk(slot, "hdrtv_ring_acquire")
-        convert(dev)
-        p._chk(p._lib.hdrtv_ring_commit(p._ctx, slot, sp), "hdrtv_ring_commit")
-        return PinnedFrame(self, slot, host.value, (h, w, 3))
+        convert(dev.value)
+        p._chk(p._lib.hdrtv_ring_commit_bytes(p._ctx, slot, sp, nbytes), "hdrtv_ring_commit_bytes")
+        return PinnedFrame(self, slot, host.value, shape)
 
     def _start_hdr_feeder(self, sink):
         """feeders.py:632-657 + 440-496: a thread that waits for each frame's ready event,

@@ -153,6 +153,55 @@ int hdrtv_post_pq_rgb48(hdrtv_ctx *ctx, void *stream, const void *dev_out, int d
 int hdrtv_post_rgb48_scaled(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W,
                             int pq, float peak_nits, uint16_t *dst, int dH, int dW);
 
+/* 10-bit limited-range Y'CbCr for an encoder (HEVC Main10, hardware encoders, ProRes): P010 and yuv420p10le are 3 bytes per pixel,
+ * yuv422p10le 4, against the 6 of RGB48.  The reference's export converts on the CPU: it pipes rgb48le into ffmpeg, zscale goes to
+ * BT.2020nc limited range and format=yuv422p10le feeds prores_ks (gui_export.py:948-1005).  The network's output is PQ-encoded BT.2020
+ * R'G'B' (what the reference tags its rgb48le stream as), so the matrix is BT.2020 non-constant luminance, the range limited, and
+ * there is no matrix parameter.  Parity with zscale / swscale is UNPINNED (ffmpeg is not part of the reference tree); the conversion
+ * is this integer rule, restated in tests/ycbcr10_ref.py, which the GPU tests hold both entry points to bit for bit.
+ *  1. codes: R, G, B in [0, 65535] = exactly what hdrtv_post_rgb48 (pq = 0; peak_nits ignored) or hdrtv_post_pq_rgb48 (pq != 0)
+ *     writes for that pixel; the conversion sees nothing but these integers.
+ *  2. coefficients, in double with rnd(v) = floor(v + 0.5), scale 2^20, Kr = 0.2627, Kb = 0.0593, sY = 876 * 2^20 / 65535,
+ *     sC = 896 * 2^20 / 65535:  A = rnd(sY) = 14016;  YR = rnd(Kr sY) = 3682, YB = rnd(Kb sY) = 831, YG = A - YR - YB = 9503;
+ *     Hc = rnd(sC / 2) = 7168;  UR = rnd(-Kr / (2 (1 - Kb)) sC) = -2002, UG = -Hc - UR = -5166, UB = Hc;
+ *     VR = Hc, VB = rnd(-Kb / (2 (1 - Kr)) sC) = -577, VG = -Hc - VB = -6591.  Green is the remainder: the luma row sums to A,
+ *     each chroma row to 0, every grey gives Cb = Cr = 512 exactly.
+ *  3. luma, per pixel (fits int32):  Y = 64 + ((YR R + YG G + YB B + 2^19) >> 20).
+ *  4. chroma: per pixel u = UR R + UG G + UB B, v likewise, unrounded; a sample is 512 + ((sum(w u) + (Wt << 19)) >> (20 + log2 Wt))
+ *     with a flooring shift, in int64 (the sum needs 36 bits); neighbour indices are clamped to the frame (edge repeat):
+ *       4:2:2 (horizontally co-sited):  columns 2i-1, 2i, 2i+1 with weights 1 2 1, every row; Wt = 4
+ *       4:2:0, HDRTV_SITING_LEFT (MPEG-2 / H.264; what ffmpeg and x265 assume when nothing is said; the siting of the 4:2:0 input
+ *              path):  the same columns, rows 2j, 2j+1 with weights 1 1; Wt = 8
+ *       4:2:0, HDRTV_SITING_TOPLEFT (BT.2100 / HDR10 delivery):  the same columns, rows 2j-1, 2j, 2j+1 with weights 1 2 1; Wt = 16
+ *     The weights are non-negative: luma stays in [64, 940], chroma in [64, 960] without a clamp.
+ *     Known answers (R, G, B) -> Y, Cb, Cr on a constant frame: black 64 512 512; 65535^3 940 512 512; 32768^3 502 512 512;
+ *     red 294 387 960; green 658 189 100; blue 116 960 476.  Against the exact double formula the per-pixel values differ by at most
+ *     0.533 code (200 000 random triples).
+ * Layouts, all little-endian u16; W even, H even for the two 4:2:0 layouts; pitches in bytes and even, y_pitch >= 2 W; no other
+ * alignment of a base or a pitch is required:
+ *   HDRTV_YCC_P010      dst_y, then dst_u = ONE interleaved CbCr plane (Cb at u16 2i, Cr at 2i+1; H/2 rows), dst_v = NULL; the value in
+ *                       the HIGH ten bits (v << 6); c_pitch >= 2 W
+ *   HDRTV_YCC_YUV420P10 dst_y, dst_u (Cb), dst_v (Cr); H/2 rows of W/2 samples; the value in the low ten bits; c_pitch >= W
+ *   HDRTV_YCC_YUV422P10 as above with chroma planes of H rows; siting must be HDRTV_SITING_LEFT
+ * hdrtv_post_ycbcr10 goes from the model's planar tensor to the planes in one kernel, without an RGB48 intermediate.
+ * hdrtv_rgb48_to_ycbcr10 applies the same rule to RGB48 codes already in device memory ([H][W][3]): a scaled frame becomes Y'CbCr in
+ * two launches, hdrtv_post_rgb48_scaled and this one.  hdrtv_ycbcr10_bytes: the bytes of a frame with its planes back to back at their
+ * minimum pitches (3 H W, 4:2:2: 4 H W), or a negative value for a bad argument.  Out of scope: dithering (the reference's
+ * dither=error_diffusion is sequential), full range, 12 bits, 4:4:4, HDR10 SEI metadata, and fusing the Lanczos pass with the conversion.
+ * Stream-ordered, no reservation needed.  HDRTV_EINVAL, with dst untouched, for a NULL pointer, a non-positive size, an odd W, an odd H
+ * with 4:2:0, a short or odd pitch, an unknown fmt, siting or dtype, P010 with a non-NULL dst_v, a siting other than LEFT with 4:2:2, or
+ * pq with peak_nits <= 0. */
+#define HDRTV_YCC_P010 0
+#define HDRTV_YCC_YUV420P10 1
+#define HDRTV_YCC_YUV422P10 2
+#define HDRTV_SITING_LEFT 0
+#define HDRTV_SITING_TOPLEFT 1
+int hdrtv_post_ycbcr10(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
+                       int fmt, int siting, uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch);
+int hdrtv_rgb48_to_ycbcr10(hdrtv_ctx *ctx, void *stream, const uint16_t *src_rgb48, int H, int W, int fmt, int siting,
+                           uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch);
+int64_t hdrtv_ycbcr10_bytes(int fmt, int H, int W);
+
 /* The host step in front of preprocess, on the device: _letterbox_bgr
  * (src/gui_scaling.py:228-244), i.e. cv2.resize preserving the aspect ratio -- INTER_AREA when shrinking,
  * INTER_CUBIC when enlarging -- centred on a black [dh][dw] canvas.  src / dst are device u8 BGR HWC.
@@ -211,6 +260,9 @@ int hdrtv_ring_acquire(hdrtv_ctx *ctx, int timeout_ms, uint16_t **host_ptr, uint
 /* After hdrtv_post_rgb48 into the slot's dev_ptr: enqueues the device -> pinned-host copy on `stream` and records
  * the slot's ready event behind it. */
 int hdrtv_ring_commit(hdrtv_ctx *ctx, int slot, void *stream);
+/* hdrtv_ring_commit copying only the first `bytes` of the slot: a Y'CbCr frame (hdrtv_ycbcr10_bytes) fits an RGB48 slot, and only its
+ * bytes cross PCIe.  0 < bytes <= H * W * 6 of hdrtv_ring_create, else HDRTV_EINVAL (the slot stays acquired). */
+int hdrtv_ring_commit_bytes(hdrtv_ctx *ctx, int slot, void *stream, size_t bytes);
 /* Blocks the calling host thread until the slot's contents are complete (wait_ready). */
 int hdrtv_ring_wait(hdrtv_ctx *ctx, int slot);
 /* Marks the slot free again (payload.release()). */
