@@ -8,6 +8,12 @@ using namespace hdrtv_host;
 // =========================================================================== exported C ABI
 extern "C" {
 
+// what a launcher (launchers.h) returned -> the entry point's return code, the failure recorded as "<what>: <HIP's text>"
+static int launched(hdrtv_ctx *c, const char *what, hipError_t e)
+{
+    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "%s: %s", what, hipGetErrorString(e));
+}
+
 #ifndef HDRTV_BUILD_ID
 #define HDRTV_BUILD_ID "unstamped"
 #endif
@@ -180,8 +186,7 @@ int hdrtv_yuv420_to_bgr_u8(hdrtv_ctx *c, void *stream, const uint8_t *y, int y_p
     Yuv420Src src;
     if (const int rc = yuv_args(c, y, y_pitch, u, v, c_pitch, layout, matrix, full_range, H, W, &src)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    const hipError_t e = yuv420_to_bgr_launch(src, H, W, bgr, (hipStream_t)stream);
-    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "yuv420_to_bgr: %s", hipGetErrorString(e));
+    return launched(c, "yuv420_to_bgr", yuv420_to_bgr_launch(src, H, W, bgr, (hipStream_t)stream));
 }
 
 int hdrtv_preprocess_yuv420(hdrtv_ctx *c, void *stream, const uint8_t *y, int y_pitch, const uint8_t *u, const uint8_t *v, int c_pitch,
@@ -270,16 +275,14 @@ int hdrtv_post_u8(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, 
 {
     if (!c || !in || !bgr || H <= 0 || W <= 0) return fail(c, HDRTV_EINVAL, "bad argument");
     HIPCHK(c, hipSetDevice(c->device));
-    hipError_t e = post_u8_launch(in, dtype == HDRTV_F32, H, W, bgr, (hipStream_t)stream);
-    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "post_u8: %s", hipGetErrorString(e));
+    return launched(c, "post_u8", post_u8_launch(in, dtype == HDRTV_F32, H, W, bgr, (hipStream_t)stream));
 }
 
 int hdrtv_post_rgb48(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, uint16_t *dst)
 {
     if (!c || !in || !dst || H <= 0 || W <= 0) return fail(c, HDRTV_EINVAL, "bad argument");
     HIPCHK(c, hipSetDevice(c->device));
-    hipError_t e = post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, 0, 0.f, (hipStream_t)stream);
-    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "post_rgb48: %s", hipGetErrorString(e));
+    return launched(c, "post_rgb48", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, 0, 0.f, (hipStream_t)stream));
 }
 
 // ST.2084 OETF in double precision (constants gui_objective_metrics.py:63-67) -> u16 code, floor(pq * 65535 + 0.5): the
@@ -314,18 +317,23 @@ static void pq_boundaries(std::vector<float> &bnd)
     }
 }
 
+// the table of pq_code (post_quant.h) in device memory: built and uploaded by the first PQ call of a context
+static int ensure_pq_table(hdrtv_ctx *c, const char *what)
+{
+    if (c->pq_bnd) return HDRTV_OK;
+    std::vector<float> bnd;
+    pq_boundaries(bnd);
+    if (hipMalloc((void **)&c->pq_bnd, bnd.size() * 4) != hipSuccess) { c->pq_bnd = nullptr; return fail(c, HDRTV_ENOMEM, "%s: table allocation failed", what); }
+    HIPCHK(c, hipMemcpy(c->pq_bnd, bnd.data(), bnd.size() * 4, hipMemcpyHostToDevice));
+    return HDRTV_OK;
+}
+
 int hdrtv_post_pq_rgb48(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, float peak_nits, uint16_t *dst)
 {
     if (!c || !in || !dst || H <= 0 || W <= 0 || !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "bad argument");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->pq_bnd) {
-        std::vector<float> bnd;
-        pq_boundaries(bnd);
-        if (hipMalloc((void **)&c->pq_bnd, bnd.size() * 4) != hipSuccess) { c->pq_bnd = nullptr; return fail(c, HDRTV_ENOMEM, "post_pq_rgb48: table allocation failed"); }
-        HIPCHK(c, hipMemcpy(c->pq_bnd, bnd.data(), bnd.size() * 4, hipMemcpyHostToDevice));
-    }
-    hipError_t e = post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, 1, peak_nits, (hipStream_t)stream, c->pq_bnd);
-    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "post_pq_rgb48: %s", hipGetErrorString(e));
+    if (int rc = ensure_pq_table(c, "post_pq_rgb48")) return rc;
+    return launched(c, "post_pq_rgb48", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, 1, peak_nits, (hipStream_t)stream, c->pq_bnd));
 }
 
 // ------------------------------------------------------------------- 10-bit Y'CbCr output
@@ -354,16 +362,10 @@ int hdrtv_post_ycbcr10(hdrtv_ctx *c, void *stream, const void *in, int dtype, in
     if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_ycbcr10: bad dtype %d", dtype);
     if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_ycbcr10: pq needs peak_nits > 0");
     HIPCHK(c, hipSetDevice(c->device));
-    if (pq && !c->pq_bnd) {
-        std::vector<float> bnd;
-        pq_boundaries(bnd);
-        if (hipMalloc((void **)&c->pq_bnd, bnd.size() * 4) != hipSuccess) { c->pq_bnd = nullptr; return fail(c, HDRTV_ENOMEM, "post_ycbcr10: table allocation failed"); }
-        HIPCHK(c, hipMemcpy(c->pq_bnd, bnd.data(), bnd.size() * 4, hipMemcpyHostToDevice));
-    }
+    if (int rc = pq ? ensure_pq_table(c, "post_ycbcr10") : HDRTV_OK) return rc;
     p.pq_bnd = c->pq_bnd;
     p.peak = pq ? peak_nits : 0.f;
-    hipError_t e = post_ycbcr10_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream);
-    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "post_ycbcr10: %s", hipGetErrorString(e));
+    return launched(c, "post_ycbcr10", post_ycbcr10_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
 int hdrtv_rgb48_to_ycbcr10(hdrtv_ctx *c, void *stream, const uint16_t *src, int H, int W, int fmt, int siting, uint16_t *dst_y,
@@ -372,8 +374,7 @@ int hdrtv_rgb48_to_ycbcr10(hdrtv_ctx *c, void *stream, const uint16_t *src, int 
     Ycbcr10Params p;
     if (int rc = ycbcr10_args(c, "rgb48_to_ycbcr10", src, H, W, fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch, p)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    hipError_t e = rgb48_to_ycbcr10_launch(p, (hipStream_t)stream);
-    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "rgb48_to_ycbcr10: %s", hipGetErrorString(e));
+    return launched(c, "rgb48_to_ycbcr10", rgb48_to_ycbcr10_launch(p, (hipStream_t)stream));
 }
 
 int64_t hdrtv_ycbcr10_bytes(int fmt, int H, int W)
@@ -419,15 +420,9 @@ int hdrtv_post_rgb48_scaled(hdrtv_ctx *c, void *stream, const void *in, int dtyp
     if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: bad dtype %d", dtype);
     if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: pq needs peak_nits > 0");
     HIPCHK(c, hipSetDevice(c->device));
-    if (pq && !c->pq_bnd) {
-        std::vector<float> bnd;
-        pq_boundaries(bnd);
-        if (hipMalloc((void **)&c->pq_bnd, bnd.size() * 4) != hipSuccess) { c->pq_bnd = nullptr; return fail(c, HDRTV_ENOMEM, "post_rgb48_scaled: table allocation failed"); }
-        HIPCHK(c, hipMemcpy(c->pq_bnd, bnd.data(), bnd.size() * 4, hipMemcpyHostToDevice));
-    }
+    if (int rc = pq ? ensure_pq_table(c, "post_rgb48_scaled") : HDRTV_OK) return rc;
     if (dH == H && dW == W) {                    // every tap table would be the identity: the unscaled kernel writes the same bytes
-        hipError_t e0 = post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd);
-        return e0 == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "post_rgb48_scaled: %s", hipGetErrorString(e0));
+        return launched(c, "post_rgb48_scaled", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd));
     }
     // first use of a geometry builds its tables (allocates, copies); every later call finds them and only launches
     const std::array<int, 4> key{H, W, dH, dW};
@@ -449,8 +444,7 @@ int hdrtv_post_rgb48_scaled(hdrtv_ctx *c, void *stream, const void *in, int dtyp
         it = c->ps_tabs.emplace(key, dev).first;
     }
     PostScaleParams p{in, dst, it->second, it->second + dW, c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
-    hipError_t e = post_scale_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream);
-    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "post_rgb48_scaled: %s", hipGetErrorString(e));
+    return launched(c, "post_rgb48_scaled", post_scale_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
 // ------------------------------------------------------------------------------- letterbox
@@ -552,8 +546,7 @@ int hdrtv_letterbox_u8(hdrtv_ctx *c, void *stream, const uint8_t *src_bgr, int s
     }
     LetterboxParams p = c->lb;
     p.src = src_bgr; p.dst = dst_bgr;
-    hipError_t e = letterbox_launch(p, (hipStream_t)stream);
-    return e == hipSuccess ? HDRTV_OK : fail(c, HDRTV_EHIP, "letterbox: %s", hipGetErrorString(e));
+    return launched(c, "letterbox", letterbox_launch(p, (hipStream_t)stream));
 }
 
 // --------------------------------------------------------------------------------- metrics

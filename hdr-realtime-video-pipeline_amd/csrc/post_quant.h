@@ -1,6 +1,7 @@
-// post_quant.h -- the u16 quantisers of the RGB48 post kernels, shared by prepost.hip (post_rgb48 / post_pq_rgb48) and
-// post_scale.hip (the same codes, then the Lanczos upscale): one definition, so the scaled entry point resamples exactly the
-// integers the unscaled one writes.
+// post_quant.h -- the pixel rule of the output kernels, "one pixel of the model's tensor -> three u16 codes" (quant_rgb, plain or
+// PQ), shared by prepost.hip (post_rgb48 / post_pq_rgb48), post_scale.hip (the same codes, then the Lanczos upscale) and
+// post_ycbcr.hip (the same codes, then the Y'CbCr matrix): one definition, so the scaled and the Y'CbCr entry points start from
+// exactly the integers the unscaled one writes.
 #pragma once
 #include "common.h"
 
@@ -45,5 +46,24 @@ __device__ __forceinline__ float gamut_row(float m0, float m1, float m2, float r
     return __fmaf_rn(m2, b, __fmaf_rn(m1, g, __fmul_rn(m0, r)));      // the oracle's rounding sequence
 }
 
+// One pixel (cr, cg, cb) of the model's output -> its three u16 codes.  PQ: ITU-R BT.2087 BT.709 -> BT.2020 (linear light), the
+// [0, 1] clamp and the exact PQ code at `peak` nits; otherwise the plain rounding of the clamped value.
+template <bool PQ>
+__device__ __forceinline__ void quant_rgb(float cr, float cg, float cb, float peak, const float *__restrict__ bnd, uint32_t &q0,
+                                          uint32_t &q1, uint32_t &q2)
+{
+    if (PQ) {
+        const float xr = gamut_row(0.6274f, 0.3293f, 0.0433f, cr, cg, cb);
+        const float xg = gamut_row(0.0691f, 0.9195f, 0.0114f, cr, cg, cb);
+        const float xb = gamut_row(0.0164f, 0.0880f, 0.8956f, cr, cg, cb);
+        q0 = pq_code(fminf(fmaxf(xr, 0.f), 1.f), peak, bnd);
+        q1 = pq_code(fminf(fmaxf(xg, 0.f), 1.f), peak, bnd);
+        q2 = pq_code(fminf(fmaxf(xb, 0.f), 1.f), peak, bnd);
+    } else {
+        q0 = quant_u16(cr);
+        q1 = quant_u16(cg);
+        q2 = quant_u16(cb);
+    }
+}
 
 }  // namespace

@@ -54,19 +54,7 @@ __global__ __launch_bounds__(256) void post_scale_kernel(PostScaleParams p)
             const size_t o = (size_t)sy * p.W + sx;
             const float cr = (float)in[o], cg = (float)in[plane + o], cb = (float)in[2 * plane + o];
             uint32_t q0, q1, q2;
-            if (PQ) {
-                // ITU-R BT.2087 BT.709 -> BT.2020 (linear light), as post_rgb48_kernel<T, true>
-                const float xr = gamut_row(0.6274f, 0.3293f, 0.0433f, cr, cg, cb);
-                const float xg = gamut_row(0.0691f, 0.9195f, 0.0114f, cr, cg, cb);
-                const float xb = gamut_row(0.0164f, 0.0880f, 0.8956f, cr, cg, cb);
-                q0 = pq_code(fminf(fmaxf(xr, 0.f), 1.f), p.peak, p.pq_bnd);
-                q1 = pq_code(fminf(fmaxf(xg, 0.f), 1.f), p.peak, p.pq_bnd);
-                q2 = pq_code(fminf(fmaxf(xb, 0.f), 1.f), p.peak, p.pq_bnd);
-            } else {
-                q0 = quant_u16(cr);
-                q1 = quant_u16(cg);
-                q2 = quant_u16(cb);
-            }
+            quant_rgb<PQ>(cr, cg, cb, p.peak, p.pq_bnd, q0, q1, q2);
             codes[0][r][c] = (uint16_t)q0;
             codes[1][r][c] = (uint16_t)q1;
             codes[2][r][c] = (uint16_t)q2;

@@ -53,22 +53,6 @@ struct TensorSrc {
     float peak;
     const float *bnd;
 
-    __device__ __forceinline__ void quant(float cr, float cg, float cb, uint32_t &q0, uint32_t &q1, uint32_t &q2) const
-    {
-        if (PQ) {
-            // ITU-R BT.2087 BT.709 -> BT.2020 (linear light), as post_rgb48_kernel<T, true>
-            const float xr = gamut_row(0.6274f, 0.3293f, 0.0433f, cr, cg, cb);
-            const float xg = gamut_row(0.0691f, 0.9195f, 0.0114f, cr, cg, cb);
-            const float xb = gamut_row(0.0164f, 0.0880f, 0.8956f, cr, cg, cb);
-            q0 = pq_code(fminf(fmaxf(xr, 0.f), 1.f), peak, bnd);
-            q1 = pq_code(fminf(fmaxf(xg, 0.f), 1.f), peak, bnd);
-            q2 = pq_code(fminf(fmaxf(xb, 0.f), 1.f), peak, bnd);
-        } else {
-            q0 = quant_u16(cr);
-            q1 = quant_u16(cg);
-            q2 = quant_u16(cb);
-        }
-    }
     __device__ __forceinline__ void wide8(const T *p, float (&v)[8]) const
     {
         if (sizeof(T) == 2) {
@@ -99,12 +83,12 @@ struct TensorSrc {
             }
         }
 #pragma unroll
-        for (int i = 0; i < 8; ++i) quant(v[0][i], v[1][i], v[2][i], q[0][i], q[1][i], q[2][i]);
+        for (int i = 0; i < 8; ++i) quant_rgb<PQ>(v[0][i], v[1][i], v[2][i], peak, bnd, q[0][i], q[1][i], q[2][i]);
     }
     __device__ __forceinline__ void px1(int y, int x, uint32_t (&q)[3]) const
     {
         const T *p = in + (size_t)y * W + x;
-        quant((float)p[0], (float)p[plane], (float)p[2 * plane], q[0], q[1], q[2]);
+        quant_rgb<PQ>((float)p[0], (float)p[plane], (float)p[2 * plane], peak, bnd, q[0], q[1], q[2]);
     }
 };
 

@@ -482,20 +482,7 @@ __global__ __launch_bounds__(256) void post_rgb48_kernel(const T *__restrict__ i
             uint32_t q[6];
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                float cr = r[i + k], cg = gg[i + k], cb = b[i + k];
-                if (PQ) {
-                    // ITU-R BT.2087 BT.709 -> BT.2020 (linear light)
-                    const float xr = gamut_row(0.6274f, 0.3293f, 0.0433f, cr, cg, cb);
-                    const float xg = gamut_row(0.0691f, 0.9195f, 0.0114f, cr, cg, cb);
-                    const float xb = gamut_row(0.0164f, 0.0880f, 0.8956f, cr, cg, cb);
-                    const float c3[3] = {xr, xg, xb};
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) q[k * 3 + ch] = pq_code(fminf(fmaxf(c3[ch], 0.f), 1.f), peak, bnd);
-                } else {
-                    q[k * 3 + 0] = quant_u16(cr);
-                    q[k * 3 + 1] = quant_u16(cg);
-                    q[k * 3 + 2] = quant_u16(cb);
-                }
+                quant_rgb<PQ>(r[i + k], gg[i + k], b[i + k], peak, bnd, q[k * 3], q[k * 3 + 1], q[k * 3 + 2]);
             }
             w[(i / 2) * 3 + 0] = q[0] | (q[1] << 16);
             w[(i / 2) * 3 + 1] = q[2] | (q[3] << 16);
@@ -508,20 +495,9 @@ __global__ __launch_bounds__(256) void post_rgb48_kernel(const T *__restrict__ i
     }
     if (blockIdx.x == 0 && threadIdx.x < (npix & 7)) {
         const size_t i = ngrp * 8 + threadIdx.x;
-        float c3[3] = {(float)in[i], (float)in[npix + i], (float)in[2 * npix + i]};
-        if (PQ) {
-            const float cr = c3[0], cg = c3[1], cb = c3[2];
-            c3[0] = gamut_row(0.6274f, 0.3293f, 0.0433f, cr, cg, cb);
-            c3[1] = gamut_row(0.0691f, 0.9195f, 0.0114f, cr, cg, cb);
-            c3[2] = gamut_row(0.0164f, 0.0880f, 0.8956f, cr, cg, cb);
-        }
-        for (int ch = 0; ch < 3; ++ch) {
-            if (PQ) {
-                rgb[i * 3 + ch] = (uint16_t)pq_code(fminf(fmaxf(c3[ch], 0.f), 1.f), peak, bnd);
-            } else {
-                rgb[i * 3 + ch] = (uint16_t)quant_u16(c3[ch]);
-            }
-        }
+        uint32_t q[3];
+        quant_rgb<PQ>((float)in[i], (float)in[npix + i], (float)in[2 * npix + i], peak, bnd, q[0], q[1], q[2]);
+        for (int ch = 0; ch < 3; ++ch) rgb[i * 3 + ch] = (uint16_t)q[ch];
     }
 }
 

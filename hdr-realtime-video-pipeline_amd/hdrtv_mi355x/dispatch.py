@@ -57,7 +57,7 @@ class _Mi355xWorker:
 
     depth = 2
     input_format = ("bgr24", 709, False)     # (pix_fmt, matrix, full_range); _worker_main sets the dispatcher's
-    output_format = None                     # (out_pix_fmt, out_siting, out_h, out_w) of Y'CbCr output slots (1-D u16); None = RGB48
+    output_format = None                     # the lib.OutputFormat of the output slots; _worker_main sets the dispatcher's
 
     def __init__(self, rank, device_index, init_args):
         import ctypes as C
@@ -101,28 +101,24 @@ class _Mi355xWorker:
                                "pageable transfers")
         self._registered = ptr
 
-    def _buffers(self, h, w, in_shape, out_hw):
+    def _buffers(self, h, w, in_shape, out):
         torch = self._torch
-        if self._hw != (h, w, in_shape, out_hw):
+        if self._hw != (h, w, in_shape, out):
             self.proc._ensure_buffers(h, w)
             self._raw = [torch.empty(in_shape, dtype=torch.uint8, device=self.dev) for _ in range(self.depth)]
-            self._u16 = [torch.empty(out_hw + (3,) if self.output_format is None else (self._out_n,), dtype=torch.uint16, device=self.dev)
-                         for _ in range(self.depth)]
+            self._u16 = [torch.empty(out.shape, dtype=torch.uint16, device=self.dev) for _ in range(self.depth)]
             self._up_ev = [torch.cuda.Event() for _ in range(self.depth)]
             self._comp_ev = [None] * self.depth
             self._dn_ev = [None] * self.depth
-            self._hw = (h, w, in_shape, out_hw)
+            self._hw = (h, w, in_shape, out)
 
     def begin(self, frame, out):
         torch, p = self._torch, self.proc
         # the processing size is the input slot's (a 4:2:0 slot is (h*3//2, w)), the delivered size the output slot's
         h, w = (frame.shape[0], frame.shape[1]) if frame.ndim == 3 else (frame.shape[0] * 2 // 3, frame.shape[1])
-        if self.output_format is None:
-            out_hw, out_fmt = (int(out.shape[0]), int(out.shape[1])), {}
-        else:                                                  # a Y'CbCr slot is the frame's planes back to back
-            out_hw, self._out_n = tuple(self.output_format[2:4]), int(out.size)
-            out_fmt = dict(out_pix_fmt=self.output_format[0], out_siting=self.output_format[1])
-        self._buffers(h, w, tuple(frame.shape), out_hw)
+        fmt = self.output_format
+        out_fmt = dict(out_hw=(fmt.h, fmt.w), out_pix_fmt=fmt.pix_fmt, out_siting=fmt.siting)
+        self._buffers(h, w, tuple(frame.shape), fmt)
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
         # frame's kernels with the next frame's (processor.enqueue_frame); one lane = the single compute stream of before
@@ -139,11 +135,11 @@ class _Mi355xWorker:
         if self._dn_ev[k] is not None:
             main.wait_event(self._dn_ev[k])                    # u16[k]'s previous frame has left the device
         if self.input_format[0] == "bgr24":
-            p.enqueue_frame(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), stream=main, out_hw=out_hw, **out_fmt)
+            p.enqueue_frame(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), stream=main, **out_fmt)
         else:
-            fmt, matrix, full = self.input_format
-            p.enqueue_frame_yuv420(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), layout=fmt, matrix=matrix,
-                                   full_range=full, stream=main, out_hw=out_hw, **out_fmt)
+            layout, matrix, full = self.input_format
+            p.enqueue_frame_yuv420(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), layout=layout, matrix=matrix,
+                                   full_range=full, stream=main, **out_fmt)
         self._comp_ev[k] = torch.cuda.Event()
         self._comp_ev[k].record(main)
         self._dn.wait_event(self._comp_ev[k])
@@ -236,17 +232,16 @@ class _SyncBody:
         return None
 
 
-def _worker_main(rank, device_index, make_worker, init_args, geom, task_q, done_q, use_numa, shm_name=None, input_format=None):
+def _worker_main(rank, device_index, make_worker, init_args, geom, out_format, task_q, done_q, use_numa, shm_name=None, input_format=None):
+    """``geom`` = (h, w, slots) of the input slots; ``out_format``: the ``lib.OutputFormat`` of the output slots."""
     shm, ins, outs, body = None, None, None, None
     code = 0
     try:
-        h, w, slots = geom[:3]
-        oh, ow = geom[3:5] if len(geom) > 3 else (h, w)        # the size of the output slots (FrameDispatcher out_height / out_width)
+        h, w, slots = geom
         input_format = tuple(input_format or ("bgr24", 709, False))
         in_shape = _in_shape(h, w, input_format[0])
-        out_pix_fmt, out_siting = geom[5:7] if len(geom) > 5 else ("rgb48le", "left")
-        out_shape = _out_shape(oh, ow, out_pix_fmt)
-        in_b, out_b = int(np.prod(in_shape)), 2 * int(np.prod(out_shape))
+        out_shape = out_format.shape
+        in_b, out_b = int(np.prod(in_shape)), out_format.nbytes
         # placement first: affinity, then the slots (created and first-touched HERE, on the GPU's node), then the GPU
         from . import numa
         info = numa.pin_to_gpu_node(device_index, apply=bool(use_numa)) if use_numa is not None else {"device": device_index, "numa_node": -1, "cpus": [], "pinned": False}
@@ -266,8 +261,8 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, task_q, done_
             body = _SyncBody(body)
         if input_format[0] != "bgr24" and hasattr(body, "input_format"):
             body.input_format = input_format
-        if out_pix_fmt != "rgb48le" and hasattr(body, "output_format"):
-            body.output_format = (out_pix_fmt, out_siting, oh, ow)
+        if hasattr(body, "output_format"):
+            body.output_format = out_format
         if hasattr(body, "pin"):
             body.pin(shm.buf)
         ins = [np.ndarray(in_shape, np.uint8, shm.buf, offset=s * in_b) for s in range(slots)]
@@ -349,13 +344,6 @@ def _in_shape(h, w, pix_fmt):
     return (h, w, 3) if pix_fmt == "bgr24" else (h * 3 // 2, w)
 
 
-def _out_shape(oh, ow, out_pix_fmt):
-    """An output slot's frame: u16 RGB48 (oh, ow, 3), or the 10-bit Y'CbCr planes back to back as a 1-D u16 array of
-    ``lib.out_frame_bytes`` bytes (hdrtv_ycbcr10_bytes' formula)."""
-    from . import lib as L
-    return (oh, ow, 3) if out_pix_fmt == "rgb48le" else (L.out_frame_bytes(out_pix_fmt, oh, ow) // 2,)
-
-
 class FrameDispatcher:
     def __init__(self, n_workers, height, width, sink, make_worker=mi355x_worker, init_args=None, devices=None, slots=3,
                  start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False, out_height=None,
@@ -384,14 +372,14 @@ class FrameDispatcher:
         if self.out_h < self.h or self.out_w < self.w:
             raise ValueError(f"output size {self.out_w}x{self.out_h} is below the processing size {self.w}x{self.h} (enlarging only)")
         from . import lib as _L
-        self.out_pix_fmt, self.out_siting = _L.check_out_format(out_pix_fmt, out_siting)
-        self._out_shape = _out_shape(self.out_h, self.out_w, self.out_pix_fmt)      # raises for an odd size of a Y'CbCr layout
+        out = _L.output_format(out_pix_fmt, out_siting, self.out_h, self.out_w)    # raises for an odd size of a Y'CbCr layout
+        self.out_pix_fmt, self.out_siting, self._out_shape = out.pix_fmt, out.siting, out.shape
         self.pix_fmt = pix_fmt
         self._in_shape = _in_shape(self.h, self.w, pix_fmt)
         fmt = (pix_fmt, int(yuv_matrix), bool(yuv_full_range))
         self._sink = sink
         ctx = mp.get_context("spawn")           # fresh interpreters: nothing GPU-related is inherited
-        self._in_b, self._out_b = int(np.prod(self._in_shape)), 2 * int(np.prod(self._out_shape))
+        self._in_b, self._out_b = int(np.prod(self._in_shape)), out.nbytes
         self._shm = [None] * self.n             # created by the workers (first touch on their GPU's node), attached below
         # ... under names chosen HERE, so that close() can unlink a segment whose worker died between creating it and saying so
         self._shm_names = [f"hdrtv_{os.getpid()}_{uuid.uuid4().hex[:12]}_{r}" for r in range(self.n)]
@@ -402,7 +390,7 @@ class FrameDispatcher:
         self._stop = False
         self._procs = [ctx.Process(target=_worker_main, daemon=True,
                                    args=(r, devices[r], make_worker, dict(init_args or {}),
-                                         (self.h, self.w, self.slots, self.out_h, self.out_w, self.out_pix_fmt, self.out_siting), self._task[r], self._done, bool(numa), self._shm_names[r], fmt))
+                                         (self.h, self.w, self.slots), out, self._task[r], self._done, bool(numa), self._shm_names[r], fmt))
                        for r in range(self.n)]
         for p in self._procs:
             p.start()

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_PKG), "lib", "libhdrtv_mi355x.so")
@@ -83,29 +84,64 @@ def check_out_format(pix_fmt, siting="left"):
     return pix_fmt, siting
 
 
-def out_frame_bytes(pix_fmt, h, w):
-    """Bytes of one contiguous output frame: H * W * 6 for rgb48le, hdrtv_ycbcr10_bytes' formula for the Y'CbCr layouts (3 H W for
-    the two 4:2:0 layouts, 4 H W for 4:2:2; W even, H even for 4:2:0)."""
+class OutputFormat(NamedTuple):
+    """What a sink receives per frame: the pixel format, the 4:2:0 chroma siting and the size the frame is delivered at.  Built by
+    ``output_format`` (which validates); a plain tuple, so it crosses into the dispatcher's worker processes as it is."""
+    pix_fmt: str
+    siting: str
+    h: int
+    w: int
+
+    @property
+    def is_rgb48(self):
+        return self.pix_fmt == "rgb48le"
+
+    @property
+    def nbytes(self):
+        """Bytes of one contiguous frame: H * W * 6 for rgb48le, hdrtv_ycbcr10_bytes' formula for the Y'CbCr layouts (3 H W for
+        the two 4:2:0 layouts, 4 H W for 4:2:2)."""
+        return self.h * self.w * (6 if self.is_rgb48 else 4 if self.pix_fmt == "yuv422p10le" else 3)
+
+    @property
+    def shape(self):
+        """The frame as a u16 array: RGB48 (h, w, 3), or the 10-bit Y'CbCr planes back to back, 1-D."""
+        return (self.h, self.w, 3) if self.is_rgb48 else (self.nbytes // 2,)
+
+    def at(self, h, w):
+        """The same format at another size."""
+        return self if (h, w) == (self.h, self.w) else output_format(self.pix_fmt, self.siting, h, w)
+
+    def planes(self, ptr):
+        """The trailing arguments of hdrtv_post_ycbcr10 / hdrtv_rgb48_to_ycbcr10 for a frame whose planes lie back to back at
+        device address ``ptr`` at their minimum pitches: (fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch)."""
+        if self.is_rgb48:
+            raise ValueError("rgb48le has no Y'CbCr planes")
+        fmt, sit, h, w = YCC_FORMATS[self.pix_fmt], YCC_SITINGS[self.siting], self.h, self.w
+        u = ptr + h * w * 2
+        if fmt == YCC_P010:
+            return fmt, sit, ptr, 2 * w, u, None, 2 * w
+        ch = h if fmt == YCC_YUV422P10 else h // 2
+        return fmt, sit, ptr, 2 * w, u, u + ch * w, w
+
+
+def output_format(pix_fmt, siting, h, w):
+    """The one constructor of ``OutputFormat``: known names, 4:2:2 only with ``left`` (``check_out_format``), and W even, H even
+    for 4:2:0, for the Y'CbCr layouts."""
+    pix_fmt, siting = check_out_format(pix_fmt, siting)
     h, w = int(h), int(w)
-    if pix_fmt == "rgb48le":
-        return h * w * 6
-    if pix_fmt not in YCC_FORMATS:
-        raise ValueError(f"out_pix_fmt must be one of {list(OUT_PIX_FMTS)}")
-    if h <= 0 or w <= 0 or w % 2 or (pix_fmt != "yuv422p10le" and h % 2):
+    if pix_fmt != "rgb48le" and (h <= 0 or w <= 0 or w % 2 or (pix_fmt != "yuv422p10le" and h % 2)):
         raise ValueError(f"{pix_fmt} needs an even width{'' if pix_fmt == 'yuv422p10le' else ' and height'} (got {w}x{h})")
-    return h * w * (4 if pix_fmt == "yuv422p10le" else 3)
+    return OutputFormat(pix_fmt, siting, h, w)
+
+
+def out_frame_bytes(pix_fmt, h, w):
+    """``OutputFormat.nbytes`` of a ``pix_fmt`` frame of ``h`` x ``w``."""
+    return output_format(pix_fmt, "left", h, w).nbytes
 
 
 def ycbcr10_planes(ptr, h, w, pix_fmt, siting="left"):
-    """The trailing arguments of hdrtv_post_ycbcr10 / hdrtv_rgb48_to_ycbcr10 for a frame whose planes lie back to back at device
-    address ``ptr`` at their minimum pitches: (fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch)."""
-    out_frame_bytes(pix_fmt, h, w)
-    fmt, sit = YCC_FORMATS[pix_fmt], YCC_SITINGS[str(siting).lower()]
-    u = ptr + h * w * 2
-    if fmt == YCC_P010:
-        return fmt, sit, ptr, 2 * w, u, None, 2 * w
-    ch = h if fmt == YCC_YUV422P10 else h // 2
-    return fmt, sit, ptr, 2 * w, u, u + ch * w, w
+    """``OutputFormat.planes`` of a ``pix_fmt`` / ``siting`` frame of ``h`` x ``w`` at device address ``ptr``."""
+    return output_format(pix_fmt, siting, h, w).planes(ptr)
 
 
 _libs = {}

@@ -258,13 +258,13 @@ class RawVideoSink(Rgb48leSink):
 
     def __init__(self, target, width, height, fps, pix_fmt="rgb48le", siting="left"):
         super().__init__(target, width, height, fps)
-        self.pix_fmt, self.siting = _lib.check_out_format(pix_fmt, siting)
-        self.frame_bytes = _lib.out_frame_bytes(self.pix_fmt, self.height, self.width)
+        self.format = _lib.output_format(pix_fmt, siting, self.height, self.width)
+        self.pix_fmt, self.siting = self.format.pix_fmt, self.format.siting
 
     def __call__(self, payload):
         try:
             view = payload.buffer_view()
-            if len(view) != self.frame_bytes:
+            if len(view) != self.format.nbytes:
                 raise ValueError(f"frame of {len(view)} bytes does not match {self.width}x{self.height} {self.pix_fmt}")
             self._f.write(view)
             self.frames += 1

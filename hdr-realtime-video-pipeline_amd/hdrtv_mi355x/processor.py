@@ -53,6 +53,11 @@ def _load_state(path_or_state, what):
     return {(k[7:] if k.startswith("module.") else k): v for k, v in payload.items()}
 
 
+def _dtype_code(t):
+    """The C ABI's dtype code of an f16 / f32 tensor."""
+    return _L.F32 if t.dtype == torch.float32 else _L.F16
+
+
 def kernel_arithmetic(tag):
     """The arithmetic class of a launch by its profile tag (csrc/api_graph.hip writes the tags): 'int8' = v_mfma_i32_*_i8,
     'fq-f16' = activation quantiser in registers + fp16 MFMA on dequantised weights, 'fq-f32' = fp32 fake-quant, 'f16'."""
@@ -229,7 +234,7 @@ class HDRTVNetMI355X:
         self._buf_hw = None
         self._gpu_input = self._gpu_cond = self._gpu_raw = None
         self._pin_input = self._pin_output = None
-        self._pin_uploaded = None                 # event behind the last upload out of _pin_input
+        self._staging = {}                     # _upload: [pinned slot, device buffer, event behind the last upload] per input path
         self._gpu_out = self._gpu_agcm = self._gpu_u8 = None
         print(f"MI355X device : {self.device}")
         # which arithmetic a W8A8 layer runs in depends on the kernel the launch sequence picks for it per resolution
@@ -279,6 +284,11 @@ class HDRTVNetMI355X:
     def _chk(self, rc, what):
         return _L.check(self._lib, self._ctx, rc, what)
 
+    @property
+    def _out_dt(self):
+        """The dtype code of the model's output tensor: f32 from the HG tail and the fp32 preset, f16 otherwise."""
+        return _L.F32 if (self._use_hg or self._fp32) else _L.F16
+
     def _warmup(self):
         h, w = 1080, 1920
         dummy = np.zeros((h, w, 3), dtype=np.uint8)
@@ -300,10 +310,10 @@ class HDRTVNetMI355X:
             self._gpu_cond = torch.empty((1, 3, ch, cw), dtype=self._dtype, device=dev)
             self._gpu_raw = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
             self._gpu_u8 = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
-            self._gpu_out = torch.empty((1, 3, h, w), dtype=torch.float32 if (self._use_hg or self._fp32) else torch.float16, device=dev)
+            self._gpu_out = torch.empty((1, 3, h, w), dtype=torch.float32 if self._out_dt == _L.F32 else torch.float16, device=dev)
             self._gpu_agcm = torch.empty((1, 3, h, w), dtype=self._dtype, device=dev)
             self._pin_input = torch.empty((h, w, 3), dtype=torch.uint8, pin_memory=True)
-            self._pin_uploaded = None
+            self._staging["bgr"] = [self._pin_input, self._gpu_raw, None]
             self._pin_output = torch.empty((h, w, 3), dtype=torch.uint8, pin_memory=True)
             # lane l > 0: its own boundary tensors (input, cond, out, agcm) and stream; lane 0 is the set above
             self._lane_bufs = [(self._gpu_input, self._gpu_cond, self._gpu_out, self._gpu_agcm)]
@@ -324,37 +334,46 @@ class HDRTVNetMI355X:
         ``_ensure_buffers``)."""
         return self._lane_streams[lane]
 
-    def _post_rgb48(self, st, tout, dt, h, w, dst_rgb48_ptr, out_hw):
-        """The tail of ``enqueue_frame*``: RGB48 at the processing size, or at ``out_hw = (out_h, out_w)`` (each >= the processing
-        size) through ``hdrtv_post_rgb48_scaled``."""
-        if out_hw is None or (int(out_hw[0]), int(out_hw[1])) == (h, w):
-            self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, tout.data_ptr(), dt, h, w, dst_rgb48_ptr), "hdrtv_post_rgb48")
+    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key):
+        """The output conversion of a frame whose planar tensor lies at ``src_ptr``, to the ``lib.OutputFormat`` ``out`` at
+        ``dst_ptr``: ``rgb48le`` at the processing size (``hdrtv_post_rgb48``) or enlarged to ``out.h`` x ``out.w``
+        (``hdrtv_post_rgb48_scaled``); a 10-bit Y'CbCr layout in one kernel at the processing size (``hdrtv_post_ycbcr10``), or,
+        enlarged, in two launches through an RGB48 scratch kept per ``scratch_key`` (``hdrtv_post_rgb48_scaled`` +
+        ``hdrtv_rgb48_to_ycbcr10``)."""
+        scaled = (out.h, out.w) != (h, w)
+        if not out.is_rgb48 and not scaled:
+            self._chk(self._lib.hdrtv_post_ycbcr10(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *out.planes(dst_ptr)), "hdrtv_post_ycbcr10")
+            return
+        rgb_ptr = dst_ptr
+        if not out.is_rgb48:
+            scratch = self._ycc_scratch.get(scratch_key)
+            if scratch is None or tuple(scratch.shape) != (out.h, out.w, 3):
+                scratch = self._ycc_scratch[scratch_key] = torch.empty((out.h, out.w, 3), dtype=torch.uint16, device=self.device)
+            rgb_ptr = scratch.data_ptr()
+        if scaled:
+            self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, rgb_ptr, out.h, out.w),
+                      "hdrtv_post_rgb48_scaled")
         else:
-            self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, tout.data_ptr(), dt, h, w, 0, 0.0, dst_rgb48_ptr,
-                                                        int(out_hw[0]), int(out_hw[1])), "hdrtv_post_rgb48_scaled")
+            self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, src_ptr, dt, h, w, rgb_ptr), "hdrtv_post_rgb48")
+        if not out.is_rgb48:
+            self._chk(self._lib.hdrtv_rgb48_to_ycbcr10(self._ctx, st, rgb_ptr, out.h, out.w, *out.planes(dst_ptr)), "hdrtv_rgb48_to_ycbcr10")
 
-    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out_hw, pix_fmt, siting, scratch_key):
-        """The output conversion of a frame whose planar tensor lies at ``src_ptr``: ``rgb48le`` as ``_post_rgb48``; a 10-bit
-        Y'CbCr layout in one kernel at the processing size (``hdrtv_post_ycbcr10``), or, at ``out_hw``, in two launches through an
-        RGB48 scratch kept per ``scratch_key`` (``hdrtv_post_rgb48_scaled`` + ``hdrtv_rgb48_to_ycbcr10``)."""
-        oh, ow = (h, w) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
-        if pix_fmt == "rgb48le":
-            if (oh, ow) == (h, w):
-                self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, src_ptr, dt, h, w, dst_ptr), "hdrtv_post_rgb48")
-            else:
-                self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, dst_ptr, oh, ow),
-                          "hdrtv_post_rgb48_scaled")
-            return
-        planes = _L.ycbcr10_planes(dst_ptr, oh, ow, pix_fmt, siting)
-        if (oh, ow) == (h, w):
-            self._chk(self._lib.hdrtv_post_ycbcr10(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *planes), "hdrtv_post_ycbcr10")
-            return
-        scratch = self._ycc_scratch.get(scratch_key)
-        if scratch is None or tuple(scratch.shape) != (oh, ow, 3):
-            scratch = self._ycc_scratch[scratch_key] = torch.empty((oh, ow, 3), dtype=torch.uint16, device=self.device)
-        self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, scratch.data_ptr(), oh, ow),
-                  "hdrtv_post_rgb48_scaled")
-        self._chk(self._lib.hdrtv_rgb48_to_ycbcr10(self._ctx, st, scratch.data_ptr(), oh, ow, *planes), "hdrtv_rgb48_to_ycbcr10")
+    def _frame_out(self, lane, h, w, out_hw, out_pix_fmt, out_siting):
+        """The argument checks ``enqueue_frame*`` share -> the ``lib.OutputFormat`` of the frame."""
+        if not 0 <= lane < self._lanes:
+            raise ValueError(f"lane {lane} of {self._lanes}")
+        return _L.output_format(out_pix_fmt, out_siting, *((h, w) if out_hw is None else out_hw))
+
+    def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out):
+        """The body of ``enqueue_frame*``: the preprocess entry point ``pre`` (named ``what``) on its source arguments ``src``,
+        ``hdrtv_infer_lane`` and ``_post_out``, all on the lane's buffers and ``stream`` (default: the lane's own)."""
+        self._ensure_buffers(h, w)
+        st = C.c_void_p((stream if stream is not None else self._lane_streams[lane]).cuda_stream)
+        tin, tcond, tout, tagcm = self._lane_bufs[lane]
+        self._chk(pre(self._ctx, st, *src, h, w, tin.data_ptr(), tcond.data_ptr()), what)
+        self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), self._out_dt,
+                                             tagcm.data_ptr()), "hdrtv_infer_lane")
+        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane))
 
     def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le",
                       out_siting="left"):
@@ -367,41 +386,44 @@ class HDRTVNetMI355X:
         ``out_pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` (``out_siting`` ``left`` / ``topleft``): ``dst`` receives the
         10-bit Y'CbCr planes back to back instead (``lib.out_frame_bytes`` bytes) -- ``hdrtv_post_ycbcr10`` at
         the processing size, with ``out_hw`` two launches through a per-lane RGB48 scratch."""
-        if not 0 <= lane < self._lanes:
-            raise ValueError(f"lane {lane} of {self._lanes}")
-        out_pix_fmt, out_siting = _L.check_out_format(out_pix_fmt, out_siting)
-        self._ensure_buffers(h, w)
-        st = C.c_void_p((stream if stream is not None else self._lane_streams[lane]).cuda_stream)
-        tin, tcond, tout, tagcm = self._lane_bufs[lane]
-        dt = _L.F32 if (self._use_hg or self._fp32) else _L.F16
-        self._chk(self._lib.hdrtv_preprocess(self._ctx, st, src_bgr_ptr, h, w, tin.data_ptr(), tcond.data_ptr()), "hdrtv_preprocess")
-        self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), dt,
-                                             tagcm.data_ptr()), "hdrtv_infer_lane")
-        if out_pix_fmt == "rgb48le":
-            self._post_rgb48(st, tout, dt, h, w, dst_rgb48_ptr, out_hw)
-        else:
-            self._post_out(st, tout.data_ptr(), dt, h, w, dst_rgb48_ptr, out_hw, out_pix_fmt, out_siting, ("lane", lane))
+        out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
+        self._enqueue(lane, self._lib.hdrtv_preprocess, "hdrtv_preprocess", (src_bgr_ptr,), h, w, dst_rgb48_ptr, stream, out)
 
     def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None,
                              out_hw=None, out_pix_fmt="rgb48le", out_siting="left"):
         """``enqueue_frame`` of an 8-bit 4:2:0 frame: the planes lie back to back at the device address ``src_ptr`` (the
         ``(h*3//2, w)`` u8 array ``preprocess_yuv420`` takes) and ``hdrtv_preprocess_yuv420`` replaces ``hdrtv_preprocess``."""
-        if not 0 <= lane < self._lanes:
-            raise ValueError(f"lane {lane} of {self._lanes}")
-        out_pix_fmt, out_siting = _L.check_out_format(out_pix_fmt, out_siting)
+        out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         planes = _yuv_planes(src_ptr, int(h), int(w), layout, matrix, full_range)
-        self._ensure_buffers(h, w)
-        st = C.c_void_p((stream if stream is not None else self._lane_streams[lane]).cuda_stream)
-        tin, tcond, tout, tagcm = self._lane_bufs[lane]
-        dt = _L.F32 if (self._use_hg or self._fp32) else _L.F16
-        self._chk(self._lib.hdrtv_preprocess_yuv420(self._ctx, st, *planes, h, w, tin.data_ptr(), tcond.data_ptr()),
-                  "hdrtv_preprocess_yuv420")
-        self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), dt,
-                                             tagcm.data_ptr()), "hdrtv_infer_lane")
-        if out_pix_fmt == "rgb48le":
-            self._post_rgb48(st, tout, dt, h, w, dst_rgb48_ptr, out_hw)
+        self._enqueue(lane, self._lib.hdrtv_preprocess_yuv420, "hdrtv_preprocess_yuv420", planes, h, w, dst_rgb48_ptr, stream, out)
+
+    def _upload(self, key, src, staged=None):
+        """Device pointer of the host u8 array ``src``, uploaded through the staging slot kept per ``key`` in ``_staging``: a
+        pinned slot, its device buffer and the event behind the last upload out of the slot (allocated on first use and on a shape
+        change; the BGR path's are ``_ensure_buffers``').  A plain memcpy into the pinned slot (GIL released), not tensor.copy_:
+        ATen parallelises a 25 MB copy over every OpenMP thread, whose spin-wait afterwards starves the HIP runtime's completion
+        handling (measured on the GPU box: every third 4K frame stalled ~55 ms behind a 128-thread copy).  ``staged``: the frame
+        already lives in page-locked memory (playback.PinnedPrefetch filled it on its own thread while the previous frame was on
+        the GPU) and is uploaded as it is."""
+        slot = self._staging.get(key)
+        if slot is None or tuple(slot[0].shape) != tuple(src.shape):
+            slot = self._staging[key] = [torch.empty(src.shape, dtype=torch.uint8, pin_memory=True),
+                                         torch.empty(src.shape, dtype=torch.uint8, device=self.device), None]
+        pin, dev, uploaded = slot
+        if staged is not None and staged.is_pinned() and tuple(staged.shape) == tuple(src.shape):
+            dev.copy_(staged, non_blocking=True)
+            return dev.data_ptr()
+        src = np.ascontiguousarray(src)
+        # the slot is reused: the last frame's upload out of it is asynchronous and must have been read before the host
+        # overwrites it (two calls without a synchronisation in between uploaded the second frame twice)
+        if uploaded is None:
+            uploaded = slot[2] = torch.cuda.Event()
         else:
-            self._post_out(st, tout.data_ptr(), dt, h, w, dst_rgb48_ptr, out_hw, out_pix_fmt, out_siting, ("lane", lane))
+            uploaded.synchronize()
+        C.memmove(pin.data_ptr(), src.ctypes.data, src.nbytes)
+        dev.copy_(pin, non_blocking=True)
+        uploaded.record(torch.cuda.current_stream(self.device))
+        return dev.data_ptr()
 
     # ------------------------------------------------------------------ API
     @torch.inference_mode()
@@ -411,34 +433,15 @@ class HDRTVNetMI355X:
             raise ValueError("frame_bgr must be uint8 [H,W,3]")
         h, w = frame_bgr.shape[:2]
         self._ensure_buffers(h, w)
-        # plain memcpy into the pinned slot (GIL released).  Not tensor.copy_: ATen parallelises a 25 MB copy
-        # over every OpenMP thread, whose spin-wait afterwards starves the HIP runtime's completion handling
-        # (measured on the GPU box: every third 4K frame stalled ~55 ms behind a 128-thread copy).
-        staged = getattr(frame_bgr, "pinned_tensor", None)
         dev_copy, ready = getattr(frame_bgr, "device_tensor", None), getattr(frame_bgr, "ready_event", None)
         if dev_copy is not None and ready is not None and dev_copy.device == self.device and tuple(dev_copy.shape) == (h, w, 3):
             # already uploaded by the prefetcher on its own stream (hipMemcpyAsync + hipEvent handoff): wait for that
             # event in stream order and unpack straight from its buffer
             torch.cuda.current_stream(self.device).wait_event(ready)
-            self._chk(self._lib.hdrtv_preprocess(self._ctx, self._stream(), dev_copy.data_ptr(), h, w,
-                                                 self._gpu_input.data_ptr(), self._gpu_cond.data_ptr()), "hdrtv_preprocess")
-            return self._gpu_input, self._gpu_cond
-        if staged is not None and staged.is_pinned() and tuple(staged.shape) == (h, w, 3):
-            # the frame already lives in page-locked memory (playback.PinnedPrefetch filled it on its own thread while
-            # the previous frame was on the GPU): upload it as it is
-            self._gpu_raw.copy_(staged, non_blocking=True)
+            raw = dev_copy.data_ptr()
         else:
-            src = np.ascontiguousarray(frame_bgr)
-            # the staging buffer is reused: the last frame's upload out of it is asynchronous and must have been read before the
-            # host overwrites it (two calls without a synchronisation in between uploaded the second frame twice)
-            if self._pin_uploaded is not None:
-                self._pin_uploaded.synchronize()
-            C.memmove(self._pin_input.data_ptr(), src.ctypes.data, src.nbytes)
-            self._gpu_raw.copy_(self._pin_input, non_blocking=True)
-            if self._pin_uploaded is None:
-                self._pin_uploaded = torch.cuda.Event()
-            self._pin_uploaded.record(torch.cuda.current_stream(self.device))
-        self._chk(self._lib.hdrtv_preprocess(self._ctx, self._stream(), self._gpu_raw.data_ptr(), h, w,
+            raw = self._upload("bgr", frame_bgr, getattr(frame_bgr, "pinned_tensor", None))
+        self._chk(self._lib.hdrtv_preprocess(self._ctx, self._stream(), raw, h, w,
                                              self._gpu_input.data_ptr(), self._gpu_cond.data_ptr()), "hdrtv_preprocess")
         return self._gpu_input, self._gpu_cond
 
@@ -455,21 +458,14 @@ class HDRTVNetMI355X:
         if (sw, sh) == (out_w, out_h):
             return self.preprocess(frame_bgr)
         self._ensure_buffers(out_h, out_w)
-        if getattr(self, "_lb_shape", None) != (sh, sw):
-            self._lb_pin = torch.empty((sh, sw, 3), dtype=torch.uint8, pin_memory=True)
-            self._lb_dev = torch.empty((sh, sw, 3), dtype=torch.uint8, device=self.device)
-            self._lb_shape = (sh, sw)
-        src = np.ascontiguousarray(frame_bgr)
-        C.memmove(self._lb_pin.data_ptr(), src.ctypes.data, src.nbytes)
-        self._lb_dev.copy_(self._lb_pin, non_blocking=True)
-        self._chk(self._lib.hdrtv_letterbox_u8(self._ctx, self._stream(), self._lb_dev.data_ptr(), sh, sw,
+        self._chk(self._lib.hdrtv_letterbox_u8(self._ctx, self._stream(), self._upload("letterbox", frame_bgr), sh, sw,
                                                self._gpu_raw.data_ptr(), out_h, out_w), "hdrtv_letterbox_u8")
         self._chk(self._lib.hdrtv_preprocess(self._ctx, self._stream(), self._gpu_raw.data_ptr(), out_h, out_w,
                                              self._gpu_input.data_ptr(), self._gpu_cond.data_ptr()), "hdrtv_preprocess")
         return self._gpu_input, self._gpu_cond
 
     def _yuv_upload(self, frame):
-        """Device pointer of an 8-bit 4:2:0 frame ``(H*3//2, W)`` u8, uploaded through a lazily allocated pinned slot (or the
+        """Device pointer of an 8-bit 4:2:0 frame ``(H*3//2, W)`` u8, uploaded through its own staging slot (``_upload``; or the
         prefetcher's own upload / pinned buffer, as ``preprocess`` uses them) -> (ptr, H, W)."""
         h, w = _yuv_frame_hw(frame)
         shape = (h * 3 // 2, w)
@@ -477,18 +473,7 @@ class HDRTVNetMI355X:
         if dev_copy is not None and ready is not None and dev_copy.device == self.device and tuple(dev_copy.shape) == shape:
             torch.cuda.current_stream(self.device).wait_event(ready)
             return dev_copy.data_ptr(), h, w
-        if getattr(self, "_yuv_shape", None) != shape:          # the BGR path's buffers stay as they are
-            self._yuv_pin = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
-            self._yuv_dev = torch.empty(shape, dtype=torch.uint8, device=self.device)
-            self._yuv_shape = shape
-        staged = getattr(frame, "pinned_tensor", None)
-        if staged is not None and staged.is_pinned() and tuple(staged.shape) == shape:
-            self._yuv_dev.copy_(staged, non_blocking=True)
-        else:
-            src = np.ascontiguousarray(frame)
-            C.memmove(self._yuv_pin.data_ptr(), src.ctypes.data, src.nbytes)
-            self._yuv_dev.copy_(self._yuv_pin, non_blocking=True)
-        return self._yuv_dev.data_ptr(), h, w
+        return self._upload("yuv", frame, getattr(frame, "pinned_tensor", None)), h, w       # the BGR path's buffers stay as they are
 
     @torch.inference_mode()
     def preprocess_yuv420(self, frame, *, layout="i420", matrix=709, full_range=False):
@@ -541,7 +526,7 @@ class HDRTVNetMI355X:
         if self._use_cuda_graphs and not self._profiling:
             return self._infer_graph(tensor, cond, h, w)
         self._chk(self._lib.hdrtv_infer(self._ctx, self._stream(), tensor.data_ptr(), cond.data_ptr(), h, w,
-                                        self._gpu_out.data_ptr(), _L.F32 if (self._use_hg or self._fp32) else _L.F16,
+                                        self._gpu_out.data_ptr(), self._out_dt,
                                         self._gpu_agcm.data_ptr()), "hdrtv_infer")
         return self._gpu_out, self._gpu_agcm
 
@@ -556,7 +541,7 @@ class HDRTVNetMI355X:
 
         def launch():
             self._chk(self._lib.hdrtv_infer(self._ctx, self._stream(), self._gpu_input.data_ptr(), self._gpu_cond.data_ptr(), h, w,
-                                            self._gpu_out.data_ptr(), _L.F32 if (self._use_hg or self._fp32) else _L.F16,
+                                            self._gpu_out.data_ptr(), self._out_dt,
                                             self._gpu_agcm.data_ptr()), "hdrtv_infer")
 
         g = self._graphs.get((h, w))
@@ -591,7 +576,7 @@ class HDRTVNetMI355X:
         h, w = int(a.shape[-2]), int(a.shape[-1])
         out = (C.c_double * 3)()
         self._chk(self._lib.hdrtv_metrics(self._ctx, self._stream(), a.data_ptr(), b.data_ptr(),
-                                          _L.F32 if dt == torch.float32 else _L.F16, h, w, float(peak_nits), out),
+                                          _dtype_code(a), h, w, float(peak_nits), out),
                   "hdrtv_metrics")
         return {"psnr_db": float(out[0]), "sssim": float(out[1]), "delta_e_itp": float(out[2])}
 
@@ -603,10 +588,9 @@ class HDRTVNetMI355X:
         h, w = int(output.shape[-2]), int(output.shape[-1])
         self._ensure_buffers(h, w)
         output = output.contiguous()
-        dt = _L.F32 if output.dtype == torch.float32 else _L.F16
         if output.dtype not in (torch.float16, torch.float32):
             raise ValueError("postprocess expects an fp16 or fp32 tensor")
-        self._chk(self._lib.hdrtv_post_u8(self._ctx, self._stream(), output.data_ptr(), dt, h, w,
+        self._chk(self._lib.hdrtv_post_u8(self._ctx, self._stream(), output.data_ptr(), _dtype_code(output), h, w,
                                           self._gpu_u8.data_ptr()), "hdrtv_post_u8")
         self._pin_output.copy_(self._gpu_u8, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
@@ -628,7 +612,7 @@ class HDRTVNetMI355X:
         output = output.contiguous()
         dst = torch.empty((out_h, out_w, 3), dtype=torch.uint16, device=self.device)
         self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, self._stream(), output.data_ptr(),
-                                                    _L.F32 if output.dtype == torch.float32 else _L.F16, h, w, 1 if pq else 0,
+                                                    _dtype_code(output), h, w, 1 if pq else 0,
                                                     float(peak_nits), dst.data_ptr(), out_h, out_w), "hdrtv_post_rgb48_scaled")
         return dst
 
@@ -643,15 +627,14 @@ class HDRTVNetMI355X:
             output = output[0]
         if output.dtype not in (torch.float16, torch.float32):
             raise ValueError("postprocess_ycbcr10 expects an fp16 or fp32 tensor")
-        pix_fmt, siting = _L.check_out_format(pix_fmt, siting)
-        if pix_fmt == "rgb48le":
+        out = _L.output_format(pix_fmt, siting, int(output.shape[-2]), int(output.shape[-1]))
+        if out.is_rgb48:
             raise ValueError("postprocess_ycbcr10 writes p010le, yuv420p10le or yuv422p10le")
-        h, w = int(output.shape[-2]), int(output.shape[-1])
         output = output.contiguous()
-        dst = torch.empty(_L.out_frame_bytes(pix_fmt, h, w) // 2, dtype=torch.uint16, device=self.device)
+        dst = torch.empty(out.shape, dtype=torch.uint16, device=self.device)
         self._chk(self._lib.hdrtv_post_ycbcr10(self._ctx, self._stream(), output.data_ptr(),
-                                               _L.F32 if output.dtype == torch.float32 else _L.F16, h, w, 1 if pq else 0,
-                                               float(peak_nits), *_L.ycbcr10_planes(dst.data_ptr(), h, w, pix_fmt, siting)),
+                                               _dtype_code(output), out.h, out.w, 1 if pq else 0,
+                                               float(peak_nits), *out.planes(dst.data_ptr())),
                   "hdrtv_post_ycbcr10")
         return dst
 

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import lib as _L
-from .processor import HDRTVNetMI355X
+from .processor import HDRTVNetMI355X, _dtype_code
 
 _RING_FRAMES = max(2, min(8, int(os.environ.get("HDRTVNET_FEEDER_GPU_RGB48_RING_FRAMES", "3") or 3)))
 
@@ -116,9 +116,9 @@ class HeadlessPipelineWorker:
         # the size frames are delivered at; None = the processing size.  It belongs to the sink, not to the
         # model: a hot-swap of the processing resolution keeps it.
         self._out_w, self._out_h = (int(out_w) if out_w else None), (int(out_h) if out_h else None)
-        # what the sink receives: "rgb48le", or 10-bit Y'CbCr ("p010le", "yuv420p10le", "yuv422p10le") with the
-        # 4:2:0 chroma siting "left" / "topleft"; then a frame is a 1-D u16 view of its planes, back to back
-        self._out_pix_fmt, self._out_siting = _L.check_out_format(out_pix_fmt, out_siting)
+        # what the sink receives, one lib.OutputFormat: "rgb48le", or 10-bit Y'CbCr ("p010le", "yuv420p10le",
+        # "yuv422p10le") with the 4:2:0 chroma siting "left" / "topleft"; then a frame is a 1-D u16 view of its planes, back to back
+        self._out = _L.output_format(out_pix_fmt, out_siting, self._out_h or self._proc_h, self._out_w or self._proc_w)
         self._processor = None
         self._precision_key = None
         self.status_messages = []
@@ -314,16 +314,14 @@ class HeadlessPipelineWorker:
             p._chk(p._lib.hdrtv_ring_create(p._ctx, _RING_FRAMES, h, w), "hdrtv_ring_create")
             self._ring_shape = (h, w)
 
-        fmt = self._out_pix_fmt
-        nbytes = _L.out_frame_bytes(fmt, h, w)
-        shape = (h, w, 3) if fmt == "rgb48le" else (nbytes // 2,)
+        out = self._out.at(h, w)
+        shape = out.shape
 
         def convert(dst):
-            p._post_out(sp, t.contiguous().data_ptr(), dt, th, tw, dst, (h, w), fmt, self._out_siting, "worker")
+            p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker")
         host, dev = C.c_void_p(), C.c_void_p()
         st = stream or torch.cuda.current_stream(p.device)
         sp = C.c_void_p(st.cuda_stream)
-        dt = _L.F32 if t.dtype == torch.float32 else _L.F16
         slot = p._lib.hdrtv_ring_acquire(p._ctx, 250, C.byref(host), C.byref(dev))
         if slot == _L.ESTATE:
             self.ring_fallbacks += 1
@@ -338,7 +336,7 @@ class HeadlessPipelineWorker:
             return HostFrame(fb_host.numpy().copy())       # the reference's host_np.tobytes(): a private copy
         p._chk(slot, "hdrtv_ring_acquire")
         convert(dev.value)
-        p._chk(p._lib.hdrtv_ring_commit_bytes(p._ctx, slot, sp, nbytes), "hdrtv_ring_commit_bytes")
+        p._chk(p._lib.hdrtv_ring_commit_bytes(p._ctx, slot, sp, out.nbytes), "hdrtv_ring_commit_bytes")
         return PinnedFrame(self, slot, host.value, shape)
 
     def _start_hdr_feeder(self, sink):
@@ -347,7 +345,7 @@ class HeadlessPipelineWorker:
         self._stop_hdr_feeder()
         self._hdr_sink = sink
         self._hdr_error = None
-        ring_hw = (self._out_h or self._proc_h, self._out_w or self._proc_w)         # the size frames are delivered at
+        ring_hw = (self._out.h, self._out.w)                                         # the size frames are delivered at
         if self._processor is not None and self._ring_shape != ring_hw:
             # pin the ring now (3 x 50 MB at 4K takes tens of ms) rather than inside the first frame's deadline
             p = self._processor

@@ -144,6 +144,28 @@ def test_post_pq_matches_oracle(proc_hr, torch_cuda):
     assert got[0, 2].tolist() == [49271, 49271, 49271] and got[0, 0].tolist() == [0, 0, 0]
 
 
+@pytest.mark.parametrize("hw", [(5, 7), (1, 7), (61, 103)])
+def test_post_pq_ragged_tail_matches_oracle(proc_hr, torch_cuda, hw):
+    """Pixel counts that are no multiple of eight: the last npix % 8 pixels leave post_rgb48_kernel<T, true> through its one-pixel
+    tail (35 = four groups + 3, 7 = the tail alone, 6283 = several blocks + 3).  Exact integers from f32 and f16 input, and nothing
+    written past the frame."""
+    import ctypes as C
+    from hdrtv_mi355x import lib as L
+    from oracle import hdrtvnet_oracle as O
+    torch = torch_cuda
+    h, w = hw
+    x = np.random.default_rng(100 * h + w).uniform(-0.05, 1.05, (3, h, w)).astype(np.float32)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for dt, tdt in ((L.F32, torch.float32), (L.F16, torch.float16)):
+        xin = torch.from_numpy(x).to("cuda").to(tdt).contiguous()
+        u16 = torch.full((h * w * 3 + 8,), 0xA5A5, dtype=torch.uint16, device="cuda")
+        assert L.load().hdrtv_post_pq_rgb48(proc_hr._ctx, st, xin.data_ptr(), dt, h, w, C.c_float(1000.0), u16.data_ptr()) == 0
+        torch.cuda.synchronize()
+        got = u16.cpu().numpy()
+        assert (got[h * w * 3:] == 0xA5A5).all()
+        assert np.array_equal(got[:h * w * 3].reshape(h, w, 3), O.post_pq_rgb48(xin.float().cpu().numpy(), 1000.0)), dt
+
+
 @pytest.mark.parametrize("name", ["hr_64x96_noise_s0", "hr_60x100_noise_s2", "hr_52x76_gradient_s5",
                                   "hr_32x96_gradient_s1_taps"])
 def test_hr_golden(proc_hr, golden_dir, hr_state, name):

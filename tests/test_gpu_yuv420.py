@@ -202,6 +202,38 @@ def test_processor_surfaces_equal_their_bgr_forms(golden_dir):
         p.close()
 
 
+def test_staged_uploads_wait_for_the_previous_upload(golden_dir):
+    """Two calls with different frames and no synchronisation between them: each returned tensor (cloned in stream order) equals
+    the one the same call returns alone after a device synchronise, bit for bit -- for every host-fed path that stages a frame
+    in a reused pinned slot (``HDRTVNetMI355X._upload``).  Without the wait for the previous upload the second memcpy may land in
+    the slot before the first upload has read it, and both calls see the second frame.  At 64x96 the first copy is nearly always
+    done by then, so on the code before the shared helper this test rarely failed: it pins the contract; the proof is the code,
+    which has one upload routine with one wait."""
+    import torch
+    from hdrtv_mi355x import weights as W
+    p = _proc(golden_dir)
+    try:
+        bgr = [W.synthetic_frame(64, 96, seed=70 + i, kind="noise") for i in range(2)]
+        yuv = [R.random_frame(64, 96, seed=80 + i) for i in range(2)]
+        calls = {"preprocess_letterboxed": [lambda f=f: p.preprocess_letterboxed(f, 128, 96) for f in bgr],
+                 "preprocess_yuv420": [lambda f=f: p.preprocess_yuv420(f) for f in yuv],
+                 "preprocess_yuv420_letterboxed": [lambda f=f: p.preprocess_yuv420_letterboxed(f, 128, 96) for f in yuv]}
+        for name, pair in calls.items():
+            alone = []
+            for call in pair:
+                torch.cuda.synchronize()
+                alone.append([t.clone() for t in call()])
+            torch.cuda.synchronize()
+            assert not torch.equal(alone[0][0], alone[1][0]), name          # the two frames do differ
+            back_to_back = [[t.clone() for t in call()] for call in pair]
+            torch.cuda.synchronize()
+            for k in range(2):
+                for got, want in zip(back_to_back[k], alone[k]):
+                    assert got.shape == want.shape and torch.equal(got, want), (name, k)
+    finally:
+        p.close()
+
+
 def test_playback_yuv420p_clip_into_rgb48le_sink(golden_dir, tmp_path):
     """End to end: a yuv420p rawvideo clip -> prefetch -> worker (device conversion) -> rgb48le sink writes the bytes the bgr24
     path writes for the rule-converted clip."""

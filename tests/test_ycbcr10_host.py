@@ -129,6 +129,57 @@ def test_python_side_formats_sizes_and_plane_arguments():
             L.check_out_format(*bad)
 
 
+OUT_SIZES = ((2, 2), (6, 10), (64, 96), (2160, 3840))
+
+
+@pytest.mark.parametrize("h,w", OUT_SIZES)
+def test_output_format_object_states_what_the_public_functions_state(h, w):
+    """lib.OutputFormat against hdrtv_ycbcr10_bytes (tests/ycbcr10_ref.frame_bytes when the library is not built), against
+    lib.ycbcr10_planes, and through pickle (it crosses into the dispatcher's worker processes)."""
+    import pickle
+    from hdrtv_mi355x import lib as L
+    try:
+        so = L.load()
+    except RuntimeError:
+        so = None
+    f = L.output_format("rgb48le", "left", h, w)
+    assert f.is_rgb48 and f.nbytes == h * w * 6 and f.shape == (h, w, 3) and int(np.prod(f.shape)) == f.nbytes // 2
+    assert pickle.loads(pickle.dumps(f)) == f and isinstance(pickle.loads(pickle.dumps(f)), L.OutputFormat)
+    with pytest.raises(ValueError):
+        f.planes(4096)
+    for fmt, siting in COMBOS:
+        f = L.output_format(fmt, siting, h, w)
+        assert tuple(f) == (fmt, siting, h, w) and not f.is_rgb48
+        want = so.hdrtv_ycbcr10_bytes(L.YCC_FORMATS[fmt], h, w) if so is not None else R.frame_bytes(fmt, h, w)
+        assert f.nbytes == want == L.out_frame_bytes(fmt, h, w)
+        assert f.shape == (f.nbytes // 2,)
+        assert f.planes(4096) == L.ycbcr10_planes(4096, h, w, fmt, siting)
+        back = pickle.loads(pickle.dumps(f))
+        assert back == f and isinstance(back, L.OutputFormat) and back.nbytes == f.nbytes and back.shape == f.shape
+
+
+def test_output_format_constructor_rejects_what_the_public_functions_reject():
+    from hdrtv_mi355x import lib as L
+    odd = [("p010le", "left", 6, 9), ("yuv420p10le", "left", 6, 9), ("yuv422p10le", "left", 6, 9),          # odd W
+           ("p010le", "left", 5, 10), ("yuv420p10le", "topleft", 5, 10)]                                    # odd H for 4:2:0
+    names = [("yuv422p10le", "topleft", 6, 10),                                                             # 4:2:2 is co-sited
+             ("yuv444p10le", "left", 6, 10), ("p010", "left", 6, 10), ("p010le", "center", 6, 10), ("rgb48le", "middle", 6, 10)]
+    for fmt, siting, h, w in odd:                            # what out_frame_bytes / ycbcr10_planes reject
+        for call in (lambda: L.out_frame_bytes(fmt, h, w), lambda: L.ycbcr10_planes(4096, h, w, fmt, siting),
+                     lambda: L.output_format(fmt, siting, h, w)):
+            with pytest.raises(ValueError):
+                call()
+    for fmt, siting, h, w in names:                          # what check_out_format rejects
+        for call in (lambda: L.check_out_format(fmt, siting), lambda: L.output_format(fmt, siting, h, w)):
+            with pytest.raises(ValueError):
+                call()
+    assert L.output_format("yuv422p10le", "left", 5, 10).nbytes == 200          # 4:2:2 takes an odd height
+    assert L.output_format("RGB48LE", "Left", 5, 9) == ("rgb48le", "left", 5, 9)
+    assert L.output_format("p010le", "left", 6, 10).at(6, 10).at(8, 12) == ("p010le", "left", 8, 12)
+    with pytest.raises(ValueError):
+        L.output_format("p010le", "left", 6, 10).at(7, 12)
+
+
 def test_library_sizes_and_refusals_without_a_device():
     from hdrtv_mi355x import lib
     so = lib.load()
@@ -201,10 +252,11 @@ def _fill_worker(rank, device_index, init_args):
 
 def test_dispatcher_sizes_its_output_slots_for_the_format():
     from hdrtv_mi355x import dispatch as D
+    from hdrtv_mi355x import lib as L
     h, w = 6, 10
     for fmt in R.FORMATS + ("rgb48le",):
         nbytes = R.frame_bytes(fmt, h, w) if fmt != "rgb48le" else h * w * 6
-        shape = D._out_shape(h, w, fmt)
+        shape = L.output_format(fmt, "left", h, w).shape
         assert 2 * int(np.prod(shape)) == nbytes and (len(shape) == 1) == (fmt != "rgb48le")
     for bad in (dict(out_pix_fmt="yuv444p10le"), dict(out_pix_fmt="yuv422p10le", out_siting="topleft"), dict(out_pix_fmt="p010le", out_height=7)):
         with pytest.raises(ValueError):

@@ -6,7 +6,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, os.path.join(REPO, "hdr-realtime-video-pipeline_amd"))
 import numpy as np
 import torch
-from hdrtv_mi355x import weights as W
+from hdrtv_mi355x import lib as L, weights as W
 from hdrtv_mi355x.dispatch import _Mi355xWorker
 
 H, Wd = 2160, 3840
@@ -16,6 +16,7 @@ def run(depth, lanes, slots, pinned, n=80):
     init = {"model_path": os.path.join(REPO, "tests", "golden", "hr_weights.hdrw"), "use_hg": True, "hg_weights": "seeded:1234",
             "frames_in_flight": depth, "lanes": lanes}
     w = _Mi355xWorker(0, 0, init)
+    w.output_format = L.output_format("rgb48le", "left", H, Wd)
     in_b, out_b = H * Wd * 3, H * Wd * 6
     if pinned:
         buf = torch.empty(slots * (in_b + out_b), dtype=torch.uint8, pin_memory=True).numpy()
