@@ -612,14 +612,29 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
 }
 
 // hg_need's program for a padded frame, from the layer table: the tensors' need maps, one list per layer.  Returns the bytes of
-// the buffer ("hg.need") all of it lies in; the layout does not depend on the variants, only HgNeedLayer::th does.
+// the buffer ("hg.need") all of it lies in; the layout does not depend on the variants (every map is sized for the finest unit
+// table), only HgNeedLayer::th and the unit table (hg_sparse = 1: 16x16 cells, else the sub-tile units) do.
+// Layout: flags | two blocks no longer used (the byte-per-cell maps of the first form; they keep the lists where they were) |
+// the layers' lists | the tensors' bit-row maps | two scratch maps.
 size_t hg_need_plan(hdrtv_ctx *c, int Hp, int Wp, HgNeedParams &p)
 {
     memset(&p, 0, sizeof p);
     p.Hp = Hp; p.Wp = Wp;
     constexpr int n_layers = (int)(sizeof hg_layers / sizeof hg_layers[0]);
     static_assert(n_layers <= HG_NEED_MAX_LAYERS && n_layers + 2 <= HG_NEED_MAX_TENSORS, "hg_need's tables are too small");
+    constexpr int max_level = [] { int m = 0; for (const HgLayer &L : hg_layers) m = L.level > m ? L.level : m; return m; }();
+    static_assert(max_level < HG_NEED_LEVELS, "hg_need's unit tables have too few levels");
+    memcpy(p.lu, hg_need_unit_log2[c->var.at("hg_sparse") == 1 ? 1 : 2], sizeof p.lu);
     auto ncell = [&](int level) { return (((Hp >> level) + 15) / 16) * (((Wp >> level) + 15) / 16); };
+    // 64-bit words of a level's bit-row map, and of a map with one row per 8-row tile (the list pass), under any unit table
+    auto nwords = [&](int level) {
+        size_t m = 0;
+        for (const auto &tab : hg_need_unit_log2) {
+            const int u = 1 << tab[level], rows = std::max(((Hp >> level) + u - 1) / u, ((Hp >> level) + 7) / 8);
+            m = std::max(m, (size_t)rows * ((((Wp >> level) + u - 1) / u + 63) / 64));
+        }
+        return m;
+    };
     const char *names[HG_NEED_MAX_TENSORS];
     int level[HG_NEED_MAX_TENSORS], nt = 0;
     auto tensor = [&](const char *name, int lev) {
@@ -640,14 +655,34 @@ size_t hg_need_plan(hdrtv_ctx *c, int Hp, int Wp, HgNeedParams &p)
         N.th = L.ks == 3 && Seq::prw_tile_rows(c, L.mode, L.cout, Hp >> L.level, Wp >> L.level) == 8 ? 8 : 16;    // conv()'s own choice
     }
     p.n_layers = n_layers;
+    // hg_need walks the table backwards: the first reader it meets stores a tensor's map, so no map needs clearing
+    bool seen[HG_NEED_MAX_TENSORS] = {};
+    for (int i = n_layers - 1; i >= 0; --i) {
+        HgNeedLayer &N = p.L[i];
+        N.in_first = !seen[N.in];
+        seen[N.in] = true;
+        if (N.skip >= 0) { N.skip_first = !seen[N.skip]; seen[N.skip] = true; }
+    }
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return (int)o; };
     p.flags_off = take((size_t)ncell(0));
-    p.kmap_off = take((size_t)ncell(0));
-    p.maps_off = (int)off;
-    for (int t = 0; t < nt; ++t) p.map_off[t] = !strcmp(names[t], "part") ? p.flags_off : take((size_t)ncell(level[t]));
-    p.maps_bytes = (int)off - p.maps_off;
+    take((size_t)ncell(0));
+    for (int t = 0; t < nt; ++t)
+        if (strcmp(names[t], "part")) take((size_t)ncell(level[t]));
     for (int i = 0; i < n_layers; ++i) p.L[i].list_off = take(4 * (2 * (size_t)ncell(p.L[i].level) + 4));
+    size_t scratch = 0;
+    for (int t = 0; t < nt; ++t) {
+        p.map_off[t] = take(8 * nwords(level[t]));
+        scratch = std::max(scratch, nwords(level[t]));
+        if (!strcmp(names[t], "part")) p.flags_map = t;
+    }
+    for (int i = 0; i < n_layers; ++i) {
+        p.L[i].out_chained = i + 1 < n_layers ? p.L[i + 1].in == p.L[i].out : p.L[i].out == p.flags_map;
+        p.L[i].in_chained = i > 0 && p.L[i - 1].out == p.L[i].in;
+    }
+    p.scratch_words = (int)scratch;
+    p.kbits_off = take(8 * scratch);
+    p.tbits_off = take(8 * scratch);
     return off;
 }
 

@@ -33,7 +33,9 @@ const std::pair<const char *, int> k_variants[] = {
     {"no_c3fuse", 0},        // 1: LE.conv_first as its own launch in front of HR_conv1
     {"no_c3q8", 0},          // 1: the W8A8 LE.conv_first through planar3_to_q8 + conv_q8 instead of conv_c3_q8
     {"glds1_old", 0},        // 1: HG 1x1 fuse convs on the non-persistent kernel
-    {"hg_sparse", 1},        // fp16 HG: the conv_prw layers compute only the tiles the highlight mask lets reach the output (hg_need.hip); 0 = every tile
+    {"hg_sparse", 2},        // fp16 HG: the conv_prw layers compute only the tiles the highlight mask lets reach the output (hg_need.hip): 2 = need tracked in
+                             // sub-tile units (4, 2, 1, 1, 1 pixels at levels 1 .. 5, a one-pixel halo per 3x3 layer), 1 = in 16x16 cells of every level (a whole
+                             // cell of halo per layer: the encoder is dense on any frame with a highlight), 0 = every tile
     {"final_recompute", 0},  // 1: HG tail recomputes conv1 (hg_final_fused) instead of reading conv1's per-pixel sums
     {"cond3_fused", 1},      // CondNet3.4 in CondNet3.2's (conv3x3s2_preg<64>) epilogue; 0 = its own conv_igemm launch
     {"cond2_fused", 1},      // CondNet2.2 + .4 in conv3x3s2_preg<192>'s epilogue; 0 = the separate cond_tail launch

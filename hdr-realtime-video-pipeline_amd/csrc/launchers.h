@@ -98,18 +98,28 @@ hipError_t agcm_fold_q8_launch(const AgcmFoldArgs &a, const AgcmFoldQ8Args &q, f
 hipError_t hg_prep_launch(const f16 *base, int H, int W, int Hp, int Wp, f16 *img_pad, uint8_t *mask, float r, float thresh,
                           hipStream_t s, uint8_t *flags = nullptr);
 // ---- hg_need.hip: the HG layers' need lists from hg_prep's flags.  Everything lies in one buffer (`base` + byte offsets).
-constexpr int HG_NEED_MAX_LAYERS = 24, HG_NEED_MAX_TENSORS = 32;
+constexpr int HG_NEED_MAX_LAYERS = 24, HG_NEED_MAX_TENSORS = 32, HG_NEED_LEVELS = 6;
+// The need maps' unit per level (0 = full resolution .. 5 = 1/32), as log2 of its side in pixels of that level, per setting of
+// variant hg_sparse.  Level 0 is hg_prep's flags (16x16).  1: one 16x16 cell everywhere; 2: 4, 2, 1, 1, 1 pixels at levels 1 .. 5,
+// i.e. 8, 8, 8, 16, 32 full-resolution pixels.  No unit is larger than a kernel tile (16).
+constexpr int hg_need_unit_log2[3][HG_NEED_LEVELS] = {{4, 4, 4, 4, 4, 4}, {4, 4, 4, 4, 4, 4}, {4, 2, 1, 0, 0, 0}};
 struct HgNeedLayer {
     int level, mode, ks;       // input level; 0 writes at its level, 1 pool-fused (one level down), 2 pixel shuffle (one level up)
     int in, skip, out;         // tensor ids (skip < 0: none)
+    int in_first, skip_first;  // this layer is the last reader in launch order (the first hg_need sees): it stores the map, others OR
+    int out_chained;           // out is the input of the next layer in launch order (the last layer: out is the flags' map) ...
+    int in_chained;            // ... in is the output of the layer before: the map may be handed on in the kernel's LDS
     int th;                    // rows of the kernel tiles the list is written for: 16 or 8
-    int list_off;              // int [0] count, [1 ..] tile indices ty * ceil(W_level / 16) + tx
+    int list_off;              // int [0] count, [1 ..] tile indices ty * ceil(W_level / 16) + tx, ascending
 };
 struct HgNeedParams {
     unsigned char *base;
     int Hp, Wp, n_layers;
-    int flags_off, maps_off, maps_bytes, kmap_off;
-    int map_off[HG_NEED_MAX_TENSORS];       // need map of tensor t: one byte per 16x16 cell of its level
+    int lu[HG_NEED_LEVELS];                 // the unit table in use
+    int flags_off;                          // hg_prep's flags, one byte per 16x16 full-resolution cell
+    int flags_map;                          // the tensor whose need map the flags are (Up_conv5's sums)
+    int kbits_off, tbits_off, scratch_words;    // two scratch maps for layers too large for the kernel's LDS
+    int map_off[HG_NEED_MAX_TENSORS];       // need map of tensor t: bit rows, 64 units per 64-bit word, ceil(units / 64) words per row
     HgNeedLayer L[HG_NEED_MAX_LAYERS];      // launch order
 };
 hipError_t hg_need_launch(const HgNeedParams &p, hipStream_t s);

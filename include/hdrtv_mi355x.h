@@ -296,10 +296,11 @@ int hdrtv_profile_get(hdrtv_ctx *ctx, int i, const char **layer, const char **ke
  * layer runs on (e.g. "le_rows": 1 = the fused row-streaming LE kernels, 0 = one launch per layer).  The table is
  * filled at hdrtv_create (defaults, then the creating process's HDRTV_VARIANTS="name=value,..."); the launch path never
  * reads the environment.  Takes effect at the next hdrtv_infer; HDRTV_EINVAL for an unknown name.
- * "hg_sparse" (default 1; fp16 HG, hdrtv_infer and hdrtv_infer_lane alike): the HG head's conv_prw layers compute only the tiles
+ * "hg_sparse" (default 2; fp16 HG, hdrtv_infer and hdrtv_infer_lane alike): the HG head's conv_prw layers compute only the tiles
  * a masked output pixel depends on -- the lists are built on the device from the frame's mask (no host round trip; the launch
- * grids do not depend on frame content) -- and the blend takes img where the mask is 0.  Output bit-identical to 0 (every
- * tile) for finite HG values; see hdrtv_get_tap for the taps.  hdrtv_infer_stats keeps reporting the dense model's MACs. */
+ * grids do not depend on frame content) -- and the blend takes img where the mask is 0.  2 tracks the dependency in sub-tile
+ * units with a one-pixel halo per 3x3 layer, 1 in 16x16 cells of every level (coarser: more tiles).  Output bit-identical to 0
+ * (every tile) for finite HG values; see hdrtv_get_tap for the taps.  hdrtv_infer_stats keeps reporting the dense model's MACs. */
 int hdrtv_set_variant(hdrtv_ctx *ctx, const char *name, int value);
 int hdrtv_get_variant(hdrtv_ctx *ctx, const char *name, int *value);
 

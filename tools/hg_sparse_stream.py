@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """HG need lists (variant hg_sparse): a stream of frames of one kind through enqueue_frame, and the executed-tile shares.
 
-  python tools/hg_sparse_stream.py --kind noise --frames 30 --sparse 1      # the worst case: ms per frame of a noise-only stream
+  python tools/hg_sparse_stream.py --kind noise --frames 30 --sparse 2      # the worst case: ms per frame of a noise-only stream
                                                                              # (bench.py's own frames of that kind: seeds 1234 / 1236 noise, 1235 / 1237 gradient)
-  python tools/hg_sparse_stream.py --shares                                  # per HG layer, executed / dense tiles on bench.py's four frames
+  python tools/hg_sparse_stream.py --kind gradient --seed0 1234             # two frames of that kind from seeds 1234 / 1236 instead
+  python tools/hg_sparse_stream.py --shares --sparse 2                      # per HG layer, executed / dense tiles on bench.py's four frames
+
+--sparse: 0 every tile, 1 need in 16x16 cells of every level, 2 (the default) in sub-tile units (csrc/hg_need.hip).
 
 Prints one line per figure; run each invocation under a time limit of its own."""
 import argparse
@@ -20,7 +23,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kind", default="noise", choices=("noise", "gradient"))
     ap.add_argument("--frames", type=int, default=30)
-    ap.add_argument("--sparse", type=int, default=1)
+    ap.add_argument("--sparse", type=int, default=2, choices=(0, 1, 2))
+    ap.add_argument("--seed0", type=int, default=None, help="seed of the stream's first frame (the second: + 2); default bench.py's frames of --kind")
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--shares", action="store_true")
@@ -39,23 +43,23 @@ def main():
                 kind = ("noise", "gradient")[i % 2]
                 f = W.synthetic_frame(h, w, seed=1234 + i, kind=kind)
                 prof = {}
-                p.set_variant("hg_sparse", 1)
+                p.set_variant("hg_sparse", a.sparse or 2)
                 p.infer(p.preprocess(f))
                 m = p.tap("hg.mask")[0, :h, :w]
                 print(f"shares {kind} {1234 + i} masked pixels {int(m.sum())} of {h * w} = {100.0 * float(m.sum()) / (h * w):.4f} %, "
                       f"16x16 cells holding one {100.0 * float((torch.nn.functional.max_pool2d(m[None, None], 16, ceil_mode=True) > 0).float().mean()):.3f} %")
-                for sparse in (0, 1):
+                for sparse in (0, a.sparse or 2):
                     p.set_variant("hg_sparse", sparse)
                     p.infer(p.preprocess(f))
                     torch.cuda.synchronize(dev)
-                    prof[sparse] = [r for r in p.profile_read() if r[0].startswith("hg.")]
+                    prof[min(sparse, 1)] = [r for r in p.profile_read() if r[0].startswith("hg.")]
                 for d, s in zip(prof[0], prof[1]):
                     assert d[0] == s[0], (d, s)
                     print(f"shares {kind} {1234 + i} {d[0]:14s} {s[1]:18s} executed/dense tiles {s[3] / d[3] if d[3] else 1.0:6.3f}  ms {d[2]:6.3f} -> {s[2]:6.3f}")
                 print(f"shares {kind} {1234 + i} HG layers total ms {sum(r[2] for r in prof[0]):6.3f} -> {sum(r[2] for r in prof[1]):6.3f}")
             return
         p.set_variant("hg_sparse", a.sparse)
-        seed0 = 1234 if a.kind == "noise" else 1235          # bench.py's frames of that kind
+        seed0 = a.seed0 if a.seed0 is not None else (1234 if a.kind == "noise" else 1235)          # bench.py's frames of that kind
         frames = [torch.from_numpy(W.synthetic_frame(h, w, seed=seed0 + 2 * i, kind=a.kind)).to(dev) for i in range(2)]
         out = torch.empty((h, w, 3), dtype=torch.uint16, device=dev)
         for i in range(5):
@@ -70,7 +74,7 @@ def main():
                 p.enqueue_frame(0, frames[i % 2].data_ptr(), h, w, out.data_ptr())
             t1.record(st)
             torch.cuda.synchronize(dev)
-            print(f"stream kind={a.kind} hg_sparse={a.sparse} {h}x{w} frames={a.frames} rep={rep}: {t0.elapsed_time(t1) / a.frames:.3f} ms/frame")
+            print(f"stream kind={a.kind} seeds={seed0},{seed0 + 2} hg_sparse={a.sparse} {h}x{w} frames={a.frames} rep={rep}: {t0.elapsed_time(t1) / a.frames:.3f} ms/frame")
     finally:
         p.close()
 
