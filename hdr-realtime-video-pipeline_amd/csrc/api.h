@@ -249,7 +249,8 @@ struct hdrtv_ctx {
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;
     // cnt != null: a launch that walks a need list of `cnt_total` tiles at most -- its executed count is read back when the entry is
-    struct ProfEntry { std::string layer, kernel; double macs, bytes; float ms; const int *cnt; int cnt_total; };
+    // (hdrtv_profile_tiles); cnt_scales: hdrtv_profile_get reports the work done (conv_prw), else the dense layer's (the other kernels)
+    struct ProfEntry { std::string layer, kernel; double macs, bytes; float ms; const int *cnt; int cnt_total; bool cnt_scales; };
     // lane 0's last frame ran with need lists: its hg.* tensors hold the needed tiles only until hdrtv_get_tap completes them
     // (taps_replayable: that frame was captured into a graph, whose replays the library does not see)
     bool taps_partial = false, taps_replayable = false;
@@ -378,13 +379,13 @@ struct Seq {
         (void)hipEventRecord(c->prof_ev[i], s);
     }
     // called after every launch: counts it, checks it and (profiling) closes its event interval
-    void chk(hipError_t e, const char *what, const char *kernel = "", double macs = 0.0, double bytes = 0.0, const int *cnt = nullptr, int cnt_total = 0)
+    void chk(hipError_t e, const char *what, const char *kernel = "", double macs = 0.0, double bytes = 0.0, const int *cnt = nullptr, int cnt_total = 0, bool cnt_scales = true)
     {
         ++c->launches;
         c->macs += macs;
         if (e != hipSuccess && rc == HDRTV_OK) rc = fail(c, HDRTV_EHIP, "launch %s failed: %s", what, hipGetErrorString(e));
         if (c->prof_on) {
-            c->prof.push_back({what, kernel, macs, bytes, 0.f, cnt, cnt_total});
+            c->prof.push_back({what, kernel, macs, bytes, 0.f, cnt, cnt_total, cnt_scales});
             mark();
         }
     }
@@ -395,7 +396,7 @@ struct Seq {
     // W8A8 LE layer on int8 MFMA (conv_q8.hip).  src: f16 NHWC (quantised on load) or this layer's int8 codes; dst: f16, or
     // (oq != nullptr) the int8 codes of the reading layer's quantiser *oq
     void convq8(const std::string &key, const void *src, bool src_i8, int src_stride, int Hi, int Wi, int act, void *dst, int dstC, const ActQf *oq);
-    void c3(const std::string &key, const f16 *in, int H, int W, int act, f16 *out, f16 *out_pool, float pool_q_inv = 0.f, float pool_q_zero = 0.f, const f16 *w2frag = nullptr, float *part2 = nullptr);
+    void c3(const std::string &key, const f16 *in, int H, int W, int act, f16 *out, f16 *out_pool, float pool_q_inv = 0.f, float pool_q_zero = 0.f, const f16 *w2frag = nullptr, float *part2 = nullptr, const int *need = nullptr, int need_tiles = 0);
     // persistent 32-channel 3x3 conv, optionally with the SFT layer `sft_key` fused in front (conv32p.hip)
     void conv32(const std::string &key, const f16 *src, const f16 *cond, const std::string &sft_key, int H, int W, int act, int mode, f16 *dst, int dstC, int Hd, int Wd, const f16 *res1 = nullptr, const f16 *res2 = nullptr, f16 *dst_planar = nullptr, const f16 *res_planar = nullptr, const f16 *c3_img = nullptr, const std::string &c3_key = "");
     // the lane's copy of workspace tensor `name`

@@ -28,7 +28,8 @@ void Seq::conv(const std::string &key, const f16 *src0, int c0, const f16 *src1,
     p.tail_w = tail_w; p.tail_b = tail_b; p.tail_s = tail_s; p.tail_out = tail_out;
     tail_w = nullptr; tail_b = nullptr; tail_s = nullptr; tail_out = nullptr;
     p.trash = const_cast<char *>(wtp<char>(c, c->dump_off));
-    // a need list set for this launch (run_hg): consumed here; only a kernel with the list's tile geometry takes it
+    // a need list set for this launch (run_hg): consumed here; only a kernel with the list's tile geometry takes it (conv_prw: 16 or 8
+    // rows, conv_pglds and conv_glds1: 16)
     const int *const need = need_list;
     const int need_rows = need_th, need_cells = need_total;
     need_list = nullptr; need_th = 0; need_total = 0;
@@ -57,7 +58,7 @@ void Seq::conv(const std::string &key, const f16 *src0, int c0, const f16 *src1,
     const char *epi = mode == ST_POOL ? "pool" : (mode == ST_PS ? "ps" : (mode == ST_PS_DOT3 ? "ps_dot3" : "nhwc"));
     char tag[64];
     hipError_t e;
-    bool list_taken = false;        // conv_prw walked the need list (a run too long for its LDS slots runs every tile)
+    bool list_taken = false;        // the kernel walked the need list (a run too long for its LDS slots runs every tile)
     switch (route) {
     case T16: snprintf(tag, sizeof tag, "conv_t16<32,3,2>"); e = conv_t16_launch(p, s, c->n_cu); break;
     case S2G:
@@ -69,8 +70,16 @@ void Seq::conv(const std::string &key, const f16 *src0, int c0, const f16 *src1,
         snprintf(tag, sizeof tag, "%s<%s>", prw_th == 8 ? "conv_prw8" : "conv_prw", epi);
         e = conv_prw_launch(p, prw_th, c->n_cu, s, &list_taken);
         break;
-    case PGLDS: snprintf(tag, sizeof tag, "conv_pglds<%s>", epi); e = conv_pglds_launch(p, c->n_cu, s); break;
-    case GLDS1: snprintf(tag, sizeof tag, "conv_glds1"); e = conv_glds1_launch(p, s, c->n_cu, c->var.at("glds1_old") != 0); break;
+    case PGLDS:
+        if (need && need_rows == 16) p.tile_list = need;
+        snprintf(tag, sizeof tag, "conv_pglds<%s>", epi);
+        e = conv_pglds_launch(p, c->n_cu, s, &list_taken);
+        break;
+    case GLDS1:
+        if (need && need_rows == 16) p.tile_list = need;
+        snprintf(tag, sizeof tag, "conv_glds1");
+        e = conv_glds1_launch(p, s, c->n_cu, c->var.at("glds1_old") != 0, &list_taken);
+        break;
     default:
         snprintf(tag, sizeof tag, "conv_igemm<%d,%d,%d,%d>", L.cin_t, L.bn, L.ks, L.stride);
         e = conv_igemm_launch(p, L.cin_t, L.bn, L.ks, L.stride, s);
@@ -85,7 +94,9 @@ void Seq::conv(const std::string &key, const f16 *src0, int c0, const f16 *src1,
                                           : (mode == ST_PLANAR3 ? 3.0 * Hd * Wd
                                                                 : (mode == ST_PS_DOT3 ? 8.0 * Hd * Wd : (double)p.Ho * p.Wo * L.cout));
     bytes += 2.0 * outel * (1 + (res1 ? 1 : 0) + (res2 ? 1 : 0) + (res_planar ? 1 : 0));
-    chk(e, key.c_str(), tag, macs, bytes, list_taken ? p.tile_list : nullptr, need_cells);
+    // the profile scales conv_prw's MACs and bytes by the tiles it walked; the other kernels keep the dense layer's (hdrtv_profile_tiles
+    // has their counts)
+    chk(e, key.c_str(), tag, macs, bytes, list_taken ? p.tile_list : nullptr, need_cells, route == PRW);
 }
 
 
@@ -153,14 +164,18 @@ void Seq::convq8(const std::string &key, const void *src, bool src_i8, int src_s
 }
 
 
-void Seq::c3(const std::string &key, const f16 *in, int H, int W, int act, f16 *out, f16 *out_pool, float pool_q_inv, float pool_q_zero, const f16 *w2frag, float *part2)
+void Seq::c3(const std::string &key, const f16 *in, int H, int W, int act, f16 *out, f16 *out_pool, float pool_q_inv, float pool_q_zero, const f16 *w2frag, float *part2, const int *need, int need_tiles)
 {
     if (!ok()) return;
     const C3Layer &L = c->c3.at(key);
-    chk(conv_c3_launch(in, H, W, wtp<f16>(c, L.wfrag), wtp<float>(c, L.scale), wtp<float>(c, L.shift), L.cout, act, out,
-                       out_pool, c->n_cu, s, pool_q_inv, pool_q_zero, w2frag, part2), key.c_str(),
+    // need: HG.conv1's need list (8 x 32 tiles); the profile keeps the dense layer's MACs and bytes (hdrtv_profile_tiles has the count)
+    bool list_taken = false;
+    const hipError_t e = conv_c3_launch(in, H, W, wtp<f16>(c, L.wfrag), wtp<float>(c, L.scale), wtp<float>(c, L.shift), L.cout, act, out,
+                                        out_pool, c->n_cu, s, pool_q_inv, pool_q_zero, w2frag, part2, need, &list_taken);
+    chk(e, key.c_str(),
         part2 ? "conv_c3<64,dot3>" : (L.cout == 64 ? "conv_c3<64>" : "conv_c3<32>"), (double)H * W * (27 * L.cout + (part2 ? 192 : 0)),
-        (double)H * W * (6.0 + (out ? 2.0 * L.cout : 0.0) + (out_pool ? (pool_q_inv > 0.f ? 0.25 : 0.5) * L.cout : 0.0) + (part2 ? 16.0 : 0.0)));
+        (double)H * W * (6.0 + (out ? 2.0 * L.cout : 0.0) + (out_pool ? (pool_q_inv > 0.f ? 0.25 : 0.5) * L.cout : 0.0) + (part2 ? 16.0 : 0.0)),
+        list_taken ? need : nullptr, need_tiles, false);
 }
 
 
@@ -615,13 +630,15 @@ int run_le(hdrtv_ctx *c, Seq &q, const f16 *img, f16 *out_planar)
 // the buffer ("hg.need") all of it lies in; the layout does not depend on the variants (every map is sized for the finest unit
 // table), only HgNeedLayer::th and the unit table (hg_sparse = 1: 16x16 cells, else the sub-tile units) do.
 // Layout: flags | two blocks no longer used (the byte-per-cell maps of the first form; they keep the lists where they were) |
-// the layers' lists | the tensors' bit-row maps | two scratch maps.
+// the layers' lists | the tensors' bit-row maps | two scratch maps | conv1's list | the map of conv1's input.
+// conv1 (conv_c3: pool-fused 3x3 at level 0, 8 x 32 tiles, img -> hg_layers[0].in) is not a row of the table; it is p.L[0], in front
+// of the table's rows, and what it adds to the buffer lies behind everything else.
 size_t hg_need_plan(hdrtv_ctx *c, int Hp, int Wp, HgNeedParams &p)
 {
     memset(&p, 0, sizeof p);
     p.Hp = Hp; p.Wp = Wp;
     constexpr int n_layers = (int)(sizeof hg_layers / sizeof hg_layers[0]);
-    static_assert(n_layers <= HG_NEED_MAX_LAYERS && n_layers + 2 <= HG_NEED_MAX_TENSORS, "hg_need's tables are too small");
+    static_assert(n_layers + 1 <= HG_NEED_MAX_LAYERS && n_layers + 3 <= HG_NEED_MAX_TENSORS, "hg_need's tables are too small");
     constexpr int max_level = [] { int m = 0; for (const HgLayer &L : hg_layers) m = L.level > m ? L.level : m; return m; }();
     static_assert(max_level < HG_NEED_LEVELS, "hg_need's unit tables have too few levels");
     memcpy(p.lu, hg_need_unit_log2[c->var.at("hg_sparse") == 1 ? 1 : 2], sizeof p.lu);
@@ -646,18 +663,27 @@ size_t hg_need_plan(hdrtv_ctx *c, int Hp, int Wp, HgNeedParams &p)
     };
     for (int i = 0; i < n_layers; ++i) {
         const HgLayer &L = hg_layers[i];
-        HgNeedLayer &N = p.L[i];
-        N.level = L.level; N.ks = L.ks;
+        HgNeedLayer &N = p.L[i + 1];
+        N.level = L.level; N.ks = L.ks; N.tw = 16;
         N.mode = L.mode == ST_POOL ? 1 : (L.ps ? 2 : 0);
         N.in = tensor(L.in, L.level);
         N.skip = L.skip ? tensor(L.skip, L.level) : -1;
         N.out = tensor(L.out, L.out_level());
         N.th = L.ks == 3 && Seq::prw_tile_rows(c, L.mode, L.cout, Hp >> L.level, Wp >> L.level) == 8 ? 8 : 16;    // conv()'s own choice
     }
-    p.n_layers = n_layers;
+    const int nt_table = nt;                         // conv1's input comes last: its map lies behind the table's
+    {
+        HgNeedLayer &N = p.L[0];
+        N.level = 0; N.ks = 3; N.mode = 1;
+        N.out = tensor(hg_layers[0].in, 1);
+        N.in = tensor("img", 0);
+        N.skip = -1;
+        N.th = 8; N.tw = 32;                         // conv_c3's tiles (le_hg_misc.hip)
+    }
+    p.n_layers = n_layers + 1;
     // hg_need walks the table backwards: the first reader it meets stores a tensor's map, so no map needs clearing
     bool seen[HG_NEED_MAX_TENSORS] = {};
-    for (int i = n_layers - 1; i >= 0; --i) {
+    for (int i = p.n_layers - 1; i >= 0; --i) {
         HgNeedLayer &N = p.L[i];
         N.in_first = !seen[N.in];
         seen[N.in] = true;
@@ -667,22 +693,25 @@ size_t hg_need_plan(hdrtv_ctx *c, int Hp, int Wp, HgNeedParams &p)
     auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return (int)o; };
     p.flags_off = take((size_t)ncell(0));
     take((size_t)ncell(0));
-    for (int t = 0; t < nt; ++t)
+    for (int t = 0; t < nt_table; ++t)
         if (strcmp(names[t], "part")) take((size_t)ncell(level[t]));
-    for (int i = 0; i < n_layers; ++i) p.L[i].list_off = take(4 * (2 * (size_t)ncell(p.L[i].level) + 4));
+    for (int i = 1; i <= n_layers; ++i) p.L[i].list_off = take(4 * (2 * (size_t)ncell(p.L[i].level) + 4));
     size_t scratch = 0;
-    for (int t = 0; t < nt; ++t) {
+    for (int t = 0; t < nt; ++t) scratch = std::max(scratch, nwords(level[t]));
+    for (int t = 0; t < nt_table; ++t) {
         p.map_off[t] = take(8 * nwords(level[t]));
-        scratch = std::max(scratch, nwords(level[t]));
         if (!strcmp(names[t], "part")) p.flags_map = t;
     }
-    for (int i = 0; i < n_layers; ++i) {
-        p.L[i].out_chained = i + 1 < n_layers ? p.L[i + 1].in == p.L[i].out : p.L[i].out == p.flags_map;
+    for (int i = 0; i < p.n_layers; ++i) {
+        p.L[i].out_chained = i + 1 < p.n_layers ? p.L[i + 1].in == p.L[i].out : p.L[i].out == p.flags_map;
         p.L[i].in_chained = i > 0 && p.L[i - 1].out == p.L[i].in;
     }
     p.scratch_words = (int)scratch;
     p.kbits_off = take(8 * scratch);
     p.tbits_off = take(8 * scratch);
+    // conv1: 8 x 32 tiles, two per 16x16 cell
+    p.L[0].list_off = take(4 * (2 * (size_t)ncell(0) + 4));
+    p.map_off[nt_table] = take(8 * nwords(0));
     return off;
 }
 
@@ -694,8 +723,9 @@ int run_hg(hdrtv_ctx *c, Seq &q, const f16 *base, void *out, int out_f32, bool c
     const int Hp = s.Hp, Wp = s.Wp;
     f16 *img = q.wsp<f16>("hg.img");
     uint8_t *mask = q.wsp<uint8_t>("hg.mask");
-    // Need lists (variant hg_sparse; fp16 HG with the per-pixel tail): the layers on conv_prw compute only the tiles a masked
-    // output pixel depends on, the blend takes img everywhere else.  Built on the device behind hg_prep (hg_need.hip).
+    // Need lists (variant hg_sparse; fp16 HG with the per-pixel tail): every layer of the head, conv1 included, computes only the
+    // tiles a masked output pixel depends on (conv_c3<64,dot3>, conv_pglds, conv_prw, conv_glds1 each walk their list),
+    // the blend takes img everywhere else.  Built on the device behind hg_prep (hg_need.hip).
     const bool sparse = !complete_taps && c->var.at("hg_sparse") != 0 && !c->hg_i8 && !c->var.at("final_recompute");
     HgNeedParams np;
     if (sparse) {
@@ -737,12 +767,15 @@ int run_hg(hdrtv_ctx *c, Seq &q, const f16 *base, void *out, int out_f32, bool c
     };
     // conv1 keeps only its pooled map, conv2's input.  W8A8: the fp16 -> int8 boundary costs no pass of its own, conv1 stores the
     // codes conv2 wants (hg_q0_inv = 0 for an fp16 HG: no quantiser)
-    q.c3("hg.conv1", img, Hp, Wp, ACT_RELU, nullptr, (f16 *)tensor(hg_layers[0].in), c->hg_q0_inv, c->hg_q0_zero, w2frag, part2);
+    // (its need list: the per-pixel tail reads part2 at masked pixels only, conv2 reads the pooled map where its own list says)
+    const bool c1_list = sparse && light;
+    q.c3("hg.conv1", img, Hp, Wp, ACT_RELU, nullptr, (f16 *)tensor(hg_layers[0].in), c->hg_q0_inv, c->hg_q0_zero, w2frag, part2,
+         c1_list ? reinterpret_cast<const int *>(np.base + np.L[0].list_off) : nullptr, c1_list ? ((Hp + 7) / 8) * ((Wp + 31) / 32) : 0);
     char key[32];
     for (const HgLayer &L : hg_layers) {
         snprintf(key, sizeof key, "hg.%s", L.name);
         if (sparse) {
-            const HgNeedLayer &N = np.L[&L - hg_layers];
+            const HgNeedLayer &N = np.L[&L - hg_layers + 1];
             q.need_list = reinterpret_cast<const int *>(np.base + N.list_off);
             q.need_th = N.th;
             q.need_total = (((Hp >> L.level) + N.th - 1) / N.th) * (((Wp >> L.level) + 15) / 16);

@@ -33,7 +33,8 @@ const std::pair<const char *, int> k_variants[] = {
     {"no_c3fuse", 0},        // 1: LE.conv_first as its own launch in front of HR_conv1
     {"no_c3q8", 0},          // 1: the W8A8 LE.conv_first through planar3_to_q8 + conv_q8 instead of conv_c3_q8
     {"glds1_old", 0},        // 1: HG 1x1 fuse convs on the non-persistent kernel
-    {"hg_sparse", 2},        // fp16 HG: the conv_prw layers compute only the tiles the highlight mask lets reach the output (hg_need.hip): 2 = need tracked in
+    {"hg_sparse", 2},        // fp16 HG: every layer of the head (conv1 on conv_c3, conv_prw, conv_pglds, the 1x1 fuse convs on conv_glds1) computes only the
+                             // tiles the highlight mask lets reach the output (hg_need.hip): 2 = need tracked in
                              // sub-tile units (4, 2, 1, 1, 1 pixels at levels 1 .. 5, a one-pixel halo per 3x3 layer), 1 = in 16x16 cells of every level (a whole
                              // cell of halo per layer: the encoder is dense on any frame with a highlight), 0 = every tile
     {"final_recompute", 0},  // 1: HG tail recomputes conv1 (hg_final_fused) instead of reading conv1's per-pixel sums

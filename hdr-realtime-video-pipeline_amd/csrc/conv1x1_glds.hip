@@ -187,9 +187,13 @@ __global__ __launch_bounds__(512) void conv_glds1_kernel(ConvParams p)
 //     32 pixels (waves 0-5 in the A slot, 6-7 in the B slot); one extra barrier per tile lets the slot be refilled;
 //   * vmcnt counts DMA pieces and stores together in issue order: every wave issues exactly NST stores per tile (masked
 //     lanes store to the trash line), so the first wait of a tile is vmcnt(6 + NST) and every other one vmcnt(6).
+// Sparse launches (ConvParams::tile_list, the HG need lists of hg_need.hip), as conv_prw: the spatial tiles are the list's entries.
+// The count is read once; every block copies the entries of ITS run into LDS beside the scale / shift fill, in front of the
+// prologue's __syncthreads() and of the first DMA, so the tile loop's only new operation is one LDS read per tile.
 constexpr int P_NST = 8;          // stores per wave and tile: 2 passes x 4
 constexpr int P_SP = 144;         // strip row pitch: 64 ch x 2 B + 16
 constexpr int P_MAXC = 512;       // most output channels the scale / shift table holds
+constexpr int P_LIST_N = 512;     // ConvParams::tile_list: most tiles of one block's run (2 KiB of LDS)
 
 __global__ __launch_bounds__(512) void conv_glds1p_kernel(ConvParams p)
 {
@@ -200,9 +204,13 @@ __global__ __launch_bounds__(512) void conv_glds1p_kernel(ConvParams p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
 
+    // scale / shift of this thread's output channel (CoutPad <= P_MAXC = the block): loaded first, so that the list's count and
+    // entries below, two dependent trips to device memory, travel beside them and not behind
+    const float my_scale = tid < p.CoutPad ? p.scale[tid] : 0.f, my_shift = tid < p.CoutPad ? p.shift[tid] : 0.f;
     // ---- this block's run of tiles: XCD x owns a contiguous range, its blocks interleave in it (as conv_pglds)
     const int ntn = p.CoutPad / BN;
-    const int total = p.tiles_x * p.tiles_y * ntn;
+    const int *const lst = p.tile_list;                      // null: every tile (dense)
+    const int total = (lst ? lst[0] : p.tiles_x * p.tiles_y) * ntn;
     int t_first, t_step, ntile;
     {
         const int G = gridDim.x, b = blockIdx.x, xcd = b & 7, slot = b >> 3;
@@ -215,10 +223,19 @@ __global__ __launch_bounds__(512) void conv_glds1p_kernel(ConvParams p)
         ntile = slot < len ? (len - slot + nslots - 1) / nslots : 0;
     }
     if (ntile == 0) return;
+    // the list entries of this block's run (the launcher passes a list only when a run fits P_LIST_N); visible behind the __syncthreads() below
+    __shared__ int s_list_mem[P_LIST_N];
+    // (an LDS-space pointer: through a generic one the volatile accesses are FLAT operations, and the write a store vmcnt would count)
+    volatile __attribute__((address_space(3))) int *s_list = (volatile __attribute__((address_space(3))) int *)s_list_mem;
+    if (lst && tid < ntile) s_list[tid] = lst[1 + (t_first + tid * t_step) / ntn];
     struct Tile { int n0, oy0, ox0; };
-    auto decode = [&](int t) {
+    // tile number k of the run
+    auto decode = [&](int k) {
         Tile o;
-        const int nt_i = t % ntn, sp = t / ntn;
+        const int t = t_first + k * t_step;
+        const int nt_i = t % ntn;
+        int sp = t / ntn;
+        if (lst) sp = __builtin_amdgcn_readfirstlane(s_list[k]);
         const int ty = sp / p.tiles_x, tx = sp - ty * p.tiles_x;
         o.n0 = nt_i * BN; o.oy0 = ty * TH; o.ox0 = tx * TW;
         return o;
@@ -274,10 +291,10 @@ __global__ __launch_bounds__(512) void conv_glds1p_kernel(ConvParams p)
     // scale / shift of every output channel in LDS, once per workgroup and before any DMA is in flight (a global load in
     // the epilogue is waited for with vmcnt(0) by hipcc, one round trip per use)
     __shared__ __attribute__((aligned(16))) float s_ss[2 * P_MAXC];
-    for (int e = tid; e < p.CoutPad; e += 512) { s_ss[e] = p.scale[e]; s_ss[P_MAXC + e] = p.shift[e]; }
+    if (tid < p.CoutPad) { s_ss[tid] = my_scale; s_ss[P_MAXC + tid] = my_shift; }
     __syncthreads();
 
-    Tile cur = decode(t_first), nxt = cur;
+    Tile cur = decode(0), nxt = cur;
     issue(cur, 0, 0);
     issue(cur, 1, 1);
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -285,7 +302,7 @@ __global__ __launch_bounds__(512) void conv_glds1p_kernel(ConvParams p)
     int slot = 0;
     for (int k = 0; k < ntile; ++k) {
         const bool has_next = k + 1 < ntile;
-        if (has_next) nxt = decode(t_first + (k + 1) * t_step);
+        if (has_next) nxt = decode(k + 1);
 #pragma unroll 1
         for (int cc = 0; cc < nchunk; ++cc) {
             const int s2 = slot == 0 ? 2 : slot - 1;          // (slot + 2) % 3
@@ -361,8 +378,10 @@ __global__ __launch_bounds__(512) void conv_glds1p_kernel(ConvParams p)
 }  // namespace
 
 // 1x1, stride 1, Cin (src0 [+ src1 concat]) multiple of 64, CoutPad multiple of 128, NHWC store, no residuals.
-hipError_t conv_glds1_launch(ConvParams p, hipStream_t stream, int n_cu, bool old_form)
+// p.tile_list (16x16 tiles) is walked by the persistent form when a block's run fits its LDS block; *list_taken says whether it was.
+hipError_t conv_glds1_launch(ConvParams p, hipStream_t stream, int n_cu, bool old_form, bool *list_taken)
 {
+    if (list_taken) *list_taken = false;
     if ((p.c0 % CT) || (p.c1 % CT) || p.c0 + p.c1 < CT || (p.CoutPad % BN) || p.res1 || p.res2 || p.dst_full ||
         p.mode != ST_NHWC || !p.zeros)
         return hipErrorInvalidValue;
@@ -388,9 +407,14 @@ hipError_t conv_glds1_launch(ConvParams p, hipStream_t stream, int n_cu, bool ol
             if (e != hipSuccess) return e;
             attr_p.done();
         }
-        hipLaunchKernelGGL(conv_glds1p_kernel, dim3(grid < n_cu ? grid : n_cu), dim3(512), SMEM, stream, p);
+        // the grid never depends on the list's count (device memory); a run too long for the LDS block: dense
+        const int g = grid < n_cu ? grid : n_cu;
+        if (p.tile_list && g >= 8 && (grid / 8 + 1 + g / 8 - 1) / (g / 8) > P_LIST_N) p.tile_list = nullptr;
+        if (list_taken) *list_taken = p.tile_list != nullptr;
+        hipLaunchKernelGGL(conv_glds1p_kernel, dim3(g), dim3(512), SMEM, stream, p);
         return hipGetLastError();
     }
+    p.tile_list = nullptr;             // the one-tile-per-workgroup form runs every tile
 #ifdef HDRTV_AB
     hipLaunchKernelGGL(conv_glds1_kernel, dim3(grid), dim3(512), SMEM, stream, p);
     return hipGetLastError();

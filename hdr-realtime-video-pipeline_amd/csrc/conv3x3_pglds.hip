@@ -18,6 +18,10 @@
 //     and LDS-DMA together in issue order, so the counted wait after a tile boundary depends on it.
 // MFMA shape 16x16x32 (lane = row & 15, k-group = lane >> 4): under load the chip holds a higher
 // clock on it than on 32x32x16 (MI355X_MICROARCH.md, DVFS give-back item 7; measured here +4 %).
+//
+// Sparse launches (ConvParams::tile_list, the HG need lists of hg_need.hip), as conv_prw: the spatial tiles are the list's
+// entries instead of all tiles_x * tiles_y.  The count is read once; every block copies the entries of ITS run into LDS in
+// the prologue (in front of the prologue's barrier), so the tile loop's only new operation is one LDS read per tile.
 #include "launchers.h"
 
 namespace {
@@ -29,7 +33,9 @@ constexpr int A_PIECES_PER_WAVE = 6, A_BYTES = 8 * A_PIECES_PER_WAVE * 1024;   /
 constexpr int B_BYTES = BN * PIXB, B_PIECES_PER_WAVE = 2;                       // 16 KiB
 constexpr int SS_OFF = 2 * A_BYTES + 3 * B_BYTES;        // two 1-KiB {scale[128], shift[128]} slots
 constexpr int DOTW_OFF = SS_OFF + 2048;                  // ST_PS_DOT3: 24 fragment pairs (hi, lo) of 32 B
-constexpr int SMEM = DOTW_OFF + 1024;                    // 147 KiB
+constexpr int LIST_OFF = DOTW_OFF + 1024;                // ConvParams::tile_list: this block's run of spatial tiles, looked up once
+constexpr int LIST_N = 512;
+constexpr int SMEM = LIST_OFF + LIST_N * 4;              // 149 KiB
 
 // stores per wave and tile, by store mode (see the epilogues)
 template <int MODE> struct NStores { static constexpr int N = MODE == ST_POOL ? 2 : (MODE == ST_PS_DOT3 ? 1 : 8); };
@@ -74,7 +80,9 @@ __global__ __launch_bounds__(512) void conv_pglds_kernel(ConvParams p)
 
     // ---- this block's run of tiles: XCD x owns a contiguous range, its blocks interleave in it --
     const int ntn = p.CoutPad / BN;
-    const int total = p.tiles_x * p.tiles_y * ntn;
+    const int *const lst = p.tile_list;                      // null: every tile (dense)
+    const int nsp = lst ? lst[0] : p.tiles_x * p.tiles_y;    // spatial tiles to compute
+    const int total = nsp * ntn;
     int t_first, t_step, ntile;
     {
         const int G = gridDim.x, b = blockIdx.x, xcd = b & 7, slot = b >> 3;
@@ -87,10 +95,25 @@ __global__ __launch_bounds__(512) void conv_pglds_kernel(ConvParams p)
         ntile = slot < len ? (len - slot + nslots - 1) / nslots : 0;
     }
     if (ntile == 0) return;
-    auto decode = [&](int t) {
+    // the list entries of this block's run (the launcher passes a list only when a run fits LIST_N); visible behind the prologue's barrier
+    // (an LDS-space pointer: through a generic one the volatile accesses are FLAT operations, and the write a store vmcnt would count)
+    volatile __attribute__((address_space(3))) int *s_list = (volatile __attribute__((address_space(3))) int *)(smem + LIST_OFF);
+    int sp_first = 0;                                        // the run's first entry: loaded beside the others, one trip to memory
+    if (lst) {
+        sp_first = lst[1 + (p.nt_slow ? t_first % nsp : t_first / ntn)];
+        if (tid < ntile) {
+            const int t = t_first + tid * t_step;
+            s_list[tid] = lst[1 + (p.nt_slow ? t % nsp : t / ntn)];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+    // tile number k of the run (k = 0: the prologue, in front of the barrier, has the entry from the list itself)
+    auto decode = [&](int k) {
         Tile o;
-        const int nsp = p.tiles_x * p.tiles_y;
-        const int nt_i = p.nt_slow ? t / nsp : t % ntn, sp = p.nt_slow ? t - nt_i * nsp : t / ntn;
+        const int t = t_first + k * t_step;
+        const int nt_i = p.nt_slow ? t / nsp : t % ntn;
+        int sp = p.nt_slow ? t - nt_i * nsp : t / ntn;
+        if (lst) sp = k ? __builtin_amdgcn_readfirstlane(s_list[k]) : sp_first;
         const int ty = sp / p.tiles_x, tx = sp - ty * p.tiles_x;
         o.n0 = nt_i * BN; o.oy0 = ty * TH; o.ox0 = tx * TW;
         return o;
@@ -171,7 +194,7 @@ __global__ __launch_bounds__(512) void conv_pglds_kernel(ConvParams p)
     const int a_lane = (wp * 4 * HW + l15) * PIXB;
 
     // ---- prologue: first tile's halo, scale/shift and weights of taps 0 and 1 -----------------
-    Tile cur = decode(t_first), nxt = cur;
+    Tile cur = decode(0), nxt = cur;
     issue_A(0, 0, cur);
     issue_SS(cur.n0, 0);
     issue_B(0, cur.n0, 0);
@@ -183,7 +206,7 @@ __global__ __launch_bounds__(512) void conv_pglds_kernel(ConvParams p)
     int gch = 0;                                  // chunks done so far: halo buffer parity
     for (int k = 0; k < ntile; ++k) {
         const bool has_next = k + 1 < ntile;
-        if (has_next) nxt = decode(t_first + (k + 1) * t_step);
+        if (has_next) nxt = decode(k + 1);
         for (int cc = 0; cc < nchunk; ++cc, ++gch) {
             const char *a = sA + (gch & 1) * A_BYTES;
             const bool last_chunk = cc + 1 == nchunk;
@@ -390,8 +413,10 @@ hipError_t launch_mode(const ConvParams &p, int grid, hipStream_t stream)
 
 // 3x3, stride 1, pad 1, Cin (src0 [+ src1 concat]) multiple of 64, Cout == CoutPad multiple of 128, no residuals;
 // store modes NHWC / PS / POOL / PS_DOT3.  One block per CU (n_cu), each walking tiles.  hipErrorInvalidValue otherwise.
-hipError_t conv_pglds_launch(ConvParams p, int n_cu, hipStream_t stream)
+// p.tile_list (16x16 tiles) is walked when a block's run fits the kernel's LDS block; *list_taken says whether it was.
+hipError_t conv_pglds_launch(ConvParams p, int n_cu, hipStream_t stream, bool *list_taken)
 {
+    if (list_taken) *list_taken = false;
     if ((p.c0 % CT) || (p.c1 % CT) || p.c0 + p.c1 < CT || (p.CoutPad % BN) || p.Cout != p.CoutPad || p.res1 || p.res2 ||
         p.dst_full || !p.zeros || !p.trash || n_cu < 8 || (p.act != ACT_RELU && p.act != ACT_NONE) ||
         (p.mode != ST_NHWC && p.mode != ST_PS && p.mode != ST_POOL && p.mode != ST_PS_DOT3) ||
@@ -401,6 +426,9 @@ hipError_t conv_pglds_launch(ConvParams p, int n_cu, hipStream_t stream)
     p.tiles_y = (p.Ho + TH - 1) / TH;
     const int total = p.tiles_x * p.tiles_y * (p.CoutPad / BN);
     const int grid = total < n_cu ? total : n_cu;
+    // the grid never depends on the list's count (device memory); a run too long for the LDS slots: dense
+    if (p.tile_list && grid >= 8 && (total / 8 + 1 + grid / 8 - 1) / (grid / 8) > LIST_N) p.tile_list = nullptr;
+    if (list_taken) *list_taken = p.tile_list != nullptr;
     switch (p.mode) {
     case ST_NHWC: return launch_mode<ST_NHWC>(p, grid, stream);
     case ST_PS: return launch_mode<ST_PS>(p, grid, stream);

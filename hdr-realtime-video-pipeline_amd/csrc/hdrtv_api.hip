@@ -797,7 +797,7 @@ int hdrtv_profile_get(hdrtv_ctx *c, int i, const char **layer, const char **kern
     HIPCHK(c, hipEventElapsedTime(&e.ms, c->prof_ev[i], c->prof_ev[i + 1]));
     // a launch that walked a need list: the work it did, not the dense layer's (the frame has finished: the count is final)
     double done = 1.0;
-    if (e.cnt && e.cnt_total > 0) {
+    if (e.cnt && e.cnt_total > 0 && e.cnt_scales) {
         int n = 0;
         HIPCHK(c, hipMemcpy(&n, e.cnt, sizeof n, hipMemcpyDeviceToHost));
         done = (double)n / (double)e.cnt_total;
@@ -807,6 +807,25 @@ int hdrtv_profile_get(hdrtv_ctx *c, int i, const char **layer, const char **kern
     if (ms) *ms = e.ms;
     if (macs) *macs = e.macs * done;
     if (bytes) *bytes = e.bytes * done;
+    return HDRTV_OK;
+}
+
+// Launch i of the last profiled frame: the tiles it computed (its need list's count, read back from the device: the frame must have
+// finished) and the tiles of a dense launch.  *total = 0: the launch had no list, or its list was dropped and it ran every tile.
+int hdrtv_profile_tiles(hdrtv_ctx *c, int i, int *executed, int *total)
+{
+    if (!c) return HDRTV_EINVAL;
+    const int n = (int)c->prof.size();
+    if (i < 0 || i >= n || (size_t)i + 1 >= c->prof_ev.size()) return fail(c, HDRTV_EINVAL, "profile index out of range");
+    const hdrtv_ctx::ProfEntry &e = c->prof[i];
+    int done = 0, all = 0;
+    if (e.cnt && e.cnt_total > 0) {
+        HIPCHK(c, hipEventSynchronize(c->prof_ev[i + 1]));
+        HIPCHK(c, hipMemcpy(&done, e.cnt, sizeof done, hipMemcpyDeviceToHost));
+        all = e.cnt_total;
+    }
+    if (executed) *executed = done;
+    if (total) *total = all;
     return HDRTV_OK;
 }
 

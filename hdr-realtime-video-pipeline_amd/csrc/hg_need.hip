@@ -18,7 +18,8 @@
 //                       between two maps whose units differ, a K unit is needed if an out unit it touches is;
 //   need(in [, skip]) |= K dilated by one unit for a 3x3 layer (its halo is one pixel: one unit or less), K itself for a 1x1 layer.
 // A tensor with two readers collects both (the layers run in reverse launch order, so every reader is seen before the producer).
-// A layer's list holds the kernel tiles (16 x 16, or 8 rows x 16 for conv_prw8) with at least one unit of K, in ascending order.
+// A layer's list holds the kernel tiles (16 x 16, 8 rows x 16 for conv_prw8, 8 rows x 32 for conv1 on conv_c3) with at least one
+// unit of K, in ascending order.
 //
 // Why a computed tile may hold wrong pixels.  A listed tile is computed whole, but only its K units had their inputs computed:
 // its other pixels are made from skipped or stale inputs -- another frame's values, after an overflow even non-finite ones.  They
@@ -128,9 +129,9 @@ __global__ __launch_bounds__(NT) void hg_need_kernel(HgNeedParams p)
         const int lu = p.lu[L.level], nk = mk.h * mk.nw;
         // a K unit x lies in the out unit x >> sh (sh = 1), is it (0), or holds the out units 2 x and 2 x + 1 (-1)
         const int sh = p.lu[olev] - lu + olev - L.level;
-        // the tiles: th rows x 16 pixels = rows [r0, r0 + nr) x bw bits of the map
-        const int lth = L.th == 8 ? 3 : 4, lbw = 4 - lu;
-        const int ty_n = ((p.Hp >> L.level) + L.th - 1) >> lth, tx_n = ((p.Wp >> L.level) + 15) >> 4, nt = ty_n * mk.nw;
+        // the tiles: th rows x tw pixels = rows [r0, r0 + nr) x bw bits of the map
+        const int lth = L.th == 8 ? 3 : 4, ltw = L.tw == 32 ? 5 : 4, lbw = ltw - lu;
+        const int ty_n = ((p.Hp >> L.level) + L.th - 1) >> lth, tx_n = ((p.Wp >> L.level) + (1 << ltw) - 1) >> ltw, nt = ty_n * mk.nw;
         const bool lds = max(nk, nt) <= LDS_WORDS;
         u64 *km = lds ? s_k : reinterpret_cast<u64 *>(p.base + p.kbits_off);
         u64 *tm = lds ? s_t : reinterpret_cast<u64 *>(p.base + p.tbits_off);
@@ -219,7 +220,9 @@ hipError_t hg_need_launch(const HgNeedParams &p, hipStream_t s)
         const int olev = L.level + (L.mode == 1 ? 1 : 0) - (L.mode == 2 ? 1 : 0);
         if (L.level < 0 || L.level >= HG_NEED_LEVELS || olev < 0 || olev >= HG_NEED_LEVELS) return hipErrorInvalidValue;
         const int sh = p.lu[olev] - p.lu[L.level] + olev - L.level;
-        if (p.lu[L.level] < 0 || p.lu[L.level] > 4 || sh < -1 || sh > 1 || (L.th != 8 && L.th != 16)) return hipErrorInvalidValue;
+        if (p.lu[L.level] < 0 || p.lu[L.level] > 4 || sh < -1 || sh > 1 || (L.th != 8 && L.th != 16) ||
+            (L.tw != 0 && L.tw != 16 && L.tw != 32))
+            return hipErrorInvalidValue;
     }
     if (p.lu[0] != 4) return hipErrorInvalidValue;      // hg_prep's flags are 16x16 cells
     hipLaunchKernelGGL(hg_need_kernel, dim3(1), dim3(NT), 0, s, p);

@@ -12,8 +12,8 @@ struct DevOnce {
 };
 
 hipError_t conv_igemm_launch(ConvParams p, int cin_t, int bn, int ks, int stride, hipStream_t stream);
-hipError_t conv_glds1_launch(ConvParams p, hipStream_t stream, int n_cu = 0, bool old_form = false);   // n_cu >= 8: the persistent form
-hipError_t conv_pglds_launch(ConvParams p, int n_cu, hipStream_t stream);
+hipError_t conv_glds1_launch(ConvParams p, hipStream_t stream, int n_cu = 0, bool old_form = false, bool *list_taken = nullptr);   // n_cu >= 8: the persistent form
+hipError_t conv_pglds_launch(ConvParams p, int n_cu, hipStream_t stream, bool *list_taken = nullptr);
 hipError_t conv_prw_launch(ConvParams p, int th, int n_cu, hipStream_t stream, bool *list_taken = nullptr);   // Cout % 256 == 0, modes NHWC / PS / POOL; th = 16 | 8
 hipError_t conv_pglds_i8_launch(ConvI8Params p, int n_cu, hipStream_t stream);
 hipError_t conv_prw_i8_launch(ConvI8Params p, int th, int n_cu, hipStream_t stream);   // Cin % 128 == 0, Cout % 256 == 0, int8 out
@@ -58,7 +58,8 @@ hipError_t agcm_mlp_launch(const f16 *in, f16 *out, size_t npix, const f16 *frag
 
 hipError_t conv_c3_launch(const f16 *in, int H, int W, const f16 *wfrag, const float *scale, const float *shift, int cout,
                           int act, f16 *out, f16 *out_pool, int n_cu, hipStream_t s, float pool_q_inv = 0.f, float pool_q_zero = 0.f,
-                          const f16 *w2frag = nullptr, float *part2 = nullptr);   // HG.conv1: + conv10's second half per pixel (f32 [H][W][4])
+                          const f16 *w2frag = nullptr, float *part2 = nullptr,    // HG.conv1: + conv10's second half per pixel (f32 [H][W][4])
+                          const int *tile_list = nullptr, bool *list_taken = nullptr);   // ... over the listed 8 x 32 tiles only (hg_need.hip)
 // LE.conv_first as a W8A8 layer: int8 A fragments [2][64 lanes][16 B] (K = (ky | kx4, c4)), scale[32], shift[16 border classes][32]
 hipError_t conv_c3_q8_launch(const f16 *in, int H, int W, const int8_t *wq, const float *scale, const float *shift, float q_inv,
                              float q_zoff, int act, f16 *out, int n_cu, hipStream_t s);
@@ -109,8 +110,8 @@ struct HgNeedLayer {
     int in_first, skip_first;  // this layer is the last reader in launch order (the first hg_need sees): it stores the map, others OR
     int out_chained;           // out is the input of the next layer in launch order (the last layer: out is the flags' map) ...
     int in_chained;            // ... in is the output of the layer before: the map may be handed on in the kernel's LDS
-    int th;                    // rows of the kernel tiles the list is written for: 16 or 8
-    int list_off;              // int [0] count, [1 ..] tile indices ty * ceil(W_level / 16) + tx, ascending
+    int th, tw;                // the kernel tiles the list is written for: 16 or 8 rows of 16 pixels (tw = 0 or 16), or of 32 (conv_c3: 8 x 32)
+    int list_off;              // int [0] count, [1 ..] tile indices ty * ceil(W_level / tw) + tx, ascending
 };
 struct HgNeedParams {
     unsigned char *base;

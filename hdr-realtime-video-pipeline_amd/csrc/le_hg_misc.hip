@@ -24,6 +24,7 @@ constexpr int C3_TH = 8, C3_TW = 32;
 constexpr int C3_HH = C3_TH + 2, C3_HW = C3_TW + 2;
 constexpr int C3_PW = C3_HW + 2;          // pixel pitch of the LDS patch: columns 34, 35 are the kx = 3 dummy reads (zero weights)
 constexpr int C3_NP = (C3_HH * C3_HW + 255) / 256;       // halo pixels per thread
+constexpr int C3_LIST_N = 512;            // conv_c3<64, DOT> with a tile list: most tiles of one workgroup's run (2 KiB of LDS)
 
 // B fragment of kernel row ky for output pixel (row, l31): pixels l31 + 2*lh and l31 + 2*lh + 1 of patch row row + ky
 __device__ __forceinline__ f16x8 c3_frag(const f16x4 *s_px, int row, int ky, int l31, int lh)
@@ -66,12 +67,15 @@ __device__ __forceinline__ void c3_stage(const C3Pre &pre, f16x4 *s_px, int tid)
 // (1x1 over conv1's 64 channels, Hallucination_arch.py:130-133) in part2 [H][W][4] f32 -- the f16 activations, as they lie in the
 // accumulator registers, are the B operand of four MFMAs against the k-permuted weight fragments w2frag (the chain
 // hg_final_fused recomputes conv1 for); with them the HG tail (hg_final_light) is a per-pixel kernel.
+// tile_list (DOT only; null: every tile): [0] = count, [1 ..] = the tiles to compute (hg_need.hip: conv1's need list).  Step k of
+// workgroup b takes entry b + k * gridDim.x; the workgroup copies its entries into LDS in the prologue and reads the first two from
+// the list itself, so the prefetches of the tiles one and two steps ahead find theirs behind the tile loop's barrier.
 template <int COUT, bool DOT = false>
 __global__ __launch_bounds__(256) void conv_c3_kernel(const f16 *__restrict__ in, int H, int W, const f16 *__restrict__ wfrag,
                                                       const float *__restrict__ scale, const float *__restrict__ shift,
                                                       int act, f16 *__restrict__ out, f16 *__restrict__ out_pool, float pool_q_inv,
                                                       float pool_q_zero, const f16 *__restrict__ w2frag = nullptr,
-                                                      float *__restrict__ part2 = nullptr)
+                                                      float *__restrict__ part2 = nullptr, const int *__restrict__ tile_list = nullptr)
 {
     static_assert(!DOT || COUT == 64, "the fused conv10 half belongs to HG.conv1");
     constexpr int MT = COUT / 32;
@@ -85,6 +89,9 @@ __global__ __launch_bounds__(256) void conv_c3_kernel(const f16 *__restrict__ in
     if (tid < COUT) { s_ss[tid] = scale[tid]; s_ss[COUT + tid] = shift[tid]; }
     __shared__ __attribute__((aligned(16))) f16x8 s_w2[DOT ? 4 * 64 : 1];      // read at use: the kernel lives on 3 workgroups per CU
     if constexpr (DOT) s_w2[tid] = reinterpret_cast<const f16x8 *>(w2frag)[tid];
+    const int *const lst = DOT ? tile_list : nullptr;
+    const int nrun = lst ? lst[0] : ntiles;                  // steps of the whole grid: listed tiles, or every tile
+    __shared__ int s_list[DOT ? C3_LIST_N : 1];              // (the launcher passes a list only when a run fits)
     f16x8 wf[MT][3];
 #pragma unroll
     for (int i = 0; i < MT; ++i)
@@ -96,24 +103,38 @@ __global__ __launch_bounds__(256) void conv_c3_kernel(const f16 *__restrict__ in
     C3Pre pre;
     auto fetch = [&](int t) { c3_fetch(pre, in, H, W, (t / tiles_x) * C3_TH, (t % tiles_x) * C3_TW, tid); };
     const float aslope = act_slope(act);
-    int t = blockIdx.x;
-    if (t < ntiles) fetch(t);
+    int t = blockIdx.x;                                      // step number in the grid's walk; the tile itself without a list
+    // DOT: the tiles of this step and of the two behind it, and this workgroup's step count
+    [[maybe_unused]] int tile = t, tile1 = t + (int)gridDim.x, tile2 = 0, k = 0;
+    if constexpr (DOT) {
+        if (lst) {
+            const int mine = t < nrun ? (nrun - t + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+            for (int j = tid; j < mine; j += 256) s_list[j] = lst[1 + t + j * (int)gridDim.x];
+            if (t < nrun) tile = lst[1 + t];
+            if (t + (int)gridDim.x < nrun) tile1 = lst[1 + t + (int)gridDim.x];
+        }
+    }
+    if (t < nrun) fetch(tile);
     // DOT (HG.conv1: pooled output only): ONE barrier per tile.  The patch of tile t+1 is staged into the other buffer while tile
     // t computes (its registers were fetched a tile earlier, the fetch of t+2 follows at once), and everything behind the MFMAs
     // is wave-private: a wave's two pixel rows hold whole 2x2 pooling windows, so it reads back only what it staged itself
     // (LDS operations of one wave complete in order).
     int pbuf = 0;
     if constexpr (DOT) {
-        if (t < ntiles) c3_stage(pre, s_px_all, tid);
-        if (t + (int)gridDim.x < ntiles) fetch(t + gridDim.x);
+        if (t < nrun) c3_stage(pre, s_px_all, tid);
+        if (t + (int)gridDim.x < nrun) fetch(tile1);
     }
-    for (; t < ntiles; t += gridDim.x) {
-    const int ox0 = (t % tiles_x) * C3_TW, oy0 = (t / tiles_x) * C3_TH;
+    for (; t < nrun; t += gridDim.x) {
+    const int cur = DOT ? tile : t;
+    const int ox0 = (cur % tiles_x) * C3_TW, oy0 = (cur / tiles_x) * C3_TH;
     if constexpr (DOT) {
         __syncthreads();                               // this tile's patch is staged; the other buffer's readers (tile t-1) are done
         s_px = s_px_all + pbuf * (C3_HH * C3_PW);
-        if (t + (int)gridDim.x < ntiles) c3_stage(pre, s_px_all + (pbuf ^ 1) * (C3_HH * C3_PW), tid);
-        if (t + 2 * (int)gridDim.x < ntiles) fetch(t + 2 * gridDim.x);
+        if (t + (int)gridDim.x < nrun) c3_stage(pre, s_px_all + (pbuf ^ 1) * (C3_HH * C3_PW), tid);
+        if (t + 2 * (int)gridDim.x < nrun) {
+            tile2 = lst ? __builtin_amdgcn_readfirstlane(s_list[k + 2]) : t + 2 * (int)gridDim.x;
+            fetch(tile2);
+        }
         pbuf ^= 1;
     } else {
         __syncthreads();                               // the previous tile is done with s_px and s_out
@@ -229,6 +250,7 @@ __global__ __launch_bounds__(256) void conv_c3_kernel(const f16 *__restrict__ in
                 }
             }
         }
+        ++k; tile = tile1; tile1 = tile2;
         continue;
     }
     __syncthreads();
@@ -583,8 +605,9 @@ inline int grid_for(size_t n, int per_block)
 
 hipError_t conv_c3_launch(const f16 *in, int H, int W, const f16 *wfrag, const float *scale, const float *shift, int cout,
                           int act, f16 *out, f16 *out_pool, int n_cu, hipStream_t s, float pool_q_inv, float pool_q_zero,
-                          const f16 *w2frag, float *part2)
+                          const f16 *w2frag, float *part2, const int *tile_list, bool *list_taken)
 {
+    if (list_taken) *list_taken = false;
     if ((w2frag != nullptr) != (part2 != nullptr) || (part2 && (cout != 64 || out || !out_pool))) return hipErrorInvalidValue;
     const int ntiles = ((W + C3_TW - 1) / C3_TW) * ((H + C3_TH - 1) / C3_TH);
     // persistent: as many workgroups as are resident at once (registers: 3 / 2 per CU today), one round
@@ -598,15 +621,18 @@ hipError_t conv_c3_launch(const f16 *in, int H, int W, const f16 *wfrag, const f
         per_cu = (e == hipSuccess && nb >= 1) ? nb : 2;
     }
     const dim3 grid(ntiles < per_cu * n_cu ? ntiles : per_cu * n_cu);
+    // a tile list (the <64, dot3> instance only): the grid never depends on its count; a run too long for the LDS block: every tile
+    if (tile_list && (!part2 || (ntiles + (int)grid.x - 1) / (int)grid.x > C3_LIST_N)) tile_list = nullptr;
+    if (list_taken) *list_taken = tile_list != nullptr;
     if (cout == 32)
         hipLaunchKernelGGL(conv_c3_kernel<32>, grid, dim3(256), 0, s, in, H, W, wfrag, scale, shift, act, out, out_pool, pool_q_inv, pool_q_zero,
-                           (const f16 *)nullptr, (float *)nullptr);
+                           (const f16 *)nullptr, (float *)nullptr, (const int *)nullptr);
     else if (cout == 64 && part2)
         hipLaunchKernelGGL((conv_c3_kernel<64, true>), grid, dim3(256), 0, s, in, H, W, wfrag, scale, shift, act, out, out_pool, pool_q_inv, pool_q_zero,
-                           w2frag, part2);
+                           w2frag, part2, tile_list);
     else if (cout == 64)
         hipLaunchKernelGGL(conv_c3_kernel<64>, grid, dim3(256), 0, s, in, H, W, wfrag, scale, shift, act, out, out_pool, pool_q_inv, pool_q_zero,
-                           (const f16 *)nullptr, (float *)nullptr);
+                           (const f16 *)nullptr, (float *)nullptr, (const int *)nullptr);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();

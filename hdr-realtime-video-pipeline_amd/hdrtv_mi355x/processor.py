@@ -767,6 +767,18 @@ class HDRTVNetMI355X:
             out.append((layer.value.decode(), kern.value.decode(), ms.value, macs.value, nbytes.value))
         return out
 
+    def profile_tiles(self):
+        """[(layer, kernel, executed, total)] of the last profiled infer(): the tiles a launch that walked an HG need list
+        computed, and the tiles of a dense launch; total = 0 for a launch without a list (or whose list was dropped)."""
+        n = self._lib.hdrtv_profile_get(self._ctx, -1, None, None, None, None, None)
+        out = []
+        for i in range(max(n, 0)):
+            layer, kern, done, total = C.c_char_p(), C.c_char_p(), C.c_int(), C.c_int()
+            self._chk(self._lib.hdrtv_profile_get(self._ctx, i, C.byref(layer), C.byref(kern), None, None, None), "hdrtv_profile_get")
+            self._chk(self._lib.hdrtv_profile_tiles(self._ctx, i, C.byref(done), C.byref(total)), "hdrtv_profile_tiles")
+            out.append((layer.value.decode(), kern.value.decode(), done.value, total.value))
+        return out
+
     def execution_summary(self, profile=None):
         """What the last profiled ``infer()`` ran on, by kernel tag: MACs (and launches) on int8 MFMA, as fake-quant on fp16 MFMA
         (W8A8 layers inside ``le_*_rows<fq>``), as fp32 fake-quant (the AGCM classifier of a full-QAT checkpoint) and on fp16

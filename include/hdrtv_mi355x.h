@@ -291,13 +291,20 @@ int hdrtv_infer_stats(hdrtv_ctx *ctx, int *launches, double *macs);
 int hdrtv_profile_enable(hdrtv_ctx *ctx, int on);
 int hdrtv_profile_get(hdrtv_ctx *ctx, int i, const char **layer, const char **kernel, float *ms, double *macs,
                       double *bytes);
+/* Launch i of the last profiled hdrtv_infer: the tiles it computed (the count of its need list, variant hg_sparse, read back
+ * from the device once the frame has finished) and the tiles of a dense launch.  *total = 0: the launch had no list, or its
+ * list was dropped and it ran every tile.  hdrtv_profile_get scales the MACs and bytes of a conv_prw launch by executed /
+ * total; for the other listed kernels (conv1 on conv_c3<64,dot3>, conv_pglds, conv_glds1) it keeps the dense layer's, and this
+ * is their executed work. */
+int hdrtv_profile_tiles(hdrtv_ctx *ctx, int i, int *executed, int *total);
 
 /* Developer / test switch with no reference counterpart: selects which of several equivalent kernels or schedules a
  * layer runs on (e.g. "le_rows": 1 = the fused row-streaming LE kernels, 0 = one launch per layer).  The table is
  * filled at hdrtv_create (defaults, then the creating process's HDRTV_VARIANTS="name=value,..."); the launch path never
  * reads the environment.  Takes effect at the next hdrtv_infer; HDRTV_EINVAL for an unknown name.
- * "hg_sparse" (default 2; fp16 HG, hdrtv_infer and hdrtv_infer_lane alike): the HG head's conv_prw layers compute only the tiles
- * a masked output pixel depends on -- the lists are built on the device from the frame's mask (no host round trip; the launch
+ * "hg_sparse" (default 2; fp16 HG, hdrtv_infer and hdrtv_infer_lane alike): every layer of the HG head, conv1 to Up_conv5 (conv1 on
+ * conv_c3<64,dot3>, conv_prw, conv_pglds and the 1x1 fuse convs on conv_glds1), computes only the tiles a masked output pixel
+ * depends on -- the lists are built on the device from the frame's mask (no host round trip; the launch
  * grids do not depend on frame content) -- and the blend takes img where the mask is 0.  2 tracks the dependency in sub-tile
  * units with a one-pixel halo per 3x3 layer, 1 in 16x16 cells of every level (coarser: more tiles).  Output bit-identical to 0
  * (every tile) for finite HG values; see hdrtv_get_tap for the taps.  hdrtv_infer_stats keeps reporting the dense model's MACs. */

@@ -53,9 +53,12 @@ def main():
                     p.infer(p.preprocess(f))
                     torch.cuda.synchronize(dev)
                     prof[min(sparse, 1)] = [r for r in p.profile_read() if r[0].startswith("hg.")]
+                # executed / dense tiles of every launch that walked a list (conv_prw, conv_pglds, conv_glds1): read back from the device
+                tiles = {r[0]: r[2:] for r in p.profile_tiles() if r[3]}
                 for d, s in zip(prof[0], prof[1]):
                     assert d[0] == s[0], (d, s)
-                    print(f"shares {kind} {1234 + i} {d[0]:14s} {s[1]:18s} executed/dense tiles {s[3] / d[3] if d[3] else 1.0:6.3f}  ms {d[2]:6.3f} -> {s[2]:6.3f}")
+                    done, total = tiles.get(s[0], (1, 1))
+                    print(f"shares {kind} {1234 + i} {d[0]:14s} {s[1]:18s} executed/dense tiles {done / total:6.3f}  ms {d[2]:6.3f} -> {s[2]:6.3f}")
                 print(f"shares {kind} {1234 + i} HG layers total ms {sum(r[2] for r in prof[0]):6.3f} -> {sum(r[2] for r in prof[1]):6.3f}")
             return
         p.set_variant("hg_sparse", a.sparse)
