@@ -42,6 +42,9 @@ const std::pair<const char *, int> k_variants[] = {
     {"cond2_fused", 1},      // CondNet2.2 + .4 in conv3x3s2_preg<192>'s epilogue; 0 = the separate cond_tail launch
     {"pre_split", 0},        // 1: preprocess as two kernels (unpack, condition resize)
     {"force_ncu", 0},        // > 0: pretend the device has this many CUs (persistent grids)
+    {"light_wgs", 2},        // hdrtv_light_stats / hdrtv_rgb48_light_stats: workgroups per CU the grid is capped at, 1 .. 8 (the record does not depend on it;
+                             // more workgroups = more loads in flight, but every workgroup ends in global atomics on the one record: 2 is the
+                             // fastest of 1 / 2 / 4 / 8 on all three inputs of profiles/light_stats_timing.txt)
     {"f32_narrow_below", 0}, // precision="fp32": workgroups per CU below which conv_f32 runs 8 channels per lane (0 = 3)
     {"f32_mfma", 1},         // precision="fp32": 3x3 / stride-1 layers on v_mfma_f32_32x32x2_f32 (conv_f32_mfma); 0 = every layer on the vector-FMA kernel
 };

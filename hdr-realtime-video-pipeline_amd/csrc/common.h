@@ -407,6 +407,15 @@ struct Ycbcr10Params {
     int H, W, y_pitch, c_pitch, fmt, siting;
 };
 
+// HDR10 content light level record (light_stats.hip; include/hdrtv_mi355x.h states the rule) of the rectangle x0, y0, rw, rh
+struct LightStatsParams {
+    const void *in;                  // planar [3][H][W] f16 / f32 (light_stats_launch) or u16 [H][W][3] RGB48 codes (rgb48_light_stats_launch)
+    const float *pq_bnd;             // PQ variant: the code boundaries of hdrtv_post_pq_rgb48
+    float peak;
+    int H, W, x0, y0, rw, rh;
+    uint32_t *stats;                 // HDRTV_LIGHT_WORDS u32, 8-byte aligned
+};
+
 // Objective metrics (metrics.hip): two unit-range images [3][H][W], per-workgroup partial sums {squared error, SSIM, dE-ITP}
 struct MetricsParams {
     const void *a, *b;

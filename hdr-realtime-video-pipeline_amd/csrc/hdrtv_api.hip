@@ -101,6 +101,7 @@ int hdrtv_set_variant(hdrtv_ctx *c, const char *name, int value)
     const std::string n(name);
     // the row kernels take any segment height >= 1 (tests/test_gpu_le_rows.py: test_short_segments_*); 0 or less is a typo
     if (n == "le_rows_min" && (value < 1 || value > 4096)) return fail(c, HDRTV_EINVAL, "variant le_rows_min must be 1 .. 4096");
+    if (n == "light_wgs" && (value < 1 || value > 8)) return fail(c, HDRTV_EINVAL, "variant light_wgs must be 1 .. 8");
     if (n == "force_ncu") {                 // sizes grids at launch time only (no workspace depends on it): takes effect at once
         if (value < 0) return fail(c, HDRTV_EINVAL, "variant force_ncu must be >= 0");
         c->n_cu = value > 0 ? value : c->dev_ncu;
@@ -383,6 +384,41 @@ int64_t hdrtv_ycbcr10_bytes(int fmt, int H, int W)
     if (fmt == HDRTV_YCC_YUV422P10) return (int64_t)H * W * 4;
     if ((fmt != HDRTV_YCC_P010 && fmt != HDRTV_YCC_YUV420P10) || (H & 1)) return HDRTV_EINVAL;
     return (int64_t)H * W * 3;
+}
+
+// ------------------------------------------------------------------- HDR10 content light level
+// The argument rules of include/hdrtv_mi355x.h shared by the two entry points; fills the launch parameters.
+static int light_args(hdrtv_ctx *c, const char *what, const void *src, int H, int W, int x0, int y0, int rw, int rh, uint32_t *stats,
+                      LightStatsParams &p)
+{
+    if (!c || !src || !stats || H <= 0 || W <= 0) return fail(c, HDRTV_EINVAL, "%s: bad argument", what);
+    if (rw <= 0 || rh <= 0 || x0 < 0 || y0 < 0 || x0 > W - rw || y0 > H - rh)
+        return fail(c, HDRTV_EINVAL, "%s: rectangle %d,%d %dx%d is empty or leaves the %dx%d frame", what, x0, y0, rw, rh, W, H);
+    if (reinterpret_cast<uintptr_t>(stats) & 7) return fail(c, HDRTV_EINVAL, "%s: dev_stats must be 8-byte aligned", what);
+    p = LightStatsParams{src, nullptr, 0.f, H, W, x0, y0, rw, rh, stats};
+    return HDRTV_OK;
+}
+
+int hdrtv_light_stats(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits, int x0, int y0,
+                      int rw, int rh, uint32_t *stats)
+{
+    LightStatsParams p;
+    if (int rc = light_args(c, "light_stats", in, H, W, x0, y0, rw, rh, stats, p)) return rc;
+    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "light_stats: bad dtype %d", dtype);
+    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "light_stats: pq needs peak_nits > 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = pq ? ensure_pq_table(c, "light_stats") : HDRTV_OK) return rc;
+    p.pq_bnd = c->pq_bnd;
+    p.peak = pq ? peak_nits : 0.f;
+    return launched(c, "light_stats", light_stats_launch(p, dtype == HDRTV_F32, pq != 0, c->var.at("light_wgs") * c->n_cu, (hipStream_t)stream));
+}
+
+int hdrtv_rgb48_light_stats(hdrtv_ctx *c, void *stream, const uint16_t *src, int H, int W, int x0, int y0, int rw, int rh, uint32_t *stats)
+{
+    LightStatsParams p;
+    if (int rc = light_args(c, "rgb48_light_stats", src, H, W, x0, y0, rw, rh, stats, p)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return launched(c, "rgb48_light_stats", rgb48_light_stats_launch(p, c->var.at("light_wgs") * c->n_cu, (hipStream_t)stream));
 }
 
 // ------------------------------------------------------------------- RGB48 at the display size

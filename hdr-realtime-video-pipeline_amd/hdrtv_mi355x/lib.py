@@ -21,6 +21,7 @@ PREC_F16, PREC_F32 = 0, 1
 YUV_I420, YUV_NV12 = 0, 1                  # hdrtv_yuv420_to_bgr_u8 / hdrtv_preprocess_yuv420 layouts
 YCC_P010, YCC_YUV420P10, YCC_YUV422P10 = 0, 1, 2   # hdrtv_post_ycbcr10 / hdrtv_rgb48_to_ycbcr10 layouts
 SITING_LEFT, SITING_TOPLEFT = 0, 1
+LIGHT_BINS, LIGHT_WORDS = 4096, 4104       # hdrtv_light_stats / hdrtv_rgb48_light_stats: the record, u32 words (lightlevel.py reads it)
 
 # every symbol include/hdrtv_mi355x.h declares: (name, restype, argtypes)
 _VP, _I, _SZ = C.c_void_p, C.c_int, C.c_size_t
@@ -45,6 +46,8 @@ SYMBOLS = [
     ("hdrtv_post_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_rgb48_to_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_ycbcr10_bytes", C.c_int64, [_I, _I, _I]),
+    ("hdrtv_light_stats", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _I, _I, _VP]),
+    ("hdrtv_rgb48_light_stats", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     ("hdrtv_letterbox_u8", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I]),
     ("hdrtv_yuv420_to_bgr_u8", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     ("hdrtv_preprocess_yuv420", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP]),

@@ -272,6 +272,12 @@ class RawVideoSink(Rgb48leSink):
         finally:
             payload.release()
 
+    @staticmethod
+    def x265_params(cll):
+        """``max-cll=<MaxCLL>,<MaxFALL>`` for the encode command's ``-x265-params`` from the worker's ``content_light``
+        (``lightlevel.ContentLightLevel``) at the end of the stream."""
+        return cll.x265_params()
+
     def mpv_args(self):
         if self.pix_fmt == "rgb48le":
             return super().mpv_args()
@@ -580,6 +586,10 @@ def main(argv=None):
                     "10-bit limited-range BT.2020nc Y'CbCr for an encoder, converted on the device (hdrtv_post_ycbcr10)")
     ap.add_argument("--out-siting", choices=sorted(_lib.YCC_SITINGS), default="left", help="chroma siting of a 4:2:0 --out-pix-fmt: left "
                     "(MPEG-2 / H.264, ffmpeg's default) or topleft (BT.2100 / HDR10)")
+    ap.add_argument("--light-level", action="store_true", help="measure the HDR10 content light level of the delivered frames on the "
+                    "device (hdrtv_light_stats): the result line gains max_cll / max_fall / light_frames")
+    ap.add_argument("--light-level-json", metavar="PATH", help="also write MaxCLL / MaxFALL and the max-cll= string for the encoder "
+                    "to PATH (implies --light-level)")
     ap.add_argument("--no-hg", action="store_true")
     ap.add_argument("--hg-weights", default=None, help="HG weight file, or seeded:<n>")
     ap.add_argument("--max-throughput", action="store_true", help="do not pace to the source clock")
@@ -601,7 +611,7 @@ def main(argv=None):
         src = PinnedPrefetch(src)
     worker = HeadlessPipelineWorker(a.weights_dir, use_hg=not a.no_hg, proc_w=wd, proc_h=ht, hg_weights=a.hg_weights,
                                     status_cb=lambda m: print(m, flush=True), out_w=owd, out_h=oht, out_pix_fmt=a.out_pix_fmt,
-                                    out_siting=a.out_siting)
+                                    out_siting=a.out_siting, light_stats=bool(a.light_level or a.light_level_json))
     if not worker._load_model(a.precision):
         return 1
     sink = None
@@ -617,6 +627,7 @@ def main(argv=None):
         worker._stop_hdr_feeder()
         sink.close()
         res["sink_frames"], res["sink_bytes"] = sink.frames, sink.bytes
+    cll = worker.content_light             # fed by the feeder, frame by frame, from what the sink received
     worker.close()
     lm = res.pop("last_metrics") or {}
     res.update({k: lm.get(k) for k in ("latency_ms", "model_latency_ms", "fps_1p_low", "proc_res", "precision")})
@@ -624,6 +635,11 @@ def main(argv=None):
         res["out_res"] = f"{owd}x{oht}"
     if a.out_pix_fmt != "rgb48le":
         res["out_pix_fmt"] = a.out_pix_fmt
+    if cll is not None:
+        res["max_cll"], res["max_fall"], res["light_frames"] = cll.max_cll, cll.max_fall, cll.frames
+        if a.light_level_json:
+            with open(a.light_level_json, "w") as f:
+                json.dump(cll.as_dict(), f, indent=1)
     print(json.dumps(res))
     return 0
 

@@ -334,13 +334,19 @@ class HDRTVNetMI355X:
         ``_ensure_buffers``)."""
         return self._lane_streams[lane]
 
-    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key):
+    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None):
         """The output conversion of a frame whose planar tensor lies at ``src_ptr``, to the ``lib.OutputFormat`` ``out`` at
         ``dst_ptr``: ``rgb48le`` at the processing size (``hdrtv_post_rgb48``) or enlarged to ``out.h`` x ``out.w``
         (``hdrtv_post_rgb48_scaled``); a 10-bit Y'CbCr layout in one kernel at the processing size (``hdrtv_post_ycbcr10``), or,
         enlarged, in two launches through an RGB48 scratch kept per ``scratch_key`` (``hdrtv_post_rgb48_scaled`` +
-        ``hdrtv_rgb48_to_ycbcr10``)."""
+        ``hdrtv_rgb48_to_ycbcr10``).  ``light_ptr``: device address of a ``lib.LIGHT_WORDS`` u32 record that receives the
+        delivered frame's content light level over ``light_rect = (x0, y0, rw, rh)`` in delivered-frame
+        coordinates (default: the whole frame): ``hdrtv_light_stats`` on the tensor for an unscaled frame, ``hdrtv_rgb48_light_stats``
+        on the scaled frame's RGB48 codes (the destination, or the Y'CbCr scratch) otherwise.  None: nothing more is launched."""
         scaled = (out.h, out.w) != (h, w)
+        rect = (0, 0, out.w, out.h) if light_rect is None else tuple(int(v) for v in light_rect)
+        if light_ptr is not None and not scaled:
+            self._chk(self._lib.hdrtv_light_stats(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *rect, light_ptr), "hdrtv_light_stats")
         if not out.is_rgb48 and not scaled:
             self._chk(self._lib.hdrtv_post_ycbcr10(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *out.planes(dst_ptr)), "hdrtv_post_ycbcr10")
             return
@@ -353,10 +359,25 @@ class HDRTVNetMI355X:
         if scaled:
             self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, rgb_ptr, out.h, out.w),
                       "hdrtv_post_rgb48_scaled")
+            if light_ptr is not None:
+                self._chk(self._lib.hdrtv_rgb48_light_stats(self._ctx, st, rgb_ptr, out.h, out.w, *rect, light_ptr), "hdrtv_rgb48_light_stats")
         else:
             self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, src_ptr, dt, h, w, rgb_ptr), "hdrtv_post_rgb48")
         if not out.is_rgb48:
             self._chk(self._lib.hdrtv_rgb48_to_ycbcr10(self._ctx, st, rgb_ptr, out.h, out.w, *out.planes(dst_ptr)), "hdrtv_rgb48_to_ycbcr10")
+
+    def light_stats(self, tensor, rect=None):
+        """The content light level record (``lib.LIGHT_WORDS`` u32, a device tensor; ``lightlevel.FrameLight.from_record`` reads
+        its host copy) of the model's output ``tensor`` ``[1, 3, H, W]`` or ``[3, H, W]``: of the RGB48 codes ``hdrtv_post_rgb48``
+        writes for it, over ``rect = (x0, y0, rw, rh)`` (default: the whole frame).  Enqueued on the current stream."""
+        t = (tensor[0] if isinstance(tensor, (tuple, list)) else tensor).contiguous()
+        h, w = int(t.shape[-2]), int(t.shape[-1])
+        rec = torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, device=t.device)
+        rect = (0, 0, w, h) if rect is None else tuple(int(v) for v in rect)
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.hdrtv_light_stats(self._ctx, self._stream(), t.data_ptr(), _dtype_code(t), h, w, 0, 0.0, *rect, rec.data_ptr()),
+                      "hdrtv_light_stats")
+        return rec
 
     def _frame_out(self, lane, h, w, out_hw, out_pix_fmt, out_siting):
         """The argument checks ``enqueue_frame*`` share -> the ``lib.OutputFormat`` of the frame."""
@@ -364,7 +385,7 @@ class HDRTVNetMI355X:
             raise ValueError(f"lane {lane} of {self._lanes}")
         return _L.output_format(out_pix_fmt, out_siting, *((h, w) if out_hw is None else out_hw))
 
-    def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out):
+    def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out, light_ptr=None, light_rect=None):
         """The body of ``enqueue_frame*``: the preprocess entry point ``pre`` (named ``what``) on its source arguments ``src``,
         ``hdrtv_infer_lane`` and ``_post_out``, all on the lane's buffers and ``stream`` (default: the lane's own)."""
         self._ensure_buffers(h, w)
@@ -373,10 +394,10 @@ class HDRTVNetMI355X:
         self._chk(pre(self._ctx, st, *src, h, w, tin.data_ptr(), tcond.data_ptr()), what)
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), self._out_dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane))
+        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect)
 
     def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le",
-                      out_siting="left"):
+                      out_siting="left", light_ptr=None, light_rect=None):
         """One frame of the hot path on lane ``lane``, stream-ordered and without any host synchronisation: u8 BGR frame in
         device memory at ``src_bgr_ptr`` -> hdrtv_preprocess -> hdrtv_infer_lane -> hdrtv_post_rgb48 -> u16 RGB48 at the device
         address ``dst_rgb48_ptr``.  ``stream``: a ``torch.cuda.Stream`` (default: the lane's own).  Frames enqueued on different
@@ -385,17 +406,20 @@ class HDRTVNetMI355X:
         out_w)``: the frame is delivered at that size (``hdrtv_post_rgb48_scaled``; ``dst`` holds out_h * out_w * 3 u16).
         ``out_pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` (``out_siting`` ``left`` / ``topleft``): ``dst`` receives the
         10-bit Y'CbCr planes back to back instead (``lib.out_frame_bytes`` bytes) -- ``hdrtv_post_ycbcr10`` at
-        the processing size, with ``out_hw`` two launches through a per-lane RGB48 scratch."""
+        the processing size, with ``out_hw`` two launches through a per-lane RGB48 scratch.  ``light_ptr`` / ``light_rect``: the
+        delivered frame's content light level record, behind the frame on the same stream (``_post_out``)."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
-        self._enqueue(lane, self._lib.hdrtv_preprocess, "hdrtv_preprocess", (src_bgr_ptr,), h, w, dst_rgb48_ptr, stream, out)
+        self._enqueue(lane, self._lib.hdrtv_preprocess, "hdrtv_preprocess", (src_bgr_ptr,), h, w, dst_rgb48_ptr, stream, out,
+                      light_ptr, light_rect)
 
     def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None,
-                             out_hw=None, out_pix_fmt="rgb48le", out_siting="left"):
+                             out_hw=None, out_pix_fmt="rgb48le", out_siting="left", light_ptr=None, light_rect=None):
         """``enqueue_frame`` of an 8-bit 4:2:0 frame: the planes lie back to back at the device address ``src_ptr`` (the
         ``(h*3//2, w)`` u8 array ``preprocess_yuv420`` takes) and ``hdrtv_preprocess_yuv420`` replaces ``hdrtv_preprocess``."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         planes = _yuv_planes(src_ptr, int(h), int(w), layout, matrix, full_range)
-        self._enqueue(lane, self._lib.hdrtv_preprocess_yuv420, "hdrtv_preprocess_yuv420", planes, h, w, dst_rgb48_ptr, stream, out)
+        self._enqueue(lane, self._lib.hdrtv_preprocess_yuv420, "hdrtv_preprocess_yuv420", planes, h, w, dst_rgb48_ptr, stream, out,
+                      light_ptr, light_rect)
 
     def _upload(self, key, src, staged=None):
         """Device pointer of the host u8 array ``src``, uploaded through the staging slot kept per ``key`` in ``_staging``: a

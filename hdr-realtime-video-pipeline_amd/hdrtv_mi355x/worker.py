@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import lib as _L
+from .lightlevel import ContentLightLevel
 from .processor import HDRTVNetMI355X, _dtype_code
 
 _RING_FRAMES = max(2, min(8, int(os.environ.get("HDRTVNET_FEEDER_GPU_RGB48_RING_FRAMES", "3") or 3)))
@@ -53,8 +54,9 @@ class PinnedFrame:
     """_PinnedMpvFrame (feeders.py:38-70): a pinned host RGB48 frame whose ring slot is released
     after the sink has consumed it."""
 
-    def __init__(self, worker, slot, host_ptr, shape):
+    def __init__(self, worker, slot, host_ptr, shape, light_host=None):
         self._w, self._slot, self._host, self._shape = worker, slot, host_ptr, shape
+        self._light_host = light_host      # the slot's pinned light level record (numpy u32 view), filled in front of the slot's commit
         self._ready_waited = self._released = False
 
     def wait_ready(self):
@@ -73,6 +75,15 @@ class PinnedFrame:
         n = int(np.prod(self._shape))
         return np.ctypeslib.as_array((C.c_uint16 * n).from_address(self._host)).reshape(self._shape)
 
+    @property
+    def light(self):
+        """The frame's content light level record (``lib.LIGHT_WORDS`` u32; ``lightlevel.FrameLight.from_record``), a private
+        copy taken once the slot is complete -- read it before ``release``; None when the worker does not measure it."""
+        if self._light_host is None:
+            return None
+        self.wait_ready()
+        return self._light_host.copy()
+
     def release(self):
         if self._released:
             return
@@ -90,8 +101,9 @@ class HostFrame:
     in the single blocking pinned buffer, already complete; same surface as ``PinnedFrame`` (the reference returns
     ``bytes`` there, which its sink treats like a released frame)."""
 
-    def __init__(self, array):
+    def __init__(self, array, light=None):
         self._a = array
+        self.light = light                 # the frame's content light level record (a private copy), or None
 
     def wait_ready(self):
         return None
@@ -108,7 +120,8 @@ class HostFrame:
 
 class HeadlessPipelineWorker:
     def __init__(self, weights_dir, use_hg=True, proc_w=1920, proc_h=1080, hg_weights=None,
-                 status_cb=None, buffer_frames=1, out_w=None, out_h=None, out_pix_fmt="rgb48le", out_siting="left"):
+                 status_cb=None, buffer_frames=1, out_w=None, out_h=None, out_pix_fmt="rgb48le", out_siting="left",
+                 light_stats=False, light_rect=None):
         self._weights_dir = weights_dir
         self._use_hg = bool(use_hg)
         self._hg_override = hg_weights
@@ -119,6 +132,17 @@ class HeadlessPipelineWorker:
         # what the sink receives, one lib.OutputFormat: "rgb48le", or 10-bit Y'CbCr ("p010le", "yuv420p10le",
         # "yuv422p10le") with the 4:2:0 chroma siting "left" / "topleft"; then a frame is a 1-D u16 view of its planes, back to back
         self._out = _L.output_format(out_pix_fmt, out_siting, self._out_h or self._proc_h, self._out_w or self._proc_w)
+        # HDR10 content light level: every delivered frame carries its record (``.light``), measured on the
+        # device from the codes the sink receives over ``light_rect = (x0, y0, rw, rh)`` in delivered-frame coordinates (None: the
+        # whole frame), and ``content_light`` accumulates MaxCLL / MaxFALL in delivery order.  Off: nothing is launched or allocated.
+        self._light = bool(light_stats)
+        self._light_rect = None if light_rect is None else tuple(int(v) for v in light_rect)
+        if self._light_rect is not None:
+            x0, y0, rw, rh = self._light_rect
+            if rw <= 0 or rh <= 0 or x0 < 0 or y0 < 0 or x0 + rw > self._out.w or y0 + rh > self._out.h:
+                raise ValueError(f"light_rect {self._light_rect} is empty or leaves the {self._out.w}x{self._out.h} frame")
+        self.content_light = ContentLightLevel() if self._light else None
+        self._light_bufs = {}              # ring slot (or "fallback") -> (device u32 record, pinned host u32 record)
         self._processor = None
         self._precision_key = None
         self.status_messages = []
@@ -188,6 +212,7 @@ class HeadlessPipelineWorker:
             self._processor = None
             self._ring_shape = None            # the pinned ring lived in the closed context
             self._fallback = None
+            self._light_bufs = {}
             torch.cuda.empty_cache()
         try:
             hg = self._hg_override
@@ -317,8 +342,20 @@ class HeadlessPipelineWorker:
         out = self._out.at(h, w)
         shape = out.shape
 
-        def convert(dst):
-            p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker")
+        def convert(dst, key):
+            """The frame into ``dst`` and, when measured, its light level record into the pinned record kept per ``key``, all on
+            ``st``: whatever is recorded on ``st`` afterwards (the slot's ready event) covers both.  Returns that record."""
+            if not self._light:
+                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker")
+                return None
+            bufs = self._light_bufs.get(key)
+            if bufs is None:
+                bufs = self._light_bufs[key] = (torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, device=p.device),
+                                                torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, pin_memory=True))
+            p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", bufs[0].data_ptr(), self._light_rect)
+            with torch.cuda.stream(st):
+                bufs[1].copy_(bufs[0], non_blocking=True)
+            return bufs[1].numpy()
         host, dev = C.c_void_p(), C.c_void_p()
         st = stream or torch.cuda.current_stream(p.device)
         sp = C.c_void_p(st.cuda_stream)
@@ -329,15 +366,16 @@ class HeadlessPipelineWorker:
                 self._fallback = (torch.empty(shape, dtype=torch.uint16, pin_memory=True),
                                   torch.empty(shape, dtype=torch.uint16, device=p.device))
             fb_host, fb_dev = self._fallback
-            convert(fb_dev.data_ptr())
+            light = convert(fb_dev.data_ptr(), "fallback")
             with torch.cuda.stream(st):
                 fb_host.copy_(fb_dev, non_blocking=True)
             st.synchronize()
-            return HostFrame(fb_host.numpy().copy())       # the reference's host_np.tobytes(): a private copy
+            # the reference's host_np.tobytes(): a private copy
+            return HostFrame(fb_host.numpy().copy(), None if light is None else light.copy())
         p._chk(slot, "hdrtv_ring_acquire")
-        convert(dev.value)
+        light = convert(dev.value, slot)
         p._chk(p._lib.hdrtv_ring_commit_bytes(p._ctx, slot, sp, out.nbytes), "hdrtv_ring_commit_bytes")
-        return PinnedFrame(self, slot, host.value, shape)
+        return PinnedFrame(self, slot, host.value, shape, light)
 
     def _start_hdr_feeder(self, sink):
         """feeders.py:632-657 + 440-496: a thread that waits for each frame's ready event,
@@ -378,6 +416,8 @@ class HeadlessPipelineWorker:
                         delay = present_t - time.perf_counter()
                         if delay > 0:
                             time.sleep(delay)
+                    if self.content_light is not None:
+                        self.content_light.update(payload.light)
                     sink(payload)
             except BaseException as exc:  # noqa: BLE001  (a dead daemon thread must not be silent: _process_frame re-raises)
                 self._hdr_error = exc

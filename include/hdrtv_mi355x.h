@@ -187,7 +187,7 @@ int hdrtv_post_rgb48_scaled(hdrtv_ctx *ctx, void *stream, const void *dev_out, i
  * hdrtv_rgb48_to_ycbcr10 applies the same rule to RGB48 codes already in device memory ([H][W][3]): a scaled frame becomes Y'CbCr in
  * two launches, hdrtv_post_rgb48_scaled and this one.  hdrtv_ycbcr10_bytes: the bytes of a frame with its planes back to back at their
  * minimum pitches (3 H W, 4:2:2: 4 H W), or a negative value for a bad argument.  Out of scope: dithering (the reference's
- * dither=error_diffusion is sequential), full range, 12 bits, 4:4:4, HDR10 SEI metadata, and fusing the Lanczos pass with the conversion.
+ * dither=error_diffusion is sequential), full range, 12 bits, 4:4:4, bitstream / SEI writing (hdrtv_light_stats measures the content light level an HDR10 SEI carries), and fusing the Lanczos pass with the conversion.
  * Stream-ordered, no reservation needed.  HDRTV_EINVAL, with dst untouched, for a NULL pointer, a non-positive size, an odd W, an odd H
  * with 4:2:0, a short or odd pitch, an unknown fmt, siting or dtype, P010 with a non-NULL dst_v, a siting other than LEFT with 4:2:2, or
  * pq with peak_nits <= 0. */
@@ -201,6 +201,45 @@ int hdrtv_post_ycbcr10(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dt
 int hdrtv_rgb48_to_ycbcr10(hdrtv_ctx *ctx, void *stream, const uint16_t *src_rgb48, int H, int W, int fmt, int siting,
                            uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch);
 int64_t hdrtv_ycbcr10_bytes(int fmt, int H, int W);
+
+/* HDR10 content light level (CTA-861.3 MaxCLL / MaxFALL; x265 max-cll=, HEVC SEI 144): the per-frame record those two numbers are
+ * made from, measured on the device from exactly the codes the sink receives.  The reference has no counterpart: its export tags the
+ * stream as PQ / BT.2020 (gui_export.py:957-977) and carries no light level.  The statistic is this integer rule, restated in
+ * tests/lightlevel_ref.py, which the GPU tests hold both entry points to bit for bit.
+ *  1. codes: R, G, B in [0, 65535] = exactly what hdrtv_post_rgb48 (pq = 0; peak_nits ignored) or hdrtv_post_pq_rgb48 (pq != 0)
+ *     writes for that pixel; the statistic sees nothing but these integers, so it describes the Y'CbCr outputs too (they are derived
+ *     from the same codes).
+ *  2. per pixel of the rectangle x0 <= x < x0 + rw, y0 <= y < y0 + rh (the active picture, which CTA-861.3 measures; the full frame
+ *     is 0, 0, W, H):  m = max(R, G, B).
+ *  3. the record, HDRTV_LIGHT_WORDS = 4104 little-endian u32 words, HDRTV_LIGHT_BINS = 4096:
+ *       [0 .. 4095]            hist[b] = the number of pixels with m >> 4 == b
+ *       [4096] [4097] [4098]   the largest R, G and B code (MaxSCL)
+ *       [4099]                 the largest m
+ *       [4100] [4101]          low and high word of the u64 sum of m over the rectangle
+ *       [4102]                 rw * rh  (= the sum of hist)
+ *       [4103]                 0
+ *     Every call overwrites the record (it is zeroed on `stream` in front of the kernel); nothing accumulates across calls.  Integer
+ *     adds and maxima only: the record is identical from run to run.
+ *  4. host side (hdrtv_mi355x/lightlevel.py), in double, the ST.2084 EOTF with the constants of gui_objective_metrics.py:486-491:
+ *       nits(c) = 10000 * (max(p - c1, 0) / (c2 - c3 p))^(1/m1),  p = (c / 65535)^(1/m2)
+ *     nits(0) = 0, nits(65535) = 10000, nits(33297) = 100.0012.., nits(49271) within 0.3 of 1000.
+ *       frame CLL  = nits(word 4099), exact;
+ *       frame FALL = sum_b hist[b] * nits(16 b + 8) / (rw * rh): off the exact per-pixel mean of nits(m) by at most the widest
+ *                    deviation inside a bin, max_c |nits(c) - nits(16 (c >> 4) + 8)|;
+ *       MaxCLL / MaxFALL of a stream = the largest frame CLL / FALL, reported as floats and as integers floor(v + 0.5).
+ * hdrtv_light_stats reads the model's planar tensor (what hdrtv_post_rgb48 / hdrtv_post_ycbcr10 read); hdrtv_rgb48_light_stats reads
+ * RGB48 codes already in device memory ([H][W][3]: a scaled frame, a ring slot's device buffer).  dev_stats: HDRTV_LIGHT_WORDS u32 of
+ * device memory, 8-byte aligned.  Both are stream-ordered, need no reservation and never synchronise; the PQ table is the context's
+ * (hdrtv_post_pq_rgb48's).  Out of scope: writing SEI / bitstream bytes (the encoder's job), mastering-display primaries, HDR10+
+ * dynamic metadata, and fusing the statistic into the post kernels.  HDRTV_EINVAL, with the record untouched, for a NULL pointer, a
+ * non-positive size, an empty rectangle or one that leaves the frame, dev_stats not 8-byte aligned, an unknown dtype, or pq with
+ * peak_nits <= 0. */
+#define HDRTV_LIGHT_BINS 4096
+#define HDRTV_LIGHT_WORDS 4104
+int hdrtv_light_stats(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
+                      int x0, int y0, int rw, int rh, uint32_t *dev_stats);
+int hdrtv_rgb48_light_stats(hdrtv_ctx *ctx, void *stream, const uint16_t *src_rgb48, int H, int W,
+                            int x0, int y0, int rw, int rh, uint32_t *dev_stats);
 
 /* The host step in front of preprocess, on the device: _letterbox_bgr
  * (src/gui_scaling.py:228-244), i.e. cv2.resize preserving the aspect ratio -- INTER_AREA when shrinking,
