@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tile_run.h"
+
 typedef _Float16 f16;
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -84,6 +86,20 @@ __device__ __forceinline__ dma_rsrc_t dma_rsrc(const void *base, unsigned bytes 
 template <int OFF = 0> __device__ __forceinline__ void dma16(dma_rsrc_t r, void *lds, unsigned voff, unsigned soff = 0)
 {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds, 16, voff, soff, OFF, 0);
+}
+// The hand-counted wait: vmcnt counts loads, stores and LDS-DMA pieces together, retired in issue order.
+template <int N> __device__ __forceinline__ void wait_vm()
+{
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// The wait that closes a tap of conv_pglds / conv_pglds_i8, in front of its barrier: the counted vmcnt AND lgkmcnt(0) as one
+// immediate.  Behind the barrier the other waves refill the ring slot (at tap NT-3 the halo buffer) this tap has read by LDS-DMA,
+// so every LDS read of the wave must have RETURNED before it arrives -- hipcc's own lgkmcnt waits sit in front of the consuming
+// MFMAs, and those it may sink below the barrier and the next tap's DMA issue (tests/test_isa_contracts.py:
+// test_no_lds_read_is_in_flight_when_its_region_is_rewritten).
+template <int N> __device__ __forceinline__ void wait_tap()
+{
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
 }
 
 // K-dimension permutation that lets a 32x32 MFMA accumulator tile be re-used, packed to f16,

@@ -41,12 +41,7 @@ __global__ __launch_bounds__(512) void conv_glds1_kernel(ConvParams p)
     const int l31 = lane & 31, lh = lane >> 5;
 
     // bijective XCD-aware remap: each XCD (own L2) gets a contiguous run of tiles
-    const int nwg = gridDim.x;
-    int t;
-    {
-        const int b = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int t = xcd_tile(gridDim.x, blockIdx.x);
     const int ntn = p.CoutPad / BN;
     const int nt_i = t % ntn, sp = t / ntn;
     const int ty = sp / p.tiles_x, tx = sp % p.tiles_x;
@@ -187,13 +182,12 @@ __global__ __launch_bounds__(512) void conv_glds1_kernel(ConvParams p)
 //     32 pixels (waves 0-5 in the A slot, 6-7 in the B slot); one extra barrier per tile lets the slot be refilled;
 //   * vmcnt counts DMA pieces and stores together in issue order: every wave issues exactly NST stores per tile (masked
 //     lanes store to the trash line), so the first wait of a tile is vmcnt(6 + NST) and every other one vmcnt(6).
-// Sparse launches (ConvParams::tile_list, the HG need lists of hg_need.hip), as conv_prw: the spatial tiles are the list's entries.
+// Sparse launches (ConvParams::tile_list, the HG need lists of hg_need.hip; tile_run.h): the spatial tiles are the list's entries.
 // The count is read once; every block copies the entries of ITS run into LDS beside the scale / shift fill, in front of the
 // prologue's __syncthreads() and of the first DMA, so the tile loop's only new operation is one LDS read per tile.
 constexpr int P_NST = 8;          // stores per wave and tile: 2 passes x 4
 constexpr int P_SP = 144;         // strip row pitch: 64 ch x 2 B + 16
 constexpr int P_MAXC = 512;       // most output channels the scale / shift table holds
-constexpr int P_LIST_N = 512;     // ConvParams::tile_list: most tiles of one block's run (2 KiB of LDS)
 
 __global__ __launch_bounds__(512) void conv_glds1p_kernel(ConvParams p)
 {
@@ -207,27 +201,17 @@ __global__ __launch_bounds__(512) void conv_glds1p_kernel(ConvParams p)
     // scale / shift of this thread's output channel (CoutPad <= P_MAXC = the block): loaded first, so that the list's count and
     // entries below, two dependent trips to device memory, travel beside them and not behind
     const float my_scale = tid < p.CoutPad ? p.scale[tid] : 0.f, my_shift = tid < p.CoutPad ? p.shift[tid] : 0.f;
-    // ---- this block's run of tiles: XCD x owns a contiguous range, its blocks interleave in it (as conv_pglds)
+    // ---- this block's run of tiles (tile_run.h)
     const int ntn = p.CoutPad / BN;
     const int *const lst = p.tile_list;                      // null: every tile (dense)
     const int total = (lst ? lst[0] : p.tiles_x * p.tiles_y) * ntn;
-    int t_first, t_step, ntile;
-    {
-        const int G = gridDim.x, b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-        const int nslots = (G - xcd + 7) >> 3;
-        const int q = total >> 3, r = total & 7;
-        const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-        const int len = q + (xcd < r ? 1 : 0);
-        t_first = base + slot;
-        t_step = nslots;
-        ntile = slot < len ? (len - slot + nslots - 1) / nslots : 0;
-    }
+    const TileRun run = tile_run(total, gridDim.x, blockIdx.x);
+    const int t_first = run.t_first, t_step = run.t_step, ntile = run.ntile;
     if (ntile == 0) return;
-    // the list entries of this block's run (the launcher passes a list only when a run fits P_LIST_N); visible behind the __syncthreads() below
-    __shared__ int s_list_mem[P_LIST_N];
-    // (an LDS-space pointer: through a generic one the volatile accesses are FLAT operations, and the write a store vmcnt would count)
-    volatile __attribute__((address_space(3))) int *s_list = (volatile __attribute__((address_space(3))) int *)s_list_mem;
-    if (lst && tid < ntile) s_list[tid] = lst[1 + (t_first + tid * t_step) / ntn];
+    // the list entries of this block's run (the launcher passes a list only when a run fits); visible behind the __syncthreads() below
+    __shared__ int s_list_mem[TILE_LIST_N];
+    const tile_list_lds_t s_list = (tile_list_lds_t)s_list_mem;
+    tile_list_stage(s_list, lst, run, tid, [&](int t) { return t / ntn; });
     struct Tile { int n0, oy0, ox0; };
     // tile number k of the run
     auto decode = [&](int k) {
@@ -235,7 +219,7 @@ __global__ __launch_bounds__(512) void conv_glds1p_kernel(ConvParams p)
         const int t = t_first + k * t_step;
         const int nt_i = t % ntn;
         int sp = t / ntn;
-        if (lst) sp = __builtin_amdgcn_readfirstlane(s_list[k]);
+        if (lst) sp = tile_list_at(s_list, k);
         const int ty = sp / p.tiles_x, tx = sp - ty * p.tiles_x;
         o.n0 = nt_i * BN; o.oy0 = ty * TH; o.ox0 = tx * TW;
         return o;
@@ -386,13 +370,8 @@ hipError_t conv_glds1_launch(ConvParams p, hipStream_t stream, int n_cu, bool ol
         p.mode != ST_NHWC || !p.zeros)
         return hipErrorInvalidValue;
 #ifdef HDRTV_AB
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_glds1_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    static DevOnce attr_once;
+    if (hipError_t e = allow_lds(attr_once, conv_glds1_kernel, SMEM)) return e;
 #endif
     p.tiles_x = (p.Wo + TW - 1) / TW;
     p.tiles_y = (p.Ho + TH - 1) / TH;
@@ -401,15 +380,10 @@ hipError_t conv_glds1_launch(ConvParams p, hipStream_t stream, int n_cu, bool ol
     const int nchunk = (p.c0 + p.c1) / CT;
     if (!old_form && n_cu >= 8 && nchunk >= 2 && p.trash && p.CoutPad <= P_MAXC && (p.act == ACT_RELU || p.act == ACT_NONE)) {
         static DevOnce attr_p;
-        if (attr_p.need()) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_glds1p_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-            if (e != hipSuccess) return e;
-            attr_p.done();
-        }
+        if (hipError_t e = allow_lds(attr_p, conv_glds1p_kernel, SMEM)) return e;
         // the grid never depends on the list's count (device memory); a run too long for the LDS block: dense
         const int g = grid < n_cu ? grid : n_cu;
-        if (p.tile_list && g >= 8 && (grid / 8 + 1 + g / 8 - 1) / (g / 8) > P_LIST_N) p.tile_list = nullptr;
+        if (!tile_list_fits(grid, g, 1)) p.tile_list = nullptr;
         if (list_taken) *list_taken = p.tile_list != nullptr;
         hipLaunchKernelGGL(conv_glds1p_kernel, dim3(g), dim3(512), SMEM, stream, p);
         return hipGetLastError();

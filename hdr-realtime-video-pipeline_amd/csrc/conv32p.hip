@@ -599,13 +599,9 @@ template <int NPASS, bool SFT, int NW, bool I8 = false, bool SQ = false>
 hipError_t launch_t(const Conv32Params &p, int n_cu, hipStream_t s)
 {
     using L = Lay<NPASS, SFT, NW, I8, SQ>;
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
+    static DevOnce attr_once;
     auto kern = conv32p_kernel<NPASS, SFT, NW, I8, SQ>;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L::SMEM);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    if (hipError_t e = allow_lds(attr_once, kern, L::SMEM)) return e;
     const int ntiles = p.tiles_x * p.tiles_y;
     const long cap = (long)n_cu * (160 * 1024 / L::SMEM);  // persistent: as many workgroups as fit the chip
     const int grid = ntiles < cap ? ntiles : (int)cap;

@@ -707,13 +707,9 @@ template <bool SFT, bool I8, bool SQ, bool PLANAR, bool C3 = false, bool SPLIT =
 hipError_t launch_k(const Conv32Params &p, int n_cu, hipStream_t s)
 {
     using L = Lay<SFT, I8, SQ, C3>;
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
+    static DevOnce attr_once;
     auto kern = conv32s_kernel<SFT, I8, SQ, PLANAR, C3, SPLIT>;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L::SMEM);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    if (hipError_t e = allow_lds(attr_once, kern, L::SMEM)) return e;
     const int ntiles = p.tiles_x * p.tiles_y;
     const int grid = ntiles < n_cu ? ntiles : n_cu;        // persistent: one workgroup per CU
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), L::SMEM, s, p);

@@ -19,7 +19,7 @@
 // MFMA shape 16x16x32 (lane = row & 15, k-group = lane >> 4): under load the chip holds a higher
 // clock on it than on 32x32x16 (MI355X_MICROARCH.md, DVFS give-back item 7; measured here +4 %).
 //
-// Sparse launches (ConvParams::tile_list, the HG need lists of hg_need.hip), as conv_prw: the spatial tiles are the list's
+// Sparse launches (ConvParams::tile_list, the HG need lists of hg_need.hip; tile_run.h): the spatial tiles are the list's
 // entries instead of all tiles_x * tiles_y.  The count is read once; every block copies the entries of ITS run into LDS in
 // the prologue (in front of the prologue's barrier), so the tile loop's only new operation is one LDS read per tile.
 #include "launchers.h"
@@ -33,37 +33,13 @@ constexpr int A_PIECES_PER_WAVE = 6, A_BYTES = 8 * A_PIECES_PER_WAVE * 1024;   /
 constexpr int B_BYTES = BN * PIXB, B_PIECES_PER_WAVE = 2;                       // 16 KiB
 constexpr int SS_OFF = 2 * A_BYTES + 3 * B_BYTES;        // two 1-KiB {scale[128], shift[128]} slots
 constexpr int DOTW_OFF = SS_OFF + 2048;                  // ST_PS_DOT3: 24 fragment pairs (hi, lo) of 32 B
-constexpr int LIST_OFF = DOTW_OFF + 1024;                // ConvParams::tile_list: this block's run of spatial tiles, looked up once
-constexpr int LIST_N = 512;
-constexpr int SMEM = LIST_OFF + LIST_N * 4;              // 149 KiB
+constexpr int LIST_OFF = DOTW_OFF + 1024;                // ConvParams::tile_list: this block's run of spatial tiles (tile_run.h)
+constexpr int SMEM = LIST_OFF + TILE_LIST_N * 4;         // 149 KiB
 
 // stores per wave and tile, by store mode (see the epilogues)
 template <int MODE> struct NStores { static constexpr int N = MODE == ST_POOL ? 2 : (MODE == ST_PS_DOT3 ? 1 : 8); };
 
-// LDS-DMA as a buffer load (see conv3x3_prw.hip): counted waits from hipcc, zeros for out-of-range lanes
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void *base, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void bdma16(rsrc_t r, void *lds, unsigned voff, unsigned soff)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds, 16, voff, soff, 0, 0);
-}
-constexpr unsigned OOB = 0x80000000u;
-
-template <int N> __device__ __forceinline__ void wait_vm()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// The wait that closes a tap, in front of its barrier: the counted vmcnt AND lgkmcnt(0) as one immediate.  Behind the barrier the
-// other waves refill the ring slot (at tap NT-3 the halo buffer) this tap has read by LDS-DMA, so every LDS read of the wave must
-// have RETURNED before it arrives -- hipcc's own lgkmcnt waits sit in front of the consuming MFMAs, and those it may sink below the
-// barrier and the next tap's DMA issue (tests/test_isa_contracts.py: test_no_lds_read_is_in_flight_when_its_region_is_rewritten).
-template <int N> __device__ __forceinline__ void wait_tap()
-{
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
+// LDS-DMA (dma_rsrc, dma16, DMA_OOB), the counted wait_vm<N> and the tap's closing wait_tap<N>: common.h
 
 struct Tile { int n0, oy0, ox0; };
 
@@ -78,33 +54,20 @@ __global__ __launch_bounds__(512) void conv_pglds_kernel(ConvParams p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, kg = lane >> 4;
 
-    // ---- this block's run of tiles: XCD x owns a contiguous range, its blocks interleave in it --
+    // ---- this block's run of tiles (tile_run.h) ----------------------------------------------------------------
     const int ntn = p.CoutPad / BN;
     const int *const lst = p.tile_list;                      // null: every tile (dense)
     const int nsp = lst ? lst[0] : p.tiles_x * p.tiles_y;    // spatial tiles to compute
     const int total = nsp * ntn;
-    int t_first, t_step, ntile;
-    {
-        const int G = gridDim.x, b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-        const int nslots = (G - xcd + 7) >> 3;
-        const int q = total >> 3, r = total & 7;
-        const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-        const int len = q + (xcd < r ? 1 : 0);
-        t_first = base + slot;
-        t_step = nslots;
-        ntile = slot < len ? (len - slot + nslots - 1) / nslots : 0;
-    }
+    const TileRun run = tile_run(total, gridDim.x, blockIdx.x);
+    const int t_first = run.t_first, t_step = run.t_step, ntile = run.ntile;
     if (ntile == 0) return;
-    // the list entries of this block's run (the launcher passes a list only when a run fits LIST_N); visible behind the prologue's barrier
-    // (an LDS-space pointer: through a generic one the volatile accesses are FLAT operations, and the write a store vmcnt would count)
-    volatile __attribute__((address_space(3))) int *s_list = (volatile __attribute__((address_space(3))) int *)(smem + LIST_OFF);
+    // the list entries of this block's run (the launcher passes a list only when a run fits); visible behind the prologue's barrier
+    const tile_list_lds_t s_list = (tile_list_lds_t)(smem + LIST_OFF);
     int sp_first = 0;                                        // the run's first entry: loaded beside the others, one trip to memory
     if (lst) {
         sp_first = lst[1 + (p.nt_slow ? t_first % nsp : t_first / ntn)];
-        if (tid < ntile) {
-            const int t = t_first + tid * t_step;
-            s_list[tid] = lst[1 + (p.nt_slow ? t % nsp : t / ntn)];
-        }
+        tile_list_stage(s_list, lst, run, tid, [&](int t) { return p.nt_slow ? t % nsp : t / ntn; });
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     // tile number k of the run (k = 0: the prologue, in front of the barrier, has the entry from the list itself)
@@ -113,7 +76,7 @@ __global__ __launch_bounds__(512) void conv_pglds_kernel(ConvParams p)
         const int t = t_first + k * t_step;
         const int nt_i = p.nt_slow ? t / nsp : t % ntn;
         int sp = p.nt_slow ? t - nt_i * nsp : t / ntn;
-        if (lst) sp = k ? __builtin_amdgcn_readfirstlane(s_list[k]) : sp_first;
+        if (lst) sp = k ? tile_list_at(s_list, k) : sp_first;
         const int ty = sp / p.tiles_x, tx = sp - ty * p.tiles_x;
         o.n0 = nt_i * BN; o.oy0 = ty * TH; o.ox0 = tx * TW;
         return o;
@@ -129,7 +92,7 @@ __global__ __launch_bounds__(512) void conv_pglds_kernel(ConvParams p)
         int cs, coff;
         if (cc < nchunk0) { src = p.src0; cs = p.s0_stride; coff = cc * CT; }
         else { src = p.src1; cs = p.s1_stride; coff = (cc - nchunk0) * CT; }
-        const rsrc_t rs = make_rsrc(src, (unsigned)p.Hi * (unsigned)p.Wi * (unsigned)cs * 2u);
+        const dma_rsrc_t rs = dma_rsrc(src, (unsigned)p.Hi * (unsigned)p.Wi * (unsigned)cs * 2u);
 #pragma unroll
         for (int it = 0; it < A_PIECES_PER_WAVE; ++it) {
             const int piece = wave + it * 8;
@@ -138,25 +101,25 @@ __global__ __launch_bounds__(512) void conv_pglds_kernel(ConvParams p)
             const int iy = T.oy0 - 1 + hy, ix = T.ox0 - 1 + hx;
             const bool ok = (hp < NPIX) & ((unsigned)iy < (unsigned)p.Hi) & ((unsigned)ix < (unsigned)p.Wi);
             const unsigned off = ((unsigned)(iy * p.Wi + ix) * (unsigned)cs + (unsigned)(coff + ((l_slot ^ (hx & 7)) << 3))) * 2u;
-            bdma16(rs, sA + buf * A_BYTES + piece * 1024, ok ? off : OOB, 0);
+            dma16(rs, sA + buf * A_BYTES + piece * 1024, ok ? off : DMA_OOB, 0);
         }
     };
     auto issue_B = [&](int it_i, int n0, int slot) {
         const int cc = it_i / 9, tap = it_i - cc * 9;
-        const rsrc_t rs = make_rsrc(p.wpk, 9u * (unsigned)nchunk * (unsigned)p.CoutPad * (unsigned)PIXB);
+        const dma_rsrc_t rs = dma_rsrc(p.wpk, 9u * (unsigned)nchunk * (unsigned)p.CoutPad * (unsigned)PIXB);
         const unsigned so = (unsigned)((tap * nchunk + cc) * p.CoutPad + n0) * (unsigned)PIXB;
 #pragma unroll
         for (int k = 0; k < B_PIECES_PER_WAVE; ++k) {
             const int piece = wave * B_PIECES_PER_WAVE + k;
             const int n = piece * 8 + l_row;
-            bdma16(rs, sB + slot * B_BYTES + piece * 1024, (unsigned)(n * CT + ((l_slot ^ (n & 7)) << 3)) * 2u, so);
+            dma16(rs, sB + slot * B_BYTES + piece * 1024, (unsigned)(n * CT + ((l_slot ^ (n & 7)) << 3)) * 2u, so);
         }
     };
     auto issue_SS = [&](int n0, int slot) {      // every wave writes the same 1 KiB: {scale[128], shift[128]}
         const char *sc = reinterpret_cast<const char *>(p.scale), *sh = reinterpret_cast<const char *>(p.shift);
         const char *lo = sc < sh ? sc : sh;                      // one (wave-uniform) resource over both arrays
-        const rsrc_t rs = make_rsrc(lo, 0xffffffffu);
-        bdma16(rs, smem + SS_OFF + slot * 1024, (unsigned)((lane < 32 ? sc : sh) - lo) + (unsigned)(lane & 31) * 16u, (unsigned)n0 * 4u);
+        const dma_rsrc_t rs = dma_rsrc(lo, 0xffffffffu);
+        dma16(rs, smem + SS_OFF + slot * 1024, (unsigned)((lane < 32 ? sc : sh) - lo) + (unsigned)(lane & 31) * 16u, (unsigned)n0 * 4u);
     };
 
     if constexpr (MODE == ST_PS_DOT3) {          // before any DMA is in flight (ordinary loads drain the queue)
@@ -398,13 +361,9 @@ __global__ __launch_bounds__(512) void conv_pglds_kernel(ConvParams p)
 template <int MODE>
 hipError_t launch_mode(const ConvParams &p, int grid, hipStream_t stream)
 {
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
+    static DevOnce attr_once;
     auto kern = conv_pglds_kernel<MODE>;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    if (hipError_t e = allow_lds(attr_once, kern, SMEM)) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SMEM, stream, p);
     return hipGetLastError();
 }
@@ -426,8 +385,8 @@ hipError_t conv_pglds_launch(ConvParams p, int n_cu, hipStream_t stream, bool *l
     p.tiles_y = (p.Ho + TH - 1) / TH;
     const int total = p.tiles_x * p.tiles_y * (p.CoutPad / BN);
     const int grid = total < n_cu ? total : n_cu;
-    // the grid never depends on the list's count (device memory); a run too long for the LDS slots: dense
-    if (p.tile_list && grid >= 8 && (total / 8 + 1 + grid / 8 - 1) / (grid / 8) > LIST_N) p.tile_list = nullptr;
+    // the grid never depends on the list's count (device memory); a run too long for the LDS block: dense (a grid below eight keeps its list)
+    if (!tile_list_fits(total, grid, 1)) p.tile_list = nullptr;
     if (list_taken) *list_taken = p.tile_list != nullptr;
     switch (p.mode) {
     case ST_NHWC: return launch_mode<ST_NHWC>(p, grid, stream);

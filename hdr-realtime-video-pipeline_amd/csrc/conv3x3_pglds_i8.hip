@@ -29,19 +29,7 @@ constexpr int SMEM = DOTW_OFF + 1024;                    // 147 KiB
 // stores per wave and tile, by store mode (see the epilogues)
 template <int MODE> struct NStores { static constexpr int N = (MODE == ST_POOL || MODE == ST_PS_DOT3) ? 1 : 4; };
 
-
-template <int N> __device__ __forceinline__ void wait_vm()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// The wait that closes a tap, in front of its barrier: the counted vmcnt AND lgkmcnt(0) as one immediate.  Behind the barrier the
-// other waves refill the ring slot (at tap NT-3 the halo buffer) this tap has read by LDS-DMA, so every LDS read of the wave must
-// have RETURNED before it arrives -- hipcc's own lgkmcnt waits sit in front of the consuming MFMAs, and those it may sink below the
-// barrier and the next tap's DMA issue (tests/test_isa_contracts.py: test_no_lds_read_is_in_flight_when_its_region_is_rewritten).
-template <int N> __device__ __forceinline__ void wait_tap()
-{
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
+// LDS-DMA, the counted wait_vm<N> and the tap's closing wait_tap<N>: common.h
 
 struct Tile { int n0, oy0, ox0; };
 
@@ -62,20 +50,11 @@ __global__ __launch_bounds__(512) void conv_pglds_i8_kernel(ConvI8Params p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, kg = lane >> 4;
 
-    // ---- this block's run of tiles: XCD x owns a contiguous range, its blocks interleave in it --
+    // ---- this block's run of tiles (tile_run.h) ----------------------------------------------------------------
     const int ntn = p.Cout / BN;
     const int total = p.tiles_x * p.tiles_y * ntn;
-    int t_first, t_step, ntile;
-    {
-        const int G = gridDim.x, b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-        const int nslots = (G - xcd + 7) >> 3;
-        const int q = total >> 3, r = total & 7;
-        const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-        const int len = q + (xcd < r ? 1 : 0);
-        t_first = base + slot;
-        t_step = nslots;
-        ntile = slot < len ? (len - slot + nslots - 1) / nslots : 0;
-    }
+    const TileRun run = tile_run(total, gridDim.x, blockIdx.x);
+    const int t_first = run.t_first, t_step = run.t_step, ntile = run.ntile;
     if (ntile == 0) return;
     auto decode = [&](int t) {
         Tile o;
@@ -429,13 +408,9 @@ __global__ __launch_bounds__(512) void conv_pglds_i8_kernel(ConvI8Params p)
 template <int MODE, bool C64>
 hipError_t launch_mode(const ConvI8Params &p, int grid, hipStream_t stream)
 {
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
+    static DevOnce attr_once;
     auto kern = conv_pglds_i8_kernel<MODE, C64>;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    if (hipError_t e = allow_lds(attr_once, kern, SMEM)) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SMEM, stream, p);
     return hipGetLastError();
 }

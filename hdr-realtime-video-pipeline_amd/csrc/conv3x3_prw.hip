@@ -15,7 +15,7 @@
 //
 // LDS: 2 x 41 KiB halo + 8 x 2 x 4 KiB weight rings + 2 x 2 KiB scale/shift + 1 KiB DMA trash + 1 KiB dot weights + 2 KiB tile list = 154 KiB.
 //
-// Sparse launches (ConvParams::tile_list, the HG need lists of hg_need.hip): the spatial tiles are the list's entries instead of all
+// Sparse launches (ConvParams::tile_list, the HG need lists of hg_need.hip; tile_run.h): the spatial tiles are the list's entries instead of all
 // tiles_x * tiles_y.  The count is read once; every block copies the entries of ITS run into LDS in the prologue (in front of the
 // prologue's barrier), so the tile loop's only new operation is one LDS read per tile -- no scalar or vector memory load enters
 // the MFMA stream, whose vmcnt waits are counted by hand.
@@ -37,30 +37,10 @@ constexpr int W_OFF = 2 * A_BYTES;
 constexpr int SS_OFF = W_OFF + 8 * 2 * W_SLOT;           // two slots of {scale[256], shift[256]}
 constexpr int TRASH_OFF = SS_OFF + 2 * 2048;
 constexpr int DOTW_OFF = TRASH_OFF + 1024;
-constexpr int LIST_OFF = DOTW_OFF + 1024;                // ConvParams::tile_list: this block's run of spatial tiles, looked up once
-constexpr int LIST_N = 512;
-constexpr int SMEM = LIST_OFF + LIST_N * 4;              // 157 696 B
+constexpr int LIST_OFF = DOTW_OFF + 1024;                // ConvParams::tile_list: this block's run of spatial tiles (tile_run.h)
+constexpr int SMEM = LIST_OFF + TILE_LIST_N * 4;         // 157 696 B
 
-// LDS-DMA as a BUFFER load (buffer_load_dwordx4 ... lds), not global_load_lds: the global form is a FLAT-encoded
-// instruction that hipcc's waitcnt pass treats as "may touch LDS and memory", after which it never counts again -- every
-// later wait becomes lgkmcnt(0) / vmcnt(0) (tools/lds_dma_oob_probe.hip and the ISA of this file show the difference).
-// Lanes whose byte offset lies outside the resource's num_records write zeros to LDS: the image border needs no zero line.
-// OFF is an immediate added to both the memory and the LDS address.
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void *base, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, (int)bytes, 0x00020000);
-}
-template <int OFF> __device__ __forceinline__ void bdma16(rsrc_t r, void *lds, unsigned voff, unsigned soff)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds, 16, voff, soff, OFF, 0);
-}
-constexpr unsigned OOB = 0x80000000u;                    // beyond any tensor here (all < 2 GiB)
-
-template <int N> __device__ __forceinline__ void wait_vm()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
+// LDS-DMA (dma_rsrc, dma16<OFF>, DMA_OOB) and the counted wait_vm<N>: common.h
 
 struct Tile { int n0, oy0, ox0; };
 
@@ -76,30 +56,17 @@ __global__ __launch_bounds__(512) void conv_prw_kernel(ConvParams p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     char *sW = smem + W_OFF + wave * (2 * W_SLOT);
 
-    // ---- this block's run of tiles: XCD x owns a contiguous range, its blocks interleave in it (as conv_pglds) --
+    // ---- this block's run of tiles (tile_run.h) ----------------------------------------------------------------
     const int ntn = p.CoutPad / BN;
     const int *const lst = p.tile_list;                      // null: every tile (dense)
     const int nsp = lst ? lst[0] : p.tiles_x * p.tiles_y;    // spatial tiles to compute
-    const int total = nsp * ntn;
-    int t_first, t_step, ntile;
-    {
-        const int G = gridDim.x, b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-        const int nslots = (G - xcd + 7) >> 3;
-        const int q = total >> 3, r = total & 7;
-        const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-        const int len = q + (xcd < r ? 1 : 0);
-        t_first = base + slot;
-        t_step = nslots;
-        ntile = slot < len ? (len - slot + nslots - 1) / nslots : 0;
-    }
+    const TileRun run = tile_run(nsp * ntn, gridDim.x, blockIdx.x);
+    const int t_first = run.t_first, t_step = run.t_step, ntile = run.ntile;
     if (ntile == 0) return;
-    // the list entries of this block's run (the launcher passes a list only when a run fits LIST_N); visible behind the prologue's barrier
-    volatile int *s_list = reinterpret_cast<volatile int *>(smem + LIST_OFF);
+    // the list entries of this block's run (the launcher passes a list only when a run fits); visible behind the prologue's barrier
+    const tile_list_lds_t s_list = (tile_list_lds_t)(smem + LIST_OFF);
     if (lst) {
-        if (tid < ntile) {
-            const int t = t_first + tid * t_step;
-            s_list[tid] = lst[1 + (p.nt_slow ? t % nsp : t / ntn)];
-        }
+        tile_list_stage(s_list, lst, run, tid, [&](int t) { return p.nt_slow ? t % nsp : t / ntn; });
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     // tile number k of the run (k = 0: the prologue, in front of the barrier, reads the list itself)
@@ -108,7 +75,7 @@ __global__ __launch_bounds__(512) void conv_prw_kernel(ConvParams p)
         const int t = t_first + k * t_step;
         const int nt_i = p.nt_slow ? t / nsp : t % ntn;
         int sp = p.nt_slow ? t - nt_i * nsp : t / ntn;
-        if (lst) sp = k ? __builtin_amdgcn_readfirstlane(s_list[k]) : lst[1 + sp];
+        if (lst) sp = k ? tile_list_at(s_list, k) : lst[1 + sp];
         const int ty = sp / p.tiles_x, tx = sp - ty * p.tiles_x;
         o.n0 = nt_i * BN; o.oy0 = ty * TH; o.ox0 = tx * TW;
         return o;
@@ -127,7 +94,7 @@ __global__ __launch_bounds__(512) void conv_prw_kernel(ConvParams p)
         int cs, coff;
         if (cc < nchunk0) { src = p.src0; cs = p.s0_stride; coff = cc * CT; }
         else { src = p.src1; cs = p.s1_stride; coff = (cc - nchunk0) * CT; }
-        const rsrc_t rs = make_rsrc(src, (unsigned)p.Hi * (unsigned)p.Wi * (unsigned)cs * 2u);
+        const dma_rsrc_t rs = dma_rsrc(src, (unsigned)p.Hi * (unsigned)p.Wi * (unsigned)cs * 2u);
 #pragma unroll
         for (int it = 0; it < A_PIECES_PER_WAVE; ++it) {
             const int piece = wave + it * 8;
@@ -136,20 +103,20 @@ __global__ __launch_bounds__(512) void conv_prw_kernel(ConvParams p)
             const int iy = T.oy0 - 1 + hy, ix = T.ox0 - 1 + hx;
             const bool ok = (hp < NPIX) & ((unsigned)iy < (unsigned)p.Hi) & ((unsigned)ix < (unsigned)p.Wi);
             const unsigned off = ((unsigned)(iy * p.Wi + ix) * (unsigned)cs + (unsigned)(coff + ((l_slot ^ (hx & 7)) << 3))) * 2u;
-            bdma16<0>(rs, piece < A_PIECES ? sA + buf * A_BYTES + piece * 1024 : smem + TRASH_OFF, ok ? off : OOB, 0);
+            dma16<0>(rs, piece < A_PIECES ? sA + buf * A_BYTES + piece * 1024 : smem + TRASH_OFF, ok ? off : DMA_OOB, 0);
         }
     };
     // this wave's 32 weight rows of (chunk cc, tap): four 1-KiB pieces = one scalar offset + four immediates
     const unsigned w_lane = (unsigned)((lane >> 3) * CT + (((lane & 7) ^ (lane >> 3)) << 3)) * 2u;
     auto issue_W = [&](int cc, int tap, int n0, int slot) {
-        const rsrc_t rs = make_rsrc(p.wpk, 9u * (unsigned)nchunk * (unsigned)p.CoutPad * (unsigned)PIXB);
+        const dma_rsrc_t rs = dma_rsrc(p.wpk, 9u * (unsigned)nchunk * (unsigned)p.CoutPad * (unsigned)PIXB);
         const unsigned so = (unsigned)((tap * nchunk + cc) * p.CoutPad + n0 + wave * WCH) * (unsigned)PIXB;
         char *d = sW + slot * W_SLOT;
-        bdma16<0>(rs, d, w_lane, so); bdma16<1024>(rs, d, w_lane, so); bdma16<2048>(rs, d, w_lane, so); bdma16<3072>(rs, d, w_lane, so);
+        dma16<0>(rs, d, w_lane, so); dma16<1024>(rs, d, w_lane, so); dma16<2048>(rs, d, w_lane, so); dma16<3072>(rs, d, w_lane, so);
     };
     auto issue_SS = [&](int n0, int slot) {      // wave 0: scale[256], wave 1: shift[256]; the others keep the piece count equal
-        const rsrc_t rs = make_rsrc(wave == 1 ? p.shift : p.scale, (unsigned)p.CoutPad * 4u);
-        bdma16<0>(rs, wave < 2 ? smem + SS_OFF + slot * 2048 + wave * 1024 : smem + TRASH_OFF, (unsigned)opaque_lane() * 16u, (unsigned)n0 * 4u);
+        const dma_rsrc_t rs = dma_rsrc(wave == 1 ? p.shift : p.scale, (unsigned)p.CoutPad * 4u);
+        dma16<0>(rs, wave < 2 ? smem + SS_OFF + slot * 2048 + wave * 1024 : smem + TRASH_OFF, (unsigned)opaque_lane() * 16u, (unsigned)n0 * 4u);
     };
 
     // ST_PS_DOT3 (Up_conv5: Cout = 256 = four pixel-shuffle positions x 64 channels): the 64 -> 3 dot products behind the
@@ -441,13 +408,9 @@ __global__ __launch_bounds__(512) void conv_prw_kernel(ConvParams p)
 template <int MODE, int TH>
 hipError_t launch_mode(const ConvParams &p, int grid, hipStream_t stream)
 {
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
+    static DevOnce attr_once;
     auto kern = conv_prw_kernel<MODE, TH>;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    if (hipError_t e = allow_lds(attr_once, kern, SMEM)) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SMEM, stream, p);
     return hipGetLastError();
 }
@@ -469,8 +432,8 @@ hipError_t conv_prw_launch(ConvParams p, int th, int n_cu, hipStream_t stream, b
     p.tiles_y = (p.Ho + th - 1) / th;
     const int total = p.tiles_x * p.tiles_y * (p.CoutPad / BN);
     const int grid = total < n_cu ? total : n_cu;
-    // the grid never depends on the list's count (device memory); a run too long for the LDS slots: dense
-    if (p.tile_list && (grid < 8 || (total / 8 + 1 + grid / 8 - 1) / (grid / 8) > LIST_N)) p.tile_list = nullptr;
+    // the grid never depends on the list's count (device memory); a grid below eight or a run too long for the LDS block: dense
+    if (!tile_list_fits(total, grid, 8)) p.tile_list = nullptr;
     if (list_taken) *list_taken = p.tile_list != nullptr;
     if (th == 16) {
         switch (p.mode) {

@@ -26,26 +26,7 @@ constexpr int TRASH_OFF = SS_OFF + 2 * 2048;
 constexpr int DOTW_OFF = TRASH_OFF + 1024;
 constexpr int SMEM = DOTW_OFF + 1024;                    // 155 648 B
 
-// LDS-DMA as a BUFFER load (buffer_load_dwordx4 ... lds), not global_load_lds: the global form is a FLAT-encoded
-// instruction that hipcc's waitcnt pass treats as "may touch LDS and memory", after which it never counts again -- every
-// later wait becomes lgkmcnt(0) / vmcnt(0) (tools/lds_dma_oob_probe.hip and the ISA of this file show the difference).
-// Lanes whose byte offset lies outside the resource's num_records write zeros to LDS: the image border needs no zero line.
-// OFF is an immediate added to both the memory and the LDS address.
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void *base, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, (int)bytes, 0x00020000);
-}
-template <int OFF> __device__ __forceinline__ void bdma16(rsrc_t r, void *lds, unsigned voff, unsigned soff)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds, 16, voff, soff, OFF, 0);
-}
-constexpr unsigned OOB = 0x80000000u;                    // beyond any tensor here (all < 2 GiB)
-
-template <int N> __device__ __forceinline__ void wait_vm()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
+// LDS-DMA (dma_rsrc, dma16<OFF>, DMA_OOB) and the counted wait_vm<N>: common.h
 
 struct Tile { int n0, oy0, ox0; };
 
@@ -61,20 +42,11 @@ __global__ __launch_bounds__(512) void conv_prw_i8_kernel(ConvI8Params p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     char *sW = smem + W_OFF + wave * (2 * W_SLOT);
 
-    // ---- this block's run of tiles: XCD x owns a contiguous range, its blocks interleave in it (as conv_pglds) --
+    // ---- this block's run of tiles (tile_run.h) ----------------------------------------------------------------
     const int ntn = p.Cout / BN;
     const int total = p.tiles_x * p.tiles_y * ntn;
-    int t_first, t_step, ntile;
-    {
-        const int G = gridDim.x, b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-        const int nslots = (G - xcd + 7) >> 3;
-        const int q = total >> 3, r = total & 7;
-        const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-        const int len = q + (xcd < r ? 1 : 0);
-        t_first = base + slot;
-        t_step = nslots;
-        ntile = slot < len ? (len - slot + nslots - 1) / nslots : 0;
-    }
+    const TileRun run = tile_run(total, gridDim.x, blockIdx.x);
+    const int t_first = run.t_first, t_step = run.t_step, ntile = run.ntile;
     if (ntile == 0) return;
     auto decode = [&](int t) {
         Tile o;
@@ -99,7 +71,7 @@ __global__ __launch_bounds__(512) void conv_prw_i8_kernel(ConvI8Params p)
         int cs, coff;
         if (cc < nchunk0) { src = p.src0; cs = p.c0; coff = cc * CT; }
         else { src = p.src1; cs = p.c1; coff = (cc - nchunk0) * CT; }
-        const rsrc_t rs = make_rsrc(src, (unsigned)p.Hi * (unsigned)p.Wi * (unsigned)cs);
+        const dma_rsrc_t rs = dma_rsrc(src, (unsigned)p.Hi * (unsigned)p.Wi * (unsigned)cs);
 #pragma unroll
         for (int it = 0; it < A_PIECES_PER_WAVE; ++it) {
             const int piece = wave + it * 8;
@@ -108,20 +80,20 @@ __global__ __launch_bounds__(512) void conv_prw_i8_kernel(ConvI8Params p)
             const int iy = T.oy0 - 1 + hy, ix = T.ox0 - 1 + hx;
             const bool ok = (hp < NPIX) & ((unsigned)iy < (unsigned)p.Hi) & ((unsigned)ix < (unsigned)p.Wi);
             const unsigned off = (unsigned)(iy * p.Wi + ix) * (unsigned)cs + (unsigned)(coff + ((l_slot ^ (hx & 7)) << 4));
-            bdma16<0>(rs, piece < A_PIECES ? sA + buf * A_BYTES + piece * 1024 : smem + TRASH_OFF, ok ? off : OOB, 0);
+            dma16<0>(rs, piece < A_PIECES ? sA + buf * A_BYTES + piece * 1024 : smem + TRASH_OFF, ok ? off : DMA_OOB, 0);
         }
     };
     // this wave's 32 weight rows of (chunk cc, tap): four 1-KiB pieces = one scalar offset + four immediates
     const unsigned w_lane = (unsigned)((lane >> 3) * CT + (((lane & 7) ^ (lane >> 3)) << 4));
     auto issue_W = [&](int cc, int tap, int n0, int slot) {
-        const rsrc_t rs = make_rsrc(p.wpk, 9u * (unsigned)nchunk * (unsigned)p.Cout * (unsigned)PIXB);
+        const dma_rsrc_t rs = dma_rsrc(p.wpk, 9u * (unsigned)nchunk * (unsigned)p.Cout * (unsigned)PIXB);
         const unsigned so = (unsigned)((tap * nchunk + cc) * p.Cout + n0 + wave * WCH) * (unsigned)PIXB;
         char *d = sW + slot * W_SLOT;
-        bdma16<0>(rs, d, w_lane, so); bdma16<1024>(rs, d, w_lane, so); bdma16<2048>(rs, d, w_lane, so); bdma16<3072>(rs, d, w_lane, so);
+        dma16<0>(rs, d, w_lane, so); dma16<1024>(rs, d, w_lane, so); dma16<2048>(rs, d, w_lane, so); dma16<3072>(rs, d, w_lane, so);
     };
     auto issue_SS = [&](int n0, int slot) {      // wave 0: scale[256], wave 1: shift[256]; the others keep the piece count equal
-        const rsrc_t rs = make_rsrc(wave == 1 ? p.shift : p.scale, (unsigned)p.Cout * 4u);
-        bdma16<0>(rs, wave < 2 ? smem + SS_OFF + slot * 2048 + wave * 1024 : smem + TRASH_OFF, (unsigned)opaque_lane() * 16u, (unsigned)n0 * 4u);
+        const dma_rsrc_t rs = dma_rsrc(wave == 1 ? p.shift : p.scale, (unsigned)p.Cout * 4u);
+        dma16<0>(rs, wave < 2 ? smem + SS_OFF + slot * 2048 + wave * 1024 : smem + TRASH_OFF, (unsigned)opaque_lane() * 16u, (unsigned)n0 * 4u);
     };
 
     i32x4 acc[2][TH];
@@ -345,13 +317,9 @@ __global__ __launch_bounds__(512) void conv_prw_i8_kernel(ConvI8Params p)
 template <int MODE, int TH>
 hipError_t launch_mode(const ConvI8Params &p, int grid, hipStream_t stream)
 {
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
+    static DevOnce attr_once;
     auto kern = conv_prw_i8_kernel<MODE, TH>;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    if (hipError_t e = allow_lds(attr_once, kern, SMEM)) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SMEM, stream, p);
     return hipGetLastError();
 }

@@ -252,13 +252,9 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3s2_preg_kernel(ConvParams p
 template <int NW>
 hipError_t launch_s2(ConvParams p, int n_cu, hipStream_t s)
 {
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
+    static DevOnce attr_once;
     auto kern = conv3x3s2_preg_kernel<NW>;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM + (NW == 12 ? TAIL_SMEM : 0));
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    if (hipError_t e = allow_lds(attr_once, kern, SMEM + (NW == 12 ? TAIL_SMEM : 0))) return e;
     const int ntiles = p.tiles_x * p.tiles_y;
     hipLaunchKernelGGL(kern, dim3(ntiles < n_cu ? ntiles : n_cu), dim3(64 * NW), SMEM + (NW == 12 ? TAIL_SMEM : 0), s, p);
     return hipGetLastError();

@@ -16,8 +16,6 @@ constexpr int A_BYTES = TP * CT, B_BYTES = BN * CT;   // 16 KiB + 16 KiB per sta
 constexpr int STAGE = A_BYTES + B_BYTES, NSTAGE = 2;
 constexpr int SMEM = NSTAGE * STAGE;                  // 64 KiB
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 template <bool OUTF16>
 __global__ __launch_bounds__(512) void conv1x1_i8_kernel(ConvI8Params p)
 {
@@ -160,16 +158,9 @@ hipError_t conv1x1_i8_launch(ConvI8Params p, hipStream_t stream)
     if ((p.c0 % CT) || (p.c1 % CT) || p.c0 + p.c1 < CT || (p.Cout % BN) || !p.padline || p.mode != ST_NHWC ||
         (p.dstC % 64) || (p.dstC < p.Cout && p.dstC + 64 != p.Cout))
         return hipErrorInvalidValue;
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_i8_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_i8_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    static DevOnce attr_once[2];         // both instantiations
+    if (hipError_t e = allow_lds(attr_once[0], conv1x1_i8_kernel<false>, SMEM)) return e;
+    if (hipError_t e = allow_lds(attr_once[1], conv1x1_i8_kernel<true>, SMEM)) return e;
     const size_t npx = (size_t)p.Hi * p.Wi;
     const int grid = (int)((npx + TP - 1) / TP) * (p.Cout / BN);
     if (p.out_f16) hipLaunchKernelGGL(conv1x1_i8_kernel<true>, dim3(grid), dim3(512), SMEM, stream, p);

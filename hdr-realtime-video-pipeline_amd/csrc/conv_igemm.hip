@@ -68,12 +68,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p)
 
     // XCD-aware, bijective remap of the 1-D grid: the 8 XCDs each get a contiguous run of tiles
     // so neighbouring tiles (shared halo, shared weights) hit the same L2.
-    const int nwg = gridDim.x;
-    int t;
-    {
-        const int b = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int t = xcd_tile(gridDim.x, blockIdx.x);
     const int ntn = p.CoutPad / BN;
     const int nt_i = t % ntn;
     const int sp = t / ntn;
@@ -326,14 +321,9 @@ template <int CIN_T, int BN, int KS, int S>
 hipError_t launch_cfg(const ConvParams &p, hipStream_t stream)
 {
     using C = Cfg<CIN_T, BN, KS, S>;
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
+    static DevOnce attr_once;
     auto kern = conv_igemm_kernel<CIN_T, BN, KS, S>;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    if (hipError_t e = allow_lds(attr_once, kern, C::SMEM)) return e;
     const int grid = p.tiles_x * p.tiles_y * (p.CoutPad / BN);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), C::SMEM, stream, p);
     return hipGetLastError();

@@ -287,13 +287,9 @@ hipError_t launch_q8(const ConvQ8Params &p, int n_cu, hipStream_t s)
     constexpr int HH = (Q8_TH - 1) * S + KS, HWD = (Q8_TW - 1) * S + KS, NPX = HH * HWD;
     const int smem = ((NPX * CIN + 255) & ~255) + KS * KS * p.CoutPad * CIN + 17 * p.CoutPad * 4;
     if (smem > 160 * 1024) return hipErrorInvalidValue;
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
+    static DevOnce attr_once;
     auto kern = conv_q8_kernel<CIN, KS, S>;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    if (hipError_t e = allow_lds(attr_once, kern, 160 * 1024)) return e;
     // persistent: as many workgroups as are resident at once with this layer's LDS footprint
     static int per_cu_of[161];                                 // by KiB of dynamic LDS; 0 = not asked yet
     int &per_cu = per_cu_of[(smem + 1023) / 1024];
@@ -315,13 +311,9 @@ hipError_t launch_multi(const ConvQ8MultiParams &p, int n_cu, hipStream_t s)
     constexpr int NPX = 17 * 33, XB = (NPX * 64 + 255) & ~255;
     constexpr int smem = NG * XB;
     static_assert(smem <= 160 * 1024, "LDS budget");
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
+    static DevOnce attr_once;
     auto kern = conv_q8_multi_kernel<NG>;
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    if (hipError_t e = allow_lds(attr_once, kern, smem)) return e;
     const int ntiles = ((p.Wo + Q8_TW - 1) / Q8_TW) * ((p.Ho + Q8_TH - 1) / Q8_TH);
     hipLaunchKernelGGL(kern, dim3(ntiles < n_cu ? ntiles : n_cu), dim3(256 * NG), smem, s, p);
     return hipGetLastError();

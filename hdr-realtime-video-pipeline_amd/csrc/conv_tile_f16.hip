@@ -103,12 +103,8 @@ hipError_t conv_t16_launch(ConvParams p, hipStream_t s, int n_cu)
         return hipErrorInvalidValue;
     constexpr int NPX = 17 * 33;
     const int smem = ((NPX * 4 + 63) / 64) * 1024 + 256 + 2048;    // halo patch (whole DMA pieces), scale / shift, the last tap's two A fragments
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_t16_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    static DevOnce attr_once;
+    if (hipError_t e = allow_lds(attr_once, conv_t16_kernel<2>, smem)) return e;
     const int ntiles = ((p.Wo + TT_TW - 1) / TT_TW) * ((p.Ho + TT_TH - 1) / TT_TH);
     const int grid = ntiles < 4 * n_cu ? ntiles : 4 * n_cu;       // four workgroups per CU are resident (LDS 36 KiB, <= 128 VGPRs)
     hipLaunchKernelGGL(conv_t16_kernel<2>, dim3(grid), dim3(256), smem, s, p);

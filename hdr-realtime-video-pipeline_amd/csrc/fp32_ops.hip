@@ -203,10 +203,7 @@ template <int MT, int KS> hipError_t conv_f32_mfma_go(const F32ConvParams &p, hi
     static DevOnce once;
     auto kern = conv_f32_mfma_kernel<MT, KS>;
     constexpr int smem = MfGeo<MT, KS>::SMEM;
-    if (once.need()) {
-        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem)) return e;
-        once.done();
-    }
+    if (hipError_t e = allow_lds(once, kern, smem)) return e;
     hipLaunchKernelGGL(kern, dim3((p.Wo + MF_TC - 1) / MF_TC, (p.Ho + MF_TR - 1) / MF_TR, p.cout / (32 * MT)), dim3(512), smem, s, p);
     return hipGetLastError();
 }

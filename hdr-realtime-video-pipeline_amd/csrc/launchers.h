@@ -10,6 +10,15 @@ struct DevOnce {
     bool need() const { return !set[cur()]; }
     void done() { set[cur()] = 1; }
 };
+// A kernel with more than 64 KiB of dynamic LDS has to be told so once.  `once` is the call site's own static DevOnce: one per
+// kernel instantiation.
+template <class K> hipError_t allow_lds(DevOnce &once, K kern, int bytes)
+{
+    if (!once.need()) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) once.done();
+    return e;
+}
 
 hipError_t conv_igemm_launch(ConvParams p, int cin_t, int bn, int ks, int stride, hipStream_t stream);
 hipError_t conv_glds1_launch(ConvParams p, hipStream_t stream, int n_cu = 0, bool old_form = false, bool *list_taken = nullptr);   // n_cu >= 8: the persistent form

@@ -357,13 +357,8 @@ __global__ __launch_bounds__(256) void planar3_to_q8_kernel(const f16 *__restric
 
 hipError_t le_cond_trunk_q8_launch(const f16 *img, int H, int W, const TrunkQ8Args &a, f16 *cond, f16 *cond1, int n_cu, hipStream_t s)
 {
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(le_cond_trunk_q8_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, TRUNK_Q8_SMEM);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    static DevOnce attr_once;
+    if (hipError_t e = allow_lds(attr_once, le_cond_trunk_q8_kernel, TRUNK_Q8_SMEM)) return e;
     TrunkQ8Params p;
     p.img = img; p.H = H; p.W = W; p.wfrag = reinterpret_cast<const i32x4 *>(a.wfrag); p.consts = a.consts;
     p.q1_inv = a.q1_inv; p.q1_zoff = a.q1_zoff; p.q4_inv = a.q4_inv;

@@ -320,16 +320,9 @@ constexpr int TRUNK_SMEM = NFRAG * 64 * 16 + ((NBIAS * 4 + 15) / 16) * 16 + SUBS
 hipError_t le_cond_trunk_launch(const f16 *img, int H, int W, const f16 *wfrag, const float *bias, f16 *cond, f16 *cond1,
                                 int n_cu, hipStream_t s, const QLastArgs *q6)
 {
-    static DevOnce attr_once;   // hipFuncSetAttribute is per (function, device)
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(le_cond_trunk_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, TRUNK_SMEM);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(le_cond_trunk_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, TRUNK_SMEM);
-        if (e != hipSuccess) return e;
-        attr_once.done();
-    }
+    static DevOnce attr_once[2];         // both instantiations
+    if (hipError_t e = allow_lds(attr_once[0], le_cond_trunk_kernel<false>, TRUNK_SMEM)) return e;
+    if (hipError_t e = allow_lds(attr_once[1], le_cond_trunk_kernel<true>, TRUNK_SMEM)) return e;
     const int ntiles = ((W + T_TW - 1) / T_TW) * ((H + T_TH - 1) / T_TH);
     const int per_cu = SUBS == 1 ? 2 : 1;                            // SUBS = 1: two workgroups per CU (LDS: ~60 KiB each)
     const int want = (ntiles + SUBS - 1) / SUBS;

@@ -194,15 +194,5 @@ template <class P> void strips(P &p, int n_cu, bool even_rows, int &nseg)
     if (even_rows) p.rows_per_seg = (p.rows_per_seg + 1) & ~1;
     nseg = (p.H + p.rows_per_seg - 1) / p.rows_per_seg;
 }
-template <class K> hipError_t set_lds(K kern, int bytes, DevOnce &once)
-{
-    if (once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        once.done();
-    }
-    return hipSuccess;
-}
-
 
 }  // namespace

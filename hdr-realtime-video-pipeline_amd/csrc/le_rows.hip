@@ -890,10 +890,10 @@ hipError_t le_rb_rows_launch(RowsRbParams p, int n_cu, hipStream_t s)
     int nseg;
     strips(p, n_cu, false, nseg);
     if (p.fq) {
-        if (hipError_t e = set_lds(le_rb_rows_kernel<3, true>, RbGeo<3>::SMEM, once_q)) return e;
+        if (hipError_t e = allow_lds(once_q, le_rb_rows_kernel<3, true>, RbGeo<3>::SMEM)) return e;
         hipLaunchKernelGGL((le_rb_rows_kernel<3, true>), dim3(p.nstrips * nseg), dim3(512), RbGeo<3>::SMEM, s, p);
     } else {
-        if (hipError_t e = set_lds(le_rb_rows_kernel<3, false>, RbGeo<3>::SMEM, once)) return e;
+        if (hipError_t e = allow_lds(once, le_rb_rows_kernel<3, false>, RbGeo<3>::SMEM)) return e;
         hipLaunchKernelGGL((le_rb_rows_kernel<3, false>), dim3(p.nstrips * nseg), dim3(512), RbGeo<3>::SMEM, s, p);
     }
     return hipGetLastError();
@@ -908,10 +908,10 @@ hipError_t le_tail_rows_launch(RowsTailParams p, int n_cu, hipStream_t s)
     int nseg;
     strips(p, n_cu, true, nseg);
     if (p.fq) {
-        if (hipError_t e = set_lds(le_tail_rows_kernel<3, true>, TailGeo<3>::SMEM, once_q)) return e;
+        if (hipError_t e = allow_lds(once_q, le_tail_rows_kernel<3, true>, TailGeo<3>::SMEM)) return e;
         hipLaunchKernelGGL((le_tail_rows_kernel<3, true>), dim3(p.nstrips * nseg), dim3(512), TailGeo<3>::SMEM, s, p);
     } else {
-        if (hipError_t e = set_lds(le_tail_rows_kernel<3, false>, TailGeo<3>::SMEM, once)) return e;
+        if (hipError_t e = allow_lds(once, le_tail_rows_kernel<3, false>, TailGeo<3>::SMEM)) return e;
         hipLaunchKernelGGL((le_tail_rows_kernel<3, false>), dim3(p.nstrips * nseg), dim3(512), TailGeo<3>::SMEM, s, p);
     }
     return hipGetLastError();
@@ -926,10 +926,10 @@ hipError_t le_head_rows_launch(RowsHeadParams p, int n_cu, hipStream_t s)
     int nseg;
     strips(p, n_cu, true, nseg);
     if (p.fq) {
-        if (hipError_t e = set_lds(le_head_rows_kernel<3, true>, HeadGeo<3>::SMEM, once_q)) return e;
+        if (hipError_t e = allow_lds(once_q, le_head_rows_kernel<3, true>, HeadGeo<3>::SMEM)) return e;
         hipLaunchKernelGGL((le_head_rows_kernel<3, true>), dim3(p.nstrips * nseg), dim3(512), HeadGeo<3>::SMEM, s, p);
     } else {
-        if (hipError_t e = set_lds(le_head_rows_kernel<3, false>, HeadGeo<3>::SMEM, once)) return e;
+        if (hipError_t e = allow_lds(once, le_head_rows_kernel<3, false>, HeadGeo<3>::SMEM)) return e;
         hipLaunchKernelGGL((le_head_rows_kernel<3, false>), dim3(p.nstrips * nseg), dim3(512), HeadGeo<3>::SMEM, s, p);
     }
     return hipGetLastError();

@@ -794,7 +794,7 @@ hipError_t le_rb_rows_i8_launch(RowsRbI8Params p, int n_cu, hipStream_t s)
     static DevOnce once;
     int nseg;
     strips(p, n_cu, false, nseg);
-    if (hipError_t e = set_lds(le_rb_rows_i8_kernel<3>, Rb8Geo<3>::SMEM, once)) return e;
+    if (hipError_t e = allow_lds(once, le_rb_rows_i8_kernel<3>, Rb8Geo<3>::SMEM)) return e;
     hipLaunchKernelGGL((le_rb_rows_i8_kernel<3>), dim3(p.nstrips * nseg), dim3(512), Rb8Geo<3>::SMEM, s, p);
     return hipGetLastError();
 }
@@ -806,7 +806,7 @@ hipError_t le_tail_rows_i8_launch(RowsTailI8Params p, int n_cu, hipStream_t s)
     static DevOnce once;
     int nseg;
     strips(p, n_cu, true, nseg);
-    if (hipError_t e = set_lds(le_tail_rows_i8_kernel<3>, Tail8Geo<3>::SMEM, once)) return e;
+    if (hipError_t e = allow_lds(once, le_tail_rows_i8_kernel<3>, Tail8Geo<3>::SMEM)) return e;
     hipLaunchKernelGGL((le_tail_rows_i8_kernel<3>), dim3(p.nstrips * nseg), dim3(512), Tail8Geo<3>::SMEM, s, p);
     return hipGetLastError();
 }
@@ -818,7 +818,7 @@ hipError_t le_head_rows_i8_launch(RowsHeadI8Params p, int n_cu, hipStream_t s)
     static DevOnce once;
     int nseg;
     strips(p, n_cu, true, nseg);
-    if (hipError_t e = set_lds(le_head_rows_i8_kernel<3>, Head8Geo<3>::SMEM, once)) return e;
+    if (hipError_t e = allow_lds(once, le_head_rows_i8_kernel<3>, Head8Geo<3>::SMEM)) return e;
     hipLaunchKernelGGL((le_head_rows_i8_kernel<3>), dim3(p.nstrips * nseg), dim3(512), Head8Geo<3>::SMEM, s, p);
     return hipGetLastError();
 }
