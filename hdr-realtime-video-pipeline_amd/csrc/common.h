@@ -423,6 +423,16 @@ struct Ycbcr10Params {
     int H, W, y_pitch, c_pitch, fmt, siting;
 };
 
+// Debanding of RGB48 codes (post_deband.hip; include/hdrtv_mi355x.h states the integer rule): a workgroup owns DB_TH x DB_TW pixels
+// and stages them with a halo of DB_HALO = the largest range on every side.
+constexpr int DB_TW = 128, DB_TH = 32, DB_HALO = 16;
+struct DebandParams {
+    const uint16_t *src;             // u16 [H][W][3]
+    uint16_t *dst;                   // u16 [H][W][3], no overlap with src
+    int H, W, range, threshold;      // range 1 .. DB_HALO, threshold 1 .. 65535
+    uint32_t seed;
+};
+
 // HDR10 content light level record (light_stats.hip; include/hdrtv_mi355x.h states the rule) of the rectangle x0, y0, rw, rh
 struct LightStatsParams {
     const void *in;                  // planar [3][H][W] f16 / f32 (light_stats_launch) or u16 [H][W][3] RGB48 codes (rgb48_light_stats_launch)

@@ -378,6 +378,47 @@ int hdrtv_rgb48_to_ycbcr10(hdrtv_ctx *c, void *stream, const uint16_t *src, int 
     return launched(c, "rgb48_to_ycbcr10", rgb48_to_ycbcr10_launch(p, (hipStream_t)stream));
 }
 
+// dither = HDRTV_DITHER_NONE: the launches of the two entry points above, byte for byte
+int hdrtv_post_ycbcr10_ex(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits, int fmt, int siting,
+                          uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch, int dither)
+{
+    if (dither != HDRTV_DITHER_NONE && dither != HDRTV_DITHER_ORDERED) return fail(c, HDRTV_EINVAL, "post_ycbcr10_ex: unknown dither %d", dither);
+    if (dither == HDRTV_DITHER_NONE) return hdrtv_post_ycbcr10(c, stream, in, dtype, H, W, pq, peak_nits, fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch);
+    Ycbcr10Params p;
+    if (int rc = ycbcr10_args(c, "post_ycbcr10_ex", in, H, W, fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch, p)) return rc;
+    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_ycbcr10_ex: bad dtype %d", dtype);
+    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_ycbcr10_ex: pq needs peak_nits > 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = pq ? ensure_pq_table(c, "post_ycbcr10_ex") : HDRTV_OK) return rc;
+    p.pq_bnd = c->pq_bnd;
+    p.peak = pq ? peak_nits : 0.f;
+    return launched(c, "post_ycbcr10_ex", post_ycbcr10_dither_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
+}
+
+int hdrtv_rgb48_to_ycbcr10_ex(hdrtv_ctx *c, void *stream, const uint16_t *src, int H, int W, int fmt, int siting, uint16_t *dst_y,
+                              int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch, int dither)
+{
+    if (dither != HDRTV_DITHER_NONE && dither != HDRTV_DITHER_ORDERED) return fail(c, HDRTV_EINVAL, "rgb48_to_ycbcr10_ex: unknown dither %d", dither);
+    if (dither == HDRTV_DITHER_NONE) return hdrtv_rgb48_to_ycbcr10(c, stream, src, H, W, fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch);
+    Ycbcr10Params p;
+    if (int rc = ycbcr10_args(c, "rgb48_to_ycbcr10_ex", src, H, W, fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch, p)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return launched(c, "rgb48_to_ycbcr10_ex", rgb48_to_ycbcr10_dither_launch(p, (hipStream_t)stream));
+}
+
+// ------------------------------------------------------------------- debanding of RGB48 codes
+int hdrtv_rgb48_deband(hdrtv_ctx *c, void *stream, const uint16_t *src, int H, int W, int range, int threshold, uint32_t seed, uint16_t *dst)
+{
+    if (!c || !src || !dst || H < 1 || W < 1) return fail(c, HDRTV_EINVAL, "rgb48_deband: bad argument");
+    if (range < 1 || range > DB_HALO) return fail(c, HDRTV_EINVAL, "rgb48_deband: range %d outside 1 .. %d", range, DB_HALO);
+    if (threshold < 1 || threshold > 65535) return fail(c, HDRTV_EINVAL, "rgb48_deband: threshold %d outside 1 .. 65535", threshold);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(src), b = reinterpret_cast<uintptr_t>(dst);
+    const uintptr_t n = (uintptr_t)H * (uintptr_t)W * 6;
+    if (a < b + n && b < a + n) return fail(c, HDRTV_EINVAL, "rgb48_deband: src and dst overlap (the rule gathers: never in place)");
+    HIPCHK(c, hipSetDevice(c->device));
+    return launched(c, "rgb48_deband", rgb48_deband_launch(DebandParams{src, dst, H, W, range, threshold, seed}, (hipStream_t)stream));
+}
+
 int64_t hdrtv_ycbcr10_bytes(int fmt, int H, int W)
 {
     if (H <= 0 || W <= 0 || (W & 1)) return HDRTV_EINVAL;

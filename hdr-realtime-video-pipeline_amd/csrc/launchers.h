@@ -150,6 +150,11 @@ hipError_t post_scale_launch(const PostScaleParams &p, int is_f32, int pq, hipSt
 // fmt 0 P010 | 1 yuv420p10 | 2 yuv422p10, siting 0 left | 1 top-left (4:2:0 only); W even, H even for 4:2:0; pq != 0 needs p.pq_bnd
 hipError_t post_ycbcr10_launch(const Ycbcr10Params &p, int is_f32, int pq, hipStream_t s);
 hipError_t rgb48_to_ycbcr10_launch(const Ycbcr10Params &p, hipStream_t s);
+// the same two with the ordered dither of include/hdrtv_mi355x.h (post_ycbcr_dither.hip)
+hipError_t post_ycbcr10_dither_launch(const Ycbcr10Params &p, int is_f32, int pq, hipStream_t s);
+hipError_t rgb48_to_ycbcr10_dither_launch(const Ycbcr10Params &p, hipStream_t s);
+// hipErrorInvalidValue, nothing enqueued, unless H, W >= 1, range in 1 .. DB_HALO, threshold in 1 .. 65535 and src != dst
+hipError_t rgb48_deband_launch(const DebandParams &p, hipStream_t s);
 // zero the record on `s`, then one kernel over the rectangle on at most max_wgs workgroups (the record does not depend on the grid);
 // hipErrorInvalidValue, nothing enqueued, unless the rectangle lies in the frame and p.stats is 8-byte aligned; pq != 0 needs p.pq_bnd
 hipError_t light_stats_launch(const LightStatsParams &p, int is_f32, int pq, int max_wgs, hipStream_t s);

@@ -74,6 +74,9 @@ class _Mi355xWorker:
         # compute lanes: 1 by default -- host-fed, the second lane's device-side gain (bench.py `one_lane` vs `value`) has not shown
         # through the upload / download hand-offs in this loop; init_args["lanes"] = 2 turns it on
         kw.setdefault("lanes", 1)
+        # deband / dither of the delivered frames (lib.OutputCleanup, validated by the dispatcher): a plain tuple in init_args
+        cleanup = kw.pop("cleanup", None)
+        self.cleanup = None if cleanup is None else L.OutputCleanup(*cleanup)
         torch.cuda.set_device(device_index)
         with contextlib.redirect_stdout(sys.stderr):   # a worker's banner must not land on the parent's stdout (bench.py's one JSON line)
             self.proc = HDRTVNetMI355X(model, device=f"cuda:{device_index}", warmup_passes=0, **kw)
@@ -117,7 +120,7 @@ class _Mi355xWorker:
         # the processing size is the input slot's (a 4:2:0 slot is (h*3//2, w)), the delivered size the output slot's
         h, w = (frame.shape[0], frame.shape[1]) if frame.ndim == 3 else (frame.shape[0] * 2 // 3, frame.shape[1])
         fmt = self.output_format
-        out_fmt = dict(out_hw=(fmt.h, fmt.w), out_pix_fmt=fmt.pix_fmt, out_siting=fmt.siting)
+        out_fmt = dict(out_hw=(fmt.h, fmt.w), out_pix_fmt=fmt.pix_fmt, out_siting=fmt.siting, cleanup=self.cleanup)
         self._buffers(h, w, tuple(frame.shape), fmt)
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
@@ -347,7 +350,8 @@ def _in_shape(h, w, pix_fmt):
 class FrameDispatcher:
     def __init__(self, n_workers, height, width, sink, make_worker=mi355x_worker, init_args=None, devices=None, slots=3,
                  start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False, out_height=None,
-                 out_width=None, out_pix_fmt="rgb48le", out_siting="left"):
+                 out_width=None, out_pix_fmt="rgb48le", out_siting="left", deband=False, deband_range=16, deband_threshold=1311,
+                 dither="none"):
         """``sink(index, rgb48_view)`` is called in index order from the reorder thread; the view is only valid during the
         call (the slot goes back to its worker afterwards).  ``numa``: workers pin themselves to their GPU's NUMA node
         (False: report only).  ``pix_fmt``: ``bgr24`` input frames are u8 (H, W, 3); ``yuv420p`` / ``nv12`` frames are u8
@@ -358,7 +362,10 @@ class FrameDispatcher:
         its RGB48 conversion (``enqueue_frame(..., out_hw=)``), stand-in workers fill slots of that size.  ``out_pix_fmt``
         ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` (``out_siting`` ``left`` / ``topleft``): the product's worker delivers 10-bit
         Y'CbCr (``enqueue_frame(..., out_pix_fmt=)``); the output slots and the sink's views are then 1-D u16 arrays of
-        ``hdrtv_ycbcr10_bytes`` bytes, the planes back to back -- half the slot bytes and D2H copy of RGB48 for 4:2:0."""
+        ``hdrtv_ycbcr10_bytes`` bytes, the planes back to back -- half the slot bytes and D2H copy of RGB48 for 4:2:0.
+        ``deband`` / ``deband_range`` / ``deband_threshold`` / ``dither``: the output cleanup of ``lib.output_cleanup``
+        (INTEGRATION.md 5f); when one is on, the tuple travels to the workers as ``init_args["cleanup"]`` and the product's worker
+        hands it to ``enqueue_frame(..., cleanup=)``.  Slot sizes do not depend on it."""
         if n_workers < 1 or slots < 2:
             raise ValueError("n_workers >= 1 and slots >= 2")
         if pix_fmt not in ("bgr24", "yuv420p", "nv12"):
@@ -374,6 +381,10 @@ class FrameDispatcher:
         from . import lib as _L
         out = _L.output_format(out_pix_fmt, out_siting, self.out_h, self.out_w)    # raises for an odd size of a Y'CbCr layout
         self.out_pix_fmt, self.out_siting, self._out_shape = out.pix_fmt, out.siting, out.shape
+        self.cleanup = _L.output_cleanup(deband, deband_range, deband_threshold, dither, pix_fmt=out.pix_fmt)
+        init_args = dict(init_args or {})
+        if self.cleanup.active:
+            init_args["cleanup"] = tuple(self.cleanup)
         self.pix_fmt = pix_fmt
         self._in_shape = _in_shape(self.h, self.w, pix_fmt)
         fmt = (pix_fmt, int(yuv_matrix), bool(yuv_full_range))

@@ -21,6 +21,8 @@ PREC_F16, PREC_F32 = 0, 1
 YUV_I420, YUV_NV12 = 0, 1                  # hdrtv_yuv420_to_bgr_u8 / hdrtv_preprocess_yuv420 layouts
 YCC_P010, YCC_YUV420P10, YCC_YUV422P10 = 0, 1, 2   # hdrtv_post_ycbcr10 / hdrtv_rgb48_to_ycbcr10 layouts
 SITING_LEFT, SITING_TOPLEFT = 0, 1
+DITHER_NONE, DITHER_ORDERED = 0, 1         # hdrtv_post_ycbcr10_ex / hdrtv_rgb48_to_ycbcr10_ex
+DEBAND_RANGE_MAX, DEBAND_RANGE, DEBAND_THRESHOLD = 16, 16, 1311     # hdrtv_rgb48_deband: the largest range and the defaults
 LIGHT_BINS, LIGHT_WORDS = 4096, 4104       # hdrtv_light_stats / hdrtv_rgb48_light_stats: the record, u32 words (lightlevel.py reads it)
 
 # every symbol include/hdrtv_mi355x.h declares: (name, restype, argtypes)
@@ -46,6 +48,9 @@ SYMBOLS = [
     ("hdrtv_post_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_rgb48_to_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_ycbcr10_bytes", C.c_int64, [_I, _I, _I]),
+    ("hdrtv_rgb48_deband", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_uint32, _VP]),
+    ("hdrtv_post_ycbcr10_ex", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I, _I]),
+    ("hdrtv_rgb48_to_ycbcr10_ex", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I, _I]),
     ("hdrtv_light_stats", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _I, _I, _VP]),
     ("hdrtv_rgb48_light_stats", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     ("hdrtv_letterbox_u8", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I]),
@@ -146,6 +151,52 @@ def out_frame_bytes(pix_fmt, h, w):
 def ycbcr10_planes(ptr, h, w, pix_fmt, siting="left"):
     """``OutputFormat.planes`` of a ``pix_fmt`` / ``siting`` frame of ``h`` x ``w`` at device address ``ptr``."""
     return output_format(pix_fmt, siting, h, w).planes(ptr)
+
+
+DITHERS = {"none": DITHER_NONE, "ordered": DITHER_ORDERED}
+
+
+class OutputCleanup(NamedTuple):
+    """The picture-quality steps of the output stage, off by default: debanding of the RGB48 codes
+    (``hdrtv_rgb48_deband`` with ``deband_range`` / ``deband_threshold``) and the dither of the 10-bit Y'CbCr conversion (``"none"``
+    or ``"ordered"``).  Built by ``output_cleanup`` (which validates); it travels beside ``OutputFormat``, a plain tuple that
+    crosses into the dispatcher's worker processes as it is."""
+    deband: bool
+    deband_range: int
+    deband_threshold: int
+    dither: str
+
+    @property
+    def active(self):
+        return self.deband or self.dither != "none"
+
+    @property
+    def dither_code(self):
+        return DITHERS[self.dither]
+
+
+def _int_in(name, v, lo, hi):
+    if isinstance(v, bool) or not hasattr(v, "__index__"):          # an integer type (numpy's included), not a float or a string
+        raise ValueError(f"{name} must be an integer in {lo} .. {hi} (got {v!r})")
+    v = int(v)
+    if not lo <= v <= hi:
+        raise ValueError(f"{name} must be in {lo} .. {hi} (got {v})")
+    return v
+
+
+def output_cleanup(deband=False, deband_range=DEBAND_RANGE, deband_threshold=DEBAND_THRESHOLD, dither="none", pix_fmt=None):
+    """The one constructor of ``OutputCleanup``: ``deband_range`` 1 .. 16 pixels, ``deband_threshold`` 1 .. 65535 u16 code units,
+    ``dither`` ``"none"`` or ``"ordered"``.  ``pix_fmt`` (when given): the output format the cleanup goes with -- 16-bit codes are
+    not dithered, so ``"ordered"`` with ``rgb48le`` is refused."""
+    if not isinstance(deband, (bool, int)) or deband not in (0, 1):
+        raise ValueError(f"deband must be True or False (got {deband!r})")
+    dither = str(dither).lower() if isinstance(dither, str) else dither
+    if dither not in DITHERS:
+        raise ValueError(f"dither must be one of {sorted(DITHERS)} (got {dither!r})")
+    if pix_fmt is not None and dither != "none" and str(pix_fmt).lower() == "rgb48le":
+        raise ValueError("dither applies to the 10-bit Y'CbCr formats: rgb48le (16-bit codes) is not dithered")
+    return OutputCleanup(bool(deband), _int_in("deband_range", deband_range, 1, DEBAND_RANGE_MAX),
+                         _int_in("deband_threshold", deband_threshold, 1, 65535), dither)
 
 
 _libs = {}

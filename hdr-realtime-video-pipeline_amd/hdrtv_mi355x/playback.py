@@ -562,12 +562,10 @@ class RealtimePlayback:
             self._csv.log(m)
 
 
-def main(argv=None):
-    """``python -m hdrtv_mi355x.playback``: synthetic (or bgr24 / yuv420p / nv12 rawvideo) source -> worker -> rgb48le sink."""
+def parse_args(argv=None):
+    """The command line of ``main`` -> the argparse namespace, checked (a bad value ends in ``ap.error``): ``.proc_wh`` and ``.out_wh``
+    hold the two sizes as ``(w, h)``, ``.cleanup`` the ``lib.OutputCleanup`` of --deband / --dither."""
     import argparse
-    import json
-
-    from .worker import HeadlessPipelineWorker
 
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("--weights-dir", required=True, help="directory holding original/HR.pt (or .hdrw) [and original/HG.pt]")
@@ -590,6 +588,13 @@ def main(argv=None):
                     "device (hdrtv_light_stats): the result line gains max_cll / max_fall / light_frames")
     ap.add_argument("--light-level-json", metavar="PATH", help="also write MaxCLL / MaxFALL and the max-cll= string for the encoder "
                     "to PATH (implies --light-level)")
+    ap.add_argument("--deband", action="store_true", help="deband the RGB48 codes of the delivered frames on the device "
+                    "(hdrtv_rgb48_deband; INTEGRATION.md 5f)")
+    ap.add_argument("--deband-range", type=int, default=_lib.DEBAND_RANGE, help="reach of the deband references in pixels, 1 .. 16")
+    ap.add_argument("--deband-threshold", type=int, default=_lib.DEBAND_THRESHOLD, help="largest difference a deband reference may "
+                    "have, in u16 code units, 1 .. 65535 (1311 = 2 %% of the range)")
+    ap.add_argument("--dither", choices=sorted(_lib.DITHERS), default="none", help="dither of the 16 -> 10 bit rounding of a Y'CbCr "
+                    "--out-pix-fmt: ordered = a 16x16 Bayer threshold (hdrtv_post_ycbcr10_ex); not for rgb48le")
     ap.add_argument("--no-hg", action="store_true")
     ap.add_argument("--hg-weights", default=None, help="HG weight file, or seeded:<n>")
     ap.add_argument("--max-throughput", action="store_true", help="do not pace to the source clock")
@@ -601,17 +606,35 @@ def main(argv=None):
     owd, oht = (int(v) for v in a.out_size.lower().split("x", 1)) if a.out_size else (wd, ht)
     if owd < wd or oht < ht:
         ap.error(f"--out-size {owd}x{oht} is below --size {wd}x{ht}: the output stage only enlarges")
+    if not a.input and a.pix_fmt != "bgr24":
+        ap.error("--pix-fmt applies to an --input file")
+    try:
+        a.cleanup = _lib.output_cleanup(a.deband, a.deband_range, a.deband_threshold, a.dither, pix_fmt=a.out_pix_fmt)
+    except ValueError as exc:
+        ap.error(str(exc))
+    a.proc_wh, a.out_wh = (wd, ht), (owd, oht)
+    return a
+
+
+def main(argv=None):
+    """``python -m hdrtv_mi355x.playback``: synthetic (or bgr24 / yuv420p / nv12 rawvideo) source -> worker -> rgb48le sink."""
+    import json
+
+    from .worker import HeadlessPipelineWorker
+
+    a = parse_args(argv)
+    (wd, ht), (owd, oht) = a.proc_wh, a.out_wh
     if a.input:
         src = RawVideoSource(a.input, wd, ht, a.fps, pix_fmt=a.pix_fmt, yuv_matrix=a.yuv_matrix, yuv_full_range=a.yuv_range == "full")
-    elif a.pix_fmt != "bgr24":
-        ap.error("--pix-fmt applies to an --input file")
     else:
         src = SyntheticSource(wd, ht, a.fps, a.frames)
     if not a.no_prefetch:
         src = PinnedPrefetch(src)
     worker = HeadlessPipelineWorker(a.weights_dir, use_hg=not a.no_hg, proc_w=wd, proc_h=ht, hg_weights=a.hg_weights,
                                     status_cb=lambda m: print(m, flush=True), out_w=owd, out_h=oht, out_pix_fmt=a.out_pix_fmt,
-                                    out_siting=a.out_siting, light_stats=bool(a.light_level or a.light_level_json))
+                                    out_siting=a.out_siting, light_stats=bool(a.light_level or a.light_level_json),
+                                    deband=a.cleanup.deband, deband_range=a.cleanup.deband_range,
+                                    deband_threshold=a.cleanup.deband_threshold, dither=a.cleanup.dither)
     if not worker._load_model(a.precision):
         return 1
     sink = None
@@ -635,6 +658,8 @@ def main(argv=None):
         res["out_res"] = f"{owd}x{oht}"
     if a.out_pix_fmt != "rgb48le":
         res["out_pix_fmt"] = a.out_pix_fmt
+    if a.cleanup.active:
+        res["deband"], res["dither"] = a.cleanup.deband, a.cleanup.dither
     if cll is not None:
         res["max_cll"], res["max_fall"], res["light_frames"] = cll.max_cll, cll.max_fall, cll.frames
         if a.light_level_json:

@@ -334,7 +334,14 @@ class HDRTVNetMI355X:
         ``_ensure_buffers``)."""
         return self._lane_streams[lane]
 
-    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None):
+    def _scratch(self, key, out):
+        """The RGB48 scratch at the output size kept per ``key``."""
+        scratch = self._ycc_scratch.get(key)
+        if scratch is None or tuple(scratch.shape) != (out.h, out.w, 3):
+            scratch = self._ycc_scratch[key] = torch.empty((out.h, out.w, 3), dtype=torch.uint16, device=self.device)
+        return scratch.data_ptr()
+
+    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None):
         """The output conversion of a frame whose planar tensor lies at ``src_ptr``, to the ``lib.OutputFormat`` ``out`` at
         ``dst_ptr``: ``rgb48le`` at the processing size (``hdrtv_post_rgb48``) or enlarged to ``out.h`` x ``out.w``
         (``hdrtv_post_rgb48_scaled``); a 10-bit Y'CbCr layout in one kernel at the processing size (``hdrtv_post_ycbcr10``), or,
@@ -342,28 +349,46 @@ class HDRTVNetMI355X:
         ``hdrtv_rgb48_to_ycbcr10``).  ``light_ptr``: device address of a ``lib.LIGHT_WORDS`` u32 record that receives the
         delivered frame's content light level over ``light_rect = (x0, y0, rw, rh)`` in delivered-frame
         coordinates (default: the whole frame): ``hdrtv_light_stats`` on the tensor for an unscaled frame, ``hdrtv_rgb48_light_stats``
-        on the scaled frame's RGB48 codes (the destination, or the Y'CbCr scratch) otherwise.  None: nothing more is launched."""
+        on the scaled frame's RGB48 codes (the destination, or the Y'CbCr scratch) otherwise.  None: nothing more is launched.
+        ``cleanup``: a ``lib.OutputCleanup`` (None or inactive: the launches above, nothing more allocated).
+        Deband: tensor -> ``hdrtv_post_rgb48`` / ``hdrtv_post_rgb48_scaled`` into a scratch -> ``hdrtv_rgb48_deband`` -> ``dst``
+        (``rgb48le``), or into a second scratch and through the conversion from codes; the light level record is then taken from
+        the debanded codes, which are what is delivered.  Dither alone: ``hdrtv_post_ycbcr10_ex`` at the processing size, the
+        ``_ex`` conversion behind the scaled codes otherwise; it does not enter the record, which is defined on RGB48 codes."""
         scaled = (out.h, out.w) != (h, w)
         rect = (0, 0, out.w, out.h) if light_rect is None else tuple(int(v) for v in light_rect)
-        if light_ptr is not None and not scaled:
+        active = cleanup is not None and cleanup.active
+        deband, dither = active and cleanup.deband, active and cleanup.dither != "none"
+        if dither and out.is_rgb48:
+            raise ValueError("dither applies to the 10-bit Y'CbCr formats: rgb48le (16-bit codes) is not dithered")
+        codes = scaled or deband                     # the frame passes through RGB48 codes in device memory
+        if light_ptr is not None and not codes:
             self._chk(self._lib.hdrtv_light_stats(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *rect, light_ptr), "hdrtv_light_stats")
-        if not out.is_rgb48 and not scaled:
-            self._chk(self._lib.hdrtv_post_ycbcr10(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *out.planes(dst_ptr)), "hdrtv_post_ycbcr10")
+        if not out.is_rgb48 and not codes:
+            if dither:
+                self._chk(self._lib.hdrtv_post_ycbcr10_ex(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *out.planes(dst_ptr), cleanup.dither_code),
+                          "hdrtv_post_ycbcr10_ex")
+            else:
+                self._chk(self._lib.hdrtv_post_ycbcr10(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *out.planes(dst_ptr)), "hdrtv_post_ycbcr10")
             return
-        rgb_ptr = dst_ptr
-        if not out.is_rgb48:
-            scratch = self._ycc_scratch.get(scratch_key)
-            if scratch is None or tuple(scratch.shape) != (out.h, out.w, 3):
-                scratch = self._ycc_scratch[scratch_key] = torch.empty((out.h, out.w, 3), dtype=torch.uint16, device=self.device)
-            rgb_ptr = scratch.data_ptr()
+        rgb_ptr = dst_ptr if out.is_rgb48 else self._scratch(scratch_key, out)
+        raw_ptr = self._scratch((scratch_key, "raw"), out) if deband else rgb_ptr       # deband never works in place
         if scaled:
-            self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, rgb_ptr, out.h, out.w),
+            self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w),
                       "hdrtv_post_rgb48_scaled")
-            if light_ptr is not None:
-                self._chk(self._lib.hdrtv_rgb48_light_stats(self._ctx, st, rgb_ptr, out.h, out.w, *rect, light_ptr), "hdrtv_rgb48_light_stats")
         else:
-            self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, src_ptr, dt, h, w, rgb_ptr), "hdrtv_post_rgb48")
-        if not out.is_rgb48:
+            self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, src_ptr, dt, h, w, raw_ptr), "hdrtv_post_rgb48")
+        if deband:
+            self._chk(self._lib.hdrtv_rgb48_deband(self._ctx, st, raw_ptr, out.h, out.w, cleanup.deband_range, cleanup.deband_threshold, 0,
+                                                   rgb_ptr), "hdrtv_rgb48_deband")
+        if light_ptr is not None and codes:
+            self._chk(self._lib.hdrtv_rgb48_light_stats(self._ctx, st, rgb_ptr, out.h, out.w, *rect, light_ptr), "hdrtv_rgb48_light_stats")
+        if out.is_rgb48:
+            return
+        if dither:
+            self._chk(self._lib.hdrtv_rgb48_to_ycbcr10_ex(self._ctx, st, rgb_ptr, out.h, out.w, *out.planes(dst_ptr), cleanup.dither_code),
+                      "hdrtv_rgb48_to_ycbcr10_ex")
+        else:
             self._chk(self._lib.hdrtv_rgb48_to_ycbcr10(self._ctx, st, rgb_ptr, out.h, out.w, *out.planes(dst_ptr)), "hdrtv_rgb48_to_ycbcr10")
 
     def light_stats(self, tensor, rect=None):
@@ -385,7 +410,16 @@ class HDRTVNetMI355X:
             raise ValueError(f"lane {lane} of {self._lanes}")
         return _L.output_format(out_pix_fmt, out_siting, *((h, w) if out_hw is None else out_hw))
 
-    def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out, light_ptr=None, light_rect=None):
+    @staticmethod
+    def _cleanup_for(cleanup, out):
+        """The ``cleanup`` argument of ``enqueue_frame*`` checked against the frame's format -> a ``lib.OutputCleanup`` or None."""
+        if cleanup is None:
+            return None
+        if not isinstance(cleanup, _L.OutputCleanup):
+            raise ValueError("cleanup must be a lib.OutputCleanup (lib.output_cleanup builds one) or None")
+        return _L.output_cleanup(*cleanup, pix_fmt=out.pix_fmt)
+
+    def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out, light_ptr=None, light_rect=None, cleanup=None):
         """The body of ``enqueue_frame*``: the preprocess entry point ``pre`` (named ``what``) on its source arguments ``src``,
         ``hdrtv_infer_lane`` and ``_post_out``, all on the lane's buffers and ``stream`` (default: the lane's own)."""
         self._ensure_buffers(h, w)
@@ -394,10 +428,10 @@ class HDRTVNetMI355X:
         self._chk(pre(self._ctx, st, *src, h, w, tin.data_ptr(), tcond.data_ptr()), what)
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), self._out_dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect)
+        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup)
 
     def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le",
-                      out_siting="left", light_ptr=None, light_rect=None):
+                      out_siting="left", light_ptr=None, light_rect=None, cleanup=None):
         """One frame of the hot path on lane ``lane``, stream-ordered and without any host synchronisation: u8 BGR frame in
         device memory at ``src_bgr_ptr`` -> hdrtv_preprocess -> hdrtv_infer_lane -> hdrtv_post_rgb48 -> u16 RGB48 at the device
         address ``dst_rgb48_ptr``.  ``stream``: a ``torch.cuda.Stream`` (default: the lane's own).  Frames enqueued on different
@@ -407,19 +441,21 @@ class HDRTVNetMI355X:
         ``out_pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` (``out_siting`` ``left`` / ``topleft``): ``dst`` receives the
         10-bit Y'CbCr planes back to back instead (``lib.out_frame_bytes`` bytes) -- ``hdrtv_post_ycbcr10`` at
         the processing size, with ``out_hw`` two launches through a per-lane RGB48 scratch.  ``light_ptr`` / ``light_rect``: the
-        delivered frame's content light level record, behind the frame on the same stream (``_post_out``)."""
+        delivered frame's content light level record, behind the frame on the same stream (``_post_out``).
+        ``cleanup``: a ``lib.OutputCleanup`` (``lib.output_cleanup``): deband and / or ordered dither of the delivered frame
+        (``_post_out``); None: neither, and the bytes of before."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         self._enqueue(lane, self._lib.hdrtv_preprocess, "hdrtv_preprocess", (src_bgr_ptr,), h, w, dst_rgb48_ptr, stream, out,
-                      light_ptr, light_rect)
+                      light_ptr, light_rect, self._cleanup_for(cleanup, out))
 
     def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None,
-                             out_hw=None, out_pix_fmt="rgb48le", out_siting="left", light_ptr=None, light_rect=None):
+                             out_hw=None, out_pix_fmt="rgb48le", out_siting="left", light_ptr=None, light_rect=None, cleanup=None):
         """``enqueue_frame`` of an 8-bit 4:2:0 frame: the planes lie back to back at the device address ``src_ptr`` (the
         ``(h*3//2, w)`` u8 array ``preprocess_yuv420`` takes) and ``hdrtv_preprocess_yuv420`` replaces ``hdrtv_preprocess``."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         planes = _yuv_planes(src_ptr, int(h), int(w), layout, matrix, full_range)
         self._enqueue(lane, self._lib.hdrtv_preprocess_yuv420, "hdrtv_preprocess_yuv420", planes, h, w, dst_rgb48_ptr, stream, out,
-                      light_ptr, light_rect)
+                      light_ptr, light_rect, self._cleanup_for(cleanup, out))
 
     def _upload(self, key, src, staged=None):
         """Device pointer of the host u8 array ``src``, uploaded through the staging slot kept per ``key`` in ``_staging``: a
@@ -641,25 +677,46 @@ class HDRTVNetMI355X:
         return dst
 
     @torch.inference_mode()
-    def postprocess_ycbcr10(self, output, pix_fmt="p010le", siting="left", pq=False, peak_nits=1000.0):
+    def postprocess_deband(self, rgb48, deband_range=_L.DEBAND_RANGE, deband_threshold=_L.DEBAND_THRESHOLD, seed=0):
+        """Debanded RGB48 codes: ``hdrtv_rgb48_deband`` on a device u16 ``(H, W, 3)`` tensor of codes (what
+        ``hdrtv_post_rgb48`` / ``postprocess_rgb48_scaled`` write).  Returns a new device tensor of the same shape; the source is
+        not touched.  Stream-ordered on the current stream, no synchronisation."""
+        if not isinstance(rgb48, torch.Tensor) or rgb48.dtype != torch.uint16 or rgb48.ndim != 3 or rgb48.shape[2] != 3 or not rgb48.is_cuda:
+            raise ValueError("postprocess_deband expects a device uint16 (H, W, 3) tensor of RGB48 codes")
+        if rgb48.shape[0] < 1 or rgb48.shape[1] < 1:
+            raise ValueError("postprocess_deband expects a non-empty frame")
+        c = _L.output_cleanup(True, deband_range, deband_threshold)
+        seed = int(seed)
+        if not 0 <= seed <= 0xFFFFFFFF:
+            raise ValueError("seed must be a u32")
+        src = rgb48.contiguous()
+        dst = torch.empty_like(src)
+        self._chk(self._lib.hdrtv_rgb48_deband(self._ctx, self._stream(), src.data_ptr(), int(src.shape[0]), int(src.shape[1]),
+                                               c.deband_range, c.deband_threshold, seed, dst.data_ptr()), "hdrtv_rgb48_deband")
+        return dst
+
+    @torch.inference_mode()
+    def postprocess_ycbcr10(self, output, pix_fmt="p010le", siting="left", pq=False, peak_nits=1000.0, dither="none"):
         """10-bit limited-range BT.2020nc Y'CbCr for an encoder: ``hdrtv_post_ycbcr10`` converts the u16 codes
         of ``hdrtv_post_rgb48`` (``pq=True``: of ``hdrtv_post_pq_rgb48`` at ``peak_nits``) in one kernel, without an RGB48
         intermediate.  ``pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le``; ``siting`` of 4:2:0 chroma ``left`` (MPEG-2 /
         H.264, ffmpeg's default) or ``topleft`` (BT.2100 / HDR10).  Returns a new contiguous 1-D device u16 tensor, the planes back
-        to back (``lib.out_frame_bytes`` bytes); stream-ordered on the current stream, no synchronisation."""
+        to back (``lib.out_frame_bytes`` bytes); stream-ordered on the current stream, no synchronisation.  ``dither="ordered"``:
+        the ordered dither of INTEGRATION.md 5f (``hdrtv_post_ycbcr10_ex``); ``"none"``: the bytes of before."""
         if isinstance(output, (tuple, list)):
             output = output[0]
         if output.dtype not in (torch.float16, torch.float32):
             raise ValueError("postprocess_ycbcr10 expects an fp16 or fp32 tensor")
+        dither = _L.output_cleanup(dither=dither).dither_code
         out = _L.output_format(pix_fmt, siting, int(output.shape[-2]), int(output.shape[-1]))
         if out.is_rgb48:
             raise ValueError("postprocess_ycbcr10 writes p010le, yuv420p10le or yuv422p10le")
         output = output.contiguous()
         dst = torch.empty(out.shape, dtype=torch.uint16, device=self.device)
-        self._chk(self._lib.hdrtv_post_ycbcr10(self._ctx, self._stream(), output.data_ptr(),
-                                               _dtype_code(output), out.h, out.w, 1 if pq else 0,
-                                               float(peak_nits), *out.planes(dst.data_ptr())),
-                  "hdrtv_post_ycbcr10")
+        self._chk(self._lib.hdrtv_post_ycbcr10_ex(self._ctx, self._stream(), output.data_ptr(),
+                                                  _dtype_code(output), out.h, out.w, 1 if pq else 0,
+                                                  float(peak_nits), *out.planes(dst.data_ptr()), dither),
+                  "hdrtv_post_ycbcr10_ex")
         return dst
 
     @torch.inference_mode()

@@ -121,7 +121,8 @@ class HostFrame:
 class HeadlessPipelineWorker:
     def __init__(self, weights_dir, use_hg=True, proc_w=1920, proc_h=1080, hg_weights=None,
                  status_cb=None, buffer_frames=1, out_w=None, out_h=None, out_pix_fmt="rgb48le", out_siting="left",
-                 light_stats=False, light_rect=None):
+                 light_stats=False, light_rect=None, deband=False, deband_range=_L.DEBAND_RANGE,
+                 deband_threshold=_L.DEBAND_THRESHOLD, dither="none"):
         self._weights_dir = weights_dir
         self._use_hg = bool(use_hg)
         self._hg_override = hg_weights
@@ -132,6 +133,9 @@ class HeadlessPipelineWorker:
         # what the sink receives, one lib.OutputFormat: "rgb48le", or 10-bit Y'CbCr ("p010le", "yuv420p10le",
         # "yuv422p10le") with the 4:2:0 chroma siting "left" / "topleft"; then a frame is a 1-D u16 view of its planes, back to back
         self._out = _L.output_format(out_pix_fmt, out_siting, self._out_h or self._proc_h, self._out_w or self._proc_w)
+        # deband / ordered dither of the delivered frames, one lib.OutputCleanup; off: nothing more is launched
+        # or allocated and the bytes are those of before.  With light_stats the record describes the debanded codes.
+        self._cleanup = _L.output_cleanup(deband, deband_range, deband_threshold, dither, pix_fmt=self._out.pix_fmt)
         # HDR10 content light level: every delivered frame carries its record (``.light``), measured on the
         # device from the codes the sink receives over ``light_rect = (x0, y0, rw, rh)`` in delivered-frame coordinates (None: the
         # whole frame), and ``content_light`` accumulates MaxCLL / MaxFALL in delivery order.  Off: nothing is launched or allocated.
@@ -346,13 +350,14 @@ class HeadlessPipelineWorker:
             """The frame into ``dst`` and, when measured, its light level record into the pinned record kept per ``key``, all on
             ``st``: whatever is recorded on ``st`` afterwards (the slot's ready event) covers both.  Returns that record."""
             if not self._light:
-                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker")
+                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup)
                 return None
             bufs = self._light_bufs.get(key)
             if bufs is None:
                 bufs = self._light_bufs[key] = (torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, device=p.device),
                                                 torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, pin_memory=True))
-            p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", bufs[0].data_ptr(), self._light_rect)
+            p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", bufs[0].data_ptr(), self._light_rect,
+                        self._cleanup)
             with torch.cuda.stream(st):
                 bufs[1].copy_(bufs[0], non_blocking=True)
             return bufs[1].numpy()

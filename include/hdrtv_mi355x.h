@@ -186,8 +186,8 @@ int hdrtv_post_rgb48_scaled(hdrtv_ctx *ctx, void *stream, const void *dev_out, i
  * hdrtv_post_ycbcr10 goes from the model's planar tensor to the planes in one kernel, without an RGB48 intermediate.
  * hdrtv_rgb48_to_ycbcr10 applies the same rule to RGB48 codes already in device memory ([H][W][3]): a scaled frame becomes Y'CbCr in
  * two launches, hdrtv_post_rgb48_scaled and this one.  hdrtv_ycbcr10_bytes: the bytes of a frame with its planes back to back at their
- * minimum pitches (3 H W, 4:2:2: 4 H W), or a negative value for a bad argument.  Out of scope: dithering (the reference's
- * dither=error_diffusion is sequential), full range, 12 bits, 4:4:4, bitstream / SEI writing (hdrtv_light_stats measures the content light level an HDR10 SEI carries), and fusing the Lanczos pass with the conversion.
+ * minimum pitches (3 H W, 4:2:2: 4 H W), or a negative value for a bad argument.  Out of scope: error-diffusion dithering (sequential; the
+ * ordered dither of the _ex entry points below takes its place), full range, 12 bits, 4:4:4, bitstream / SEI writing (hdrtv_light_stats measures the content light level an HDR10 SEI carries), and fusing the Lanczos pass with the conversion.
  * Stream-ordered, no reservation needed.  HDRTV_EINVAL, with dst untouched, for a NULL pointer, a non-positive size, an odd W, an odd H
  * with 4:2:0, a short or odd pitch, an unknown fmt, siting or dtype, P010 with a non-NULL dst_v, a siting other than LEFT with 4:2:2, or
  * pq with peak_nits <= 0. */
@@ -201,6 +201,48 @@ int hdrtv_post_ycbcr10(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dt
 int hdrtv_rgb48_to_ycbcr10(hdrtv_ctx *ctx, void *stream, const uint16_t *src_rgb48, int H, int W, int fmt, int siting,
                            uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch);
 int64_t hdrtv_ycbcr10_bytes(int fmt, int H, int W);
+
+/* Output cleanup: debanding of the RGB48 codes and ordered dither of the 10-bit Y'CbCr conversion.  The reference's export never
+ * hands its encoder a bare 16 -> 10 bit rounding: its ffmpeg chain is deband, zscale=...:dither=error_diffusion, format=yuv422p10le
+ * (gui_export.py:948-962), on the CPU.  Error diffusion is sequential; zscale's dither=ordered and a debanding gather are per-pixel
+ * integer rules.  Parity with ffmpeg's deband and zscale's ordered dither is UNPINNED (ffmpeg is not part of the reference tree);
+ * both steps are the integer rules below, restated in tests/cleanup_ref.py, which the GPU tests hold every entry point to bit for
+ * bit.  Both are off unless asked for, and each can be used alone.
+ *
+ * Deband rule (hdrtv_rgb48_deband): u16 RGB48 codes [H][W][3] in, [H][W][3] out, never in place.  range R in 1..16 (default 16),
+ * threshold T in 1..65535 u16 code units (default 1311 = rnd(0.02 * 65535), the share ffmpeg's deband defaults to), seed S any u32
+ * (default 0; the pattern is the same in every frame).  Per pixel (x, y), all arithmetic in u32 unless said otherwise:
+ *   h = S * 0x9E3779B9 + y * W + x;  h ^= h >> 16;  h *= 0x7feb352d;  h ^= h >> 15;  h *= 0x846ca68b;  h ^= h >> 16
+ *   dx = (((h & 0xffff) * (2R + 1)) >> 16) - R;  dy = (((h >> 16) * (2R + 1)) >> 16) - R      (each in [-R, R])
+ *   four reference pixels ref_0..3 at (x + dx, y + dy), (x - dx, y + dy), (x - dx, y - dy), (x + dx, y - dy), every coordinate
+ *   clamped to the frame; the three channels use the same four positions.
+ *   If |ref_k,c - src_c| < T for all four references and all three channels, every channel c becomes
+ *   (ref_0,c + ref_1,c + ref_2,c + ref_3,c + 2) >> 2; otherwise the pixel is copied unchanged (all or nothing: hue is kept).
+ * Any H, W >= 1.  HDRTV_EINVAL, with dst untouched, for a NULL pointer, H or W < 1, src == dst or overlapping buffers, a range
+ * outside 1..16 or a threshold outside 1..65535.
+ *
+ * Ordered-dither rule (hdrtv_post_ycbcr10_ex / hdrtv_rgb48_to_ycbcr10_ex, dither = HDRTV_DITHER_ORDERED): the Y'CbCr rule above with
+ * its rounding constants replaced by a 16 x 16 Bayer threshold.  M(x, y) in 0..255: with a = (x ^ y) & 15 and b = y & 15, bit i of a
+ * goes to bit 7 - 2i of M and bit i of b to bit 6 - 2i, i = 0..3 (the recursive matrix built from [[0, 2], [3, 1]]; a permutation
+ * of 0..255 over every aligned 16 x 16 block; no table).
+ *   luma:    Y = 64 + ((YR R + YG G + YB B + t) >> 20),  t = (2 M(x, y) + 1) << 11  (the mean of t over a block is exactly 2^19)
+ *   chroma:  the sums and the shift SH = 20 + log2 Wt stay; the constant Wt << 19 becomes (2 M(i, j) + 1) << (SH - 9), where (i, j)
+ *            is the sample's column and row in the chroma plane.
+ * Luma stays in [64, 940] (the largest sum is 14016 * 65535 < 876 * 2^20) and chroma in [64, 960] without a clamp, in the integer
+ * widths of the undithered rule; over an aligned 16 x 16 block of one colour the mean of Y is within 1/512 code of the unrounded
+ * value.  P010 shifts left by 6 as before.  dither = HDRTV_DITHER_NONE launches the kernels of hdrtv_post_ycbcr10 /
+ * hdrtv_rgb48_to_ycbcr10 and writes their bytes; any other value of dither is HDRTV_EINVAL, as is everything those refuse.
+ * Out of scope: error diffusion, random or blue-noise dither, temporal variation of either pattern, dithering the u8 or RGB48
+ * outputs, debanding the model's float tensor, grain synthesis, and fusing deband with the conversion or the Lanczos pass. */
+#define HDRTV_DITHER_NONE 0
+#define HDRTV_DITHER_ORDERED 1
+int hdrtv_rgb48_deband(hdrtv_ctx *ctx, void *stream, const uint16_t *src_rgb48, int H, int W, int range, int threshold,
+                       uint32_t seed, uint16_t *dst_rgb48);
+int hdrtv_post_ycbcr10_ex(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
+                          int fmt, int siting, uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch,
+                          int dither);
+int hdrtv_rgb48_to_ycbcr10_ex(hdrtv_ctx *ctx, void *stream, const uint16_t *src_rgb48, int H, int W, int fmt, int siting,
+                              uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch, int dither);
 
 /* HDR10 content light level (CTA-861.3 MaxCLL / MaxFALL; x265 max-cll=, HEVC SEI 144): the per-frame record those two numbers are
  * made from, measured on the device from exactly the codes the sink receives.  The reference has no counterpart: its export tags the
