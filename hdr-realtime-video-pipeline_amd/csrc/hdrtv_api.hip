@@ -3,6 +3,7 @@
 // (api.h).  No kernel lives in this file.
 #include "api.h"
 #include "yuv420.h"
+#include "ycbcr10_in.h"
 
 using namespace hdrtv_host;
 // =========================================================================== exported C ABI
@@ -213,6 +214,51 @@ int hdrtv_preprocess_yuv420(hdrtv_ctx *c, void *stream, const uint8_t *y, int y_
     q.chk(pre_fused_yuv_launch(src, (f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
                                q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"), c->cond_mode, s),
           "pre_fused_yuv");
+    return q.rc;
+}
+
+// The argument rule of both 10-bit input entry points (include/hdrtv_mi355x.h; ycc10_check); fills `src` on success.
+static int ycc10_args(hdrtv_ctx *c, const char *what, const uint16_t *y, int y_pitch, const uint16_t *u, const uint16_t *v, int c_pitch,
+                      int fmt, int matrix, int full_range, int H, int W, Ycc10Src *src)
+{
+    if (const char *why = ycc10_check(y, y_pitch, u, v, c_pitch, fmt, H, W)) return fail(c, HDRTV_EINVAL, "%s: %s (fmt %d, %dx%d, pitches %d / %d)", what, why, fmt, W, H, y_pitch, c_pitch);
+    Ycc10Coef k;
+    if (!ycc10_coef(matrix, full_range, &k)) return fail(c, HDRTV_EINVAL, "%s: matrix %d / range %d (601, 709, 2020; 0 or 1)", what, matrix, full_range);
+    *src = Ycc10Src{y, u, v, y_pitch, c_pitch, fmt, k};
+    return HDRTV_OK;
+}
+
+int hdrtv_ycbcr10_to_rgb10(hdrtv_ctx *c, void *stream, const uint16_t *y, int y_pitch, const uint16_t *u, const uint16_t *v, int c_pitch,
+                           int fmt, int matrix, int full_range, int H, int W, uint16_t *rgb)
+{
+    if (!c || !rgb) return fail(c, HDRTV_EINVAL, "null argument");
+    Ycc10Src src;
+    if (const int rc = ycc10_args(c, "ycbcr10_to_rgb10", y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, H, W, &src)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return launched(c, "ycbcr10_to_rgb10", ycbcr10_to_rgb10_launch(src, H, W, rgb, (hipStream_t)stream));
+}
+
+int hdrtv_preprocess_ycbcr10(hdrtv_ctx *c, void *stream, const uint16_t *y, int y_pitch, const uint16_t *u, const uint16_t *v, int c_pitch,
+                             int fmt, int matrix, int full_range, int H, int W, void *rgb, void *cond)
+{
+    if (!c || !rgb || !cond) return fail(c, HDRTV_EINVAL, "null argument");
+    Ycc10Src src;
+    if (const int rc = ycc10_args(c, "preprocess_ycbcr10", y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, H, W, &src)) return rc;
+    if (c->H != H || c->W != W || c->lane_ws.empty()) return fail(c, HDRTV_ESTATE, "call hdrtv_reserve(%d,%d) first", H, W);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    Seq q{c, s, c->lane_ws[0]};          // lane 0's resize tables, as hdrtv_preprocess
+    const Shapes sh = shapes_for(H, W);
+    if (c->fp32) {                       // two launches, as hdrtv_preprocess_yuv420
+        q.chk(pre_unpack_ycbcr10_f32_launch(src, H, W, (float *)rgb, s), "pre_unpack_ycbcr10_f32");
+        q.chk(cond_resize_f32_launch((const float *)rgb, (float *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
+                                     q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"),
+                                     c->cond_mode, s), "cond_resize_f32");
+        return q.rc;
+    }
+    q.chk(pre_fused_ycbcr10_launch(src, (f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
+                                   q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"), c->cond_mode, s),
+          "pre_fused_ycbcr10");
     return q.rc;
 }
 

@@ -118,10 +118,14 @@ class _Mi355xWorker:
     def begin(self, frame, out):
         torch, p = self._torch, self.proc
         # the processing size is the input slot's (a 4:2:0 slot is (h*3//2, w)), the delivered size the output slot's
-        h, w = (frame.shape[0], frame.shape[1]) if frame.ndim == 3 else (frame.shape[0] * 2 // 3, frame.shape[1])
+        ten = self.input_format[0] in self._L.YCBCR10_IN_FORMATS
+        if ten:
+            h, w = self._L.ycbcr10_frame_hw(frame, self.input_format[0])
+        else:
+            h, w = (frame.shape[0], frame.shape[1]) if frame.ndim == 3 else (frame.shape[0] * 2 // 3, frame.shape[1])
         fmt = self.output_format
         out_fmt = dict(out_hw=(fmt.h, fmt.w), out_pix_fmt=fmt.pix_fmt, out_siting=fmt.siting, cleanup=self.cleanup)
-        self._buffers(h, w, tuple(frame.shape), fmt)
+        self._buffers(h, w, tuple(frame.shape) + ((2,) if ten else ()), fmt)       # _raw is bytes: a u16 sample is two
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
         # frame's kernels with the next frame's (processor.enqueue_frame); one lane = the single compute stream of before
@@ -139,6 +143,10 @@ class _Mi355xWorker:
             main.wait_event(self._dn_ev[k])                    # u16[k]'s previous frame has left the device
         if self.input_format[0] == "bgr24":
             p.enqueue_frame(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), stream=main, **out_fmt)
+        elif ten:
+            pix_fmt, matrix, full = self.input_format
+            p.enqueue_frame_ycbcr10(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), pix_fmt=pix_fmt, matrix=matrix,
+                                    full_range=full, stream=main, **out_fmt)
         else:
             layout, matrix, full = self.input_format
             p.enqueue_frame_yuv420(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), layout=layout, matrix=matrix,
@@ -244,7 +252,8 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, out_format, t
         input_format = tuple(input_format or ("bgr24", 709, False))
         in_shape = _in_shape(h, w, input_format[0])
         out_shape = out_format.shape
-        in_b, out_b = int(np.prod(in_shape)), out_format.nbytes
+        in_dtype = _in_dtype(input_format[0])
+        in_b, out_b = int(np.prod(in_shape)) * np.dtype(in_dtype).itemsize, out_format.nbytes
         # placement first: affinity, then the slots (created and first-touched HERE, on the GPU's node), then the GPU
         from . import numa
         info = numa.pin_to_gpu_node(device_index, apply=bool(use_numa)) if use_numa is not None else {"device": device_index, "numa_node": -1, "cpus": [], "pinned": False}
@@ -268,7 +277,7 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, out_format, t
             body.output_format = out_format
         if hasattr(body, "pin"):
             body.pin(shm.buf)
-        ins = [np.ndarray(in_shape, np.uint8, shm.buf, offset=s * in_b) for s in range(slots)]
+        ins = [np.ndarray(in_shape, in_dtype, shm.buf, offset=s * in_b) for s in range(slots)]
         outs = [np.ndarray(out_shape, np.uint16, shm.buf, offset=slots * in_b + s * out_b) for s in range(slots)]
         depth = max(1, int(getattr(body, "depth", 1)))
         free_out = list(range(slots))
@@ -343,8 +352,18 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, out_format, t
 
 
 def _in_shape(h, w, pix_fmt):
-    """An input slot's frame: u8 BGR (h, w, 3), or the planes of a 4:2:0 frame back to back (h*3//2, w)."""
+    """An input slot's frame: u8 BGR (h, w, 3), the planes of an 8-bit 4:2:0 frame back to back (h*3//2, w), or the u16 planes of a
+    10-bit frame (``lib.ycbcr10_frame_shape``: (h*3//2, w), or (2*h, w) for yuv422p10le)."""
+    from . import lib as _L
+    if pix_fmt in _L.YCBCR10_IN_FORMATS:
+        return _L.ycbcr10_frame_shape(pix_fmt, h, w)
     return (h, w, 3) if pix_fmt == "bgr24" else (h * 3 // 2, w)
+
+
+def _in_dtype(pix_fmt):
+    """u16 samples for the 10-bit formats, bytes for the others."""
+    from . import lib as _L
+    return np.uint16 if pix_fmt in _L.YCBCR10_IN_FORMATS else np.uint8
 
 
 class FrameDispatcher:
@@ -356,8 +375,10 @@ class FrameDispatcher:
         call (the slot goes back to its worker afterwards).  ``numa``: workers pin themselves to their GPU's NUMA node
         (False: report only).  ``pix_fmt``: ``bgr24`` input frames are u8 (H, W, 3); ``yuv420p`` / ``nv12`` frames are u8
         (H*3//2, W), the planes back to back (half the slot bytes and copies), which the product's worker converts on the device
-        with ``yuv_matrix`` / ``yuv_full_range`` (``HDRTVNetMI355X.enqueue_frame_yuv420``); stand-in workers receive them as they
-        are.  Output slots, order and sink do not depend on it.  ``out_height`` / ``out_width`` (default: the processing size, not
+        with ``yuv_matrix`` / ``yuv_full_range`` (``HDRTVNetMI355X.enqueue_frame_yuv420``); ``p010le`` / ``yuv420p10le`` /
+        ``yuv422p10le`` frames are u16 (H*3//2, W), or (2*H, W) for 4:2:2 (``enqueue_frame_ycbcr10``; the processing size is the
+        frame's: 10-bit input has no letterbox); stand-in workers receive them as they are.  Output slots, order and sink do not
+        depend on it.  ``out_height`` / ``out_width`` (default: the processing size, not
         below it): the output slots and the sink's views are ``(out_height, out_width, 3)``; the product's worker upscales in
         its RGB48 conversion (``enqueue_frame(..., out_hw=)``), stand-in workers fill slots of that size.  ``out_pix_fmt``
         ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` (``out_siting`` ``left`` / ``topleft``): the product's worker delivers 10-bit
@@ -368,9 +389,10 @@ class FrameDispatcher:
         hands it to ``enqueue_frame(..., cleanup=)``.  Slot sizes do not depend on it."""
         if n_workers < 1 or slots < 2:
             raise ValueError("n_workers >= 1 and slots >= 2")
-        if pix_fmt not in ("bgr24", "yuv420p", "nv12"):
-            raise ValueError("pix_fmt must be bgr24, yuv420p or nv12")
-        if pix_fmt != "bgr24" and (int(height) % 2 or int(width) % 2):
+        from . import lib as _L
+        if pix_fmt not in ("bgr24", "yuv420p", "nv12") + tuple(_L.YCBCR10_IN_FORMATS):
+            raise ValueError(f"pix_fmt must be bgr24, yuv420p, nv12 or one of {sorted(_L.YCBCR10_IN_FORMATS)}")
+        if pix_fmt in ("yuv420p", "nv12") and (int(height) % 2 or int(width) % 2):
             raise ValueError(f"{pix_fmt} frames have even sizes")
         if int(yuv_matrix) not in (601, 709, 2020):
             raise ValueError("yuv_matrix must be 601, 709 or 2020")
@@ -378,7 +400,6 @@ class FrameDispatcher:
         self.out_h, self.out_w = int(out_height or height), int(out_width or width)
         if self.out_h < self.h or self.out_w < self.w:
             raise ValueError(f"output size {self.out_w}x{self.out_h} is below the processing size {self.w}x{self.h} (enlarging only)")
-        from . import lib as _L
         out = _L.output_format(out_pix_fmt, out_siting, self.out_h, self.out_w)    # raises for an odd size of a Y'CbCr layout
         self.out_pix_fmt, self.out_siting, self._out_shape = out.pix_fmt, out.siting, out.shape
         self.cleanup = _L.output_cleanup(deband, deband_range, deband_threshold, dither, pix_fmt=out.pix_fmt)
@@ -386,11 +407,11 @@ class FrameDispatcher:
         if self.cleanup.active:
             init_args["cleanup"] = tuple(self.cleanup)
         self.pix_fmt = pix_fmt
-        self._in_shape = _in_shape(self.h, self.w, pix_fmt)
+        self._in_shape, self._in_dtype = _in_shape(self.h, self.w, pix_fmt), _in_dtype(pix_fmt)     # raises for an odd 10-bit size
         fmt = (pix_fmt, int(yuv_matrix), bool(yuv_full_range))
         self._sink = sink
         ctx = mp.get_context("spawn")           # fresh interpreters: nothing GPU-related is inherited
-        self._in_b, self._out_b = int(np.prod(self._in_shape)), out.nbytes
+        self._in_b, self._out_b = int(np.prod(self._in_shape)) * np.dtype(self._in_dtype).itemsize, out.nbytes
         self._shm = [None] * self.n             # created by the workers (first touch on their GPU's node), attached below
         # ... under names chosen HERE, so that close() can unlink a segment whose worker died between creating it and saying so
         self._shm_names = [f"hdrtv_{os.getpid()}_{uuid.uuid4().hex[:12]}_{r}" for r in range(self.n)]
@@ -439,7 +460,7 @@ class FrameDispatcher:
                 self._shm[rank] = shared_memory.SharedMemory(name=name)
                 self.placement[rank] = payload
                 buf = self._shm[rank].buf
-                self._ins[rank] = [np.ndarray(self._in_shape, np.uint8, buf, offset=s * self._in_b) for s in range(self.slots)]
+                self._ins[rank] = [np.ndarray(self._in_shape, self._in_dtype, buf, offset=s * self._in_b) for s in range(self.slots)]
                 self._outs[rank] = [np.ndarray(self._out_shape, np.uint16, buf, offset=self.slots * self._in_b + s * self._out_b)
                                     for s in range(self.slots)]
                 continue

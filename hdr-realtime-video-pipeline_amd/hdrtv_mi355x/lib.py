@@ -19,7 +19,7 @@ OK, EINVAL, EWEIGHTS, EHIP, ENOMEM, ESTATE = 0, -1, -2, -3, -4, -5
 F16, F32 = 0, 1
 PREC_F16, PREC_F32 = 0, 1
 YUV_I420, YUV_NV12 = 0, 1                  # hdrtv_yuv420_to_bgr_u8 / hdrtv_preprocess_yuv420 layouts
-YCC_P010, YCC_YUV420P10, YCC_YUV422P10 = 0, 1, 2   # hdrtv_post_ycbcr10 / hdrtv_rgb48_to_ycbcr10 layouts
+YCC_P010, YCC_YUV420P10, YCC_YUV422P10 = 0, 1, 2   # hdrtv_post_ycbcr10 / hdrtv_rgb48_to_ycbcr10 / hdrtv_preprocess_ycbcr10 layouts
 SITING_LEFT, SITING_TOPLEFT = 0, 1
 DITHER_NONE, DITHER_ORDERED = 0, 1         # hdrtv_post_ycbcr10_ex / hdrtv_rgb48_to_ycbcr10_ex
 DEBAND_RANGE_MAX, DEBAND_RANGE, DEBAND_THRESHOLD = 16, 16, 1311     # hdrtv_rgb48_deband: the largest range and the defaults
@@ -56,6 +56,8 @@ SYMBOLS = [
     ("hdrtv_letterbox_u8", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I]),
     ("hdrtv_yuv420_to_bgr_u8", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     ("hdrtv_preprocess_yuv420", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP]),
+    ("hdrtv_ycbcr10_to_rgb10", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
+    ("hdrtv_preprocess_ycbcr10", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP]),
     ("hdrtv_metrics", _I, [_VP, _VP, _VP, _VP, _I, _I, _I, C.c_float, C.POINTER(C.c_double)]),
     ("hdrtv_ring_create", _I, [_VP, _I, _I, _I]),
     ("hdrtv_ring_acquire", _I, [_VP, _I, C.POINTER(_VP), C.POINTER(_VP)]),
@@ -141,6 +143,34 @@ def output_format(pix_fmt, siting, h, w):
     if pix_fmt != "rgb48le" and (h <= 0 or w <= 0 or w % 2 or (pix_fmt != "yuv422p10le" and h % 2)):
         raise ValueError(f"{pix_fmt} needs an even width{'' if pix_fmt == 'yuv422p10le' else ' and height'} (got {w}x{h})")
     return OutputFormat(pix_fmt, siting, h, w)
+
+
+YCBCR10_IN_FORMATS = dict(YCC_FORMATS)      # the 10-bit input pixel formats: the names and codes of the output side
+
+
+def ycbcr10_frame_shape(pix_fmt, h, w):
+    """The u16 array shape of an ``h`` x ``w`` 10-bit frame with its planes back to back at minimum pitch: ``(h*3//2, w)`` for
+    ``p010le`` / ``yuv420p10le``, ``(2*h, w)`` for ``yuv422p10le``.  W even; H even for the two 4:2:0 formats."""
+    if pix_fmt not in YCBCR10_IN_FORMATS:
+        raise ValueError(f"pix_fmt must be one of {sorted(YCBCR10_IN_FORMATS)}")
+    h, w = int(h), int(w)
+    c422 = pix_fmt == "yuv422p10le"
+    if h <= 0 or w <= 0 or w % 2 or (not c422 and h % 2):
+        raise ValueError(f"{pix_fmt} needs an even width{'' if c422 else ' and height'} (got {w}x{h})")
+    return (2 * h, w) if c422 else (h * 3 // 2, w)
+
+
+def ycbcr10_frame_hw(frame, pix_fmt):
+    """(H, W) of a 10-bit frame held as the u16 array of ``ycbcr10_frame_shape``."""
+    if pix_fmt not in YCBCR10_IN_FORMATS:
+        raise ValueError(f"pix_fmt must be one of {sorted(YCBCR10_IN_FORMATS)}")
+    c422 = pix_fmt == "yuv422p10le"
+    if getattr(frame, "ndim", 0) != 2 or str(frame.dtype) != "uint16" or frame.shape[0] % (2 if c422 else 3):
+        raise ValueError(f"a {pix_fmt} frame must be uint16 [{'2*H' if c422 else 'H*3//2'}, W]")
+    h, w = (frame.shape[0] // 2 if c422 else frame.shape[0] // 3 * 2), frame.shape[1]
+    if tuple(frame.shape) != ycbcr10_frame_shape(pix_fmt, h, w):
+        raise ValueError(f"a {pix_fmt} frame must be uint16 [{'2*H' if c422 else 'H*3//2'}, W]")
+    return h, w
 
 
 def out_frame_bytes(pix_fmt, h, w):

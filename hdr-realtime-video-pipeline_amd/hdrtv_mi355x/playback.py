@@ -170,10 +170,12 @@ class PinnedPrefetch:
 class RawVideoSource:
     """Headerless rawvideo file (what ``ffmpeg -f rawvideo -pix_fmt <pix_fmt>`` writes), memory-mapped.  ``pix_fmt``:
     ``bgr24`` frames are u8 ``(H, W, 3)``; ``yuv420p`` (I420) and ``nv12`` frames are u8 ``(H*3//2, W)``, the planes back to back
-    (``HDRTVNetMI355X.preprocess_yuv420``), even sizes only.  ``yuv_matrix`` (601 / 709 / 2020) and ``yuv_full_range`` say how
+    (``HDRTVNetMI355X.preprocess_yuv420``), even sizes only; ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` frames are little-endian
+    u16 ``(H*3//2, W)``, or ``(2*H, W)`` for 4:2:2 (``HDRTVNetMI355X.preprocess_ycbcr10``; at the processing size only: 10-bit input
+    has no letterbox).  ``yuv_matrix`` (601 / 709 / 2020) and ``yuv_full_range`` say how
     the 4:2:0 frames convert to RGB (the stream's ``color_space`` / ``color_range``)."""
 
-    PIX_FMTS = ("bgr24", "yuv420p", "nv12")
+    PIX_FMTS = ("bgr24", "yuv420p", "nv12") + tuple(_lib.YCBCR10_IN_FORMATS)
 
     def __init__(self, path, width, height, fps, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False):
         self.width, self.height, self.fps = int(width), int(height), float(fps)
@@ -182,18 +184,21 @@ class RawVideoSource:
         if int(yuv_matrix) not in (601, 709, 2020):
             raise ValueError("yuv_matrix must be 601, 709 or 2020")
         self.pix_fmt, self.yuv_matrix, self.yuv_full_range = pix_fmt, int(yuv_matrix), bool(yuv_full_range)
+        dtype = np.uint8
         if pix_fmt == "bgr24":
             shape = (self.height, self.width, 3)
+        elif pix_fmt in _lib.YCBCR10_IN_FORMATS:
+            shape, dtype = _lib.ycbcr10_frame_shape(pix_fmt, self.height, self.width), np.dtype("<u2")
         else:
             if self.width % 2 or self.height % 2:
                 raise ValueError(f"{pix_fmt} frames have even sizes (got {self.width}x{self.height})")
             shape = (self.height * 3 // 2, self.width)
-        fb = int(np.prod(shape))
+        fb = int(np.prod(shape)) * np.dtype(dtype).itemsize
         size = os.path.getsize(path)
         if size < fb or size % fb:
             raise ValueError(f"{path}: size {size} is not a whole number of {self.width}x{self.height} {pix_fmt} frames")
         self.frame_count = size // fb
-        self._mm = np.memmap(path, dtype=np.uint8, mode="r", shape=(self.frame_count,) + shape)
+        self._mm = np.memmap(path, dtype=dtype, mode="r", shape=(self.frame_count,) + shape)
         self._i = 0
 
     def read(self):
@@ -577,8 +582,8 @@ def parse_args(argv=None):
     ap.add_argument("--frames", type=int, default=240)
     ap.add_argument("--input", help="rawvideo file at --size in --pix-fmt (default: synthetic frames)")
     ap.add_argument("--pix-fmt", choices=RawVideoSource.PIX_FMTS, default="bgr24", help="pixel format of --input")
-    ap.add_argument("--yuv-matrix", type=int, choices=(601, 709, 2020), default=709, help="Y'CbCr matrix of a yuv420p / nv12 input")
-    ap.add_argument("--yuv-range", choices=("limited", "full"), default="limited", help="Y'CbCr range of a yuv420p / nv12 input")
+    ap.add_argument("--yuv-matrix", type=int, choices=(601, 709, 2020), default=709, help="Y'CbCr matrix of a yuv420p / nv12 / 10-bit input")
+    ap.add_argument("--yuv-range", choices=("limited", "full"), default="limited", help="Y'CbCr range of a yuv420p / nv12 / 10-bit input")
     ap.add_argument("--out", help="rawvideo output in --out-pix-fmt (file or fifo); omit to run without a display sink")
     ap.add_argument("--out-pix-fmt", choices=_lib.OUT_PIX_FMTS, default="rgb48le", help="what the sink receives: full-range RGB48, or "
                     "10-bit limited-range BT.2020nc Y'CbCr for an encoder, converted on the device (hdrtv_post_ycbcr10)")
@@ -617,7 +622,7 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
-    """``python -m hdrtv_mi355x.playback``: synthetic (or bgr24 / yuv420p / nv12 rawvideo) source -> worker -> rgb48le sink."""
+    """``python -m hdrtv_mi355x.playback``: synthetic (or bgr24 / yuv420p / nv12 / 10-bit Y'CbCr rawvideo) source -> worker -> rgb48le sink."""
     import json
 
     from .worker import HeadlessPipelineWorker

@@ -457,6 +457,16 @@ class HDRTVNetMI355X:
         self._enqueue(lane, self._lib.hdrtv_preprocess_yuv420, "hdrtv_preprocess_yuv420", planes, h, w, dst_rgb48_ptr, stream, out,
                       light_ptr, light_rect, self._cleanup_for(cleanup, out))
 
+    def enqueue_frame_ycbcr10(self, lane, src_ptr, h, w, dst_ptr, *, pix_fmt, matrix=709, full_range=False, stream=None, out_hw=None,
+                              out_pix_fmt="rgb48le", out_siting="left", cleanup=None):
+        """``enqueue_frame`` of a 10-bit Y'CbCr frame (``pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le``): the planes lie
+        back to back at the device address ``src_ptr`` (the u16 array ``preprocess_ycbcr10`` takes) and
+        ``hdrtv_preprocess_ycbcr10`` replaces ``hdrtv_preprocess``."""
+        out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
+        planes = _ycbcr10_planes(src_ptr, int(h), int(w), pix_fmt, matrix, full_range)
+        self._enqueue(lane, self._lib.hdrtv_preprocess_ycbcr10, "hdrtv_preprocess_ycbcr10", planes, h, w, dst_ptr, stream, out,
+                      cleanup=self._cleanup_for(cleanup, out))
+
     def _upload(self, key, src, staged=None):
         """Device pointer of the host u8 array ``src``, uploaded through the staging slot kept per ``key`` in ``_staging``: a
         pinned slot, its device buffer and the event behind the last upload out of the slot (allocated on first use and on a shape
@@ -568,6 +578,22 @@ class HDRTVNetMI355X:
                   "hdrtv_letterbox_u8")
         self._chk(self._lib.hdrtv_preprocess(self._ctx, st, self._gpu_raw.data_ptr(), out_h, out_w, self._gpu_input.data_ptr(),
                                              self._gpu_cond.data_ptr()), "hdrtv_preprocess")
+        return self._gpu_input, self._gpu_cond
+
+    @torch.inference_mode()
+    def preprocess_ycbcr10(self, frame, *, pix_fmt, matrix=709, full_range=False):
+        """``preprocess`` of a 10-bit Y'CbCr frame: ``frame`` is u16, the planes back to back at their minimum pitches as ``ffmpeg
+        -f rawvideo -pix_fmt <pix_fmt>`` writes them -- ``(H*3//2, W)`` for ``p010le`` and ``yuv420p10le``, ``(2*H, W)`` for
+        ``yuv422p10le``.  The conversion to RGB (include/hdrtv_mi355x.h: ``matrix`` 601 / 709 / 2020, limited or ``full_range``)
+        runs inside the preprocess kernel and keeps the ten bits: the tensor holds ``fp16(code / 1023)``.  Returns the same
+        processor-owned ``(tensor, cond)``."""
+        h, w = ycbcr10_frame_hw(frame, pix_fmt)
+        # the upload path moves bytes: the frame goes through it as the u8 view of its little-endian samples
+        ptr = self._upload("ycbcr10", np.ascontiguousarray(frame).view(np.uint8))
+        planes = _ycbcr10_planes(ptr, h, w, pix_fmt, matrix, full_range)
+        self._ensure_buffers(h, w)
+        self._chk(self._lib.hdrtv_preprocess_ycbcr10(self._ctx, self._stream(), *planes, h, w, self._gpu_input.data_ptr(),
+                                                     self._gpu_cond.data_ptr()), "hdrtv_preprocess_ycbcr10")
         return self._gpu_input, self._gpu_cond
 
     @torch.inference_mode()
@@ -728,6 +754,12 @@ class HDRTVNetMI355X:
     def process_yuv420(self, frame, *, layout="i420", matrix=709, full_range=False):
         """``process`` of an 8-bit 4:2:0 frame (``preprocess_yuv420``): u8 BGR out, as ``process``."""
         tensor, cond = self.preprocess_yuv420(frame, layout=layout, matrix=matrix, full_range=full_range)
+        return self.postprocess(self.infer((tensor, cond)))
+
+    @torch.inference_mode()
+    def process_ycbcr10(self, frame, *, pix_fmt, matrix=709, full_range=False):
+        """``process`` of a 10-bit Y'CbCr frame (``preprocess_ycbcr10``): u8 BGR out, as ``process``."""
+        tensor, cond = self.preprocess_ycbcr10(frame, pix_fmt=pix_fmt, matrix=matrix, full_range=full_range)
         return self.postprocess(self.infer((tensor, cond)))
 
     @torch.inference_mode()
@@ -914,6 +946,23 @@ def _yuv_planes(ptr, h, w, layout, matrix, full_range):
     if code == _L.YUV_NV12:
         return ptr, w, u, None, w, code, int(matrix), int(bool(full_range))
     return ptr, w, u, u + (h // 2) * (w // 2), w // 2, code, int(matrix), int(bool(full_range))
+
+
+YCBCR10_IN_FORMATS, ycbcr10_frame_shape, ycbcr10_frame_hw = _L.YCBCR10_IN_FORMATS, _L.ycbcr10_frame_shape, _L.ycbcr10_frame_hw
+
+
+def _ycbcr10_planes(ptr, h, w, pix_fmt, matrix, full_range):
+    """The plane arguments of hdrtv_ycbcr10_to_rgb10 / hdrtv_preprocess_ycbcr10 for a frame whose planes lie back to back at
+    device address ``ptr`` at their minimum pitches: (y, y_pitch, u, v, c_pitch, fmt, matrix, full_range)."""
+    ycbcr10_frame_shape(pix_fmt, h, w)
+    if int(matrix) not in (601, 709, 2020):
+        raise ValueError("matrix must be 601, 709 or 2020")
+    fmt = YCBCR10_IN_FORMATS[pix_fmt]
+    u = ptr + h * w * 2
+    if fmt == _L.YCC_P010:
+        return ptr, 2 * w, u, None, 2 * w, fmt, int(matrix), int(bool(full_range))
+    ch = h if fmt == _L.YCC_YUV422P10 else h // 2
+    return ptr, 2 * w, u, u + ch * w, w, fmt, int(matrix), int(bool(full_range))
 
 
 def _hip_memcpy_d2d(dst, src, nbytes):

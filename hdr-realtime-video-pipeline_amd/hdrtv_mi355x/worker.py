@@ -25,6 +25,7 @@ import torch
 
 from . import lib as _L
 from .lightlevel import ContentLightLevel
+from .lib import YCBCR10_IN_FORMATS, ycbcr10_frame_hw
 from .processor import HDRTVNetMI355X, _dtype_code
 
 _RING_FRAMES = max(2, min(8, int(os.environ.get("HDRTVNET_FEEDER_GPU_RGB48_RING_FRAMES", "3") or 3)))
@@ -165,10 +166,14 @@ class HeadlessPipelineWorker:
         self._yuv_format = dict(layout="i420", matrix=709, full_range=False)     # how 2-D (4:2:0) frames convert
 
     def set_input_format(self, pix_fmt, yuv_matrix=709, yuv_full_range=False):
-        """How ``_process_frame`` reads a 2-D u8 frame ``(H*3//2, W)``: ``pix_fmt`` ``yuv420p`` or ``nv12``, the matrix and the
-        range of ``HDRTVNetMI355X.preprocess_yuv420``.  3-D frames are BGR whatever is set here."""
+        """How ``_process_frame`` reads a 2-D frame: u8 ``(H*3//2, W)`` with ``pix_fmt`` ``yuv420p`` or ``nv12``
+        (``HDRTVNetMI355X.preprocess_yuv420``), or u16 with ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` (``preprocess_ycbcr10``; at
+        the processing size only: 10-bit input has no letterbox), and its matrix and range.  3-D frames are BGR whatever is set here."""
+        if pix_fmt in YCBCR10_IN_FORMATS:      # 2-D u16 frames: HDRTVNetMI355X.preprocess_ycbcr10
+            self._yuv_format = dict(pix_fmt=pix_fmt, matrix=int(yuv_matrix), full_range=bool(yuv_full_range))
+            return
         if pix_fmt not in ("yuv420p", "nv12"):
-            raise ValueError("pix_fmt must be yuv420p or nv12")
+            raise ValueError(f"pix_fmt must be yuv420p, nv12 or one of {sorted(YCBCR10_IN_FORMATS)}")
         self._yuv_format = dict(layout=pix_fmt, matrix=int(yuv_matrix), full_range=bool(yuv_full_range))
 
     # ---------------------------------------------------------------- status
@@ -286,7 +291,16 @@ class HeadlessPipelineWorker:
         if ow < pw or oh < ph:
             raise ValueError(f"output size {ow}x{oh} is below the processing size {pw}x{ph} (enlarging only)")
         with torch.inference_mode():
-            if frame.ndim == 2:
+            if frame.ndim == 2 and frame.dtype == np.uint16:
+                # 10-bit Y'CbCr planes (set_input_format): converted inside the preprocess kernel; there is no 10-bit letterbox
+                if "pix_fmt" not in self._yuv_format:
+                    raise ValueError("a uint16 frame needs set_input_format('p010le' | 'yuv420p10le' | 'yuv422p10le')")
+                fh, fw = ycbcr10_frame_hw(frame, self._yuv_format["pix_fmt"])
+                if fw != pw or fh != ph:
+                    raise ValueError(f"a {self._yuv_format['pix_fmt']} source of {fw}x{fh} differs from the processing size {pw}x{ph}: "
+                                     "10-bit input has no letterbox (out of scope), feed it at the processing size")
+                tensor, cond = self._processor.preprocess_ycbcr10(frame, **self._yuv_format)
+            elif frame.ndim == 2:
                 # 8-bit 4:2:0 planes: converted on the device (set_input_format), letterboxed there when the sizes differ
                 fh = frame.shape[0] // 3 * 2
                 if frame.shape[1] != pw or fh != ph:

@@ -322,6 +322,41 @@ int hdrtv_preprocess_yuv420(hdrtv_ctx *ctx, void *stream, const uint8_t *dev_y, 
                             const uint8_t *dev_u, const uint8_t *dev_v, int c_pitch, int layout,
                             int matrix, int full_range, int H, int W, void *dev_rgb_chw, void *dev_cond);
 
+/* 10-bit Y'CbCr input: a ProRes / DNxHR mezzanine (yuv422p10le), a broadcast master, a 10-bit HEVC / AV1 SDR stream (a hardware
+ * decoder's P010).  The rule above at ten bits; the ten source bits reach the network's fp16 tensor (all 1024 values
+ * fp16(float(c) * fp32(1/1023)) are distinct), four times the levels of u8 / 255.  10-bit 4:2:0 is 3 bytes per pixel, as bgr24:
+ * the gain is precision and a removed host pass, not PCIe bytes.  Layouts, planes and pitches are those of the output side
+ * (HDRTV_YCC_P010 / _YUV420P10 / _YUV422P10 above), samples little-endian u16:
+ *   HDRTV_YCC_P010      dev_y, dev_u = the interleaved CbCr plane (Cb at u16 2i, Cr at 2i+1; H/2 rows), dev_v = NULL;
+ *                       v = word >> 6 (the low six bits are ignored); c_pitch >= 2 W
+ *   HDRTV_YCC_YUV420P10 dev_y, dev_u (Cb), dev_v (Cr); H/2 rows of W/2 samples; v = word & 0x3ff; c_pitch >= W
+ *   HDRTV_YCC_YUV422P10 as above with chroma planes of H rows
+ * Pitches are in bytes and even, y_pitch >= 2 W; no base or pitch needs more than two-byte alignment.  W even; H even for the two
+ * 4:2:0 layouts.  matrix and full_range as for the 8-bit entry points.  Chroma planes Hc rows by Wc = W/2 samples:
+ *  1. chroma upsampling to 8 x chroma, per chroma plane C (4:2:0: MPEG-2 siting only, the 8-bit rule's integers):
+ *       4:2:0, luma row y: j = y>>1; n = (y odd) ? min(j+1, Hc-1) : max(j-1, 0); V4[i] = 3*C[j][i] + C[n][i]
+ *       4:2:2, luma row y: V4[i] = 4*C[y][i]
+ *       luma column x:     i = x>>1; i2 = (x odd) ? min(i+1, Wc-1) : i;          C8 = V4[i] + V4[i2]
+ *  2. offsets: y = Y - 64 (limited) or Y (full); cb = C8_U - 4096; cr = C8_V - 4096
+ *  3. matrix, int32 with arithmetic (flooring) shifts, each result clamped to [0, 1023]:
+ *       R = (A*y + RV*cr + 32768) >> 16;  G = (A*y - GU*cb - GV*cr + 32768) >> 16;  B = (A*y + BU*cb + 32768) >> 16
+ *     the coefficients by the 8-bit formulas with sY = 1023/876 and sC = 1023/896 (limited) or 1 and 1 (full).
+ *     BT.709 limited: A 76533, RV 14729, GU 1752, GV 4378, BU 17356.  Every intermediate stays below 2^28; the result is within
+ *     0.57 code of the exact formula (0.5 rounding + 0.0073 from A + 2 x 0.031 from the chroma coefficients).
+ * tests/ycbcr10_in_ref.py restates the rule in numpy; the GPU tests hold both entry points to it bit for bit.
+ * hdrtv_ycbcr10_to_rgb10 writes the codes as u16 [H][W][3] R, G, B in 0..1023 and needs no reservation.
+ * hdrtv_preprocess_ycbcr10 writes the tensor fp16(float(code) * fp32(1/1023)) of those codes (the same expression in fp32 for an
+ * fp32 context) and its condition map, in one pass over the planes (fp16; two launches in an fp32 context); same reservation rule
+ * as hdrtv_preprocess.  HDRTV_EINVAL, the destinations untouched, for a NULL pointer, a non-positive or odd W, an odd H with
+ * 4:2:0, a short or odd pitch, an unknown fmt, matrix or range, P010 with a non-NULL dev_v or a planar layout with a NULL dev_v;
+ * HDRTV_ESTATE (preprocess) before hdrtv_reserve(H, W). */
+int hdrtv_ycbcr10_to_rgb10(hdrtv_ctx *ctx, void *stream, const uint16_t *dev_y, int y_pitch,
+                           const uint16_t *dev_u, const uint16_t *dev_v, int c_pitch, int fmt,
+                           int matrix, int full_range, int H, int W, uint16_t *dev_rgb_hwc);
+int hdrtv_preprocess_ycbcr10(hdrtv_ctx *ctx, void *stream, const uint16_t *dev_y, int y_pitch,
+                             const uint16_t *dev_u, const uint16_t *dev_v, int c_pitch, int fmt,
+                             int matrix, int full_range, int H, int W, void *dev_rgb_chw, void *dev_cond);
+
 /* Objective metrics of the reference's metrics dict between two device images [3][H][W]
  * (R, G, B planes, unit range, f16 or f32): out3 = { PSNR dB, SSIM, dE-ITP } as _psnr_bgr / _ssim_bgr /
  * _delta_e_itp_bgr compute them (src/gui_objective_metrics.py:438-528; peak_nits = HDRTVNET_OBJECTIVE_HDR_PEAK_NITS,
