@@ -470,11 +470,12 @@ TAPS = {
 class Check:
     """One comparison: the launches `stages` evaluated as one primitive list on the taps `ins`, compared at `outs`."""
 
-    def __init__(self, stages, drop=()):
-        self.stages = [BY_NAME[s] for s in stages]
+    def __init__(self, stages, drop=(), by_name=None, taps=None):
+        by_name, taps = by_name or BY_NAME, taps or TAPS        # another network's stage table (tests/hg_layer_ref.py)
+        self.stages = [by_name[s] for s in stages]
         made = [t for s in self.stages for t in s.outs]
         self.ins = tuple(dict.fromkeys(t for s in self.stages for t in s.ins if t not in made))
-        self.outs = tuple(t for t in made if (t in TAPS or t == "out") and t not in drop)
+        self.outs = tuple(t for t in made if (t in taps or t == "out") and t not in drop)
         self.name = "+".join(stages) if len(stages) <= 3 else f"{stages[0]}..{stages[-1]}"
         self.composite = len(stages) > 1
         # recon_trunk3.0 - 3.2 as one six-launch composite: an extra beyond the launches that can be isolated.  Its bound has gone
@@ -615,12 +616,15 @@ def evaluate(check, P, taps, model=None):
 def metrics(r, got):
     """Figures of one output: `got` (device or a mutated model) against v / d / the rounding model."""
     err = (got - r["v"]).abs()
-    merr = (r["model"] - r["v"]).abs()
+    vp = r.get("v_prec", r["v"])        # tests/hg_layer_ref.py: the precision condition's own reference, where it differs from v
+    perr, merr = (got - vp).abs(), (r["model"] - vp).abs()
+    # d = 0 (an output the launch must reproduce exactly; no LE bound is ever 0): ratio 0 where it does, inf where it does not
+    ratio = torch.where(r["d"] > 0, err / r["d"].clamp(min=1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
     return {
         "n": got.numel(),
-        "max_ratio": float((err / r["d"]).max()),
+        "max_ratio": float(ratio.max()),
         "violations": int((err > r["d"]).sum()),
-        "mean_err": float(err.mean()),
+        "mean_err": float(perr.mean()),
         "mean_model": float(merr.mean()),
         "bit_equal": float((got == r["model"]).double().mean()),
         "significant": float((r["v"].abs() > 8 * r["d"]).double().mean()),
