@@ -77,6 +77,8 @@ class _Mi355xWorker:
         # deband / dither of the delivered frames (lib.OutputCleanup, validated by the dispatcher): a plain tuple in init_args
         cleanup = kw.pop("cleanup", None)
         self.cleanup = None if cleanup is None else L.OutputCleanup(*cleanup)
+        # anti-ringing of enlarged frames (a strength in [0, 1] or "auto", validated by the dispatcher); absent: off
+        self.antiring = kw.pop("antiring", 0.0)
         torch.cuda.set_device(device_index)
         with contextlib.redirect_stdout(sys.stderr):   # a worker's banner must not land on the parent's stdout (bench.py's one JSON line)
             self.proc = HDRTVNetMI355X(model, device=f"cuda:{device_index}", warmup_passes=0, **kw)
@@ -125,6 +127,8 @@ class _Mi355xWorker:
             h, w = (frame.shape[0], frame.shape[1]) if frame.ndim == 3 else (frame.shape[0] * 2 // 3, frame.shape[1])
         fmt = self.output_format
         out_fmt = dict(out_hw=(fmt.h, fmt.w), out_pix_fmt=fmt.pix_fmt, out_siting=fmt.siting, cleanup=self.cleanup)
+        if self.antiring:
+            out_fmt["antiring"] = self.antiring
         self._buffers(h, w, tuple(frame.shape) + ((2,) if ten else ()), fmt)       # _raw is bytes: a u16 sample is two
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
@@ -370,7 +374,7 @@ class FrameDispatcher:
     def __init__(self, n_workers, height, width, sink, make_worker=mi355x_worker, init_args=None, devices=None, slots=3,
                  start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False, out_height=None,
                  out_width=None, out_pix_fmt="rgb48le", out_siting="left", deband=False, deband_range=16, deband_threshold=1311,
-                 dither="none"):
+                 dither="none", antiring=0.0):
         """``sink(index, rgb48_view)`` is called in index order from the reorder thread; the view is only valid during the
         call (the slot goes back to its worker afterwards).  ``numa``: workers pin themselves to their GPU's NUMA node
         (False: report only).  ``pix_fmt``: ``bgr24`` input frames are u8 (H, W, 3); ``yuv420p`` / ``nv12`` frames are u8
@@ -386,7 +390,10 @@ class FrameDispatcher:
         ``hdrtv_ycbcr10_bytes`` bytes, the planes back to back -- half the slot bytes and D2H copy of RGB48 for 4:2:0.
         ``deband`` / ``deband_range`` / ``deband_threshold`` / ``dither``: the output cleanup of ``lib.output_cleanup``
         (INTEGRATION.md 5f); when one is on, the tuple travels to the workers as ``init_args["cleanup"]`` and the product's worker
-        hands it to ``enqueue_frame(..., cleanup=)``.  Slot sizes do not depend on it."""
+        hands it to ``enqueue_frame(..., cleanup=)``.  Slot sizes do not depend on it.  ``antiring``: the anti-ringing strength of
+        enlarged frames, 0 .. 1, or ``"auto"`` = ``lib.scale_antiring`` of the processing and the output size,
+        kept as ``.antiring``; when it is not off it travels as ``init_args["antiring"]`` and the product's worker hands it to
+        ``enqueue_frame(..., antiring=)``.  Off (0.0, the default): the ``init_args`` of before."""
         if n_workers < 1 or slots < 2:
             raise ValueError("n_workers >= 1 and slots >= 2")
         from . import lib as _L
@@ -406,6 +413,9 @@ class FrameDispatcher:
         init_args = dict(init_args or {})
         if self.cleanup.active:
             init_args["cleanup"] = tuple(self.cleanup)
+        self.antiring = _L.check_antiring(antiring)
+        if self.antiring:
+            init_args["antiring"] = self.antiring
         self.pix_fmt = pix_fmt
         self._in_shape, self._in_dtype = _in_shape(self.h, self.w, pix_fmt), _in_dtype(pix_fmt)     # raises for an odd 10-bit size
         fmt = (pix_fmt, int(yuv_matrix), bool(yuv_full_range))

@@ -45,6 +45,7 @@ SYMBOLS = [
     ("hdrtv_post_rgb48", _I, [_VP, _VP, _VP, _I, _I, _I, _VP]),
     ("hdrtv_post_pq_rgb48", _I, [_VP, _VP, _VP, _I, _I, _I, C.c_float, _VP]),
     ("hdrtv_post_rgb48_scaled", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I]),
+    ("hdrtv_post_rgb48_scaled_ex", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I]),
     ("hdrtv_post_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_rgb48_to_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_ycbcr10_bytes", C.c_int64, [_I, _I, _I]),
@@ -227,6 +228,53 @@ def output_cleanup(deband=False, deband_range=DEBAND_RANGE, deband_threshold=DEB
         raise ValueError("dither applies to the 10-bit Y'CbCr formats: rgb48le (16-bit codes) is not dithered")
     return OutputCleanup(bool(deband), _int_in("deband_range", deband_range, 1, DEBAND_RANGE_MAX),
                          _int_in("deband_threshold", deband_threshold, 1, 65535), dither)
+
+
+ANTIRING_ONE = 256                         # hdrtv_post_rgb48_scaled_ex: the code of full strength
+
+
+def antiring_code(value):
+    """The ``antiring`` argument of ``hdrtv_post_rgb48_scaled_ex`` for a strength in [0, 1]: ``floor(value * 256 + 0.5)``, 0 .. 256.
+    ``ValueError`` for anything that is not such a number (a bool, a string -- ``"auto"`` is resolved by ``resolve_antiring``
+    where the two sizes are known --, None, NaN, a value outside the range)."""
+    if isinstance(value, (bool, str, bytes)) or value is None:
+        raise ValueError(f"antiring must be a number in [0, 1] (got {value!r})")
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"antiring must be a number in [0, 1] (got {value!r})") from None
+    if not 0.0 <= v <= 1.0:                  # NaN fails both comparisons
+        raise ValueError(f"antiring must be in [0, 1] (got {value!r})")
+    return int(v * ANTIRING_ONE + 0.5)
+
+
+def check_antiring(value):
+    """An ``antiring`` option as the worker, the dispatcher and the command line take it: ``"auto"`` (any case) -> ``"auto"``, a
+    strength in [0, 1] -> that float; ``ValueError`` otherwise."""
+    if isinstance(value, str) and value.lower() == "auto":
+        return "auto"
+    antiring_code(value)
+    return float(value)
+
+
+def scale_antiring(proc_w, proc_h, out_w, out_h):
+    """The reference's anti-ringing strength for a separable Lanczos kernel (gui_scaling.py:82-111, 150-162: what it hands mpv as
+    ``scale-antiring`` in its lower-resolution processing mode): 0.0 unless both axes are enlarged, else 0.30 for a processing
+    size of at most 960x540 (either extent), 0.22 up to 1280x720, 0.10 above."""
+    proc_w, proc_h, out_w, out_h = int(proc_w), int(proc_h), int(out_w), int(out_h)
+    if not (out_w > proc_w and out_h > proc_h):
+        return 0.0
+    if proc_h <= 540 or proc_w <= 960:
+        return 0.30
+    if proc_h <= 720 or proc_w <= 1280:
+        return 0.22
+    return 0.10
+
+
+def resolve_antiring(value, proc_w, proc_h, out_w, out_h):
+    """``check_antiring``'s result for a frame of known sizes -> a strength in [0, 1]: ``"auto"`` through ``scale_antiring``."""
+    value = check_antiring(value)
+    return scale_antiring(proc_w, proc_h, out_w, out_h) if value == "auto" else value
 
 
 _libs = {}

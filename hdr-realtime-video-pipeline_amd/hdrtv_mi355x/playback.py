@@ -569,7 +569,8 @@ class RealtimePlayback:
 
 def parse_args(argv=None):
     """The command line of ``main`` -> the argparse namespace, checked (a bad value ends in ``ap.error``): ``.proc_wh`` and ``.out_wh``
-    hold the two sizes as ``(w, h)``, ``.cleanup`` the ``lib.OutputCleanup`` of --deband / --dither."""
+    hold the two sizes as ``(w, h)``, ``.cleanup`` the ``lib.OutputCleanup`` of --deband / --dither, ``.antiring`` ``"auto"`` or the
+    strength as a float (0.0: off)."""
     import argparse
 
     ap = argparse.ArgumentParser(description=main.__doc__)
@@ -600,6 +601,9 @@ def parse_args(argv=None):
                     "have, in u16 code units, 1 .. 65535 (1311 = 2 %% of the range)")
     ap.add_argument("--dither", choices=sorted(_lib.DITHERS), default="none", help="dither of the 16 -> 10 bit rounding of a Y'CbCr "
                     "--out-pix-fmt: ordered = a 16x16 Bayer threshold (hdrtv_post_ycbcr10_ex); not for rgb48le")
+    ap.add_argument("--antiring", default=None, metavar="{auto|0..1}", help="anti-ringing of the --out-size upscale "
+                    "(hdrtv_post_rgb48_scaled_ex; INTEGRATION.md 5c): a strength in 0 .. 1, or auto = the reference's schedule by "
+                    "processing size (0.30 up to 960x540, 0.22 up to 1280x720, 0.10 above); default: off")
     ap.add_argument("--no-hg", action="store_true")
     ap.add_argument("--hg-weights", default=None, help="HG weight file, or seeded:<n>")
     ap.add_argument("--max-throughput", action="store_true", help="do not pace to the source clock")
@@ -617,6 +621,15 @@ def parse_args(argv=None):
         a.cleanup = _lib.output_cleanup(a.deband, a.deband_range, a.deband_threshold, a.dither, pix_fmt=a.out_pix_fmt)
     except ValueError as exc:
         ap.error(str(exc))
+    if a.antiring is None:
+        a.antiring = 0.0
+    else:
+        if (owd, oht) == (wd, ht):
+            ap.error("--antiring applies to an upscale: --out-size equals --size")
+        try:
+            a.antiring = _lib.check_antiring(a.antiring if a.antiring.lower() == "auto" else float(a.antiring))
+        except ValueError as exc:
+            ap.error(f"--antiring: {exc}")
     a.proc_wh, a.out_wh = (wd, ht), (owd, oht)
     return a
 
@@ -639,7 +652,7 @@ def main(argv=None):
                                     status_cb=lambda m: print(m, flush=True), out_w=owd, out_h=oht, out_pix_fmt=a.out_pix_fmt,
                                     out_siting=a.out_siting, light_stats=bool(a.light_level or a.light_level_json),
                                     deband=a.cleanup.deband, deband_range=a.cleanup.deband_range,
-                                    deband_threshold=a.cleanup.deband_threshold, dither=a.cleanup.dither)
+                                    deband_threshold=a.cleanup.deband_threshold, dither=a.cleanup.dither, antiring=a.antiring)
     if not worker._load_model(a.precision):
         return 1
     sink = None
@@ -665,6 +678,8 @@ def main(argv=None):
         res["out_pix_fmt"] = a.out_pix_fmt
     if a.cleanup.active:
         res["deband"], res["dither"] = a.cleanup.deband, a.cleanup.dither
+    if a.antiring:
+        res["antiring"] = _lib.resolve_antiring(a.antiring, wd, ht, owd, oht)
     if cll is not None:
         res["max_cll"], res["max_fall"], res["light_frames"] = cll.max_cll, cll.max_fall, cll.frames
         if a.light_level_json:

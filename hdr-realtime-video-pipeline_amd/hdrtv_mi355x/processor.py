@@ -341,7 +341,7 @@ class HDRTVNetMI355X:
             scratch = self._ycc_scratch[key] = torch.empty((out.h, out.w, 3), dtype=torch.uint16, device=self.device)
         return scratch.data_ptr()
 
-    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None):
+    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None, antiring=0):
         """The output conversion of a frame whose planar tensor lies at ``src_ptr``, to the ``lib.OutputFormat`` ``out`` at
         ``dst_ptr``: ``rgb48le`` at the processing size (``hdrtv_post_rgb48``) or enlarged to ``out.h`` x ``out.w``
         (``hdrtv_post_rgb48_scaled``); a 10-bit Y'CbCr layout in one kernel at the processing size (``hdrtv_post_ycbcr10``), or,
@@ -354,7 +354,10 @@ class HDRTVNetMI355X:
         Deband: tensor -> ``hdrtv_post_rgb48`` / ``hdrtv_post_rgb48_scaled`` into a scratch -> ``hdrtv_rgb48_deband`` -> ``dst``
         (``rgb48le``), or into a second scratch and through the conversion from codes; the light level record is then taken from
         the debanded codes, which are what is delivered.  Dither alone: ``hdrtv_post_ycbcr10_ex`` at the processing size, the
-        ``_ex`` conversion behind the scaled codes otherwise; it does not enter the record, which is defined on RGB48 codes."""
+        ``_ex`` conversion behind the scaled codes otherwise; it does not enter the record, which is defined on RGB48 codes.
+        ``antiring``: the anti-ringing code of an enlarged frame, 0 .. 256 (``lib.antiring_code``).  Nonzero and
+        enlarged: ``hdrtv_post_rgb48_scaled_ex`` replaces ``hdrtv_post_rgb48_scaled``, and everything behind the scaler -- deband,
+        the conversion from codes, the record -- works on the anti-ringed codes.  0, or an unscaled frame: the launches above."""
         scaled = (out.h, out.w) != (h, w)
         rect = (0, 0, out.w, out.h) if light_rect is None else tuple(int(v) for v in light_rect)
         active = cleanup is not None and cleanup.active
@@ -373,7 +376,10 @@ class HDRTVNetMI355X:
             return
         rgb_ptr = dst_ptr if out.is_rgb48 else self._scratch(scratch_key, out)
         raw_ptr = self._scratch((scratch_key, "raw"), out) if deband else rgb_ptr       # deband never works in place
-        if scaled:
+        if scaled and antiring:
+            self._chk(self._lib.hdrtv_post_rgb48_scaled_ex(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, int(antiring)),
+                      "hdrtv_post_rgb48_scaled_ex")
+        elif scaled:
             self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w),
                       "hdrtv_post_rgb48_scaled")
         else:
@@ -419,7 +425,15 @@ class HDRTVNetMI355X:
             raise ValueError("cleanup must be a lib.OutputCleanup (lib.output_cleanup builds one) or None")
         return _L.output_cleanup(*cleanup, pix_fmt=out.pix_fmt)
 
-    def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out, light_ptr=None, light_rect=None, cleanup=None):
+    @staticmethod
+    def _antiring_for(antiring, h, w, out):
+        """The ``antiring`` argument of ``enqueue_frame*`` (a strength in [0, 1], or ``"auto"``: ``lib.scale_antiring`` of the two
+        sizes) -> the code ``_post_out`` takes."""
+        if type(antiring) in (float, int) and antiring == 0:          # off, the default: nothing to resolve on the hot path
+            return 0
+        return _L.antiring_code(_L.resolve_antiring(antiring, w, h, out.w, out.h))
+
+    def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out, light_ptr=None, light_rect=None, cleanup=None, antiring=0):
         """The body of ``enqueue_frame*``: the preprocess entry point ``pre`` (named ``what``) on its source arguments ``src``,
         ``hdrtv_infer_lane`` and ``_post_out``, all on the lane's buffers and ``stream`` (default: the lane's own)."""
         self._ensure_buffers(h, w)
@@ -428,10 +442,10 @@ class HDRTVNetMI355X:
         self._chk(pre(self._ctx, st, *src, h, w, tin.data_ptr(), tcond.data_ptr()), what)
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), self._out_dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup)
+        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, antiring)
 
     def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le",
-                      out_siting="left", light_ptr=None, light_rect=None, cleanup=None):
+                      out_siting="left", light_ptr=None, light_rect=None, cleanup=None, antiring=0.0):
         """One frame of the hot path on lane ``lane``, stream-ordered and without any host synchronisation: u8 BGR frame in
         device memory at ``src_bgr_ptr`` -> hdrtv_preprocess -> hdrtv_infer_lane -> hdrtv_post_rgb48 -> u16 RGB48 at the device
         address ``dst_rgb48_ptr``.  ``stream``: a ``torch.cuda.Stream`` (default: the lane's own).  Frames enqueued on different
@@ -443,29 +457,32 @@ class HDRTVNetMI355X:
         the processing size, with ``out_hw`` two launches through a per-lane RGB48 scratch.  ``light_ptr`` / ``light_rect``: the
         delivered frame's content light level record, behind the frame on the same stream (``_post_out``).
         ``cleanup``: a ``lib.OutputCleanup`` (``lib.output_cleanup``): deband and / or ordered dither of the delivered frame
-        (``_post_out``); None: neither, and the bytes of before."""
+        (``_post_out``); None: neither, and the bytes of before.  ``antiring``: the anti-ringing strength of an
+        enlarged frame, 0 .. 1, or ``"auto"`` = ``lib.scale_antiring`` of the two sizes (``hdrtv_post_rgb48_scaled_ex``;
+        INTEGRATION.md 5c); 0.0, or a frame delivered at the processing size: the launches and bytes of before."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         self._enqueue(lane, self._lib.hdrtv_preprocess, "hdrtv_preprocess", (src_bgr_ptr,), h, w, dst_rgb48_ptr, stream, out,
-                      light_ptr, light_rect, self._cleanup_for(cleanup, out))
+                      light_ptr, light_rect, self._cleanup_for(cleanup, out), self._antiring_for(antiring, h, w, out))
 
     def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None,
-                             out_hw=None, out_pix_fmt="rgb48le", out_siting="left", light_ptr=None, light_rect=None, cleanup=None):
+                             out_hw=None, out_pix_fmt="rgb48le", out_siting="left", light_ptr=None, light_rect=None, cleanup=None,
+                             antiring=0.0):
         """``enqueue_frame`` of an 8-bit 4:2:0 frame: the planes lie back to back at the device address ``src_ptr`` (the
         ``(h*3//2, w)`` u8 array ``preprocess_yuv420`` takes) and ``hdrtv_preprocess_yuv420`` replaces ``hdrtv_preprocess``."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         planes = _yuv_planes(src_ptr, int(h), int(w), layout, matrix, full_range)
         self._enqueue(lane, self._lib.hdrtv_preprocess_yuv420, "hdrtv_preprocess_yuv420", planes, h, w, dst_rgb48_ptr, stream, out,
-                      light_ptr, light_rect, self._cleanup_for(cleanup, out))
+                      light_ptr, light_rect, self._cleanup_for(cleanup, out), self._antiring_for(antiring, h, w, out))
 
     def enqueue_frame_ycbcr10(self, lane, src_ptr, h, w, dst_ptr, *, pix_fmt, matrix=709, full_range=False, stream=None, out_hw=None,
-                              out_pix_fmt="rgb48le", out_siting="left", cleanup=None):
+                              out_pix_fmt="rgb48le", out_siting="left", cleanup=None, antiring=0.0):
         """``enqueue_frame`` of a 10-bit Y'CbCr frame (``pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le``): the planes lie
         back to back at the device address ``src_ptr`` (the u16 array ``preprocess_ycbcr10`` takes) and
         ``hdrtv_preprocess_ycbcr10`` replaces ``hdrtv_preprocess``."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         planes = _ycbcr10_planes(src_ptr, int(h), int(w), pix_fmt, matrix, full_range)
         self._enqueue(lane, self._lib.hdrtv_preprocess_ycbcr10, "hdrtv_preprocess_ycbcr10", planes, h, w, dst_ptr, stream, out,
-                      cleanup=self._cleanup_for(cleanup, out))
+                      cleanup=self._cleanup_for(cleanup, out), antiring=self._antiring_for(antiring, h, w, out))
 
     def _upload(self, key, src, staged=None):
         """Device pointer of the host u8 array ``src``, uploaded through the staging slot kept per ``key`` in ``_staging``: a
@@ -683,10 +700,12 @@ class HDRTVNetMI355X:
         return self._pin_output.numpy()
 
     @torch.inference_mode()
-    def postprocess_rgb48_scaled(self, output, out_w, out_h, pq=False, peak_nits=1000.0):
+    def postprocess_rgb48_scaled(self, output, out_w, out_h, pq=False, peak_nits=1000.0, antiring=0.0):
         """RGB48 at the display size: the u16 codes of ``hdrtv_post_rgb48`` (``pq=True``: of
         ``hdrtv_post_pq_rgb48`` at ``peak_nits``) upscaled to ``out_h`` x ``out_w`` by ``hdrtv_post_rgb48_scaled`` in one kernel.
-        Returns a new device u16 ``(out_h, out_w, 3)`` tensor; stream-ordered on the current stream, no synchronisation."""
+        ``antiring``: the anti-ringing strength, 0 .. 1, or ``"auto"`` = ``lib.scale_antiring`` of the two sizes; nonzero:
+        ``hdrtv_post_rgb48_scaled_ex``.  Returns a new device u16 ``(out_h, out_w, 3)`` tensor; stream-ordered on the current stream,
+        no synchronisation."""
         if isinstance(output, (tuple, list)):
             output = output[0]
         if output.dtype not in (torch.float16, torch.float32):
@@ -695,11 +714,15 @@ class HDRTVNetMI355X:
         out_w, out_h = int(out_w), int(out_h)
         if out_w < w or out_h < h:
             raise ValueError(f"output size {out_w}x{out_h} is below the processing size {w}x{h} (enlarging only)")
+        code = _L.antiring_code(_L.resolve_antiring(antiring, w, h, out_w, out_h))
         output = output.contiguous()
         dst = torch.empty((out_h, out_w, 3), dtype=torch.uint16, device=self.device)
-        self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, self._stream(), output.data_ptr(),
-                                                    _dtype_code(output), h, w, 1 if pq else 0,
-                                                    float(peak_nits), dst.data_ptr(), out_h, out_w), "hdrtv_post_rgb48_scaled")
+        args = (self._ctx, self._stream(), output.data_ptr(), _dtype_code(output), h, w, 1 if pq else 0, float(peak_nits), dst.data_ptr(),
+                out_h, out_w)
+        if code:
+            self._chk(self._lib.hdrtv_post_rgb48_scaled_ex(*args, code), "hdrtv_post_rgb48_scaled_ex")
+        else:
+            self._chk(self._lib.hdrtv_post_rgb48_scaled(*args), "hdrtv_post_rgb48_scaled")
         return dst
 
     @torch.inference_mode()

@@ -134,8 +134,8 @@ int hdrtv_post_pq_rgb48(hdrtv_ctx *ctx, void *stream, const void *dev_out, int d
  * Parity with mpv's or OpenCV's scalers is UNPINNED (neither is part of the reference tree, and their float paths are not
  * reproducible); the resampling is this integer rule, restated in tests/rgb48_scale_ref.py, which the GPU tests hold this entry
  * point to bit for bit.  Enlarging only (dH >= H, dW >= W); the whole frame maps onto the whole output (black bars of a
- * letterboxed input are scaled with it), the axes are independent, aspect is the caller's business.  No anti-ringing, no
- * shrinking, no crop rectangle.
+ * letterboxed input are scaled with it), the axes are independent, aspect is the caller's business.  Anti-ringing is
+ * hdrtv_post_rgb48_scaled_ex's (below); no shrinking, no crop rectangle.
  *  1. codes: s[c][y][x] = the u16 code hdrtv_post_rgb48 / hdrtv_post_pq_rgb48 writes for that source value; the resampling sees
  *     nothing but these integers.
  *  2. per axis, source extent n, destination extent m, for d = 0..m-1, in double:
@@ -152,6 +152,33 @@ int hdrtv_post_pq_rgb48(hdrtv_ctx *ctx, void *stream, const void *dev_out, int d
  * or pq with peak_nits <= 0; dst is not touched then. */
 int hdrtv_post_rgb48_scaled(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W,
                             int pq, float peak_nits, uint16_t *dst, int dH, int dW);
+
+/* hdrtv_post_rgb48_scaled with anti-ringing of strength antiring / 256, antiring = 0..256 (256 = full strength).  Lanczos overshoots
+ * at a hard edge; on PQ codes the halo of a 0.25 / 0.75 step reaches 3382 codes (5.2 % of the range) and enters everything
+ * behind the scaler (the Y'CbCr conversion, deband, the content light level record).  The reference never shows an upscaled HDR
+ * frame without it: in its lower-resolution processing mode it sets mpv's scale-antiring from the processing size
+ * (_select_hdr_scale_antiring, gui_scaling.py:82-111).  Modelled on that separable form -- each pass is clamped to the two samples
+ * that bracket the sampling position and blended by the strength -- but mpv is not part of the reference tree: parity with it is
+ * UNPINNED, and the device is held to this integer rule, restated in tests/rgb48_antiring_ref.py, bit for bit.  Codes, tables and
+ * taps are steps 1 and 2 of hdrtv_post_rgb48_scaled; with a = antiring, tap_k the source index clamp(i0 - 2 + k), k = 0..5:
+ *  3a. horizontal, per source row y, channel and dx:
+ *        raw = sum_k s[y][tap_k] * qx_k                               (int32, as in step 3)
+ *        lo  = min(s[y][tap_2], s[y][tap_3]) << 14;   hi = max(s[y][tap_2], s[y][tap_3]) << 14
+ *        d   = clamp(raw, lo, hi) - raw
+ *        hor[y][dx] = raw + ((d * a + 128) >> 8)                      (flooring shift; d * a needs 64 bits; |hor| < 2^31)
+ *  3b. vertical, taps at rows tap_k = clamp(j0 - 2 + k) of hor:
+ *        raw = sum_k hor[tap_k][dx] * qy_k                            (int64)
+ *        lo  = min(hor[tap_2][dx], hor[tap_3][dx]) << 14;   hi = max(hor[tap_2][dx], hor[tap_3][dx]) << 14
+ *        d   = clamp(raw, lo, hi) - raw
+ *        v   = raw + ((d * a + 128) >> 8)
+ *        out = clamp((v + 2^27) >> 28, 0, 65535)
+ * a = 0 is hdrtv_post_rgb48_scaled exactly: the same launches (the delegation to the unscaled kernel at dH == H && dW == W
+ * included) and the same bytes.  An axis with m == n is untouched by any a (raw = the inner tap << 14 lies in [lo, hi]), so with a
+ * nonzero strength equal sizes delegate too.  a = 256 puts every output inside the min / max of the 2 x 2 source codes around it.
+ * A strength s in [0, 1] maps to a = floor(s * 256 + 0.5).  Shares the tap tables of hdrtv_post_rgb48_scaled; HDRTV_EINVAL for
+ * antiring outside 0..256 and for everything hdrtv_post_rgb48_scaled refuses; dst is not touched then. */
+int hdrtv_post_rgb48_scaled_ex(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W,
+                               int pq, float peak_nits, uint16_t *dst, int dH, int dW, int antiring);
 
 /* 10-bit limited-range Y'CbCr for an encoder (HEVC Main10, hardware encoders, ProRes): P010 and yuv420p10le are 3 bytes per pixel,
  * yuv422p10le 4, against the 6 of RGB48.  The reference's export converts on the CPU: it pipes rgb48le into ffmpeg, zscale goes to
