@@ -535,19 +535,21 @@ static void lanczos_taps(int n, int m, int4 *out)
     }
 }
 
-// Both entry points: antiring 0 = the plain rule (post_scale.hip's kernels), 1 .. 256 = post_scale_ar.hip's; one tap-table cache.
+// The three entry points: antiring 0 = the plain rule (post_scale.hip's kernels), 1 .. 256 = post_scale_ar.hip's; cas 0 = those,
+// 1032 .. 4096 = post_scale_cas.hip's with either kind of pass; one tap-table cache.
 static int post_rgb48_scaled(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
-                             uint16_t *dst, int dH, int dW, int antiring)
+                             uint16_t *dst, int dH, int dW, int antiring, int cas)
 {
     if (!c || !in || !dst || H <= 0 || W <= 0 || dH <= 0 || dW <= 0) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: bad argument");
     if (dH < H || dW < W) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: %dx%d -> %dx%d shrinks (enlarging only)", W, H, dW, dH);
     if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: bad dtype %d", dtype);
     if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: pq needs peak_nits > 0");
     if (antiring < 0 || antiring > 256) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled_ex: antiring %d is outside 0 .. 256", antiring);
+    if (cas != 0 && (cas < 1032 || cas > 4096)) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled_cas: cas %d is neither 0 nor in 1032 .. 4096", cas);
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = pq ? ensure_pq_table(c, "post_rgb48_scaled") : HDRTV_OK) return rc;
     // every tap table would be the identity, and anti-ringing leaves an identity alone (the sum lies between its inner taps): the
-    // unscaled kernel writes the same bytes
+    // unscaled kernel writes the same bytes.  Sharpening belongs to an upscale (the reference's chain): equal sizes are not sharpened
     if (dH == H && dW == W) {
         return launched(c, "post_rgb48_scaled", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd));
     }
@@ -571,6 +573,7 @@ static int post_rgb48_scaled(hdrtv_ctx *c, void *stream, const void *in, int dty
         it = c->ps_tabs.emplace(key, dev).first;
     }
     PostScaleParams p{in, dst, it->second, it->second + dW, c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
+    if (cas) return launched(c, "post_rgb48_scaled_cas", post_scale_cas_launch(p, antiring, cas, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
     if (antiring) return launched(c, "post_rgb48_scaled_ex", post_scale_ar_launch(p, antiring, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
     return launched(c, "post_rgb48_scaled", post_scale_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
@@ -578,13 +581,19 @@ static int post_rgb48_scaled(hdrtv_ctx *c, void *stream, const void *in, int dty
 int hdrtv_post_rgb48_scaled(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
                             uint16_t *dst, int dH, int dW)
 {
-    return post_rgb48_scaled(c, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, 0);
+    return post_rgb48_scaled(c, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, 0, 0);
 }
 
 int hdrtv_post_rgb48_scaled_ex(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
                                uint16_t *dst, int dH, int dW, int antiring)
 {
-    return post_rgb48_scaled(c, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, antiring);
+    return post_rgb48_scaled(c, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, antiring, 0);
+}
+
+int hdrtv_post_rgb48_scaled_cas(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
+                                uint16_t *dst, int dH, int dW, int antiring, int cas)
+{
+    return post_rgb48_scaled(c, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, antiring, cas);
 }
 
 // ------------------------------------------------------------------------------- letterbox

@@ -1,6 +1,7 @@
 // post_scale_tile.h -- the tile body of the fused quantise + Lanczos-3 upscale (gfx950), shared by post_scale.hip (AR = false:
-// hdrtv_post_rgb48_scaled, nothing of the anti-ringing is compiled) and post_scale_ar.hip (AR = true: hdrtv_post_rgb48_scaled_ex
-// with a strength of 1 .. 256).  include/hdrtv_mi355x.h states both integer rules.
+// hdrtv_post_rgb48_scaled, nothing of the anti-ringing is compiled), post_scale_ar.hip (AR = true: hdrtv_post_rgb48_scaled_ex
+// with a strength of 1 .. 256) and post_scale_cas.hip (CAS = true, AR either: hdrtv_post_rgb48_scaled_cas, contrast-adaptive
+// sharpening of the codes in front of the passes).  include/hdrtv_mi355x.h states the three integer rules.
 //
 // A workgroup of 256 lanes owns PS_TH x PS_TW = 32 x 64 output pixels:
 //   1. stage   the source footprint -- rows [ys0, ys0 + nr), columns [xs0, xs0 + nc), nr <= 38 and nc <= 70 whatever the ratio
@@ -26,6 +27,17 @@
 // (same dword = broadcast), its writes 64 consecutive dwords; the vertical ds_read_b128 of a 16-lane group covers one 256-byte
 // row of `hor` (rows are 64 dwords apart, so lanes of different output rows in a group still hit different banks).
 // 16.0 KiB + 28.5 KiB of LDS: three workgroups per CU.
+// Sharpening (CAS) splits the staging in two.  1a quantises the footprint with a halo of one pixel -- rows [ys0 - 1, ys0 + nr],
+// columns [xs0 - 1, xs0 + nc], clamped to the frame like the footprint itself -- into raw[ch][40][72] u16, 16.9 KiB that lie in
+// `hor`'s storage: `hor` is not written before the horizontal pass, and raw is dead once `codes` is complete, so the barrier that
+// already separates staging from the horizontal pass separates the two uses, and 1a / 1b need one barrier more.  1b writes
+// codes[ch][r][c] = the sharpened code of the FRAME pixel (cy, cx) = clamp(ys0 + r), clamp(xs0 + c), whose neighbours are the frame
+// pixels clamp(cy +- 1), clamp(cx +- 1): a tap outside the frame reads the sharpened edge pixel, as the rule has it, not a pixel
+// sharpened from neighbours that were clamped by position.  Frame row y lies at raw row y - (ys0 - 1), which is inside 0 .. nr + 1
+// for every row asked for (ys0 <= H - 3 and ys0 + nr - 1 >= 2, from the tap tables), columns alike; no index is clamped twice.
+// A lane takes one pixel and its three channels; consecutive lanes take consecutive columns, so the nine u16 reads of a wave are
+// 64 consecutive u16 = 32 consecutive dwords (two lanes per dword broadcast), split over two rows 36 dwords apart at a row's end.
+// The two floor divisions and the root are a float reciprocal / root and one exact integer correction step each (ps_cas below).
 #pragma once
 #include "common.h"
 #include "post_quant.h"
@@ -56,20 +68,78 @@ __device__ __forceinline__ long long ps_antiring_v(long long raw, int h2, int h3
     return raw + (long long)dh * (a << 8) + ((__mul24(dl, a) + 128) >> 8);
 }
 
-// a = the anti-ringing strength, 1 .. 256 (read only where AR)
-template <typename T, bool PQ, bool AR>
-__device__ __forceinline__ void post_scale_tile(const PostScaleParams p, const int a)
+// The sharpened code of e in the 3 x 3 neighbourhood a b c / d e f / g h i, K = the CAS code 1032 .. 4096 (include/hdrtv_mi355x.h
+// states the rule).  Every product is 24 x 24 bits.
+//   r = floor(n / m), n = q << 15 < 2^31, m <= 131070, r <= 32768: the float estimate n * rcp(m) is off by less than 2^-6 (three
+//       roundings of 2^-23 relative on a value <= 2^15), so its truncation is r or r +- 1 and the remainder says which.
+//   A = floor(sqrt(x)), x = r << 9 <= 2^24 exact in float, the root within one ulp of a value <= 4096: A or A +- 1, squares decide.
+//   floor(N / den), |N| < 2^31, 128 <= den <= 65536: only quotients inside +-65535 can survive the clamp of e + quotient, so the
+//       estimate is clamped to +-70000 first (there it is off by less than 2^-5; beyond, the true quotient is beyond +-69990 and the
+//       result saturates whatever the correction does), then corrected by its remainder, which fits int32 where it matters.
+__device__ __forceinline__ uint32_t ps_cas(int a, int b, int c, int d, int e, int f, int g, int h, int i, int K)
+{
+    const int mn5 = min(min(min(b, d), min(f, h)), e), mx5 = max(max(max(b, d), max(f, h)), e);
+    const int mn = mn5 + min(mn5, min(min(a, c), min(g, i))), mx = mx5 + max(mx5, max(max(a, c), max(g, i)));
+    const int n = min(mn, 131070 - mx) << 15, m = max(mx, 1);
+    int r = (int)((float)n * __builtin_amdgcn_rcpf((float)m));
+    const int rr = n - __mul24(r, m);
+    r += (rr >= m) - (rr < 0);
+    const int x = r << 9;
+    int A = (int)__builtin_amdgcn_sqrtf((float)x);
+    A += (__mul24(A + 1, A + 1) <= x) - (__mul24(A, A) > x);
+    const int den = 16 * K - 4 * A;
+    const int N = __mul24(A, 4 * e - (b + d + f + h)) + (den >> 1);
+    int v = (int)floorf(fminf(fmaxf((float)N * __builtin_amdgcn_rcpf((float)den), -70000.f), 70000.f));
+    const int vr = N - __mul24(v, den);
+    v += (vr >= den) - (vr < 0);
+    return (uint32_t)min(max(e + v, 0), 65535);
+}
+
+constexpr int PS_RR = PS_SR + 2, PS_RC = PS_SC + 2;        // the raw codes of the CAS form: the footprint and its halo
+
+// a = the anti-ringing strength, 1 .. 256 (read only where AR); cas = the CAS code, 1032 .. 4096 (read only where CAS)
+template <typename T, bool PQ, bool AR, bool CAS = false>
+__device__ __forceinline__ void post_scale_tile(const PostScaleParams p, const int a, const int cas = 0)
 {
     __shared__ uint16_t codes[3][PS_SR][PS_SCP];
     __shared__ __attribute__((aligned(16))) int hor[3][PS_SR][PS_TW];
+    static_assert(sizeof(uint16_t) * 3 * PS_RR * PS_RC <= sizeof(hor), "the raw codes of the CAS form lie in hor");
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * PS_TW, y0 = blockIdx.y * PS_TH;
     const int xl = min(x0 + PS_TW, p.dW) - 1, yl = min(y0 + PS_TH, p.dH) - 1;
     const int xs0 = p.xtab[x0].x, ys0 = p.ytab[y0].x;
     const int nc = min(p.xtab[xl].x + 6 - xs0, PS_SC), nr = min(p.ytab[yl].x + 6 - ys0, PS_SR);
 
-    // 1. stage + quantise
-    {
+    // 1a / 1b. stage + quantise with a halo, sharpen
+    if constexpr (CAS) {
+        uint16_t(*raw)[PS_RR][PS_RC] = reinterpret_cast<uint16_t(*)[PS_RR][PS_RC]>(&hor[0][0][0]);
+        const T *__restrict__ in = static_cast<const T *>(p.in);
+        const size_t plane = (size_t)p.H * p.W;
+        const int nch = nc + 2;
+        for (int i = tid; i < (nr + 2) * nch; i += 256) {
+            const int r = i / nch, c = i - r * nch;
+            const int sy = min(max(ys0 - 1 + r, 0), p.H - 1), sx = min(max(xs0 - 1 + c, 0), p.W - 1);
+            const size_t o = (size_t)sy * p.W + sx;
+            const float cr = (float)in[o], cg = (float)in[plane + o], cb = (float)in[2 * plane + o];
+            uint32_t q0, q1, q2;
+            quant_rgb<PQ>(cr, cg, cb, p.peak, p.pq_bnd, q0, q1, q2);
+            raw[0][r][c] = (uint16_t)q0;
+            raw[1][r][c] = (uint16_t)q1;
+            raw[2][r][c] = (uint16_t)q2;
+        }
+        __syncthreads();
+        for (int i = tid; i < nr * nc; i += 256) {
+            const int r = i / nc, c = i - r * nc;
+            const int cy = min(max(ys0 + r, 0), p.H - 1), cx = min(max(xs0 + c, 0), p.W - 1);
+            const int r1 = cy - (ys0 - 1), r0 = max(cy - 1, 0) - (ys0 - 1), r2 = min(cy + 1, p.H - 1) - (ys0 - 1);
+            const int c1 = cx - (xs0 - 1), c0 = max(cx - 1, 0) - (xs0 - 1), c2 = min(cx + 1, p.W - 1) - (xs0 - 1);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const uint16_t *t = raw[ch][r0], *m = raw[ch][r1], *b = raw[ch][r2];
+                codes[ch][r][c] = (uint16_t)ps_cas(t[c0], t[c1], t[c2], m[c0], m[c1], m[c2], b[c0], b[c1], b[c2], cas);
+            }
+        }
+    } else {
         const T *__restrict__ in = static_cast<const T *>(p.in);
         const size_t plane = (size_t)p.H * p.W;
         for (int i = tid; i < nr * nc; i += 256) {

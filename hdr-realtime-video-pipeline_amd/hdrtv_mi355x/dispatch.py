@@ -79,6 +79,8 @@ class _Mi355xWorker:
         self.cleanup = None if cleanup is None else L.OutputCleanup(*cleanup)
         # anti-ringing of enlarged frames (a strength in [0, 1] or "auto", validated by the dispatcher); absent: off
         self.antiring = kw.pop("antiring", 0.0)
+        # contrast-adaptive sharpening in front of that upscale (likewise); absent: off
+        self.cas = kw.pop("cas", 0.0)
         torch.cuda.set_device(device_index)
         with contextlib.redirect_stdout(sys.stderr):   # a worker's banner must not land on the parent's stdout (bench.py's one JSON line)
             self.proc = HDRTVNetMI355X(model, device=f"cuda:{device_index}", warmup_passes=0, **kw)
@@ -129,6 +131,8 @@ class _Mi355xWorker:
         out_fmt = dict(out_hw=(fmt.h, fmt.w), out_pix_fmt=fmt.pix_fmt, out_siting=fmt.siting, cleanup=self.cleanup)
         if self.antiring:
             out_fmt["antiring"] = self.antiring
+        if self.cas:
+            out_fmt["cas"] = self.cas
         self._buffers(h, w, tuple(frame.shape) + ((2,) if ten else ()), fmt)       # _raw is bytes: a u16 sample is two
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
@@ -374,7 +378,7 @@ class FrameDispatcher:
     def __init__(self, n_workers, height, width, sink, make_worker=mi355x_worker, init_args=None, devices=None, slots=3,
                  start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False, out_height=None,
                  out_width=None, out_pix_fmt="rgb48le", out_siting="left", deband=False, deband_range=16, deband_threshold=1311,
-                 dither="none", antiring=0.0):
+                 dither="none", antiring=0.0, cas=0.0):
         """``sink(index, rgb48_view)`` is called in index order from the reorder thread; the view is only valid during the
         call (the slot goes back to its worker afterwards).  ``numa``: workers pin themselves to their GPU's NUMA node
         (False: report only).  ``pix_fmt``: ``bgr24`` input frames are u8 (H, W, 3); ``yuv420p`` / ``nv12`` frames are u8
@@ -393,7 +397,9 @@ class FrameDispatcher:
         hands it to ``enqueue_frame(..., cleanup=)``.  Slot sizes do not depend on it.  ``antiring``: the anti-ringing strength of
         enlarged frames, 0 .. 1, or ``"auto"`` = ``lib.scale_antiring`` of the processing and the output size,
         kept as ``.antiring``; when it is not off it travels as ``init_args["antiring"]`` and the product's worker hands it to
-        ``enqueue_frame(..., antiring=)``.  Off (0.0, the default): the ``init_args`` of before."""
+        ``enqueue_frame(..., antiring=)``.  Off (0.0, the default): the ``init_args`` of before.  ``cas``: the strength of the
+        contrast-adaptive sharpening in front of that upscale, 0 .. 1, or ``"auto"`` = ``lib.scale_cas`` of the two sizes
+        (INTEGRATION.md 5c), kept as ``.cas`` and handed on as ``init_args["cas"]`` under the same condition."""
         if n_workers < 1 or slots < 2:
             raise ValueError("n_workers >= 1 and slots >= 2")
         from . import lib as _L
@@ -416,6 +422,9 @@ class FrameDispatcher:
         self.antiring = _L.check_antiring(antiring)
         if self.antiring:
             init_args["antiring"] = self.antiring
+        self.cas = _L.check_cas(cas)
+        if self.cas:
+            init_args["cas"] = self.cas
         self.pix_fmt = pix_fmt
         self._in_shape, self._in_dtype = _in_shape(self.h, self.w, pix_fmt), _in_dtype(pix_fmt)     # raises for an odd 10-bit size
         fmt = (pix_fmt, int(yuv_matrix), bool(yuv_full_range))

@@ -46,6 +46,7 @@ SYMBOLS = [
     ("hdrtv_post_pq_rgb48", _I, [_VP, _VP, _VP, _I, _I, _I, C.c_float, _VP]),
     ("hdrtv_post_rgb48_scaled", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I]),
     ("hdrtv_post_rgb48_scaled_ex", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I]),
+    ("hdrtv_post_rgb48_scaled_cas", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, _I]),
     ("hdrtv_post_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_rgb48_to_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_ycbcr10_bytes", C.c_int64, [_I, _I, _I]),
@@ -275,6 +276,56 @@ def resolve_antiring(value, proc_w, proc_h, out_w, out_h):
     """``check_antiring``'s result for a frame of known sizes -> a strength in [0, 1]: ``"auto"`` through ``scale_antiring``."""
     value = check_antiring(value)
     return scale_antiring(proc_w, proc_h, out_w, out_h) if value == "auto" else value
+
+
+CAS_CODE_MIN, CAS_CODE_MAX = 1032, 4096    # hdrtv_post_rgb48_scaled_cas: the CAS codes it takes beside 0 = off
+
+
+def cas_code(value):
+    """The ``cas`` argument of ``hdrtv_post_rgb48_scaled_cas`` for a sharpening strength in [0, 1] (ffmpeg's ``cas=<strength>``):
+    with ``c = floor(value * 256 + 0.5)``, 0 (off) for ``c == 0``, else ``K = 4096 - ((c * 3064 + 128) >> 8)``, 1032 .. 4084 --
+    ``K / 256`` is the filter's ``lerp(16, 4.03, strength)``.  The reference's 0.22 / 0.20 / 0.16 are 3426 / 3486 / 3605.
+    ``ValueError`` for anything that is not such a number (a bool, a string -- ``"auto"`` is resolved by ``resolve_cas`` where
+    the two sizes are known --, None, NaN, a value outside the range)."""
+    if isinstance(value, (bool, str, bytes)) or value is None:
+        raise ValueError(f"cas must be a number in [0, 1] (got {value!r})")
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"cas must be a number in [0, 1] (got {value!r})") from None
+    if not 0.0 <= v <= 1.0:                  # NaN fails both comparisons
+        raise ValueError(f"cas must be in [0, 1] (got {value!r})")
+    c = int(v * 256 + 0.5)
+    return 0 if c == 0 else 4096 - ((c * 3064 + 128) >> 8)
+
+
+def check_cas(value):
+    """A ``cas`` option as the worker, the dispatcher and the command line take it: ``"auto"`` (any case) -> ``"auto"``, a
+    strength in [0, 1] -> that float; ``ValueError`` otherwise."""
+    if isinstance(value, str) and value.lower() == "auto":
+        return "auto"
+    cas_code(value)
+    return float(value)
+
+
+def scale_cas(proc_w, proc_h, out_w, out_h):
+    """The reference's sharpening strength for a separable Lanczos kernel (``_select_mpv_cas_strength``, gui_scaling.py:114-138: what
+    it appends as ``cas=`` to the filter chain of its HDR frames when it upscales without its FSR shader): 0.0 unless both axes are
+    enlarged, else 0.22 for a processing size of at most 960x540 (either extent), 0.20 up to 1280x720, 0.16 above."""
+    proc_w, proc_h, out_w, out_h = int(proc_w), int(proc_h), int(out_w), int(out_h)
+    if not (out_w > proc_w and out_h > proc_h):
+        return 0.0
+    if proc_h <= 540 or proc_w <= 960:
+        return 0.22
+    if proc_h <= 720 or proc_w <= 1280:
+        return 0.20
+    return 0.16
+
+
+def resolve_cas(value, proc_w, proc_h, out_w, out_h):
+    """``check_cas``'s result for a frame of known sizes -> a strength in [0, 1]: ``"auto"`` through ``scale_cas``."""
+    value = check_cas(value)
+    return scale_cas(proc_w, proc_h, out_w, out_h) if value == "auto" else value
 
 
 _libs = {}

@@ -569,7 +569,7 @@ class RealtimePlayback:
 
 def parse_args(argv=None):
     """The command line of ``main`` -> the argparse namespace, checked (a bad value ends in ``ap.error``): ``.proc_wh`` and ``.out_wh``
-    hold the two sizes as ``(w, h)``, ``.cleanup`` the ``lib.OutputCleanup`` of --deband / --dither, ``.antiring`` ``"auto"`` or the
+    hold the two sizes as ``(w, h)``, ``.cleanup`` the ``lib.OutputCleanup`` of --deband / --dither, ``.antiring`` and ``.cas`` ``"auto"`` or the
     strength as a float (0.0: off)."""
     import argparse
 
@@ -604,6 +604,10 @@ def parse_args(argv=None):
     ap.add_argument("--antiring", default=None, metavar="{auto|0..1}", help="anti-ringing of the --out-size upscale "
                     "(hdrtv_post_rgb48_scaled_ex; INTEGRATION.md 5c): a strength in 0 .. 1, or auto = the reference's schedule by "
                     "processing size (0.30 up to 960x540, 0.22 up to 1280x720, 0.10 above); default: off")
+    ap.add_argument("--cas", default=None, metavar="{auto|0..1}", help="contrast-adaptive sharpening in front of the --out-size "
+                    "upscale (hdrtv_post_rgb48_scaled_cas; INTEGRATION.md 5c): a strength in 0 .. 1 as ffmpeg's cas filter takes it, "
+                    "or auto = the reference's schedule by processing size (0.22 up to 960x540, 0.20 up to 1280x720, 0.16 above); "
+                    "default: off")
     ap.add_argument("--no-hg", action="store_true")
     ap.add_argument("--hg-weights", default=None, help="HG weight file, or seeded:<n>")
     ap.add_argument("--max-throughput", action="store_true", help="do not pace to the source clock")
@@ -630,6 +634,15 @@ def parse_args(argv=None):
             a.antiring = _lib.check_antiring(a.antiring if a.antiring.lower() == "auto" else float(a.antiring))
         except ValueError as exc:
             ap.error(f"--antiring: {exc}")
+    if a.cas is None:
+        a.cas = 0.0
+    else:
+        if (owd, oht) == (wd, ht):
+            ap.error("--cas applies to an upscale: --out-size equals --size")
+        try:
+            a.cas = _lib.check_cas(a.cas if a.cas.lower() == "auto" else float(a.cas))
+        except ValueError as exc:
+            ap.error(f"--cas: {exc}")
     a.proc_wh, a.out_wh = (wd, ht), (owd, oht)
     return a
 
@@ -652,7 +665,8 @@ def main(argv=None):
                                     status_cb=lambda m: print(m, flush=True), out_w=owd, out_h=oht, out_pix_fmt=a.out_pix_fmt,
                                     out_siting=a.out_siting, light_stats=bool(a.light_level or a.light_level_json),
                                     deband=a.cleanup.deband, deband_range=a.cleanup.deband_range,
-                                    deband_threshold=a.cleanup.deband_threshold, dither=a.cleanup.dither, antiring=a.antiring)
+                                    deband_threshold=a.cleanup.deband_threshold, dither=a.cleanup.dither, antiring=a.antiring,
+                                    cas=a.cas)
     if not worker._load_model(a.precision):
         return 1
     sink = None
@@ -680,6 +694,8 @@ def main(argv=None):
         res["deband"], res["dither"] = a.cleanup.deband, a.cleanup.dither
     if a.antiring:
         res["antiring"] = _lib.resolve_antiring(a.antiring, wd, ht, owd, oht)
+    if a.cas:
+        res["cas"] = _lib.resolve_cas(a.cas, wd, ht, owd, oht)
     if cll is not None:
         res["max_cll"], res["max_fall"], res["light_frames"] = cll.max_cll, cll.max_fall, cll.frames
         if a.light_level_json:

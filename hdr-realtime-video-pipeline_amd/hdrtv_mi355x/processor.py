@@ -341,7 +341,7 @@ class HDRTVNetMI355X:
             scratch = self._ycc_scratch[key] = torch.empty((out.h, out.w, 3), dtype=torch.uint16, device=self.device)
         return scratch.data_ptr()
 
-    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None, antiring=0):
+    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None, antiring=0, cas=0):
         """The output conversion of a frame whose planar tensor lies at ``src_ptr``, to the ``lib.OutputFormat`` ``out`` at
         ``dst_ptr``: ``rgb48le`` at the processing size (``hdrtv_post_rgb48``) or enlarged to ``out.h`` x ``out.w``
         (``hdrtv_post_rgb48_scaled``); a 10-bit Y'CbCr layout in one kernel at the processing size (``hdrtv_post_ycbcr10``), or,
@@ -357,7 +357,11 @@ class HDRTVNetMI355X:
         ``_ex`` conversion behind the scaled codes otherwise; it does not enter the record, which is defined on RGB48 codes.
         ``antiring``: the anti-ringing code of an enlarged frame, 0 .. 256 (``lib.antiring_code``).  Nonzero and
         enlarged: ``hdrtv_post_rgb48_scaled_ex`` replaces ``hdrtv_post_rgb48_scaled``, and everything behind the scaler -- deband,
-        the conversion from codes, the record -- works on the anti-ringed codes.  0, or an unscaled frame: the launches above."""
+        the conversion from codes, the record -- works on the anti-ringed codes.  0, or an unscaled frame: the launches above.
+        ``cas``: the CAS code of an enlarged frame, 0 or 1032 .. 4096 (``lib.cas_code``).  Nonzero and enlarged:
+        ``hdrtv_post_rgb48_scaled_cas`` (which takes ``antiring`` too) sharpens the codes in front of the scaler, and everything
+        behind it sees the sharpened, scaled codes.  0, or an unscaled frame: the launches above.  This is the one place that
+        chooses among the three entry points."""
         scaled = (out.h, out.w) != (h, w)
         rect = (0, 0, out.w, out.h) if light_rect is None else tuple(int(v) for v in light_rect)
         active = cleanup is not None and cleanup.active
@@ -376,7 +380,10 @@ class HDRTVNetMI355X:
             return
         rgb_ptr = dst_ptr if out.is_rgb48 else self._scratch(scratch_key, out)
         raw_ptr = self._scratch((scratch_key, "raw"), out) if deband else rgb_ptr       # deband never works in place
-        if scaled and antiring:
+        if scaled and cas:
+            self._chk(self._lib.hdrtv_post_rgb48_scaled_cas(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, int(antiring),
+                                                            int(cas)), "hdrtv_post_rgb48_scaled_cas")
+        elif scaled and antiring:
             self._chk(self._lib.hdrtv_post_rgb48_scaled_ex(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, int(antiring)),
                       "hdrtv_post_rgb48_scaled_ex")
         elif scaled:
@@ -433,7 +440,16 @@ class HDRTVNetMI355X:
             return 0
         return _L.antiring_code(_L.resolve_antiring(antiring, w, h, out.w, out.h))
 
-    def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out, light_ptr=None, light_rect=None, cleanup=None, antiring=0):
+    @staticmethod
+    def _cas_for(cas, h, w, out):
+        """The ``cas`` argument of ``enqueue_frame*`` (a strength in [0, 1], or ``"auto"``: ``lib.scale_cas`` of the two sizes) -> the
+        code ``_post_out`` takes."""
+        if type(cas) in (float, int) and cas == 0:                    # off, the default: nothing to resolve on the hot path
+            return 0
+        return _L.cas_code(_L.resolve_cas(cas, w, h, out.w, out.h))
+
+    def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out, light_ptr=None, light_rect=None, cleanup=None, antiring=0,
+                 cas=0):
         """The body of ``enqueue_frame*``: the preprocess entry point ``pre`` (named ``what``) on its source arguments ``src``,
         ``hdrtv_infer_lane`` and ``_post_out``, all on the lane's buffers and ``stream`` (default: the lane's own)."""
         self._ensure_buffers(h, w)
@@ -442,10 +458,10 @@ class HDRTVNetMI355X:
         self._chk(pre(self._ctx, st, *src, h, w, tin.data_ptr(), tcond.data_ptr()), what)
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), self._out_dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, antiring)
+        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, antiring, cas)
 
     def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le",
-                      out_siting="left", light_ptr=None, light_rect=None, cleanup=None, antiring=0.0):
+                      out_siting="left", light_ptr=None, light_rect=None, cleanup=None, antiring=0.0, cas=0.0):
         """One frame of the hot path on lane ``lane``, stream-ordered and without any host synchronisation: u8 BGR frame in
         device memory at ``src_bgr_ptr`` -> hdrtv_preprocess -> hdrtv_infer_lane -> hdrtv_post_rgb48 -> u16 RGB48 at the device
         address ``dst_rgb48_ptr``.  ``stream``: a ``torch.cuda.Stream`` (default: the lane's own).  Frames enqueued on different
@@ -459,30 +475,35 @@ class HDRTVNetMI355X:
         ``cleanup``: a ``lib.OutputCleanup`` (``lib.output_cleanup``): deband and / or ordered dither of the delivered frame
         (``_post_out``); None: neither, and the bytes of before.  ``antiring``: the anti-ringing strength of an
         enlarged frame, 0 .. 1, or ``"auto"`` = ``lib.scale_antiring`` of the two sizes (``hdrtv_post_rgb48_scaled_ex``;
-        INTEGRATION.md 5c); 0.0, or a frame delivered at the processing size: the launches and bytes of before."""
+        INTEGRATION.md 5c); 0.0, or a frame delivered at the processing size: the launches and bytes of before.  ``cas``: the strength
+        of the contrast-adaptive sharpening in front of that upscale, 0 .. 1, or ``"auto"`` = ``lib.scale_cas`` of the two sizes
+        (``hdrtv_post_rgb48_scaled_cas``); 0.0, or a frame at the processing size: the launches and bytes of before."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         self._enqueue(lane, self._lib.hdrtv_preprocess, "hdrtv_preprocess", (src_bgr_ptr,), h, w, dst_rgb48_ptr, stream, out,
-                      light_ptr, light_rect, self._cleanup_for(cleanup, out), self._antiring_for(antiring, h, w, out))
+                      light_ptr, light_rect, self._cleanup_for(cleanup, out), self._antiring_for(antiring, h, w, out),
+                      self._cas_for(cas, h, w, out))
 
     def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None,
                              out_hw=None, out_pix_fmt="rgb48le", out_siting="left", light_ptr=None, light_rect=None, cleanup=None,
-                             antiring=0.0):
+                             antiring=0.0, cas=0.0):
         """``enqueue_frame`` of an 8-bit 4:2:0 frame: the planes lie back to back at the device address ``src_ptr`` (the
         ``(h*3//2, w)`` u8 array ``preprocess_yuv420`` takes) and ``hdrtv_preprocess_yuv420`` replaces ``hdrtv_preprocess``."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         planes = _yuv_planes(src_ptr, int(h), int(w), layout, matrix, full_range)
         self._enqueue(lane, self._lib.hdrtv_preprocess_yuv420, "hdrtv_preprocess_yuv420", planes, h, w, dst_rgb48_ptr, stream, out,
-                      light_ptr, light_rect, self._cleanup_for(cleanup, out), self._antiring_for(antiring, h, w, out))
+                      light_ptr, light_rect, self._cleanup_for(cleanup, out), self._antiring_for(antiring, h, w, out),
+                      self._cas_for(cas, h, w, out))
 
     def enqueue_frame_ycbcr10(self, lane, src_ptr, h, w, dst_ptr, *, pix_fmt, matrix=709, full_range=False, stream=None, out_hw=None,
-                              out_pix_fmt="rgb48le", out_siting="left", cleanup=None, antiring=0.0):
+                              out_pix_fmt="rgb48le", out_siting="left", cleanup=None, antiring=0.0, cas=0.0):
         """``enqueue_frame`` of a 10-bit Y'CbCr frame (``pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le``): the planes lie
         back to back at the device address ``src_ptr`` (the u16 array ``preprocess_ycbcr10`` takes) and
         ``hdrtv_preprocess_ycbcr10`` replaces ``hdrtv_preprocess``."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         planes = _ycbcr10_planes(src_ptr, int(h), int(w), pix_fmt, matrix, full_range)
         self._enqueue(lane, self._lib.hdrtv_preprocess_ycbcr10, "hdrtv_preprocess_ycbcr10", planes, h, w, dst_ptr, stream, out,
-                      cleanup=self._cleanup_for(cleanup, out), antiring=self._antiring_for(antiring, h, w, out))
+                      cleanup=self._cleanup_for(cleanup, out), antiring=self._antiring_for(antiring, h, w, out),
+                      cas=self._cas_for(cas, h, w, out))
 
     def _upload(self, key, src, staged=None):
         """Device pointer of the host u8 array ``src``, uploaded through the staging slot kept per ``key`` in ``_staging``: a
@@ -700,11 +721,12 @@ class HDRTVNetMI355X:
         return self._pin_output.numpy()
 
     @torch.inference_mode()
-    def postprocess_rgb48_scaled(self, output, out_w, out_h, pq=False, peak_nits=1000.0, antiring=0.0):
+    def postprocess_rgb48_scaled(self, output, out_w, out_h, pq=False, peak_nits=1000.0, antiring=0.0, cas=0.0):
         """RGB48 at the display size: the u16 codes of ``hdrtv_post_rgb48`` (``pq=True``: of
         ``hdrtv_post_pq_rgb48`` at ``peak_nits``) upscaled to ``out_h`` x ``out_w`` by ``hdrtv_post_rgb48_scaled`` in one kernel.
         ``antiring``: the anti-ringing strength, 0 .. 1, or ``"auto"`` = ``lib.scale_antiring`` of the two sizes; nonzero:
-        ``hdrtv_post_rgb48_scaled_ex``.  Returns a new device u16 ``(out_h, out_w, 3)`` tensor; stream-ordered on the current stream,
+        ``hdrtv_post_rgb48_scaled_ex``.  ``cas``: the strength of the contrast-adaptive sharpening in front of the upscale, 0 .. 1, or
+        ``"auto"`` = ``lib.scale_cas`` of the two sizes; nonzero: ``hdrtv_post_rgb48_scaled_cas``.  Returns a new device u16 ``(out_h, out_w, 3)`` tensor; stream-ordered on the current stream,
         no synchronisation."""
         if isinstance(output, (tuple, list)):
             output = output[0]
@@ -715,11 +737,14 @@ class HDRTVNetMI355X:
         if out_w < w or out_h < h:
             raise ValueError(f"output size {out_w}x{out_h} is below the processing size {w}x{h} (enlarging only)")
         code = _L.antiring_code(_L.resolve_antiring(antiring, w, h, out_w, out_h))
+        kcas = _L.cas_code(_L.resolve_cas(cas, w, h, out_w, out_h))
         output = output.contiguous()
         dst = torch.empty((out_h, out_w, 3), dtype=torch.uint16, device=self.device)
         args = (self._ctx, self._stream(), output.data_ptr(), _dtype_code(output), h, w, 1 if pq else 0, float(peak_nits), dst.data_ptr(),
                 out_h, out_w)
-        if code:
+        if kcas:
+            self._chk(self._lib.hdrtv_post_rgb48_scaled_cas(*args, code, kcas), "hdrtv_post_rgb48_scaled_cas")
+        elif code:
             self._chk(self._lib.hdrtv_post_rgb48_scaled_ex(*args, code), "hdrtv_post_rgb48_scaled_ex")
         else:
             self._chk(self._lib.hdrtv_post_rgb48_scaled(*args), "hdrtv_post_rgb48_scaled")

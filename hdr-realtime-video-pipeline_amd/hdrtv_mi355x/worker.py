@@ -123,7 +123,7 @@ class HeadlessPipelineWorker:
     def __init__(self, weights_dir, use_hg=True, proc_w=1920, proc_h=1080, hg_weights=None,
                  status_cb=None, buffer_frames=1, out_w=None, out_h=None, out_pix_fmt="rgb48le", out_siting="left",
                  light_stats=False, light_rect=None, deband=False, deband_range=_L.DEBAND_RANGE,
-                 deband_threshold=_L.DEBAND_THRESHOLD, dither="none", antiring=0.0):
+                 deband_threshold=_L.DEBAND_THRESHOLD, dither="none", antiring=0.0, cas=0.0):
         self._weights_dir = weights_dir
         self._use_hg = bool(use_hg)
         self._hg_override = hg_weights
@@ -141,6 +141,10 @@ class HeadlessPipelineWorker:
         # processing and delivered size (what the reference hands mpv), so a hot-swap of the processing resolution changes it.  Off
         # (0.0, the default), or a frame delivered at the processing size: the launches and bytes of before.
         self._antiring = _L.check_antiring(antiring)
+        # contrast-adaptive sharpening in front of that upscale: a strength in [0, 1], or "auto" = lib.scale_cas of
+        # each frame's two sizes (what the reference appends to its filter chain as cas=), resolved per frame like the anti-ringing.
+        # Off (0.0, the default), or a frame delivered at the processing size: the launches and bytes of before.
+        self._cas = _L.check_cas(cas)
         # HDR10 content light level: every delivered frame carries its record (``.light``), measured on the
         # device from the codes the sink receives over ``light_rect = (x0, y0, rw, rh)`` in delivered-frame coordinates (None: the
         # whole frame), and ``content_light`` accumulates MaxCLL / MaxFALL in delivery order.  Off: nothing is launched or allocated.
@@ -349,7 +353,8 @@ class HeadlessPipelineWorker:
         within 250 ms, feeders.py:166-167) falls back to one blocking pinned buffer as the reference
         does (209-235): convert, copy, synchronise the stream, hand the finished frame over.  ``out_hw = (out_h, out_w)``: the
         ring, the fallback buffer and the frame are at that size and the conversion is ``hdrtv_post_rgb48_scaled`` (with the
-        worker's ``antiring``, resolved here from the tensor's and the delivered size: ``hdrtv_post_rgb48_scaled_ex``).  With a
+        worker's ``antiring``, resolved here from the tensor's and the delivered size: ``hdrtv_post_rgb48_scaled_ex``; with its ``cas``, resolved alike:
+        ``hdrtv_post_rgb48_scaled_cas``).  With a
         Y'CbCr ``out_pix_fmt`` the slot (an RGB48 slot holds any of the layouts) receives the planes, only the frame's bytes are
         committed (``hdrtv_ring_commit_bytes``) and the frame is a 1-D u16 view of them."""
         p = self._processor
@@ -365,19 +370,20 @@ class HeadlessPipelineWorker:
         out = self._out.at(h, w)
         shape = out.shape
         antiring = _L.antiring_code(_L.resolve_antiring(self._antiring, tw, th, w, h)) if self._antiring else 0
+        cas = _L.cas_code(_L.resolve_cas(self._cas, tw, th, w, h)) if self._cas else 0
 
         def convert(dst, key):
             """The frame into ``dst`` and, when measured, its light level record into the pinned record kept per ``key``, all on
             ``st``: whatever is recorded on ``st`` afterwards (the slot's ready event) covers both.  Returns that record."""
             if not self._light:
-                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, antiring=antiring)
+                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, antiring=antiring, cas=cas)
                 return None
             bufs = self._light_bufs.get(key)
             if bufs is None:
                 bufs = self._light_bufs[key] = (torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, device=p.device),
                                                 torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, pin_memory=True))
             p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", bufs[0].data_ptr(), self._light_rect,
-                        self._cleanup, antiring)
+                        self._cleanup, antiring, cas)
             with torch.cuda.stream(st):
                 bufs[1].copy_(bufs[0], non_blocking=True)
             return bufs[1].numpy()

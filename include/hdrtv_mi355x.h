@@ -180,6 +180,35 @@ int hdrtv_post_rgb48_scaled(hdrtv_ctx *ctx, void *stream, const void *dev_out, i
 int hdrtv_post_rgb48_scaled_ex(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W,
                                int pq, float peak_nits, uint16_t *dst, int dH, int dW, int antiring);
 
+/* hdrtv_post_rgb48_scaled_ex with contrast-adaptive sharpening of the codes in front of the scaler.  For any upscale that does not go
+ * through its FSR shader the reference appends cas=<strength> to the video filter chain of its HDR frames
+ * (_select_mpv_cas_strength, gui_scaling.py:114-138; 0.22 / 0.20 / 0.16 by processing size): FidelityFX CAS as ffmpeg's cas filter,
+ * in vf, so on the PQ-coded RGB48 frame at the processing size, before the display scaler and its anti-ringing.  A headless sink
+ * has no such chain in front of it.  ffmpeg is not part of the reference tree: parity with its float filter is UNPINNED, and the
+ * device is held to this integer rule, restated in tests/rgb48_cas_ref.py, bit for bit.  cas = 0 is off; otherwise cas = K, the
+ * CAS code 1032..4096; a strength s in (0, 1] maps to K = 4096 - ((c * 3064 + 128) >> 8) with c = floor(s * 256 + 0.5), 1032..4084
+ * (K / 256 = ffmpeg's lerp(16, 4.03, s); 0.22 -> 3426, 0.20 -> 3486, 0.16 -> 3605).
+ *  1s. between steps 1 and 2 of hdrtv_post_rgb48_scaled, per channel, on the u16 codes s of the FRAME: for e = s[y][x] with the
+ *      3 x 3 neighbourhood a b c / d e f / g h i, the frame's edge pixels repeated (row y - 1 is row max(y - 1, 0), ...):
+ *        mn  = min(b,d,e,f,h) + min(a..i);   mx = max(b,d,e,f,h) + max(a..i)
+ *        q   = min(mn, 131070 - mx)                                   (0 <= q <= mx)
+ *        r   = floor((q << 15) / mx), 0 for mx = 0                    (r <= 32768; q << 15 < 2^32)
+ *        A   = floor(sqrt(r << 9))                                    (0..4096: the amplitude in Q12)
+ *        den = 16 * K - 4 * A                                         (> 0, as K >= 1032)
+ *        t   = 4 * e - (b + d + f + h)
+ *        s'[y][x] = clamp(e + floor((A * t + (den >> 1)) / den), 0, 65535)     (floor towards minus infinity; |A * t| < 2^30)
+ *      This is ffmpeg's (e + w * (b+d+f+h)) / (1 + 4w), w = -amp / lerp(16, 4.03, s), amp = sqrt(clip(min(mn, 2*max - mx) / mx, 0, 1)),
+ *      written as e + A * t / den.  A flat neighbourhood returns e.
+ *  Steps 2, 3 / 3a, 3b then run on s': a tap outside the frame reads the SHARPENED edge pixel (whose neighbourhood was clamped from
+ *  the edge pixel), and anti-ringing of strength antiring acts on the sharpened codes, as in the reference's chain.
+ * cas = 0 is hdrtv_post_rgb48_scaled_ex exactly: the same launches and the same bytes.  Equal sizes (dH == H && dW == W) delegate to
+ * the unscaled kernel and are NOT sharpened, whatever cas: the reference sharpens only when it upscales.  With one axis at identity
+ * the filter applies in full (it is two-dimensional on the source).  Shares the tap tables; the LDS of the plain form.
+ * HDRTV_EINVAL for a cas that is neither 0 nor in 1032..4096 and for everything hdrtv_post_rgb48_scaled_ex refuses, before any
+ * device call; dst is not touched then. */
+int hdrtv_post_rgb48_scaled_cas(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W,
+                                int pq, float peak_nits, uint16_t *dst, int dH, int dW, int antiring, int cas);
+
 /* 10-bit limited-range Y'CbCr for an encoder (HEVC Main10, hardware encoders, ProRes): P010 and yuv420p10le are 3 bytes per pixel,
  * yuv422p10le 4, against the 6 of RGB48.  The reference's export converts on the CPU: it pipes rgb48le into ffmpeg, zscale goes to
  * BT.2020nc limited range and format=yuv422p10le feeds prores_ks (gui_export.py:948-1005).  The network's output is PQ-encoded BT.2020
