@@ -264,6 +264,8 @@ struct hdrtv_ctx {
     float *pq_bnd = nullptr;              // hdrtv_post_pq_rgb48: the 65536 code boundaries of the PQ quantiser (built on first use)
     // hdrtv_post_rgb48_scaled: device tap tables per (H, W, dH, dW), xtab [dW] then ytab [dH]; built on first use of a geometry
     std::map<std::array<int, 4>, int4 *> ps_tabs;
+    // hdrtv_post_rgb48_fsr: device position tables per (H, W, dH, dW), xtab [dW] then ytab [dH]; built on first use of a geometry
+    std::map<std::array<int, 4>, int2 *> fsr_tabs;
     // objective metrics partial sums
     double *mt_dev = nullptr;
     size_t mt_cap = 0;

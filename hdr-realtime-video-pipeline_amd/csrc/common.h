@@ -412,6 +412,18 @@ struct PostScaleParams {
     int H, W, dH, dW;
 };
 
+// Fused quantise + FSR upscale (post_fsr.hip): the same tensors and the same PS_TH x PS_TW tile, H <= dH <= 2H and W <= dW <= 2W.
+// xtab [dW] / ytab [dH]: per destination index {fp = floor(p), the bits of the float32 pp = p - fp}, p = (d + 0.5) * n / m - 0.5 in
+// double (include/hdrtv_mi355x.h states the rule).
+struct PostFsrParams {
+    const void *in;
+    uint16_t *dst;
+    const int2 *xtab, *ytab;
+    const float *pq_bnd;             // PQ variant: the code boundaries of hdrtv_post_pq_rgb48
+    float peak;
+    int H, W, dH, dW;
+};
+
 // 10-bit limited-range BT.2020nc Y'CbCr output (post_ycbcr.hip; include/hdrtv_mi355x.h states the integer rule): a workgroup owns
 // YC_TH x YC_TW luma pixels.  fmt / siting carry the header's HDRTV_YCC_* / HDRTV_SITING_* values; pitches in u16 elements.
 constexpr int YC_TW = 128, YC_TH = 16;

@@ -76,6 +76,7 @@ int hdrtv_destroy(hdrtv_ctx *c)
     if (c->pq_bnd) (void)hipFree(c->pq_bnd);
     if (c->lb_dev) (void)hipFree(c->lb_dev);
     for (auto &kv : c->ps_tabs) (void)hipFree(kv.second);
+    for (auto &kv : c->fsr_tabs) (void)hipFree(kv.second);
     if (c->mt_dev) (void)hipFree(c->mt_dev);
     free_workspaces(c);
     if (c->wts.dev) (void)hipFree(c->wts.dev);
@@ -594,6 +595,61 @@ int hdrtv_post_rgb48_scaled_cas(hdrtv_ctx *c, void *stream, const void *in, int 
                                 uint16_t *dst, int dH, int dW, int antiring, int cas)
 {
     return post_rgb48_scaled(c, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, antiring, cas);
+}
+
+// Position table of one axis of hdrtv_post_rgb48_fsr (the rule: include/hdrtv_mi355x.h), n source -> m destination samples: per
+// destination index fp = floor(p) and the bits of the float32 pp = p - fp.
+static void fsr_positions(int n, int m, int2 *out)
+{
+    for (int d = 0; d < m; ++d) {
+        const double p = (d + 0.5) * n / m - 0.5, f = std::floor(p);
+        const float pp = (float)(p - f);
+        int bits;
+        memcpy(&bits, &pp, sizeof bits);
+        out[d] = make_int2((int)f, bits);
+    }
+}
+
+int hdrtv_post_rgb48_fsr(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
+                         uint16_t *dst, int dH, int dW, int rcas, float sharpness)
+{
+    if (!c || !in || !dst || H <= 0 || W <= 0 || dH <= 0 || dW <= 0) return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: bad argument");
+    if (dH < H || dW < W) return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: %dx%d -> %dx%d shrinks (enlarging only)", W, H, dW, dH);
+    if (dH > 2 * (long long)H || dW > 2 * (long long)W)
+        return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: %dx%d -> %dx%d is more than 2x on an axis", W, H, dW, dH);
+    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: bad dtype %d", dtype);
+    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: pq needs peak_nits > 0");
+    if (rcas != 0 && rcas != 1) return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: rcas %d is neither 0 nor 1", rcas);
+    if (rcas && !(sharpness >= 0.f && sharpness <= 2.f))          // NaN fails both comparisons
+        return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: sharpness %g is outside 0 .. 2", (double)sharpness);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = pq ? ensure_pq_table(c, "post_rgb48_fsr") : HDRTV_OK) return rc;
+    // the shader runs only when the frame is enlarged: equal sizes are the unscaled kernel's bytes, whatever rcas
+    if (dH == H && dW == W) {
+        return launched(c, "post_rgb48_fsr", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd));
+    }
+    // first use of a geometry builds its tables (allocates, copies); every later call finds them and only launches
+    const std::array<int, 4> key{H, W, dH, dW};
+    auto it = c->fsr_tabs.find(key);
+    if (it == c->fsr_tabs.end()) {
+        if (c->fsr_tabs.size() >= 16) {
+            for (auto &kv : c->fsr_tabs) (void)hipFree(kv.second);
+            c->fsr_tabs.clear();
+        }
+        std::vector<int2> tab((size_t)dW + dH);
+        fsr_positions(W, dW, tab.data());
+        fsr_positions(H, dH, tab.data() + dW);
+        int2 *dev = nullptr;
+        if (hipMalloc((void **)&dev, tab.size() * sizeof(int2)) != hipSuccess) return fail(c, HDRTV_ENOMEM, "post_rgb48_fsr: table allocation failed");
+        if (hipMemcpy(dev, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(dev);
+            return fail(c, HDRTV_EHIP, "post_rgb48_fsr: table upload failed");
+        }
+        it = c->fsr_tabs.emplace(key, dev).first;
+    }
+    PostFsrParams p{in, dst, it->second, it->second + dW, c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
+    const float sharp = rcas ? (float)std::exp2(-(double)sharpness) : 0.f;
+    return launched(c, "post_rgb48_fsr", post_fsr_launch(p, rcas, sharp, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
 // ------------------------------------------------------------------------------- letterbox

@@ -81,6 +81,9 @@ class _Mi355xWorker:
         self.antiring = kw.pop("antiring", 0.0)
         # contrast-adaptive sharpening in front of that upscale (likewise); absent: off
         self.cas = kw.pop("cas", 0.0)
+        # the scaler of enlarged frames ("fsr" = hdrtv_post_rgb48_fsr with its RCAS sharpness, or None = EASU alone); absent: Lanczos
+        self.scaler = kw.pop("scaler", "lanczos")
+        self.fsr_sharpness = kw.pop("fsr_sharpness", L.FSR_SHARPNESS)
         torch.cuda.set_device(device_index)
         with contextlib.redirect_stdout(sys.stderr):   # a worker's banner must not land on the parent's stdout (bench.py's one JSON line)
             self.proc = HDRTVNetMI355X(model, device=f"cuda:{device_index}", warmup_passes=0, **kw)
@@ -133,6 +136,8 @@ class _Mi355xWorker:
             out_fmt["antiring"] = self.antiring
         if self.cas:
             out_fmt["cas"] = self.cas
+        if self.scaler != "lanczos":
+            out_fmt["scaler"], out_fmt["fsr_sharpness"] = self.scaler, self.fsr_sharpness
         self._buffers(h, w, tuple(frame.shape) + ((2,) if ten else ()), fmt)       # _raw is bytes: a u16 sample is two
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
@@ -378,7 +383,7 @@ class FrameDispatcher:
     def __init__(self, n_workers, height, width, sink, make_worker=mi355x_worker, init_args=None, devices=None, slots=3,
                  start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False, out_height=None,
                  out_width=None, out_pix_fmt="rgb48le", out_siting="left", deband=False, deband_range=16, deband_threshold=1311,
-                 dither="none", antiring=0.0, cas=0.0):
+                 dither="none", antiring=0.0, cas=0.0, scaler="lanczos", fsr_sharpness=0.2):
         """``sink(index, rgb48_view)`` is called in index order from the reorder thread; the view is only valid during the
         call (the slot goes back to its worker afterwards).  ``numa``: workers pin themselves to their GPU's NUMA node
         (False: report only).  ``pix_fmt``: ``bgr24`` input frames are u8 (H, W, 3); ``yuv420p`` / ``nv12`` frames are u8
@@ -399,7 +404,12 @@ class FrameDispatcher:
         kept as ``.antiring``; when it is not off it travels as ``init_args["antiring"]`` and the product's worker hands it to
         ``enqueue_frame(..., antiring=)``.  Off (0.0, the default): the ``init_args`` of before.  ``cas``: the strength of the
         contrast-adaptive sharpening in front of that upscale, 0 .. 1, or ``"auto"`` = ``lib.scale_cas`` of the two sizes
-        (INTEGRATION.md 5c), kept as ``.cas`` and handed on as ``init_args["cas"]`` under the same condition."""
+        (INTEGRATION.md 5c), kept as ``.cas`` and handed on as ``init_args["cas"]`` under the same condition.  ``scaler``: ``"lanczos"``
+        (the default) or ``"fsr"`` = the product's worker enlarges through ``hdrtv_post_rgb48_fsr``, the reference's default upscaler
+        (INTEGRATION.md 5c): the output size is then at most twice the processing size per axis, ``antiring`` and ``cas`` are 0
+        (``"auto"`` resolves to 0, an explicit nonzero value is a ``ValueError``), and ``fsr_sharpness`` is its RCAS sharpness, 0 .. 2,
+        or None = EASU alone; kept as ``.scaler`` / ``.fsr_sharpness`` and handed on as ``init_args["scaler"]`` /
+        ``init_args["fsr_sharpness"]`` only when the scaler is not the default: otherwise the ``init_args`` of before."""
         if n_workers < 1 or slots < 2:
             raise ValueError("n_workers >= 1 and slots >= 2")
         from . import lib as _L
@@ -419,12 +429,16 @@ class FrameDispatcher:
         init_args = dict(init_args or {})
         if self.cleanup.active:
             init_args["cleanup"] = tuple(self.cleanup)
-        self.antiring = _L.check_antiring(antiring)
+        self.scaler = _L.check_scaler(scaler)
+        self.antiring, self.cas = _L.scaler_options(self.scaler, antiring, cas)
+        self.fsr_sharpness = _L.check_fsr_sharpness(fsr_sharpness)
         if self.antiring:
             init_args["antiring"] = self.antiring
-        self.cas = _L.check_cas(cas)
         if self.cas:
             init_args["cas"] = self.cas
+        if self.scaler == "fsr":
+            _L.check_fsr_size(self.w, self.h, self.out_w, self.out_h)
+            init_args["scaler"], init_args["fsr_sharpness"] = self.scaler, self.fsr_sharpness
         self.pix_fmt = pix_fmt
         self._in_shape, self._in_dtype = _in_shape(self.h, self.w, pix_fmt), _in_dtype(pix_fmt)     # raises for an odd 10-bit size
         fmt = (pix_fmt, int(yuv_matrix), bool(yuv_full_range))

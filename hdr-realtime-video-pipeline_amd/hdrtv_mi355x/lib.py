@@ -47,6 +47,7 @@ SYMBOLS = [
     ("hdrtv_post_rgb48_scaled", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I]),
     ("hdrtv_post_rgb48_scaled_ex", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I]),
     ("hdrtv_post_rgb48_scaled_cas", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, _I]),
+    ("hdrtv_post_rgb48_fsr", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, C.c_float]),
     ("hdrtv_post_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_rgb48_to_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_ycbcr10_bytes", C.c_int64, [_I, _I, _I]),
@@ -326,6 +327,60 @@ def resolve_cas(value, proc_w, proc_h, out_w, out_h):
     """``check_cas``'s result for a frame of known sizes -> a strength in [0, 1]: ``"auto"`` through ``scale_cas``."""
     value = check_cas(value)
     return scale_cas(proc_w, proc_h, out_w, out_h) if value == "auto" else value
+
+
+SCALERS = ("lanczos", "fsr")               # what enlarges a frame to the delivered size: the fused Lanczos passes, or hdrtv_post_rgb48_fsr
+FSR_MAX_RATIO = 2                          # hdrtv_post_rgb48_fsr: the largest ratio per axis (the shader's EASU stage stops there)
+FSR_SHARPNESS = 0.2                        # the reference's RCAS sharpness (0 = the sharpest, 2 = the mildest)
+
+
+def check_scaler(value="lanczos"):
+    """A ``scaler`` option as the processor, the worker, the dispatcher and the command line take it: ``"lanczos"`` (the default: the
+    fused Lanczos upscale with its ``antiring`` and ``cas``) or ``"fsr"`` (``hdrtv_post_rgb48_fsr``, the reference's default), any
+    case; ``ValueError`` otherwise."""
+    if not isinstance(value, str) or value.lower() not in SCALERS:
+        raise ValueError(f"scaler must be one of {list(SCALERS)} (got {value!r})")
+    return value.lower()
+
+
+def check_fsr_sharpness(value):
+    """An ``fsr_sharpness`` option: ``None`` = EASU alone (``rcas = 0``), else the RCAS sharpness, a float in [0, 2] (0 = the
+    sharpest; the reference's 0.2).  ``ValueError`` for anything else (a bool, a string, NaN, a value outside the range)."""
+    if value is None:
+        return None
+    if isinstance(value, (bool, str, bytes)):
+        raise ValueError(f"fsr_sharpness must be None or a number in [0, 2] (got {value!r})")
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"fsr_sharpness must be None or a number in [0, 2] (got {value!r})") from None
+    if not 0.0 <= v <= 2.0:                  # NaN fails both comparisons
+        raise ValueError(f"fsr_sharpness must be in [0, 2] (got {value!r})")
+    return v
+
+
+def check_fsr_size(proc_w, proc_h, out_w, out_h):
+    """``ValueError`` unless ``hdrtv_post_rgb48_fsr`` takes the two sizes: not below the processing size and at most
+    ``FSR_MAX_RATIO`` times it on either axis."""
+    proc_w, proc_h, out_w, out_h = int(proc_w), int(proc_h), int(out_w), int(out_h)
+    if out_w < proc_w or out_h < proc_h:
+        raise ValueError(f"output size {out_w}x{out_h} is below the processing size {proc_w}x{proc_h} (enlarging only)")
+    if out_w > FSR_MAX_RATIO * proc_w or out_h > FSR_MAX_RATIO * proc_h:
+        raise ValueError(f"scaler 'fsr' enlarges by at most {FSR_MAX_RATIO}x per axis: {proc_w}x{proc_h} -> {out_w}x{out_h} is more "
+                         f"(the limit is {FSR_MAX_RATIO * proc_w}x{FSR_MAX_RATIO * proc_h})")
+
+
+def scaler_options(scaler, antiring=0.0, cas=0.0):
+    """``antiring`` and ``cas`` as they hold under ``scaler`` -> ``(antiring, cas)``, each checked.  ``"lanczos"``: unchanged.
+    ``"fsr"``: the reference's schedules give 0 for both when its FSR shader does the enlargement (up to 2x), so ``"auto"`` resolves to
+    0.0 here; an explicit nonzero value belongs to the Lanczos scaler and is a ``ValueError``."""
+    scaler, antiring, cas = check_scaler(scaler), check_antiring(antiring), check_cas(cas)
+    if scaler != "fsr":
+        return antiring, cas
+    for name, v in (("antiring", antiring), ("cas", cas)):
+        if v != "auto" and v != 0:
+            raise ValueError(f"{name}={v!r} belongs to scaler 'lanczos': scaler 'fsr' takes 0 or 'auto' (which is 0)")
+    return 0.0, 0.0
 
 
 _libs = {}

@@ -570,7 +570,8 @@ class RealtimePlayback:
 def parse_args(argv=None):
     """The command line of ``main`` -> the argparse namespace, checked (a bad value ends in ``ap.error``): ``.proc_wh`` and ``.out_wh``
     hold the two sizes as ``(w, h)``, ``.cleanup`` the ``lib.OutputCleanup`` of --deband / --dither, ``.antiring`` and ``.cas`` ``"auto"`` or the
-    strength as a float (0.0: off)."""
+    strength as a float (0.0: off; both 0.0 under ``--scaler fsr``), ``.scaler`` ``"lanczos"`` or ``"fsr"``, ``.fsr_sharpness`` the RCAS
+    sharpness as a float or None (EASU alone)."""
     import argparse
 
     ap = argparse.ArgumentParser(description=main.__doc__)
@@ -608,6 +609,11 @@ def parse_args(argv=None):
                     "upscale (hdrtv_post_rgb48_scaled_cas; INTEGRATION.md 5c): a strength in 0 .. 1 as ffmpeg's cas filter takes it, "
                     "or auto = the reference's schedule by processing size (0.22 up to 960x540, 0.20 up to 1280x720, 0.16 above); "
                     "default: off")
+    ap.add_argument("--scaler", choices=_lib.SCALERS, default="lanczos", help="what enlarges to --out-size: lanczos (the fused Lanczos "
+                    "upscale with --antiring / --cas) or fsr (hdrtv_post_rgb48_fsr, the reference's default upscaler: EASU + RCAS; at "
+                    "most 2x per axis; --antiring and --cas are 0 there; INTEGRATION.md 5c)")
+    ap.add_argument("--fsr-sharpness", default=None, metavar="{none|0..2}", help="RCAS sharpness of --scaler fsr: 0 (the sharpest) .. 2, "
+                    "or none = EASU alone; default: the reference's 0.2")
     ap.add_argument("--no-hg", action="store_true")
     ap.add_argument("--hg-weights", default=None, help="HG weight file, or seeded:<n>")
     ap.add_argument("--max-throughput", action="store_true", help="do not pace to the source clock")
@@ -643,6 +649,23 @@ def parse_args(argv=None):
             a.cas = _lib.check_cas(a.cas if a.cas.lower() == "auto" else float(a.cas))
         except ValueError as exc:
             ap.error(f"--cas: {exc}")
+    if a.fsr_sharpness is not None and a.scaler != "fsr":
+        ap.error("--fsr-sharpness applies to --scaler fsr")
+    try:
+        if a.fsr_sharpness is None:
+            a.fsr_sharpness = _lib.FSR_SHARPNESS
+        else:
+            a.fsr_sharpness = _lib.check_fsr_sharpness(None if a.fsr_sharpness.lower() == "none" else float(a.fsr_sharpness))
+    except ValueError as exc:
+        ap.error(f"--fsr-sharpness: {exc}")
+    if a.scaler == "fsr":
+        if (owd, oht) == (wd, ht):
+            ap.error("--scaler fsr applies to an upscale: --out-size equals --size")
+        try:
+            _lib.check_fsr_size(wd, ht, owd, oht)
+            a.antiring, a.cas = _lib.scaler_options("fsr", a.antiring, a.cas)
+        except ValueError as exc:
+            ap.error(f"--scaler fsr: {exc}")
     a.proc_wh, a.out_wh = (wd, ht), (owd, oht)
     return a
 
@@ -666,7 +689,7 @@ def main(argv=None):
                                     out_siting=a.out_siting, light_stats=bool(a.light_level or a.light_level_json),
                                     deband=a.cleanup.deband, deband_range=a.cleanup.deband_range,
                                     deband_threshold=a.cleanup.deband_threshold, dither=a.cleanup.dither, antiring=a.antiring,
-                                    cas=a.cas)
+                                    cas=a.cas, scaler=a.scaler, fsr_sharpness=a.fsr_sharpness)
     if not worker._load_model(a.precision):
         return 1
     sink = None
@@ -696,6 +719,8 @@ def main(argv=None):
         res["antiring"] = _lib.resolve_antiring(a.antiring, wd, ht, owd, oht)
     if a.cas:
         res["cas"] = _lib.resolve_cas(a.cas, wd, ht, owd, oht)
+    if a.scaler != "lanczos":
+        res["scaler"], res["fsr_sharpness"] = a.scaler, a.fsr_sharpness
     if cll is not None:
         res["max_cll"], res["max_fall"], res["light_frames"] = cll.max_cll, cll.max_fall, cll.frames
         if a.light_level_json:

@@ -123,7 +123,8 @@ class HeadlessPipelineWorker:
     def __init__(self, weights_dir, use_hg=True, proc_w=1920, proc_h=1080, hg_weights=None,
                  status_cb=None, buffer_frames=1, out_w=None, out_h=None, out_pix_fmt="rgb48le", out_siting="left",
                  light_stats=False, light_rect=None, deband=False, deband_range=_L.DEBAND_RANGE,
-                 deband_threshold=_L.DEBAND_THRESHOLD, dither="none", antiring=0.0, cas=0.0):
+                 deband_threshold=_L.DEBAND_THRESHOLD, dither="none", antiring=0.0, cas=0.0, scaler="lanczos",
+                 fsr_sharpness=_L.FSR_SHARPNESS):
         self._weights_dir = weights_dir
         self._use_hg = bool(use_hg)
         self._hg_override = hg_weights
@@ -145,6 +146,15 @@ class HeadlessPipelineWorker:
         # each frame's two sizes (what the reference appends to its filter chain as cas=), resolved per frame like the anti-ringing.
         # Off (0.0, the default), or a frame delivered at the processing size: the launches and bytes of before.
         self._cas = _L.check_cas(cas)
+        # what enlarges a frame: "lanczos" (the default: the fused Lanczos upscale with the two options above), or
+        # "fsr" = hdrtv_post_rgb48_fsr, the reference's default upscaler, at most 2x per axis, with RCAS at fsr_sharpness (0 .. 2, the
+        # reference's 0.2) or, with None, EASU alone.  Under "fsr" antiring and cas are 0 ("auto" resolves to 0, as the reference's
+        # schedules do; an explicit nonzero value is refused).  A frame delivered at the processing size is untouched by either.
+        self._scaler = _L.check_scaler(scaler)
+        self._antiring, self._cas = _L.scaler_options(self._scaler, self._antiring, self._cas)
+        self._fsr_sharpness = _L.check_fsr_sharpness(fsr_sharpness)
+        if self._scaler == "fsr":
+            _L.check_fsr_size(self._proc_w, self._proc_h, self._out.w, self._out.h)
         # HDR10 content light level: every delivered frame carries its record (``.light``), measured on the
         # device from the codes the sink receives over ``light_rect = (x0, y0, rw, rh)`` in delivered-frame coordinates (None: the
         # whole frame), and ``content_light`` accumulates MaxCLL / MaxFALL in delivery order.  Off: nothing is launched or allocated.
@@ -354,7 +364,7 @@ class HeadlessPipelineWorker:
         does (209-235): convert, copy, synchronise the stream, hand the finished frame over.  ``out_hw = (out_h, out_w)``: the
         ring, the fallback buffer and the frame are at that size and the conversion is ``hdrtv_post_rgb48_scaled`` (with the
         worker's ``antiring``, resolved here from the tensor's and the delivered size: ``hdrtv_post_rgb48_scaled_ex``; with its ``cas``, resolved alike:
-        ``hdrtv_post_rgb48_scaled_cas``).  With a
+        ``hdrtv_post_rgb48_scaled_cas``; with ``scaler="fsr"`` ``hdrtv_post_rgb48_fsr`` does the enlargement).  With a
         Y'CbCr ``out_pix_fmt`` the slot (an RGB48 slot holds any of the layouts) receives the planes, only the frame's bytes are
         committed (``hdrtv_ring_commit_bytes``) and the frame is a 1-D u16 view of them."""
         p = self._processor
@@ -371,19 +381,23 @@ class HeadlessPipelineWorker:
         shape = out.shape
         antiring = _L.antiring_code(_L.resolve_antiring(self._antiring, tw, th, w, h)) if self._antiring else 0
         cas = _L.cas_code(_L.resolve_cas(self._cas, tw, th, w, h)) if self._cas else 0
+        fsr = None
+        if self._scaler == "fsr" and (h, w) != (th, tw):
+            _L.check_fsr_size(tw, th, w, h)            # a hot-swap of the processing resolution may have moved the ratio past 2x
+            fsr = (0, 0.0) if self._fsr_sharpness is None else (1, self._fsr_sharpness)
 
         def convert(dst, key):
             """The frame into ``dst`` and, when measured, its light level record into the pinned record kept per ``key``, all on
             ``st``: whatever is recorded on ``st`` afterwards (the slot's ready event) covers both.  Returns that record."""
             if not self._light:
-                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, antiring=antiring, cas=cas)
+                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, antiring=antiring, cas=cas, fsr=fsr)
                 return None
             bufs = self._light_bufs.get(key)
             if bufs is None:
                 bufs = self._light_bufs[key] = (torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, device=p.device),
                                                 torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, pin_memory=True))
             p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", bufs[0].data_ptr(), self._light_rect,
-                        self._cleanup, antiring, cas)
+                        self._cleanup, antiring, cas, fsr)
             with torch.cuda.stream(st):
                 bufs[1].copy_(bufs[0], non_blocking=True)
             return bufs[1].numpy()

@@ -209,6 +209,58 @@ int hdrtv_post_rgb48_scaled_ex(hdrtv_ctx *ctx, void *stream, const void *dev_out
 int hdrtv_post_rgb48_scaled_cas(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W,
                                 int pq, float peak_nits, uint16_t *dst, int dH, int dW, int antiring, int cas);
 
+/* RGB48 at the display size through FSR, the reference's DEFAULT upscaler (UPSCALER_CHOICES / DEFAULT_UPSCALER = "FSR",
+ * gui_scaling.py:42-43): hdrtv_post_rgb48 (pq = 0; peak_nits ignored) or hdrtv_post_pq_rgb48 (pq != 0), then EASU and, with
+ * rcas = 1, RCAS, in one kernel without a frame-sized intermediate.  For this branch the reference selects cas = 0 and
+ * scale-antiring = 0 and lets its shader do the whole enlargement: assets/shaders/FSR.glsl, FidelityFX FSR 1.0.2 on RGB (EASU
+ * de-ringing on, full analysis, no early exit; RCAS with sharpness 0.20 and the denoise term).  Unlike mpv's Lanczos or ffmpeg's cas
+ * that arithmetic IS part of the reference tree, so this rule is the shader's, operation by operation, in float32: every multiply,
+ * add, subtract and divide is rounded on its own (no fused multiply-add), divisions are correctly rounded, denormals are kept.
+ * tests/rgb48_fsr_ref.py restates it in NumPy and the GPU tests hold this entry point to it bit for bit.  What the GLSL compiler of
+ * a display makes of the shader (fused operations, approximate divisions) is UNPINNED.
+ *  1. codes: c = exactly what hdrtv_post_rgb48 / hdrtv_post_pq_rgb48 writes at the processing size; the rule sees only these integers.
+ *  2. samples: s = float32(c) / float32(65535), one correctly rounded division (a unorm16 texture fetch); indices outside the frame
+ *     read the clamped pixel.
+ *  3. positions, per axis, source extent n, destination extent m, for d = 0..m-1, in double on the host:
+ *       p = (d + 0.5) * n / m - 0.5;  fp[d] = floor(p) (int32);  pp[d] = float32(p - fp[d])
+ *     exact 2x gives pp = 0.75, 0.25, 0.75, ... with fp[0] = -1; m == n gives pp = 0, fp[d] = d.
+ *  4. EASU, per output pixel with (fx, fy) = fp and (ppx, ppy) = pp of its column and row.  Twelve taps b c / e f g h / i j k l / n o
+ *     at (fx, fy) + (0,-1) (1,-1) / (-1,0) (0,0) (1,0) (2,0) / (-1,1) (0,1) (1,1) (2,1) / (0,2) (1,2); luma L = (0.2126 r + 0.7152 g)
+ *     + 0.0722 b.  rcp~(a) = the float32 whose bits are 0x7ef07ebb - bits(a), rsq~(a) = bits 0x5f347d74 - (bits(a) >> 1), on the u32
+ *     pattern; sat(x) = min(max(x, 0), 1).  dir = (0, 0), len = 0, then four analyses with the bilinear weights
+ *     w = (1-ppx)(1-ppy), ppx (1-ppy), (1-ppx) ppy, ppx ppy on the luma crosses (A / B C D / E) = (b / e f g / j), (c / f g h / k),
+ *     (f / i j k / n), (g / j k l / o):
+ *       dirX = D - B;  lenX = sat(|dirX| * rcp~(max(|D - C|, |C - B|)));  lenX = lenX * lenX;  Y alike with E - A, E - C, C - A
+ *       dir = dir + (dirX, dirY) * w;  len = len + ((w * lenX) + (w * lenY))
+ *     then  dirR = dir.x dir.x + dir.y dir.y;  zro = dirR < 1 / 32768;  dirR = zro ? 1 : rsq~(dirR);  dir.x = zro ? 1 : dir.x;
+ *       dir = dir * dirR;  len = len * 0.5;  len = len * len
+ *       stretch = (dir.x dir.x + dir.y dir.y) * rcp~(max(|dir.x|, |dir.y|))
+ *       len2 = (1 + (stretch - 1) * len, 1 + (-0.5) * len);  lob = 0.5 + float32((0.25 - 0.04) - 0.5) * len;  clp = rcp~(lob)
+ *     and the taps accumulate in the order b c i j f e k l h g o n, for a tap at offset (ox, oy) with colour c:
+ *       off = (ox - ppx, oy - ppy);  v = ((off.x dir.x + off.y dir.y) * len2.x, (off.x * -dir.y + off.y dir.x) * len2.y)
+ *       d2 = min(v.x v.x + v.y v.y, clp);  wB = float32(2/5) d2 + (-1);  wA = lob d2 + (-1);  wB = wB wB;  wA = wA wA
+ *       wB = (25/16) wB + (-(25/16 - 1));  w = wB * wA;  aC = aC + c * w;  aW = aW + w
+ *     pix = aC / aW (correctly rounded), clamped to the min / max of f g j k per channel, then sat.  A flat frame returns its code.
+ *  5. RCAS (rcas = 1), on the float32 EASU image at the output size, no quantisation in between; neighbours b d f h at (0,-1) (-1,0)
+ *     (1,0) (0,1), clamped to the image; per channel, mn / mx = min / max of b d f h, eps = float32(1e-6):
+ *       hitMin = min(mn, e) / max(4 mx, eps);  hitMax = (1 - max(mx, e)) / min(4 mn - 4, -eps)
+ *       lobe = max(-(0.25 - 1/16), min(max(-hitMin, hitMax), 0)) * float32(2^-sharpness)      (the factor in double on the host)
+ *       nz = |0.25 * (((b + d) + f) + h) - e| / max(max(mx, e) - min(mn, e), eps)
+ *     lobe = lobe * (-0.5 * sat(max over the three channels of nz) + 1);  rcp = 1 / (4 lobe + 1) (correctly rounded)
+ *     pix = sat(((((lobe b + lobe d) + lobe h) + lobe f) + e) * rcp)
+ *  6. output code: (int)(x * 65535 + 0.5), the quantiser of the unscaled entry point, both operations float32.
+ * Sizes: H <= dH <= 2H and W <= dW <= 2W.  The shader's EASU stage scales to min(OUTPUT, 2 * MAIN) per axis and leaves the rest to
+ * mpv's scaler; that residual pass is not part of this entry point, and a larger ratio is refused.  The reference's headline case,
+ * 1080p -> 2160p, is exactly 2x.  Equal sizes (dH == H && dW == W) delegate to the unscaled kernel and write its bytes, whatever rcas
+ * (the shader runs only when the output area is larger); with one axis at identity the filter applies in full.  rcas is 0 (EASU
+ * alone, sharpness ignored) or 1; sharpness is in [0, 2], 0 the sharpest, the reference's value 0.20.  Stream-ordered, needs no
+ * reservation; the position tables are built at the first call with a geometry -- that call allocates and copies -- and kept in the
+ * context beside the tap tables.  HDRTV_EINVAL, before any device call and with dst untouched, for everything
+ * hdrtv_post_rgb48_scaled refuses, for dH > 2H or dW > 2W, for rcas outside {0, 1} and, with rcas = 1, for a sharpness that is NaN,
+ * infinite or outside [0, 2]. */
+int hdrtv_post_rgb48_fsr(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
+                         uint16_t *dst, int dH, int dW, int rcas, float sharpness);
+
 /* 10-bit limited-range Y'CbCr for an encoder (HEVC Main10, hardware encoders, ProRes): P010 and yuv420p10le are 3 bytes per pixel,
  * yuv422p10le 4, against the 6 of RGB48.  The reference's export converts on the CPU: it pipes rgb48le into ffmpeg, zscale goes to
  * BT.2020nc limited range and format=yuv422p10le feeds prores_ks (gui_export.py:948-1005).  The network's output is PQ-encoded BT.2020
