@@ -266,6 +266,10 @@ struct hdrtv_ctx {
     std::map<std::array<int, 4>, int4 *> ps_tabs;
     // hdrtv_post_rgb48_fsr: device position tables per (H, W, dH, dW), xtab [dW] then ytab [dH]; built on first use of a geometry
     std::map<std::array<int, 4>, int2 *> fsr_tabs;
+    // hdrtv_post_rgb48_down: device tables per (H, W, dH, dW) in one allocation -- info [dW + dH] int4, then the integer coefficients
+    // [dW * ntx + dH * nty], then as many float32 L2 weights; built on first use of a geometry
+    struct DownTabs { int4 *dev; int ntx, nty; };
+    std::map<std::array<int, 4>, DownTabs> down_tabs;
     // objective metrics partial sums
     double *mt_dev = nullptr;
     size_t mt_cap = 0;

@@ -424,6 +424,22 @@ struct PostFsrParams {
     int H, W, dH, dW;
 };
 
+// Fused quantise + Mitchell / SSimDownscaler shrink (post_down.hip): the same tensors, dH <= H <= 4 dH and dW <= W <= 4 dW.
+// xinfo [dW] / yinfo [dH]: per destination index {first source tap (unclamped), tap count, the two inner taps of the pull}; xq / yq:
+// ntx / nty integer coefficients per index (sum 16384, zero-padded); xw / yw: as many float32 L2 weights (include/hdrtv_mi355x.h
+// states the rule).  A workgroup owns DN_TH2 x DN_TW output pixels up to a ratio of 2 on both axes, DN_TH4 x DN_TW up to 4.
+constexpr int DN_TW = 32, DN_TH2 = 16, DN_TH4 = 8;
+struct PostDownParams {
+    const void *in;
+    uint16_t *dst;
+    const int4 *xinfo, *yinfo;
+    const int *xq, *yq;
+    const float *xw, *yw;
+    const float *pq_bnd;             // PQ variant: the code boundaries of hdrtv_post_pq_rgb48
+    float peak;
+    int H, W, dH, dW, ntx, nty;
+};
+
 // 10-bit limited-range BT.2020nc Y'CbCr output (post_ycbcr.hip; include/hdrtv_mi355x.h states the integer rule): a workgroup owns
 // YC_TH x YC_TW luma pixels.  fmt / siting carry the header's HDRTV_YCC_* / HDRTV_SITING_* values; pitches in u16 elements.
 constexpr int YC_TW = 128, YC_TH = 16;

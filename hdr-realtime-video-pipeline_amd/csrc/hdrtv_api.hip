@@ -77,6 +77,7 @@ int hdrtv_destroy(hdrtv_ctx *c)
     if (c->lb_dev) (void)hipFree(c->lb_dev);
     for (auto &kv : c->ps_tabs) (void)hipFree(kv.second);
     for (auto &kv : c->fsr_tabs) (void)hipFree(kv.second);
+    for (auto &kv : c->down_tabs) (void)hipFree(kv.second.dev);
     if (c->mt_dev) (void)hipFree(c->mt_dev);
     free_workspaces(c);
     if (c->wts.dev) (void)hipFree(c->wts.dev);
@@ -650,6 +651,124 @@ int hdrtv_post_rgb48_fsr(hdrtv_ctx *c, void *stream, const void *in, int dtype, 
     PostFsrParams p{in, dst, it->second, it->second + dW, c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
     const float sharp = rcas ? (float)std::exp2(-(double)sharpness) : 0.f;
     return launched(c, "post_rgb48_fsr", post_fsr_launch(p, rcas, sharp, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
+}
+
+// Tables of one axis of hdrtv_post_rgb48_down (the rule: include/hdrtv_mi355x.h), n source -> m destination samples, m <= n <= 4 m:
+// per destination index {first tap, tap count, the two inner taps of the pull}, the Mitchell coefficients (int, sum 16384) and the
+// Catmull-Rom weights of the L2 passes (divided by their sum in double, then float32), both padded with zeros to nt = the largest count.
+struct DownAxis {
+    std::vector<int4> info;
+    std::vector<int> q;
+    std::vector<float> w;
+    int nt = 1;
+};
+static void down_axis(int n, int m, DownAxis &t)
+{
+    t.info.resize(m);
+    if (m == n) {                                 // one tap, k = d, weight one; the pull of an identity is a no-op on any pair of taps
+        t.nt = 1;
+        t.q.assign(m, 16384);
+        t.w.assign(m, 1.f);
+        for (int d = 0; d < m; ++d) t.info[d] = make_int4(d, 1, d, d);
+        return;
+    }
+    auto mitchell = [](double x) {
+        x = std::fabs(x);
+        if (x < 1.0) return ((7.0 * x - 12.0) * x * x + 16.0 / 3.0) / 6.0;
+        if (x < 2.0) return ((((-7.0 / 3.0) * x + 12.0) * x - 20.0) * x + 32.0 / 3.0) / 6.0;
+        return 0.0;
+    };
+    auto catrom = [](double x) {
+        x = std::fabs(x);
+        if (x < 1.0) return (1.5 * x - 2.5) * x * x + 1.0;
+        return ((-0.5 * x + 2.5) * x - 4.0) * x + 2.0;
+    };
+    const double hw = 2.0 * n / m;
+    int nt = 1;
+    for (int d = 0; d < m; ++d) {
+        const double ctr = (d + 0.5) * n / m;
+        const int lo = (int)std::ceil(ctr - hw - 0.5), hi = (int)std::floor(ctr + hw - 0.5), k2 = (int)std::floor(ctr - 0.5);
+        t.info[d] = make_int4(lo, hi - lo + 1, k2, k2 + 1);
+        nt = std::max(nt, hi - lo + 1);
+    }
+    t.nt = nt;
+    t.q.assign((size_t)m * nt, 0);
+    t.w.assign((size_t)m * nt, 0.f);
+    for (int d = 0; d < m; ++d) {
+        const double ctr = (d + 0.5) * n / m;
+        const int lo = t.info[d].x, cnt = t.info[d].y;
+        double v[17], cr[17], s = 0.0, cs = 0.0;
+        for (int k = 0; k < cnt; ++k) {
+            const double x = (lo + k + 0.5 - ctr) * m / n;
+            v[k] = mitchell(x);
+            cr[k] = catrom(x);
+            s += v[k];
+            cs += cr[k];
+        }
+        int *q = &t.q[(size_t)d * nt], tot = 0, big = 0;
+        for (int k = 0; k < cnt; ++k) {
+            q[k] = (int)std::floor(v[k] / s * 16384.0 + 0.5);
+            tot += q[k];
+            if (q[k] > q[big]) big = k;           // the lowest k on a tie
+            t.w[(size_t)d * nt + k] = (float)(cr[k] / cs);
+        }
+        q[big] += 16384 - tot;
+    }
+}
+
+int hdrtv_post_rgb48_down(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
+                          uint16_t *dst, int dH, int dW, int antiring, int ssim)
+{
+    if (!c || !in || !dst || H <= 0 || W <= 0 || dH <= 0 || dW <= 0) return fail(c, HDRTV_EINVAL, "post_rgb48_down: bad argument");
+    if (dH > H || dW > W) return fail(c, HDRTV_EINVAL, "post_rgb48_down: %dx%d -> %dx%d enlarges (shrinking only)", W, H, dW, dH);
+    if (4 * (long long)dH < H || 4 * (long long)dW < W)
+        return fail(c, HDRTV_EINVAL, "post_rgb48_down: %dx%d -> %dx%d is more than 4x on an axis", W, H, dW, dH);
+    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_rgb48_down: bad dtype %d", dtype);
+    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_rgb48_down: pq needs peak_nits > 0");
+    if (antiring < 0 || antiring > 256) return fail(c, HDRTV_EINVAL, "post_rgb48_down: antiring %d is outside 0 .. 256", antiring);
+    if (ssim != 0 && ssim != 1) return fail(c, HDRTV_EINVAL, "post_rgb48_down: ssim %d is neither 0 nor 1", ssim);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = pq ? ensure_pq_table(c, "post_rgb48_down") : HDRTV_OK) return rc;
+    // the reference's downscaler runs only when the output is smaller: equal sizes are the unscaled kernel's bytes, whatever the options
+    if (dH == H && dW == W) {
+        return launched(c, "post_rgb48_down", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd));
+    }
+    // first use of a geometry builds its tables (allocates, copies); every later call finds them and only launches
+    const std::array<int, 4> key{H, W, dH, dW};
+    auto it = c->down_tabs.find(key);
+    if (it == c->down_tabs.end()) {
+        if (c->down_tabs.size() >= 16) {
+            for (auto &kv : c->down_tabs) (void)hipFree(kv.second.dev);
+            c->down_tabs.clear();
+        }
+        DownAxis ax, ay;
+        down_axis(W, dW, ax);
+        down_axis(H, dH, ay);
+        const size_t ni = (size_t)dW + dH, nq = ax.q.size() + ay.q.size();
+        std::vector<char> host(ni * sizeof(int4) + nq * (sizeof(int) + sizeof(float)));
+        char *h = host.data();
+        memcpy(h, ax.info.data(), dW * sizeof(int4));
+        memcpy(h + dW * sizeof(int4), ay.info.data(), dH * sizeof(int4));
+        h += ni * sizeof(int4);
+        memcpy(h, ax.q.data(), ax.q.size() * sizeof(int));
+        memcpy(h + ax.q.size() * sizeof(int), ay.q.data(), ay.q.size() * sizeof(int));
+        h += nq * sizeof(int);
+        memcpy(h, ax.w.data(), ax.w.size() * sizeof(float));
+        memcpy(h + ax.w.size() * sizeof(float), ay.w.data(), ay.w.size() * sizeof(float));
+        int4 *dev = nullptr;
+        if (hipMalloc((void **)&dev, host.size()) != hipSuccess) return fail(c, HDRTV_ENOMEM, "post_rgb48_down: table allocation failed");
+        if (hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(dev);
+            return fail(c, HDRTV_EHIP, "post_rgb48_down: table upload failed");
+        }
+        it = c->down_tabs.emplace(key, hdrtv_ctx::DownTabs{dev, ax.nt, ay.nt}).first;
+    }
+    const hdrtv_ctx::DownTabs &t = it->second;
+    const int *q = reinterpret_cast<const int *>(t.dev + dW + dH);
+    const size_t nqx = (size_t)dW * t.ntx, nq = nqx + (size_t)dH * t.nty;
+    const float *w = reinterpret_cast<const float *>(q + nq);
+    PostDownParams p{in, dst, t.dev, t.dev + dW, q, q + nqx, w, w + nqx, c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW, t.ntx, t.nty};
+    return launched(c, "post_rgb48_down", post_down_launch(p, antiring, ssim, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
 // ------------------------------------------------------------------------------- letterbox

@@ -84,6 +84,10 @@ class _Mi355xWorker:
         # the scaler of enlarged frames ("fsr" = hdrtv_post_rgb48_fsr with its RCAS sharpness, or None = EASU alone); absent: Lanczos
         self.scaler = kw.pop("scaler", "lanczos")
         self.fsr_sharpness = kw.pop("fsr_sharpness", L.FSR_SHARPNESS)
+        # what shrinks frames delivered below the processing size ("mitchell" / "ssim" = hdrtv_post_rgb48_down) and its anti-ringing
+        # strength (validated by the dispatcher); absent: none
+        self.downscaler = kw.pop("downscaler", None)
+        self.down_antiring = kw.pop("down_antiring", 0.0)
         torch.cuda.set_device(device_index)
         with contextlib.redirect_stdout(sys.stderr):   # a worker's banner must not land on the parent's stdout (bench.py's one JSON line)
             self.proc = HDRTVNetMI355X(model, device=f"cuda:{device_index}", warmup_passes=0, **kw)
@@ -138,6 +142,8 @@ class _Mi355xWorker:
             out_fmt["cas"] = self.cas
         if self.scaler != "lanczos":
             out_fmt["scaler"], out_fmt["fsr_sharpness"] = self.scaler, self.fsr_sharpness
+        if self.downscaler is not None:
+            out_fmt["downscaler"], out_fmt["down_antiring"] = self.downscaler, self.down_antiring
         self._buffers(h, w, tuple(frame.shape) + ((2,) if ten else ()), fmt)       # _raw is bytes: a u16 sample is two
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
@@ -383,7 +389,8 @@ class FrameDispatcher:
     def __init__(self, n_workers, height, width, sink, make_worker=mi355x_worker, init_args=None, devices=None, slots=3,
                  start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False, out_height=None,
                  out_width=None, out_pix_fmt="rgb48le", out_siting="left", deband=False, deband_range=16, deband_threshold=1311,
-                 dither="none", antiring=0.0, cas=0.0, scaler="lanczos", fsr_sharpness=0.2):
+                 dither="none", antiring=0.0, cas=0.0, scaler="lanczos", fsr_sharpness=0.2, downscaler=None,
+                 down_antiring=0.0):
         """``sink(index, rgb48_view)`` is called in index order from the reorder thread; the view is only valid during the
         call (the slot goes back to its worker afterwards).  ``numa``: workers pin themselves to their GPU's NUMA node
         (False: report only).  ``pix_fmt``: ``bgr24`` input frames are u8 (H, W, 3); ``yuv420p`` / ``nv12`` frames are u8
@@ -409,7 +416,14 @@ class FrameDispatcher:
         (INTEGRATION.md 5c): the output size is then at most twice the processing size per axis, ``antiring`` and ``cas`` are 0
         (``"auto"`` resolves to 0, an explicit nonzero value is a ``ValueError``), and ``fsr_sharpness`` is its RCAS sharpness, 0 .. 2,
         or None = EASU alone; kept as ``.scaler`` / ``.fsr_sharpness`` and handed on as ``init_args["scaler"]`` /
-        ``init_args["fsr_sharpness"]`` only when the scaler is not the default: otherwise the ``init_args`` of before."""
+        ``init_args["fsr_sharpness"]`` only when the scaler is not the default: otherwise the ``init_args`` of before.
+        ``downscaler``: None (the default: an output size below the processing size is a ``ValueError``, as before), ``"mitchell"``
+        or ``"ssim"`` = the output size lies below the processing size, by at most 4x per axis, and the product's worker shrinks
+        through ``hdrtv_post_rgb48_down`` with the anti-ringing strength ``down_antiring``, 0 .. 1 (``"auto"`` =
+        the reference's 0.20, resolved here); ``lib.down_options`` has the refusals (a mixed request, more than 4x, ``scaler="fsr"``
+        or a nonzero ``antiring`` / ``cas``, nothing to shrink).  Kept as ``.downscaler`` / ``.down_antiring`` and handed on as
+        ``init_args["downscaler"]`` / ``init_args["down_antiring"]`` only when a downscaler is given; stand-in workers fill slots of
+        the smaller size."""
         if n_workers < 1 or slots < 2:
             raise ValueError("n_workers >= 1 and slots >= 2")
         from . import lib as _L
@@ -421,7 +435,11 @@ class FrameDispatcher:
             raise ValueError("yuv_matrix must be 601, 709 or 2020")
         self.n, self.h, self.w, self.slots = int(n_workers), int(height), int(width), int(slots)
         self.out_h, self.out_w = int(out_height or height), int(out_width or width)
-        if self.out_h < self.h or self.out_w < self.w:
+        self.downscaler = _L.check_downscaler(downscaler)
+        self.down_antiring = _L.check_down_antiring(down_antiring)
+        if _L.down_options(self.downscaler, down_antiring, self.w, self.h, self.out_w, self.out_h, scaler, antiring, cas) is not None:
+            antiring = cas = 0.0                # checked to be 0 or "auto", which is 0 where nothing is enlarged
+        if self.downscaler is None and (self.out_h < self.h or self.out_w < self.w):
             raise ValueError(f"output size {self.out_w}x{self.out_h} is below the processing size {self.w}x{self.h} (enlarging only)")
         out = _L.output_format(out_pix_fmt, out_siting, self.out_h, self.out_w)    # raises for an odd size of a Y'CbCr layout
         self.out_pix_fmt, self.out_siting, self._out_shape = out.pix_fmt, out.siting, out.shape
@@ -439,6 +457,8 @@ class FrameDispatcher:
         if self.scaler == "fsr":
             _L.check_fsr_size(self.w, self.h, self.out_w, self.out_h)
             init_args["scaler"], init_args["fsr_sharpness"] = self.scaler, self.fsr_sharpness
+        if self.downscaler is not None:
+            init_args["downscaler"], init_args["down_antiring"] = self.downscaler, self.down_antiring
         self.pix_fmt = pix_fmt
         self._in_shape, self._in_dtype = _in_shape(self.h, self.w, pix_fmt), _in_dtype(pix_fmt)     # raises for an odd 10-bit size
         fmt = (pix_fmt, int(yuv_matrix), bool(yuv_full_range))

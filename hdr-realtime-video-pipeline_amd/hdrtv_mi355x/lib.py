@@ -48,6 +48,7 @@ SYMBOLS = [
     ("hdrtv_post_rgb48_scaled_ex", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I]),
     ("hdrtv_post_rgb48_scaled_cas", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, _I]),
     ("hdrtv_post_rgb48_fsr", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, C.c_float]),
+    ("hdrtv_post_rgb48_down", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, _I]),
     ("hdrtv_post_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_rgb48_to_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_ycbcr10_bytes", C.c_int64, [_I, _I, _I]),
@@ -381,6 +382,64 @@ def scaler_options(scaler, antiring=0.0, cas=0.0):
         if v != "auto" and v != 0:
             raise ValueError(f"{name}={v!r} belongs to scaler 'lanczos': scaler 'fsr' takes 0 or 'auto' (which is 0)")
     return 0.0, 0.0
+
+
+DOWNSCALERS = ("mitchell", "ssim")         # what shrinks a frame to the delivered size: hdrtv_post_rgb48_down without / with its SSimDownscaler stage
+DOWN_MAX_RATIO = 4                         # hdrtv_post_rgb48_down: the largest ratio per axis
+DOWN_ANTIRING = 0.20                       # the reference's dscale-antiring (gui_mpv_widget.py _mpv_downscale_antiring)
+
+
+def check_downscaler(value=None):
+    """A ``downscaler`` option as the processor, the worker, the dispatcher and the command line take it: ``None`` (the default: a
+    delivered size below the processing size stays a ``ValueError``), ``"mitchell"`` (``hdrtv_post_rgb48_down`` with ``ssim = 0``) or
+    ``"ssim"`` (the reference's chain: Mitchell, then its SSimDownscaler shader), any case; ``ValueError`` otherwise."""
+    if value is None:
+        return None
+    if not isinstance(value, str) or value.lower() not in DOWNSCALERS:
+        raise ValueError(f"downscaler must be None or one of {list(DOWNSCALERS)} (got {value!r})")
+    return value.lower()
+
+
+def check_down_antiring(value=0.0):
+    """A ``down_antiring`` option: ``"auto"`` (any case) -> the reference's ``DOWN_ANTIRING``, a strength in [0, 1] -> that float;
+    ``ValueError`` otherwise.  Unlike the enlarging ``antiring`` the reference's value does not depend on the sizes."""
+    value = check_antiring(value)
+    return DOWN_ANTIRING if value == "auto" else value
+
+
+def check_down_size(proc_w, proc_h, out_w, out_h):
+    """``ValueError`` unless ``hdrtv_post_rgb48_down`` has something to do with the two sizes: no axis above the processing size (a
+    mixed request, one axis up and one down, included), none below a ``DOWN_MAX_RATIO``-th of it, and at least one axis below it."""
+    proc_w, proc_h, out_w, out_h = int(proc_w), int(proc_h), int(out_w), int(out_h)
+    if out_w < 1 or out_h < 1:
+        raise ValueError(f"output size {out_w}x{out_h} is not positive")
+    if out_w > proc_w or out_h > proc_h:
+        what = "one axis up and one down" if out_w < proc_w or out_h < proc_h else "enlarging"
+        raise ValueError(f"a downscaler shrinks: {proc_w}x{proc_h} -> {out_w}x{out_h} is {what}")
+    if DOWN_MAX_RATIO * out_w < proc_w or DOWN_MAX_RATIO * out_h < proc_h:
+        raise ValueError(f"a downscaler shrinks by at most {DOWN_MAX_RATIO}x per axis: {proc_w}x{proc_h} -> {out_w}x{out_h} is more")
+    if out_w == proc_w and out_h == proc_h:
+        raise ValueError(f"a downscaler applies to a shrunk frame: the output size equals the processing size {proc_w}x{proc_h}")
+
+
+def down_options(downscaler, down_antiring, proc_w, proc_h, out_w, out_h, scaler="lanczos", antiring=0.0, cas=0.0):
+    """The ``downscaler`` / ``down_antiring`` options of a frame of known sizes -> None (no downscaler: everything as before, a
+    smaller output size refused where it was), or ``(antiring code, ssim)`` as ``hdrtv_post_rgb48_down`` takes them, after the
+    checks: the sizes (``check_down_size``), and that nothing of the enlarging path came along -- ``scaler`` must be ``"lanczos"``
+    and ``antiring`` / ``cas`` 0 or ``"auto"`` (which is 0 unless both axes are enlarged).  An explicit nonzero ``down_antiring``
+    without a downscaler is a ``ValueError`` too."""
+    downscaler, strength = check_downscaler(downscaler), check_down_antiring(down_antiring)
+    if downscaler is None:
+        if strength != 0 and not (isinstance(down_antiring, str) and down_antiring.lower() == "auto"):
+            raise ValueError(f"down_antiring={down_antiring!r} needs a downscaler")
+        return None
+    check_down_size(proc_w, proc_h, out_w, out_h)
+    if check_scaler(scaler) != "lanczos":
+        raise ValueError(f"scaler {scaler!r} enlarges: it does not go with downscaler {downscaler!r}")
+    for name, v in (("antiring", check_antiring(antiring)), ("cas", check_cas(cas))):
+        if v != "auto" and v != 0:
+            raise ValueError(f"{name}={v!r} belongs to enlarging: downscaler {downscaler!r} takes down_antiring")
+    return antiring_code(strength), 1 if downscaler == "ssim" else 0
 
 
 _libs = {}

@@ -571,7 +571,8 @@ def parse_args(argv=None):
     """The command line of ``main`` -> the argparse namespace, checked (a bad value ends in ``ap.error``): ``.proc_wh`` and ``.out_wh``
     hold the two sizes as ``(w, h)``, ``.cleanup`` the ``lib.OutputCleanup`` of --deband / --dither, ``.antiring`` and ``.cas`` ``"auto"`` or the
     strength as a float (0.0: off; both 0.0 under ``--scaler fsr``), ``.scaler`` ``"lanczos"`` or ``"fsr"``, ``.fsr_sharpness`` the RCAS
-    sharpness as a float or None (EASU alone)."""
+    sharpness as a float or None (EASU alone), ``.downscaler`` None, ``"mitchell"`` or ``"ssim"``, ``.down_antiring`` its anti-ringing
+    strength as a float (``auto`` resolved to the reference's 0.20)."""
     import argparse
 
     ap = argparse.ArgumentParser(description=main.__doc__)
@@ -579,7 +580,7 @@ def parse_args(argv=None):
     ap.add_argument("--precision", default="FP16")
     ap.add_argument("--size", default="3840x2160", help="processing size WxH: the size the network runs at")
     ap.add_argument("--out-size", default=None, help="size WxH the sink receives frames at (default: --size; not below it on either "
-                    "axis): the RGB48 conversion upscales on the device (hdrtv_post_rgb48_scaled)")
+                    "axis unless --downscaler is given): the RGB48 conversion upscales on the device (hdrtv_post_rgb48_scaled)")
     ap.add_argument("--fps", type=float, default=60.0)
     ap.add_argument("--frames", type=int, default=240)
     ap.add_argument("--input", help="rawvideo file at --size in --pix-fmt (default: synthetic frames)")
@@ -614,6 +615,11 @@ def parse_args(argv=None):
                     "most 2x per axis; --antiring and --cas are 0 there; INTEGRATION.md 5c)")
     ap.add_argument("--fsr-sharpness", default=None, metavar="{none|0..2}", help="RCAS sharpness of --scaler fsr: 0 (the sharpest) .. 2, "
                     "or none = EASU alone; default: the reference's 0.2")
+    ap.add_argument("--downscaler", choices=_lib.DOWNSCALERS, default=None, help="what shrinks to an --out-size below --size, by at "
+                    "most 4x per axis (hdrtv_post_rgb48_down; INTEGRATION.md 5c): mitchell, or ssim = the reference's chain, Mitchell "
+                    "and its SSimDownscaler shader; default: none, a smaller --out-size is refused")
+    ap.add_argument("--down-antiring", default=None, metavar="{auto|0..1}", help="anti-ringing of --downscaler: a strength in 0 .. 1, or "
+                    "auto = the reference's 0.20; default: off")
     ap.add_argument("--no-hg", action="store_true")
     ap.add_argument("--hg-weights", default=None, help="HG weight file, or seeded:<n>")
     ap.add_argument("--max-throughput", action="store_true", help="do not pace to the source clock")
@@ -623,8 +629,10 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     wd, ht = (int(v) for v in a.size.lower().split("x", 1))
     owd, oht = (int(v) for v in a.out_size.lower().split("x", 1)) if a.out_size else (wd, ht)
-    if owd < wd or oht < ht:
-        ap.error(f"--out-size {owd}x{oht} is below --size {wd}x{ht}: the output stage only enlarges")
+    if a.downscaler is None and (owd < wd or oht < ht):
+        ap.error(f"--out-size {owd}x{oht} is below --size {wd}x{ht}: the output stage only enlarges unless --downscaler is given")
+    if a.down_antiring is not None and a.downscaler is None:
+        ap.error("--down-antiring applies to --downscaler")
     if not a.input and a.pix_fmt != "bgr24":
         ap.error("--pix-fmt applies to an --input file")
     try:
@@ -666,6 +674,12 @@ def parse_args(argv=None):
             a.antiring, a.cas = _lib.scaler_options("fsr", a.antiring, a.cas)
         except ValueError as exc:
             ap.error(f"--scaler fsr: {exc}")
+    try:
+        a.down_antiring = 0.0 if a.down_antiring is None else _lib.check_down_antiring(
+            a.down_antiring if a.down_antiring.lower() == "auto" else float(a.down_antiring))
+        _lib.down_options(a.downscaler, a.down_antiring, wd, ht, owd, oht, a.scaler, a.antiring, a.cas)
+    except ValueError as exc:
+        ap.error(f"--downscaler: {exc}")
     a.proc_wh, a.out_wh = (wd, ht), (owd, oht)
     return a
 
@@ -689,7 +703,8 @@ def main(argv=None):
                                     out_siting=a.out_siting, light_stats=bool(a.light_level or a.light_level_json),
                                     deband=a.cleanup.deband, deband_range=a.cleanup.deband_range,
                                     deband_threshold=a.cleanup.deband_threshold, dither=a.cleanup.dither, antiring=a.antiring,
-                                    cas=a.cas, scaler=a.scaler, fsr_sharpness=a.fsr_sharpness)
+                                    cas=a.cas, scaler=a.scaler, fsr_sharpness=a.fsr_sharpness, downscaler=a.downscaler,
+                                    down_antiring=a.down_antiring)
     if not worker._load_model(a.precision):
         return 1
     sink = None
@@ -721,6 +736,8 @@ def main(argv=None):
         res["cas"] = _lib.resolve_cas(a.cas, wd, ht, owd, oht)
     if a.scaler != "lanczos":
         res["scaler"], res["fsr_sharpness"] = a.scaler, a.fsr_sharpness
+    if a.downscaler is not None:
+        res["downscaler"], res["down_antiring"] = a.downscaler, a.down_antiring
     if cll is not None:
         res["max_cll"], res["max_fall"], res["light_frames"] = cll.max_cll, cll.max_fall, cll.frames
         if a.light_level_json:

@@ -342,7 +342,7 @@ class HDRTVNetMI355X:
         return scratch.data_ptr()
 
     def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None, antiring=0, cas=0,
-                  fsr=None):
+                  fsr=None, down=None):
         """The output conversion of a frame whose planar tensor lies at ``src_ptr``, to the ``lib.OutputFormat`` ``out`` at
         ``dst_ptr``: ``rgb48le`` at the processing size (``hdrtv_post_rgb48``) or enlarged to ``out.h`` x ``out.w``
         (``hdrtv_post_rgb48_scaled``); a 10-bit Y'CbCr layout in one kernel at the processing size (``hdrtv_post_ycbcr10``), or,
@@ -363,7 +363,10 @@ class HDRTVNetMI355X:
         ``hdrtv_post_rgb48_scaled_cas`` (which takes ``antiring`` too) sharpens the codes in front of the scaler, and everything
         behind it sees the sharpened, scaled codes.  0, or an unscaled frame: the launches above.  ``fsr``: None, or ``(rcas,
         sharpness)`` = the enlarged frame goes through ``hdrtv_post_rgb48_fsr`` instead (``_fsr_for``; ``antiring`` and ``cas`` are 0
-        then), and everything behind the scaler sees the FSR codes.  This is the one place that chooses among the four entry points."""
+        then), and everything behind the scaler sees the FSR codes.  ``down``: None, or ``(antiring code, ssim)`` = a frame delivered
+        BELOW the processing size goes through ``hdrtv_post_rgb48_down`` (``lib.down_options``; the other three are off then), and
+        everything behind it -- deband, the conversion from codes, the record -- sees the shrunk codes.  This is the one place that
+        chooses among the five entry points."""
         scaled = (out.h, out.w) != (h, w)
         rect = (0, 0, out.w, out.h) if light_rect is None else tuple(int(v) for v in light_rect)
         active = cleanup is not None and cleanup.active
@@ -382,7 +385,10 @@ class HDRTVNetMI355X:
             return
         rgb_ptr = dst_ptr if out.is_rgb48 else self._scratch(scratch_key, out)
         raw_ptr = self._scratch((scratch_key, "raw"), out) if deband else rgb_ptr       # deband never works in place
-        if scaled and fsr is not None:
+        if scaled and down is not None:
+            self._chk(self._lib.hdrtv_post_rgb48_down(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, down[0], down[1]),
+                      "hdrtv_post_rgb48_down")
+        elif scaled and fsr is not None:
             self._chk(self._lib.hdrtv_post_rgb48_fsr(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, fsr[0], fsr[1]),
                       "hdrtv_post_rgb48_fsr")
         elif scaled and cas:
@@ -467,15 +473,19 @@ class HDRTVNetMI355X:
         sharp = _L.check_fsr_sharpness(fsr_sharpness)
         return (0, 0.0) if sharp is None else (1, sharp)
 
-    def _scale_for(self, antiring, cas, scaler, fsr_sharpness, h, w, out):
-        """The four scaler arguments of ``enqueue_frame*`` -> ``(antiring code, CAS code, fsr)`` as ``_post_out`` takes them."""
+    def _scale_for(self, antiring, cas, scaler, fsr_sharpness, h, w, out, downscaler=None, down_antiring=0.0):
+        """The scaler arguments of ``enqueue_frame*`` -> ``(antiring code, CAS code, fsr, down)`` as ``_post_out`` takes them."""
+        if downscaler is not None or not (type(down_antiring) in (float, int) and down_antiring == 0):
+            down = _L.down_options(downscaler, down_antiring, w, h, out.w, out.h, scaler, antiring, cas)
+            if down is not None:
+                return 0, 0, None, down
         fsr = self._fsr_for(scaler, fsr_sharpness, antiring, cas, h, w, out.h, out.w)
         if fsr is not None:
-            return 0, 0, fsr
-        return self._antiring_for(antiring, h, w, out), self._cas_for(cas, h, w, out), None
+            return 0, 0, fsr, None
+        return self._antiring_for(antiring, h, w, out), self._cas_for(cas, h, w, out), None, None
 
     def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out, light_ptr=None, light_rect=None, cleanup=None, antiring=0,
-                 cas=0, fsr=None):
+                 cas=0, fsr=None, down=None):
         """The body of ``enqueue_frame*``: the preprocess entry point ``pre`` (named ``what``) on its source arguments ``src``,
         ``hdrtv_infer_lane`` and ``_post_out``, all on the lane's buffers and ``stream`` (default: the lane's own)."""
         self._ensure_buffers(h, w)
@@ -484,11 +494,11 @@ class HDRTVNetMI355X:
         self._chk(pre(self._ctx, st, *src, h, w, tin.data_ptr(), tcond.data_ptr()), what)
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), self._out_dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, antiring, cas, fsr)
+        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, antiring, cas, fsr, down)
 
     def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le",
                       out_siting="left", light_ptr=None, light_rect=None, cleanup=None, antiring=0.0, cas=0.0,
-                      scaler="lanczos", fsr_sharpness=_L.FSR_SHARPNESS):
+                      scaler="lanczos", fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
         """One frame of the hot path on lane ``lane``, stream-ordered and without any host synchronisation: u8 BGR frame in
         device memory at ``src_bgr_ptr`` -> hdrtv_preprocess -> hdrtv_infer_lane -> hdrtv_post_rgb48 -> u16 RGB48 at the device
         address ``dst_rgb48_ptr``.  ``stream``: a ``torch.cuda.Stream`` (default: the lane's own).  Frames enqueued on different
@@ -508,31 +518,35 @@ class HDRTVNetMI355X:
         ``scaler``: ``"lanczos"`` (the default: all of the above) or ``"fsr"``: an enlarged frame goes through ``hdrtv_post_rgb48_fsr``,
         the reference's default upscaler, at most 2x per axis; ``antiring`` and ``cas`` must then be 0 or ``"auto"``
         (which is 0 there).  ``fsr_sharpness``: its RCAS sharpness, 0 .. 2 (0 = the sharpest; the reference's 0.2), or None = EASU
-        alone.  A frame at the processing size is not touched by either."""
+        alone.  A frame at the processing size is not touched by either.  ``downscaler``: None (the default: an ``out_hw`` below the
+        processing size is refused, as before), ``"mitchell"`` or ``"ssim"``: a frame delivered below the processing size, by at most
+        4x per axis, goes through ``hdrtv_post_rgb48_down`` with the anti-ringing strength ``down_antiring``, 0 .. 1
+        or ``"auto"`` = the reference's 0.20; ``scaler`` must then be ``"lanczos"`` and ``antiring`` / ``cas`` 0 or ``"auto"``, and an
+        ``out_hw`` with nothing to shrink is a ``ValueError`` (``lib.down_options``)."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         self._enqueue(lane, self._lib.hdrtv_preprocess, "hdrtv_preprocess", (src_bgr_ptr,), h, w, dst_rgb48_ptr, stream, out,
-                      light_ptr, light_rect, self._cleanup_for(cleanup, out), *self._scale_for(antiring, cas, scaler, fsr_sharpness, h, w, out))
+                      light_ptr, light_rect, self._cleanup_for(cleanup, out), *self._scale_for(antiring, cas, scaler, fsr_sharpness, h, w, out, downscaler, down_antiring))
 
     def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None,
                              out_hw=None, out_pix_fmt="rgb48le", out_siting="left", light_ptr=None, light_rect=None, cleanup=None,
-                             antiring=0.0, cas=0.0, scaler="lanczos", fsr_sharpness=_L.FSR_SHARPNESS):
+                             antiring=0.0, cas=0.0, scaler="lanczos", fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
         """``enqueue_frame`` of an 8-bit 4:2:0 frame: the planes lie back to back at the device address ``src_ptr`` (the
         ``(h*3//2, w)`` u8 array ``preprocess_yuv420`` takes) and ``hdrtv_preprocess_yuv420`` replaces ``hdrtv_preprocess``."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         planes = _yuv_planes(src_ptr, int(h), int(w), layout, matrix, full_range)
         self._enqueue(lane, self._lib.hdrtv_preprocess_yuv420, "hdrtv_preprocess_yuv420", planes, h, w, dst_rgb48_ptr, stream, out,
-                      light_ptr, light_rect, self._cleanup_for(cleanup, out), *self._scale_for(antiring, cas, scaler, fsr_sharpness, h, w, out))
+                      light_ptr, light_rect, self._cleanup_for(cleanup, out), *self._scale_for(antiring, cas, scaler, fsr_sharpness, h, w, out, downscaler, down_antiring))
 
     def enqueue_frame_ycbcr10(self, lane, src_ptr, h, w, dst_ptr, *, pix_fmt, matrix=709, full_range=False, stream=None, out_hw=None,
                               out_pix_fmt="rgb48le", out_siting="left", cleanup=None, antiring=0.0, cas=0.0, scaler="lanczos",
-                              fsr_sharpness=_L.FSR_SHARPNESS):
+                              fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
         """``enqueue_frame`` of a 10-bit Y'CbCr frame (``pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le``): the planes lie
         back to back at the device address ``src_ptr`` (the u16 array ``preprocess_ycbcr10`` takes) and
         ``hdrtv_preprocess_ycbcr10`` replaces ``hdrtv_preprocess``."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         planes = _ycbcr10_planes(src_ptr, int(h), int(w), pix_fmt, matrix, full_range)
         self._enqueue(lane, self._lib.hdrtv_preprocess_ycbcr10, "hdrtv_preprocess_ycbcr10", planes, h, w, dst_ptr, stream, out,
-                      None, None, self._cleanup_for(cleanup, out), *self._scale_for(antiring, cas, scaler, fsr_sharpness, h, w, out))
+                      None, None, self._cleanup_for(cleanup, out), *self._scale_for(antiring, cas, scaler, fsr_sharpness, h, w, out, downscaler, down_antiring))
 
     def _upload(self, key, src, staged=None):
         """Device pointer of the host u8 array ``src``, uploaded through the staging slot kept per ``key`` in ``_staging``: a
@@ -751,14 +765,17 @@ class HDRTVNetMI355X:
 
     @torch.inference_mode()
     def postprocess_rgb48_scaled(self, output, out_w, out_h, pq=False, peak_nits=1000.0, antiring=0.0, cas=0.0, scaler="lanczos",
-                                 fsr_sharpness=_L.FSR_SHARPNESS):
+                                 fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
         """RGB48 at the display size: the u16 codes of ``hdrtv_post_rgb48`` (``pq=True``: of
         ``hdrtv_post_pq_rgb48`` at ``peak_nits``) upscaled to ``out_h`` x ``out_w`` by ``hdrtv_post_rgb48_scaled`` in one kernel.
         ``antiring``: the anti-ringing strength, 0 .. 1, or ``"auto"`` = ``lib.scale_antiring`` of the two sizes; nonzero:
         ``hdrtv_post_rgb48_scaled_ex``.  ``cas``: the strength of the contrast-adaptive sharpening in front of the upscale, 0 .. 1, or
         ``"auto"`` = ``lib.scale_cas`` of the two sizes; nonzero: ``hdrtv_post_rgb48_scaled_cas``.  ``scaler="fsr"``: ``hdrtv_post_rgb48_fsr`` instead, the reference's default upscaler, at most 2x
         per axis (more is a ``ValueError``); ``antiring`` and ``cas`` must then be 0 or ``"auto"`` (which is 0 there); ``fsr_sharpness``:
-        the RCAS sharpness, 0 .. 2 (the reference's 0.2), or None = EASU alone.  Returns a new device u16 ``(out_h, out_w, 3)`` tensor; stream-ordered on the current stream,
+        the RCAS sharpness, 0 .. 2 (the reference's 0.2), or None = EASU alone.  ``downscaler``: None (a size below the processing size is a ``ValueError``, as before),
+        ``"mitchell"`` or ``"ssim"``: ``hdrtv_post_rgb48_down`` shrinks to a size below the processing size, by at most 4x per axis, with
+        the anti-ringing strength ``down_antiring`` (0 .. 1, or ``"auto"`` = the reference's 0.20); ``lib.down_options`` has the refusals
+        (a mixed or larger request, ``scaler="fsr"``, a nonzero ``antiring`` / ``cas``, nothing to shrink).  Returns a new device u16 ``(out_h, out_w, 3)`` tensor; stream-ordered on the current stream,
         no synchronisation."""
         if isinstance(output, (tuple, list)):
             output = output[0]
@@ -766,6 +783,13 @@ class HDRTVNetMI355X:
             raise ValueError("postprocess_rgb48_scaled expects an fp16 or fp32 tensor")
         h, w = int(output.shape[-2]), int(output.shape[-1])
         out_w, out_h = int(out_w), int(out_h)
+        down = _L.down_options(downscaler, down_antiring, w, h, out_w, out_h, scaler, antiring, cas)
+        if down is not None:
+            output = output.contiguous()
+            dst = torch.empty((out_h, out_w, 3), dtype=torch.uint16, device=self.device)
+            self._chk(self._lib.hdrtv_post_rgb48_down(self._ctx, self._stream(), output.data_ptr(), _dtype_code(output), h, w, 1 if pq else 0,
+                                                      float(peak_nits), dst.data_ptr(), out_h, out_w, *down), "hdrtv_post_rgb48_down")
+            return dst
         if out_w < w or out_h < h:
             raise ValueError(f"output size {out_w}x{out_h} is below the processing size {w}x{h} (enlarging only)")
         fsr = self._fsr_for(scaler, fsr_sharpness, antiring, cas, h, w, out_h, out_w)

@@ -124,7 +124,7 @@ class HeadlessPipelineWorker:
                  status_cb=None, buffer_frames=1, out_w=None, out_h=None, out_pix_fmt="rgb48le", out_siting="left",
                  light_stats=False, light_rect=None, deband=False, deband_range=_L.DEBAND_RANGE,
                  deband_threshold=_L.DEBAND_THRESHOLD, dither="none", antiring=0.0, cas=0.0, scaler="lanczos",
-                 fsr_sharpness=_L.FSR_SHARPNESS):
+                 fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
         self._weights_dir = weights_dir
         self._use_hg = bool(use_hg)
         self._hg_override = hg_weights
@@ -155,6 +155,13 @@ class HeadlessPipelineWorker:
         self._fsr_sharpness = _L.check_fsr_sharpness(fsr_sharpness)
         if self._scaler == "fsr":
             _L.check_fsr_size(self._proc_w, self._proc_h, self._out.w, self._out.h)
+        # what shrinks a frame delivered BELOW the processing size: None (the default: such a size is refused, as
+        # before), "mitchell" or "ssim" = hdrtv_post_rgb48_down, at most 4x per axis, with the anti-ringing strength down_antiring
+        # (0 .. 1, or "auto" = the reference's 0.20).  lib.down_options has the refusals: a mixed request, an enlarging scaler option,
+        # a downscaler with nothing to shrink.
+        self._downscaler, self._down_antiring = _L.check_downscaler(downscaler), down_antiring
+        _L.down_options(self._downscaler, self._down_antiring, self._proc_w, self._proc_h, self._out.w, self._out.h, self._scaler,
+                        self._antiring, self._cas)
         # HDR10 content light level: every delivered frame carries its record (``.light``), measured on the
         # device from the codes the sink receives over ``light_rect = (x0, y0, rw, rh)`` in delivered-frame coordinates (None: the
         # whole frame), and ``content_light`` accumulates MaxCLL / MaxFALL in delivery order.  Off: nothing is launched or allocated.
@@ -306,7 +313,7 @@ class HeadlessPipelineWorker:
         start.record(torch.cuda.current_stream())
         pw, ph = int(proc_w or self._proc_w), int(proc_h or self._proc_h)
         ow, oh = int(out_w or self._out_w or pw), int(out_h or self._out_h or ph)
-        if ow < pw or oh < ph:
+        if self._downscaler is None and (ow < pw or oh < ph):
             raise ValueError(f"output size {ow}x{oh} is below the processing size {pw}x{ph} (enlarging only)")
         with torch.inference_mode():
             if frame.ndim == 2 and frame.dtype == np.uint16:
@@ -364,14 +371,15 @@ class HeadlessPipelineWorker:
         does (209-235): convert, copy, synchronise the stream, hand the finished frame over.  ``out_hw = (out_h, out_w)``: the
         ring, the fallback buffer and the frame are at that size and the conversion is ``hdrtv_post_rgb48_scaled`` (with the
         worker's ``antiring``, resolved here from the tensor's and the delivered size: ``hdrtv_post_rgb48_scaled_ex``; with its ``cas``, resolved alike:
-        ``hdrtv_post_rgb48_scaled_cas``; with ``scaler="fsr"`` ``hdrtv_post_rgb48_fsr`` does the enlargement).  With a
+        ``hdrtv_post_rgb48_scaled_cas``; with ``scaler="fsr"`` ``hdrtv_post_rgb48_fsr`` does the enlargement; with a ``downscaler`` and a size below the tensor's
+        ``hdrtv_post_rgb48_down`` shrinks).  With a
         Y'CbCr ``out_pix_fmt`` the slot (an RGB48 slot holds any of the layouts) receives the planes, only the frame's bytes are
         committed (``hdrtv_ring_commit_bytes``) and the frame is a 1-D u16 view of them."""
         p = self._processor
         t = tensor[0] if isinstance(tensor, (tuple, list)) else tensor
         th, tw = int(t.shape[-2]), int(t.shape[-1])
         h, w = (int(out_hw[0]), int(out_hw[1])) if out_hw is not None else (th, tw)
-        if h < th or w < tw:
+        if self._downscaler is None and (h < th or w < tw):
             raise ValueError(f"output size {w}x{h} is below the tensor's {tw}x{th} (enlarging only)")
         if self._ring_shape != (h, w):
             p._chk(p._lib.hdrtv_ring_create(p._ctx, _RING_FRAMES, h, w), "hdrtv_ring_create")
@@ -385,19 +393,23 @@ class HeadlessPipelineWorker:
         if self._scaler == "fsr" and (h, w) != (th, tw):
             _L.check_fsr_size(tw, th, w, h)            # a hot-swap of the processing resolution may have moved the ratio past 2x
             fsr = (0, 0.0) if self._fsr_sharpness is None else (1, self._fsr_sharpness)
+        down = None
+        if self._downscaler is not None and (h, w) != (th, tw):      # hdrtv_post_rgb48_down; a hot-swap may have moved the ratio
+            down = _L.down_options(self._downscaler, self._down_antiring, tw, th, w, h, self._scaler, self._antiring, self._cas)
+            antiring = cas = 0
 
         def convert(dst, key):
             """The frame into ``dst`` and, when measured, its light level record into the pinned record kept per ``key``, all on
             ``st``: whatever is recorded on ``st`` afterwards (the slot's ready event) covers both.  Returns that record."""
             if not self._light:
-                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, antiring=antiring, cas=cas, fsr=fsr)
+                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, antiring=antiring, cas=cas, fsr=fsr, down=down)
                 return None
             bufs = self._light_bufs.get(key)
             if bufs is None:
                 bufs = self._light_bufs[key] = (torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, device=p.device),
                                                 torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, pin_memory=True))
             p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", bufs[0].data_ptr(), self._light_rect,
-                        self._cleanup, antiring, cas, fsr)
+                        self._cleanup, antiring, cas, fsr, down)
             with torch.cuda.stream(st):
                 bufs[1].copy_(bufs[0], non_blocking=True)
             return bufs[1].numpy()

@@ -261,6 +261,57 @@ int hdrtv_post_rgb48_scaled_cas(hdrtv_ctx *ctx, void *stream, const void *dev_ou
 int hdrtv_post_rgb48_fsr(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
                          uint16_t *dst, int dH, int dW, int rcas, float sharpness);
 
+/* RGB48 BELOW the processing size: hdrtv_post_rgb48 (pq = 0; peak_nits ignored) or hdrtv_post_pq_rgb48 (pq != 0), then the
+ * reference's downscaling chain, in one kernel without a frame at the processing size in device memory.  For an output smaller than
+ * the source the reference has a fixed, default-on path: dscale=mitchell, correct-downscaling=yes, linear-downscaling=no,
+ * dscale-antiring=0.20 (_apply_presentation_scaler_defaults, gui_mpv_widget.py) and assets/shaders/SSimDownscaler.glsl first in
+ * every shader chain (_build_shader_paths), whose passes run exactly when the output is smaller.  Stage A is mpv's part: mpv is not
+ * in the reference tree, parity with its own Mitchell arithmetic is UNPINNED, and the device is held to the integer rule below.
+ * Stage B (ssim = 1) is the shader's, which IS in the reference tree: its arithmetic in float32, operation by operation (every
+ * multiply, add, subtract, divide and square root rounded on its own, no fused multiply-add, denormals kept); what a display's GLSL
+ * compiler makes of the shader is UNPINNED.  tests/rgb48_down_ref.py restates both in NumPy and the GPU tests hold this entry
+ * point to it bit for bit.
+ *  1. codes: c = exactly what hdrtv_post_rgb48 / hdrtv_post_pq_rgb48 writes at the processing size, [H][W][3]; the rule sees only
+ *     these integers.  Indices outside the frame read the clamped pixel.
+ *  2. footprint, per axis, source extent n, destination extent m, n / 4 <= m <= n, in double on the host for d = 0..m-1:
+ *       ctr = (d + 0.5) * n / m;  hw = 2.0 * n / m;  k_lo = ceil(ctr - hw - 0.5);  k_hi = floor(ctr + hw - 0.5)
+ *       tap k lies at x_k = (k + 0.5 - ctr) * m / n, in destination pixels;  k2 = floor(ctr - 0.5)
+ *     The kernel is stretched by the ratio (correct-downscaling; also the low / high / rel of the shader's L2 passes): at most
+ *     floor(4 n / m) + 1 <= 17 taps.  An axis with m == n is one tap, k = d, weight one, in stage A and stage B alike.
+ *  3. stage A, Mitchell (B = C = 1/3) with w(x), x = |x_k|, in double:
+ *       x < 1: ((7 x - 12) x x + 16/3) / 6;   x < 2: ((((-7/3) x + 12) x - 20) x + 32/3) / 6;   else 0
+ *     summed in tap order to s; q_k = floor(w_k / s * 16384 + 0.5), the remainder 16384 - sum q to the largest coefficient (the
+ *     lowest k on a tie).  With a = antiring and the shapes of hdrtv_post_rgb48_scaled_ex's steps 3a / 3b:
+ *       horizontal, per source row y, channel and dx:  raw = sum_k c[y][clamp(k)] * qx_k   (int32)
+ *         lo / hi = min / max(c[y][clamp(k2)], c[y][clamp(k2 + 1)]) << 14;  d = clamp(raw, lo, hi) - raw
+ *         hor[y][dx] = raw + ((d * a + 128) >> 8)                           (flooring shift, 64 bits; |hor| < 2^31)
+ *       vertical, on rows clamp(k) of hor:  raw = sum_k hor[clamp(k)][dx] * qy_k   (int64); lo / hi from hor[clamp(k2)],
+ *         hor[clamp(k2 + 1)] likewise;  v = raw + ((d * a + 128) >> 8);  M = clamp((v + 2^27) >> 28, 0, 65535)
+ *     M are the Mitchell codes; with ssim = 0 they are the output.  a = 0 is the plain passes, a = 256 puts every output inside the
+ *     min / max of the 2 x 2 source codes that bracket it; the reference's 0.20 is a = floor(0.20 * 256 + 0.5) = 51.
+ *  4. stage B, samples: s = float32(c) / float32(65535), Ms = float32(M) / float32(65535), one correctly rounded division each (the
+ *     shader's POSTKERNEL is a 16-bit texture: the quantised Mitchell codes), so stage B is a pure function of (c, M).
+ *  5. L2, the Catmull-Rom mean of squares on the footprint of step 2: weight cr(|x_k|) in double, cr(x) = (1.5 x - 2.5) x x + 1 for
+ *     x < 1, else ((-0.5 x + 2.5) x - 4) x + 2, divided by the sum of the axis' weights (double, tap order), then rounded to float32
+ *     (the shader's division by W folded into the table).  Pass 1, vertical, on s * s (one rounded multiply):
+ *     acc = acc + wy_k * (s * s) for k ascending from acc = 0; pass 2, horizontal, on pass 1's float32 values, likewise.
+ *  6. mean3(v), at the output size: taps -1, 0, 1 with the weights 0.5, 1, 0.5, neighbours clamped to the image; inside each row
+ *     h = ((0.5 v[-1] + v[0]) + 0.5 v[1]) / 2, then over the rows ((0.5 h[-1] + h[0]) + 0.5 h[1]) / 2.
+ *  7. MR: mM = mean3(Ms), mQ = mean3(Ms * Ms), mL = mean3(L2) per channel;  Sl = Luma(max(mQ - mM * mM, 0)),
+ *     Sh = Luma(max(mL - mM * mM, 0)),  Luma = (0.2126 r + 0.7152 g) + 0.0722 b;  sigma = float32(10 / (255 * 255));
+ *       R = Sl > Sh ? min(max(Sh / Sl, 0), 1) : sqrt((Sh + sigma) / (Sl + sigma))           (a select; oversharp = 0 drops out)
+ *  8. final: a0 = mean3(R * mM), a1 = mean3(mM), a2 = mean3(R);  pix = sat((a1 + a2 * Ms) - a0);  the output code is
+ *     (int)(pix * 65535 + 0.5), the quantiser of the unscaled entry point.  A flat frame returns its code: the sums are exact,
+ *     Sl = Sh = 0, R = 1.
+ * Sizes: H / 4 <= dH <= H and W / 4 <= dW <= W (4 dH >= H, 4 dW >= W).  Equal sizes (dH == H && dW == W) delegate to the unscaled
+ * kernel and write its bytes, whatever the options; with one axis at identity both stages apply in full.  Out of scope: more than
+ * 4x, one axis up and one down, linear-light downscaling (the reference sets linear-downscaling=no).  Stream-ordered, needs no
+ * reservation; the tables are built at the first call with a geometry -- that call allocates and copies -- and kept in the context
+ * beside the tap tables.  HDRTV_EINVAL, before any device call and with dst untouched, for a NULL pointer, an unknown dtype, H, W, dH
+ * or dW < 1, pq with peak_nits <= 0, dH > H or dW > W, 4 dH < H or 4 dW < W, antiring outside 0..256, ssim outside {0, 1}. */
+int hdrtv_post_rgb48_down(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
+                          uint16_t *dst, int dH, int dW, int antiring, int ssim);
+
 /* 10-bit limited-range Y'CbCr for an encoder (HEVC Main10, hardware encoders, ProRes): P010 and yuv420p10le are 3 bytes per pixel,
  * yuv422p10le 4, against the 6 of RGB48.  The reference's export converts on the CPU: it pipes rgb48le into ffmpeg, zscale goes to
  * BT.2020nc limited range and format=yuv422p10le feeds prores_ks (gui_export.py:948-1005).  The network's output is PQ-encoded BT.2020
