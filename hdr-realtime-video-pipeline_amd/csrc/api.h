@@ -270,6 +270,9 @@ struct hdrtv_ctx {
     // [dW * ntx + dH * nty], then as many float32 L2 weights; built on first use of a geometry
     struct DownTabs { int4 *dev; int ntx, nty; };
     std::map<std::array<int, 4>, DownTabs> down_tabs;
+    // hdrtv_post_rgb48_ssimsr: device tables per (H, W, dH, dW) in one allocation -- int4 [2 (dW + dH) + W + H] (xsp, ysp, xfin, yfin,
+    // xlow, ylow), then SR_NT float32 weights per source index [W + H]; built on first use of a geometry
+    std::map<std::array<int, 4>, int4 *> ssimsr_tabs;
     // objective metrics partial sums
     double *mt_dev = nullptr;
     size_t mt_cap = 0;

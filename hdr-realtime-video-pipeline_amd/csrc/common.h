@@ -440,6 +440,26 @@ struct PostDownParams {
     int H, W, dH, dW, ntx, nty;
 };
 
+// Fused quantise + spline36 / SSimSuperRes enlargement (post_ssimsr.hip): the same tensors, H < dH <= 2 H and W < dW <= 2 W.
+// Per destination index of an axis, xsp [dW] / ysp [dH]: the spline36 taps in PostScaleParams' form; xfin / yfin: {ip, the bits of the
+// three float32 Hann weights at -1, 0, 1}.  Per source index, xlow [W] / ylow [H]: {first high-resolution tap (unclamped), tap count,
+// b0, the bits of the float32 f of pass II's linear fetch}; xw / yw: SR_NT float32 weights per source index, zero-padded
+// (include/hdrtv_mi355x.h states the rule).  A workgroup owns SR_TH x SR_TW output pixels; the extents of the regions it keeps in
+// LDS (post_ssimsr.hip's header derives them): low-resolution positions, spline36 codes and source codes, with stage B / without.
+constexpr int SR_TW = 32, SR_TH = 16, SR_NT = 9;
+constexpr int sr_nl(int t) { return t + 4; }                                  // low-resolution pixels: Lr
+constexpr int sr_np(bool ssim, int t) { return ssim ? t + 18 : t; }           // spline36 codes
+constexpr int sr_nc(bool ssim, int t) { return ssim ? t + 14 : t + 5; }       // source codes
+struct PostSsimsrParams {
+    const void *in;
+    uint16_t *dst;
+    const int4 *xsp, *ysp, *xfin, *yfin, *xlow, *ylow;
+    const float *xw, *yw;
+    const float *pq_bnd;             // PQ variant: the code boundaries of hdrtv_post_pq_rgb48
+    float peak;
+    int H, W, dH, dW;
+};
+
 // 10-bit limited-range BT.2020nc Y'CbCr output (post_ycbcr.hip; include/hdrtv_mi355x.h states the integer rule): a workgroup owns
 // YC_TH x YC_TW luma pixels.  fmt / siting carry the header's HDRTV_YCC_* / HDRTV_SITING_* values; pitches in u16 elements.
 constexpr int YC_TW = 128, YC_TH = 16;

@@ -78,6 +78,7 @@ int hdrtv_destroy(hdrtv_ctx *c)
     for (auto &kv : c->ps_tabs) (void)hipFree(kv.second);
     for (auto &kv : c->fsr_tabs) (void)hipFree(kv.second);
     for (auto &kv : c->down_tabs) (void)hipFree(kv.second.dev);
+    for (auto &kv : c->ssimsr_tabs) (void)hipFree(kv.second);
     if (c->mt_dev) (void)hipFree(c->mt_dev);
     free_workspaces(c);
     if (c->wts.dev) (void)hipFree(c->wts.dev);
@@ -769,6 +770,161 @@ int hdrtv_post_rgb48_down(hdrtv_ctx *c, void *stream, const void *in, int dtype,
     const float *w = reinterpret_cast<const float *>(q + nq);
     PostDownParams p{in, dst, t.dev, t.dev + dW, q, q + nqx, w, w + nqx, c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW, t.ntx, t.nty};
     return launched(c, "post_rgb48_down", post_down_launch(p, antiring, ssim, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
+}
+
+// Tables of one axis of hdrtv_post_rgb48_ssimsr (the rule: include/hdrtv_mi355x.h), n source -> m destination samples, n < m <= 2 n.
+// Per destination index: sp, the spline36 taps in lanczos_taps' form; fin, {ip, the bits of the Hann weights at -1, 0, 1}.  Per
+// source index: low, {first tap of the step-4 footprint (unclamped), tap count, b0, the bits of f}; w, SR_NT weights (divided by their
+// sum in double, then float32, zero-padded).
+struct SsimsrAxis {
+    std::vector<int4> sp, fin, low;
+    std::vector<float> w;
+};
+static int float_bits(float v)
+{
+    int b;
+    memcpy(&b, &v, sizeof b);
+    return b;
+}
+static bool ssimsr_axis(int n, int m, SsimsrAxis &t)
+{
+    const double PI = 3.14159265358979323846;
+    auto spline36 = [](double x) {
+        x = std::fabs(x);
+        if (x < 1.0) return ((13.0 / 11.0 * x - 453.0 / 209.0) * x - 3.0 / 209.0) * x + 1.0;
+        if (x < 2.0) { const double y = x - 1.0; return ((-6.0 / 11.0 * y + 270.0 / 209.0) * y - 156.0 / 209.0) * y; }
+        if (x < 3.0) { const double y = x - 2.0; return ((1.0 / 11.0 * y - 45.0 / 209.0) * y + 26.0 / 209.0) * y; }
+        return 0.0;
+    };
+    auto mn = [](double x) {
+        const double b = 0.334, c = 0.333;
+        x = std::fabs(x);
+        if (x < 1.0) return ((2.0 - 1.5 * b - c) * x + (-3.0 + 2.0 * b + c)) * x * x + (1.0 - b / 3.0);
+        return (((-b / 6.0 - c) * x + (b + 5.0 * c)) * x + (-2.0 * b - 8.0 * c)) * x + (4.0 / 3.0 * b + 4.0 * c);
+    };
+    t.sp.resize(m);
+    t.fin.resize(m);
+    for (int d = 0; d < m; ++d) {
+        const double c = (d + 0.5) * n / m - 0.5, f = std::floor(c), tt = c - f;
+        double w[6], sum = 0.0;
+        for (int k = 0; k < 6; ++k) {
+            w[k] = spline36(tt - (k - 2));
+            sum += w[k];
+        }
+        int q[6], tot = 0, big = 0;
+        for (int k = 0; k < 6; ++k) {
+            q[k] = (int)std::floor(w[k] / sum * 16384.0 + 0.5);
+            tot += q[k];
+            if (q[k] > q[big]) big = k;          // the lowest k on a tie
+        }
+        q[big] += 16384 - tot;
+        auto pack = [](int lo, int hi) { return (int)(((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16)); };
+        t.sp[d] = make_int4((int)f - 2, pack(q[0], q[1]), pack(q[2], q[3]), pack(q[4], q[5]));
+        const double ip = std::floor(c + 0.5), off = c - ip;           // GLSL's round with the tie going up
+        t.fin[d] = make_int4((int)ip, float_bits((float)std::cos(PI * (-1.0 - off) / 3.0)), float_bits((float)std::cos(PI * (0.0 - off) / 3.0)),
+                             float_bits((float)std::cos(PI * (1.0 - off) / 3.0)));
+    }
+    t.low.resize(n);
+    t.w.assign((size_t)n * SR_NT, 0.f);
+    const double hw = 2.0 * m / n;
+    for (int j = 0; j < n; ++j) {
+        const double ctr = (j + 0.5) * m / n;
+        const int lo = (int)std::ceil(ctr - hw - 0.5), hi = (int)std::floor(ctr + hw - 0.5), cnt = hi - lo + 1;
+        if (cnt < 1 || cnt > SR_NT) return false;
+        double v[SR_NT], s = 0.0;
+        for (int k = 0; k < cnt; ++k) {
+            v[k] = mn((lo + k + 0.5 - ctr) * n / m);
+            s += v[k];
+        }
+        for (int k = 0; k < cnt; ++k) t.w[(size_t)j * SR_NT + k] = (float)(v[k] / s);
+        const double u = ctr - 0.5, b0 = std::floor(u);
+        t.low[j] = make_int4(lo, cnt, (int)b0, float_bits((float)(u - b0)));
+    }
+    return true;
+}
+
+// What post_ssimsr.hip's header derives, checked on the tables themselves: along one axis, every tile's regions fit the kernel's
+// arrays and every index a phase reads lies in the region the phase before it filled.
+static bool ssimsr_axis_fits(const SsimsrAxis &t, int n, int m, int T, bool ssim)
+{
+    auto cl = [](int v, int hi) { return std::min(std::max(v, 0), hi); };
+    for (int d0 = 0; d0 < m; d0 += T) {
+        const int d1 = std::min(d0 + T, m) - 1;
+        int fa = 0, fb = 0, la = 0, lb = 0, pa = d0, pb = d1;
+        if (ssim) {
+            fa = std::max(t.fin[d0].x - 1, 0), fb = std::min(t.fin[d1].x + 1, n - 1);
+            la = std::max(fa - 1, 0), lb = std::min(fb + 1, n - 1);
+            pa = std::max(t.low[la].x, 0), pb = std::min(t.low[lb].x + t.low[lb].y - 1, m - 1);
+        }
+        const int ca = std::max(t.sp[pa].x, 0), cb = std::min(t.sp[pb].x + 5, n - 1);
+        if (pa > pb || ca > cb || pb - pa + 1 > sr_np(ssim, T) || cb - ca + 1 > sr_nc(ssim, T)) return false;
+        for (int d = pa; d <= pb; ++d)
+            if (cl(t.sp[d].x, n - 1) < ca || cl(t.sp[d].x + 5, n - 1) > cb) return false;
+        if (!ssim) continue;
+        if (fa > fb || lb - la + 1 > sr_nl(T) || fb - fa + 1 > T + 2 || la < ca || lb > cb || d0 < pa || d1 > pb) return false;
+        for (int j = la; j <= lb; ++j) {
+            const int4 e = t.low[j];
+            if (cl(e.x, m - 1) < pa || cl(e.x + e.y - 1, m - 1) > pb || cl(e.z, m - 1) < pa || cl(e.z + 1, m - 1) > pb) return false;
+        }
+        for (int d = d0; d <= d1; ++d)
+            if (cl(t.fin[d].x - 1, n - 1) < fa || cl(t.fin[d].x + 1, n - 1) > fb || t.fin[d].x < 0 || t.fin[d].x > n - 1) return false;
+    }
+    return true;
+}
+
+int hdrtv_post_rgb48_ssimsr(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
+                            uint16_t *dst, int dH, int dW, int ssim)
+{
+    if (!c || !in || !dst || H <= 0 || W <= 0 || dH <= 0 || dW <= 0) return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: bad argument");
+    const bool same = dH == H && dW == W;
+    if (!same && (dH <= H || dW <= W))
+        return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: %dx%d -> %dx%d does not enlarge both axes", W, H, dW, dH);
+    if (dH > 2 * (long long)H || dW > 2 * (long long)W)
+        return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: %dx%d -> %dx%d is more than 2x on an axis", W, H, dW, dH);
+    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: bad dtype %d", dtype);
+    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: pq needs peak_nits > 0");
+    if (ssim != 0 && ssim != 1) return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: ssim %d is neither 0 nor 1", ssim);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = pq ? ensure_pq_table(c, "post_rgb48_ssimsr") : HDRTV_OK) return rc;
+    // the reference's upscaler runs only when the frame is enlarged: equal sizes are the unscaled kernel's bytes, whatever ssim
+    if (same) {
+        return launched(c, "post_rgb48_ssimsr", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd));
+    }
+    // first use of a geometry builds its tables (allocates, copies); every later call finds them and only launches
+    const std::array<int, 4> key{H, W, dH, dW};
+    auto it = c->ssimsr_tabs.find(key);
+    if (it == c->ssimsr_tabs.end()) {
+        SsimsrAxis ax, ay;
+        if (!ssimsr_axis(W, dW, ax) || !ssimsr_axis(H, dH, ay) || !ssimsr_axis_fits(ax, W, dW, SR_TW, false) ||
+            !ssimsr_axis_fits(ax, W, dW, SR_TW, true) || !ssimsr_axis_fits(ay, H, dH, SR_TH, false) || !ssimsr_axis_fits(ay, H, dH, SR_TH, true))
+            return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: the tables of %dx%d -> %dx%d leave the kernel's tile bounds", W, H, dW, dH);
+        if (c->ssimsr_tabs.size() >= 16) {
+            for (auto &kv : c->ssimsr_tabs) (void)hipFree(kv.second);
+            c->ssimsr_tabs.clear();
+        }
+        const size_t ni = 2 * ((size_t)dW + dH) + W + H, nw = ((size_t)W + H) * SR_NT;
+        std::vector<char> host(ni * sizeof(int4) + nw * sizeof(float));
+        int4 *h = reinterpret_cast<int4 *>(host.data());
+        for (const std::vector<int4> *v : {&ax.sp, &ay.sp, &ax.fin, &ay.fin, &ax.low, &ay.low}) {
+            memcpy(h, v->data(), v->size() * sizeof(int4));
+            h += v->size();
+        }
+        float *hwt = reinterpret_cast<float *>(h);
+        memcpy(hwt, ax.w.data(), ax.w.size() * sizeof(float));
+        memcpy(hwt + ax.w.size(), ay.w.data(), ay.w.size() * sizeof(float));
+        int4 *dev = nullptr;
+        if (hipMalloc((void **)&dev, host.size()) != hipSuccess) return fail(c, HDRTV_ENOMEM, "post_rgb48_ssimsr: table allocation failed");
+        if (hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(dev);
+            return fail(c, HDRTV_EHIP, "post_rgb48_ssimsr: table upload failed");
+        }
+        it = c->ssimsr_tabs.emplace(key, dev).first;
+    }
+    const int4 *t = it->second;
+    const float *w = reinterpret_cast<const float *>(t + 2 * ((size_t)dW + dH) + W + H);
+    PostSsimsrParams p{in, dst, t, t + dW, t + dW + dH, t + 2 * (size_t)dW + dH, t + 2 * ((size_t)dW + dH), t + 2 * ((size_t)dW + dH) + W,
+                       w, w + (size_t)W * SR_NT, c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
+    return launched(c, "post_rgb48_ssimsr", post_ssimsr_launch(p, ssim, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
 // ------------------------------------------------------------------------------- letterbox

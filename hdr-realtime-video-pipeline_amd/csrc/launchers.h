@@ -157,6 +157,9 @@ hipError_t post_fsr_launch(const PostFsrParams &p, int rcas, float sharp, int is
 // quantise + Mitchell shrink (post_down.hip) with anti-ringing 0 .. 256, and with ssim != 0 the SSimDownscaler correction behind it;
 // hipErrorInvalidValue, nothing enqueued, unless 1 <= dH <= H <= 4 dH, 1 <= dW <= W <= 4 dW and 1 <= ntx, nty <= 17; pq != 0 needs p.pq_bnd
 hipError_t post_down_launch(const PostDownParams &p, int antiring, int ssim, int is_f32, int pq, hipStream_t s);
+// quantise + spline36 enlargement (post_ssimsr.hip), and with ssim != 0 the SSimSuperRes passes behind it; hipErrorInvalidValue,
+// nothing enqueued, unless 1 <= H < dH <= 2 H and 1 <= W < dW <= 2 W; pq != 0 needs p.pq_bnd
+hipError_t post_ssimsr_launch(const PostSsimsrParams &p, int ssim, int is_f32, int pq, hipStream_t s);
 // fmt 0 P010 | 1 yuv420p10 | 2 yuv422p10, siting 0 left | 1 top-left (4:2:0 only); W even, H even for 4:2:0; pq != 0 needs p.pq_bnd
 hipError_t post_ycbcr10_launch(const Ycbcr10Params &p, int is_f32, int pq, hipStream_t s);
 hipError_t rgb48_to_ycbcr10_launch(const Ycbcr10Params &p, hipStream_t s);

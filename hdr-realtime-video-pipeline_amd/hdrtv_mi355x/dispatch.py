@@ -415,7 +415,8 @@ class FrameDispatcher:
         (the default) or ``"fsr"`` = the product's worker enlarges through ``hdrtv_post_rgb48_fsr``, the reference's default upscaler
         (INTEGRATION.md 5c): the output size is then at most twice the processing size per axis, ``antiring`` and ``cas`` are 0
         (``"auto"`` resolves to 0, an explicit nonzero value is a ``ValueError``), and ``fsr_sharpness`` is its RCAS sharpness, 0 .. 2,
-        or None = EASU alone; kept as ``.scaler`` / ``.fsr_sharpness`` and handed on as ``init_args["scaler"]`` /
+        or None = EASU alone; ``"spline36"`` / ``"ssim_superres"`` = ``hdrtv_post_rgb48_ssimsr`` without / with the reference's
+        SSimSuperRes shader stage (both axes enlarged, by at most 2x; ``antiring`` and ``cas`` 0 likewise); kept as ``.scaler`` / ``.fsr_sharpness`` and handed on as ``init_args["scaler"]`` /
         ``init_args["fsr_sharpness"]`` only when the scaler is not the default: otherwise the ``init_args`` of before.
         ``downscaler``: None (the default: an output size below the processing size is a ``ValueError``, as before), ``"mitchell"``
         or ``"ssim"`` = the output size lies below the processing size, by at most 4x per axis, and the product's worker shrinks
@@ -457,6 +458,9 @@ class FrameDispatcher:
         if self.scaler == "fsr":
             _L.check_fsr_size(self.w, self.h, self.out_w, self.out_h)
             init_args["scaler"], init_args["fsr_sharpness"] = self.scaler, self.fsr_sharpness
+        if self.scaler in _L.SSIMSR_SCALERS:
+            _L.check_ssimsr_size(self.w, self.h, self.out_w, self.out_h)
+            init_args["scaler"] = self.scaler
         if self.downscaler is not None:
             init_args["downscaler"], init_args["down_antiring"] = self.downscaler, self.down_antiring
         self.pix_fmt = pix_fmt

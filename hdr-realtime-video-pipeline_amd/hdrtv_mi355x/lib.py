@@ -49,6 +49,7 @@ SYMBOLS = [
     ("hdrtv_post_rgb48_scaled_cas", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, _I]),
     ("hdrtv_post_rgb48_fsr", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, C.c_float]),
     ("hdrtv_post_rgb48_down", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, _I]),
+    ("hdrtv_post_rgb48_ssimsr", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I]),
     ("hdrtv_post_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_rgb48_to_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_ycbcr10_bytes", C.c_int64, [_I, _I, _I]),
@@ -333,14 +334,19 @@ def resolve_cas(value, proc_w, proc_h, out_w, out_h):
 SCALERS = ("lanczos", "fsr")               # what enlarges a frame to the delivered size: the fused Lanczos passes, or hdrtv_post_rgb48_fsr
 FSR_MAX_RATIO = 2                          # hdrtv_post_rgb48_fsr: the largest ratio per axis (the shader's EASU stage stops there)
 FSR_SHARPNESS = 0.2                        # the reference's RCAS sharpness (0 = the sharpest, 2 = the mildest)
+# every enlarging choice: the two above, and hdrtv_post_rgb48_ssimsr without ("spline36") / with ("ssim_superres", the reference's
+# third upscaler) its SSimSuperRes stage
+UPSCALERS = SCALERS + ("spline36", "ssim_superres")
+SSIMSR_SCALERS = UPSCALERS[len(SCALERS):]
+SSIMSR_MAX_RATIO = 2                       # hdrtv_post_rgb48_ssimsr: the largest ratio per axis
 
 
 def check_scaler(value="lanczos"):
     """A ``scaler`` option as the processor, the worker, the dispatcher and the command line take it: ``"lanczos"`` (the default: the
-    fused Lanczos upscale with its ``antiring`` and ``cas``) or ``"fsr"`` (``hdrtv_post_rgb48_fsr``, the reference's default), any
-    case; ``ValueError`` otherwise."""
-    if not isinstance(value, str) or value.lower() not in SCALERS:
-        raise ValueError(f"scaler must be one of {list(SCALERS)} (got {value!r})")
+    fused Lanczos upscale with its ``antiring`` and ``cas``), ``"fsr"`` (``hdrtv_post_rgb48_fsr``, the reference's default),
+    ``"spline36"`` or ``"ssim_superres"`` (``hdrtv_post_rgb48_ssimsr`` with ``ssim`` 0 / 1), any case; ``ValueError`` otherwise."""
+    if not isinstance(value, str) or value.lower() not in UPSCALERS:
+        raise ValueError(f"scaler must be one of {list(UPSCALERS)} (got {value!r})")
     return value.lower()
 
 
@@ -371,16 +377,31 @@ def check_fsr_size(proc_w, proc_h, out_w, out_h):
                          f"(the limit is {FSR_MAX_RATIO * proc_w}x{FSR_MAX_RATIO * proc_h})")
 
 
+def check_ssimsr_size(proc_w, proc_h, out_w, out_h):
+    """``ValueError`` unless ``hdrtv_post_rgb48_ssimsr`` takes the two sizes: equal to the processing size (nothing is enlarged), or
+    above it on BOTH axes and at most ``SSIMSR_MAX_RATIO`` times it on either."""
+    proc_w, proc_h, out_w, out_h = int(proc_w), int(proc_h), int(out_w), int(out_h)
+    if out_w < proc_w or out_h < proc_h:
+        raise ValueError(f"output size {out_w}x{out_h} is below the processing size {proc_w}x{proc_h} (enlarging only)")
+    if out_w > SSIMSR_MAX_RATIO * proc_w or out_h > SSIMSR_MAX_RATIO * proc_h:
+        raise ValueError(f"scalers 'spline36' and 'ssim_superres' enlarge by at most {SSIMSR_MAX_RATIO}x per axis: {proc_w}x{proc_h} -> "
+                         f"{out_w}x{out_h} is more (the limit is {SSIMSR_MAX_RATIO * proc_w}x{SSIMSR_MAX_RATIO * proc_h})")
+    if (out_w == proc_w) != (out_h == proc_h):
+        raise ValueError(f"scalers 'spline36' and 'ssim_superres' enlarge both axes: {proc_w}x{proc_h} -> {out_w}x{out_h} leaves one "
+                         f"at identity (the limit is {SSIMSR_MAX_RATIO}x per axis)")
+
+
 def scaler_options(scaler, antiring=0.0, cas=0.0):
     """``antiring`` and ``cas`` as they hold under ``scaler`` -> ``(antiring, cas)``, each checked.  ``"lanczos"``: unchanged.
     ``"fsr"``: the reference's schedules give 0 for both when its FSR shader does the enlargement (up to 2x), so ``"auto"`` resolves to
-    0.0 here; an explicit nonzero value belongs to the Lanczos scaler and is a ``ValueError``."""
+    0.0 here; an explicit nonzero value belongs to the Lanczos scaler and is a ``ValueError``.  ``"spline36"`` and
+    ``"ssim_superres"`` likewise: the reference sets scale-antiring = 0 and cas = 0 beside its SSimSuperRes shader."""
     scaler, antiring, cas = check_scaler(scaler), check_antiring(antiring), check_cas(cas)
-    if scaler != "fsr":
+    if scaler == "lanczos":
         return antiring, cas
     for name, v in (("antiring", antiring), ("cas", cas)):
         if v != "auto" and v != 0:
-            raise ValueError(f"{name}={v!r} belongs to scaler 'lanczos': scaler 'fsr' takes 0 or 'auto' (which is 0)")
+            raise ValueError(f"{name}={v!r} belongs to scaler 'lanczos': scaler {scaler!r} takes 0 or 'auto' (which is 0)")
     return 0.0, 0.0
 
 

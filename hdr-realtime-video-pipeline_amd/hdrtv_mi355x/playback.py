@@ -570,7 +570,7 @@ class RealtimePlayback:
 def parse_args(argv=None):
     """The command line of ``main`` -> the argparse namespace, checked (a bad value ends in ``ap.error``): ``.proc_wh`` and ``.out_wh``
     hold the two sizes as ``(w, h)``, ``.cleanup`` the ``lib.OutputCleanup`` of --deband / --dither, ``.antiring`` and ``.cas`` ``"auto"`` or the
-    strength as a float (0.0: off; both 0.0 under ``--scaler fsr``), ``.scaler`` ``"lanczos"`` or ``"fsr"``, ``.fsr_sharpness`` the RCAS
+    strength as a float (0.0: off; both 0.0 under any ``--scaler`` but lanczos), ``.scaler`` one of ``lib.UPSCALERS``, ``.fsr_sharpness`` the RCAS
     sharpness as a float or None (EASU alone), ``.downscaler`` None, ``"mitchell"`` or ``"ssim"``, ``.down_antiring`` its anti-ringing
     strength as a float (``auto`` resolved to the reference's 0.20)."""
     import argparse
@@ -610,9 +610,10 @@ def parse_args(argv=None):
                     "upscale (hdrtv_post_rgb48_scaled_cas; INTEGRATION.md 5c): a strength in 0 .. 1 as ffmpeg's cas filter takes it, "
                     "or auto = the reference's schedule by processing size (0.22 up to 960x540, 0.20 up to 1280x720, 0.16 above); "
                     "default: off")
-    ap.add_argument("--scaler", choices=_lib.SCALERS, default="lanczos", help="what enlarges to --out-size: lanczos (the fused Lanczos "
-                    "upscale with --antiring / --cas) or fsr (hdrtv_post_rgb48_fsr, the reference's default upscaler: EASU + RCAS; at "
-                    "most 2x per axis; --antiring and --cas are 0 there; INTEGRATION.md 5c)")
+    ap.add_argument("--scaler", choices=_lib.UPSCALERS, default="lanczos", help="what enlarges to --out-size: lanczos (the fused Lanczos "
+                    "upscale with --antiring / --cas), fsr (hdrtv_post_rgb48_fsr, the reference's default upscaler: EASU + RCAS; at "
+                    "most 2x per axis), spline36 or ssim_superres (hdrtv_post_rgb48_ssimsr without / with the reference's SSimSuperRes "
+                    "shader stage; both axes enlarged, at most 2x); --antiring and --cas are 0 under all but lanczos; INTEGRATION.md 5c")
     ap.add_argument("--fsr-sharpness", default=None, metavar="{none|0..2}", help="RCAS sharpness of --scaler fsr: 0 (the sharpest) .. 2, "
                     "or none = EASU alone; default: the reference's 0.2")
     ap.add_argument("--downscaler", choices=_lib.DOWNSCALERS, default=None, help="what shrinks to an --out-size below --size, by at "
@@ -674,6 +675,14 @@ def parse_args(argv=None):
             a.antiring, a.cas = _lib.scaler_options("fsr", a.antiring, a.cas)
         except ValueError as exc:
             ap.error(f"--scaler fsr: {exc}")
+    if a.scaler in _lib.SSIMSR_SCALERS:
+        if (owd, oht) == (wd, ht):
+            ap.error(f"--scaler {a.scaler} applies to an upscale: --out-size equals --size")
+        try:
+            _lib.check_ssimsr_size(wd, ht, owd, oht)
+            a.antiring, a.cas = _lib.scaler_options(a.scaler, a.antiring, a.cas)
+        except ValueError as exc:
+            ap.error(f"--scaler {a.scaler}: {exc}")
     try:
         a.down_antiring = 0.0 if a.down_antiring is None else _lib.check_down_antiring(
             a.down_antiring if a.down_antiring.lower() == "auto" else float(a.down_antiring))

@@ -342,7 +342,7 @@ class HDRTVNetMI355X:
         return scratch.data_ptr()
 
     def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None, antiring=0, cas=0,
-                  fsr=None, down=None):
+                  fsr=None, down=None, ssimsr=None):
         """The output conversion of a frame whose planar tensor lies at ``src_ptr``, to the ``lib.OutputFormat`` ``out`` at
         ``dst_ptr``: ``rgb48le`` at the processing size (``hdrtv_post_rgb48``) or enlarged to ``out.h`` x ``out.w``
         (``hdrtv_post_rgb48_scaled``); a 10-bit Y'CbCr layout in one kernel at the processing size (``hdrtv_post_ycbcr10``), or,
@@ -365,8 +365,10 @@ class HDRTVNetMI355X:
         sharpness)`` = the enlarged frame goes through ``hdrtv_post_rgb48_fsr`` instead (``_fsr_for``; ``antiring`` and ``cas`` are 0
         then), and everything behind the scaler sees the FSR codes.  ``down``: None, or ``(antiring code, ssim)`` = a frame delivered
         BELOW the processing size goes through ``hdrtv_post_rgb48_down`` (``lib.down_options``; the other three are off then), and
-        everything behind it -- deband, the conversion from codes, the record -- sees the shrunk codes.  This is the one place that
-        chooses among the five entry points."""
+        everything behind it -- deband, the conversion from codes, the record -- sees the shrunk codes.  ``ssimsr``: None, or 0 / 1 = the
+        enlarged frame goes through ``hdrtv_post_rgb48_ssimsr`` with that ``ssim`` (``_ssimsr_for``: spline36 alone, or the
+        reference's SSimSuperRes chain; the other four are off then), and everything behind the scaler sees its codes.  This is the
+        one place that chooses among the six entry points."""
         scaled = (out.h, out.w) != (h, w)
         rect = (0, 0, out.w, out.h) if light_rect is None else tuple(int(v) for v in light_rect)
         active = cleanup is not None and cleanup.active
@@ -391,6 +393,9 @@ class HDRTVNetMI355X:
         elif scaled and fsr is not None:
             self._chk(self._lib.hdrtv_post_rgb48_fsr(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, fsr[0], fsr[1]),
                       "hdrtv_post_rgb48_fsr")
+        elif scaled and ssimsr is not None:
+            self._chk(self._lib.hdrtv_post_rgb48_ssimsr(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, int(ssimsr)),
+                      "hdrtv_post_rgb48_ssimsr")
         elif scaled and cas:
             self._chk(self._lib.hdrtv_post_rgb48_scaled_cas(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, int(antiring),
                                                             int(cas)), "hdrtv_post_rgb48_scaled_cas")
@@ -466,26 +471,44 @@ class HDRTVNetMI355X:
         be 0 or ``"auto"`` (``lib.scaler_options``), the delivered size at most twice the processing size (``lib.check_fsr_size``)."""
         if scaler == "lanczos":                                       # the default: nothing to resolve on the hot path
             return None
-        if _L.check_scaler(scaler) == "lanczos":
+        if _L.check_scaler(scaler) != "fsr":
             return None
         _L.scaler_options("fsr", antiring, cas)
         _L.check_fsr_size(w, h, out_w, out_h)
         sharp = _L.check_fsr_sharpness(fsr_sharpness)
         return (0, 0.0) if sharp is None else (1, sharp)
 
+    @staticmethod
+    def _ssimsr_for(scaler, antiring, cas, h, w, out_h, out_w):
+        """The ``scaler`` argument of ``enqueue_frame*`` and ``postprocess_rgb48_scaled`` -> what ``_post_out`` takes as ``ssimsr``:
+        None unless it is ``"spline36"`` (0) or ``"ssim_superres"`` (1), after the checks -- ``antiring`` and ``cas`` must be 0 or
+        ``"auto"`` (``lib.scaler_options``), the delivered size the processing size or above it on both axes, by at most 2x
+        (``lib.check_ssimsr_size``)."""
+        if scaler == "lanczos":                                       # the default: nothing to resolve on the hot path
+            return None
+        scaler = _L.check_scaler(scaler)
+        if scaler not in _L.SSIMSR_SCALERS:
+            return None
+        _L.scaler_options(scaler, antiring, cas)
+        _L.check_ssimsr_size(w, h, out_w, out_h)
+        return 1 if scaler == "ssim_superres" else 0
+
     def _scale_for(self, antiring, cas, scaler, fsr_sharpness, h, w, out, downscaler=None, down_antiring=0.0):
-        """The scaler arguments of ``enqueue_frame*`` -> ``(antiring code, CAS code, fsr, down)`` as ``_post_out`` takes them."""
+        """The scaler arguments of ``enqueue_frame*`` -> ``(antiring code, CAS code, fsr, down, ssimsr)`` as ``_post_out`` takes them."""
         if downscaler is not None or not (type(down_antiring) in (float, int) and down_antiring == 0):
             down = _L.down_options(downscaler, down_antiring, w, h, out.w, out.h, scaler, antiring, cas)
             if down is not None:
-                return 0, 0, None, down
+                return 0, 0, None, down, None
         fsr = self._fsr_for(scaler, fsr_sharpness, antiring, cas, h, w, out.h, out.w)
         if fsr is not None:
-            return 0, 0, fsr, None
-        return self._antiring_for(antiring, h, w, out), self._cas_for(cas, h, w, out), None, None
+            return 0, 0, fsr, None, None
+        ssimsr = self._ssimsr_for(scaler, antiring, cas, h, w, out.h, out.w)
+        if ssimsr is not None:
+            return 0, 0, None, None, ssimsr
+        return self._antiring_for(antiring, h, w, out), self._cas_for(cas, h, w, out), None, None, None
 
     def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out, light_ptr=None, light_rect=None, cleanup=None, antiring=0,
-                 cas=0, fsr=None, down=None):
+                 cas=0, fsr=None, down=None, ssimsr=None):
         """The body of ``enqueue_frame*``: the preprocess entry point ``pre`` (named ``what``) on its source arguments ``src``,
         ``hdrtv_infer_lane`` and ``_post_out``, all on the lane's buffers and ``stream`` (default: the lane's own)."""
         self._ensure_buffers(h, w)
@@ -494,7 +517,7 @@ class HDRTVNetMI355X:
         self._chk(pre(self._ctx, st, *src, h, w, tin.data_ptr(), tcond.data_ptr()), what)
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), self._out_dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, antiring, cas, fsr, down)
+        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, antiring, cas, fsr, down, ssimsr)
 
     def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le",
                       out_siting="left", light_ptr=None, light_rect=None, cleanup=None, antiring=0.0, cas=0.0,
@@ -518,7 +541,9 @@ class HDRTVNetMI355X:
         ``scaler``: ``"lanczos"`` (the default: all of the above) or ``"fsr"``: an enlarged frame goes through ``hdrtv_post_rgb48_fsr``,
         the reference's default upscaler, at most 2x per axis; ``antiring`` and ``cas`` must then be 0 or ``"auto"``
         (which is 0 there).  ``fsr_sharpness``: its RCAS sharpness, 0 .. 2 (0 = the sharpest; the reference's 0.2), or None = EASU
-        alone.  A frame at the processing size is not touched by either.  ``downscaler``: None (the default: an ``out_hw`` below the
+        alone.  ``"spline36"`` / ``"ssim_superres"``: ``hdrtv_post_rgb48_ssimsr`` without / with the reference's SSimSuperRes shader
+        stage, both axes enlarged, by at most 2x; ``antiring`` and ``cas`` 0 or ``"auto"`` there too.  A frame at the processing size is
+        not touched by any of them.  ``downscaler``: None (the default: an ``out_hw`` below the
         processing size is refused, as before), ``"mitchell"`` or ``"ssim"``: a frame delivered below the processing size, by at most
         4x per axis, goes through ``hdrtv_post_rgb48_down`` with the anti-ringing strength ``down_antiring``, 0 .. 1
         or ``"auto"`` = the reference's 0.20; ``scaler`` must then be ``"lanczos"`` and ``antiring`` / ``cas`` 0 or ``"auto"``, and an
@@ -772,7 +797,9 @@ class HDRTVNetMI355X:
         ``hdrtv_post_rgb48_scaled_ex``.  ``cas``: the strength of the contrast-adaptive sharpening in front of the upscale, 0 .. 1, or
         ``"auto"`` = ``lib.scale_cas`` of the two sizes; nonzero: ``hdrtv_post_rgb48_scaled_cas``.  ``scaler="fsr"``: ``hdrtv_post_rgb48_fsr`` instead, the reference's default upscaler, at most 2x
         per axis (more is a ``ValueError``); ``antiring`` and ``cas`` must then be 0 or ``"auto"`` (which is 0 there); ``fsr_sharpness``:
-        the RCAS sharpness, 0 .. 2 (the reference's 0.2), or None = EASU alone.  ``downscaler``: None (a size below the processing size is a ``ValueError``, as before),
+        the RCAS sharpness, 0 .. 2 (the reference's 0.2), or None = EASU alone.  ``scaler="spline36"`` / ``"ssim_superres"``:
+        ``hdrtv_post_rgb48_ssimsr`` with ``ssim`` 0 / 1, the reference's third upscaler: both axes enlarged, by at most 2x (anything else
+        but equal sizes is a ``ValueError``), ``antiring`` and ``cas`` 0 or ``"auto"``.  ``downscaler``: None (a size below the processing size is a ``ValueError``, as before),
         ``"mitchell"`` or ``"ssim"``: ``hdrtv_post_rgb48_down`` shrinks to a size below the processing size, by at most 4x per axis, with
         the anti-ringing strength ``down_antiring`` (0 .. 1, or ``"auto"`` = the reference's 0.20); ``lib.down_options`` has the refusals
         (a mixed or larger request, ``scaler="fsr"``, a nonzero ``antiring`` / ``cas``, nothing to shrink).  Returns a new device u16 ``(out_h, out_w, 3)`` tensor; stream-ordered on the current stream,
@@ -793,14 +820,18 @@ class HDRTVNetMI355X:
         if out_w < w or out_h < h:
             raise ValueError(f"output size {out_w}x{out_h} is below the processing size {w}x{h} (enlarging only)")
         fsr = self._fsr_for(scaler, fsr_sharpness, antiring, cas, h, w, out_h, out_w)
-        code = 0 if fsr is not None else _L.antiring_code(_L.resolve_antiring(antiring, w, h, out_w, out_h))
-        kcas = 0 if fsr is not None else _L.cas_code(_L.resolve_cas(cas, w, h, out_w, out_h))
+        ssimsr = None if fsr is not None else self._ssimsr_for(scaler, antiring, cas, h, w, out_h, out_w)
+        other = fsr is not None or ssimsr is not None
+        code = 0 if other else _L.antiring_code(_L.resolve_antiring(antiring, w, h, out_w, out_h))
+        kcas = 0 if other else _L.cas_code(_L.resolve_cas(cas, w, h, out_w, out_h))
         output = output.contiguous()
         dst = torch.empty((out_h, out_w, 3), dtype=torch.uint16, device=self.device)
         args = (self._ctx, self._stream(), output.data_ptr(), _dtype_code(output), h, w, 1 if pq else 0, float(peak_nits), dst.data_ptr(),
                 out_h, out_w)
         if fsr is not None:
             self._chk(self._lib.hdrtv_post_rgb48_fsr(*args, *fsr), "hdrtv_post_rgb48_fsr")
+        elif ssimsr is not None:
+            self._chk(self._lib.hdrtv_post_rgb48_ssimsr(*args, ssimsr), "hdrtv_post_rgb48_ssimsr")
         elif kcas:
             self._chk(self._lib.hdrtv_post_rgb48_scaled_cas(*args, code, kcas), "hdrtv_post_rgb48_scaled_cas")
         elif code:

@@ -149,12 +149,16 @@ class HeadlessPipelineWorker:
         # what enlarges a frame: "lanczos" (the default: the fused Lanczos upscale with the two options above), or
         # "fsr" = hdrtv_post_rgb48_fsr, the reference's default upscaler, at most 2x per axis, with RCAS at fsr_sharpness (0 .. 2, the
         # reference's 0.2) or, with None, EASU alone.  Under "fsr" antiring and cas are 0 ("auto" resolves to 0, as the reference's
-        # schedules do; an explicit nonzero value is refused).  A frame delivered at the processing size is untouched by either.
+        # schedules do; an explicit nonzero value is refused).  "spline36" / "ssim_superres" = hdrtv_post_rgb48_ssimsr without / with the
+        # reference's SSimSuperRes shader stage: both axes enlarged, by at most 2x, antiring and cas 0 likewise.  A frame delivered at
+        # the processing size is untouched by any of them.
         self._scaler = _L.check_scaler(scaler)
         self._antiring, self._cas = _L.scaler_options(self._scaler, self._antiring, self._cas)
         self._fsr_sharpness = _L.check_fsr_sharpness(fsr_sharpness)
         if self._scaler == "fsr":
             _L.check_fsr_size(self._proc_w, self._proc_h, self._out.w, self._out.h)
+        if self._scaler in _L.SSIMSR_SCALERS:
+            _L.check_ssimsr_size(self._proc_w, self._proc_h, self._out.w, self._out.h)
         # what shrinks a frame delivered BELOW the processing size: None (the default: such a size is refused, as
         # before), "mitchell" or "ssim" = hdrtv_post_rgb48_down, at most 4x per axis, with the anti-ringing strength down_antiring
         # (0 .. 1, or "auto" = the reference's 0.20).  lib.down_options has the refusals: a mixed request, an enlarging scaler option,
@@ -371,7 +375,7 @@ class HeadlessPipelineWorker:
         does (209-235): convert, copy, synchronise the stream, hand the finished frame over.  ``out_hw = (out_h, out_w)``: the
         ring, the fallback buffer and the frame are at that size and the conversion is ``hdrtv_post_rgb48_scaled`` (with the
         worker's ``antiring``, resolved here from the tensor's and the delivered size: ``hdrtv_post_rgb48_scaled_ex``; with its ``cas``, resolved alike:
-        ``hdrtv_post_rgb48_scaled_cas``; with ``scaler="fsr"`` ``hdrtv_post_rgb48_fsr`` does the enlargement; with a ``downscaler`` and a size below the tensor's
+        ``hdrtv_post_rgb48_scaled_cas``; with ``scaler="fsr"`` ``hdrtv_post_rgb48_fsr`` does the enlargement, with ``"spline36"`` / ``"ssim_superres"`` ``hdrtv_post_rgb48_ssimsr``; with a ``downscaler`` and a size below the tensor's
         ``hdrtv_post_rgb48_down`` shrinks).  With a
         Y'CbCr ``out_pix_fmt`` the slot (an RGB48 slot holds any of the layouts) receives the planes, only the frame's bytes are
         committed (``hdrtv_ring_commit_bytes``) and the frame is a 1-D u16 view of them."""
@@ -393,6 +397,10 @@ class HeadlessPipelineWorker:
         if self._scaler == "fsr" and (h, w) != (th, tw):
             _L.check_fsr_size(tw, th, w, h)            # a hot-swap of the processing resolution may have moved the ratio past 2x
             fsr = (0, 0.0) if self._fsr_sharpness is None else (1, self._fsr_sharpness)
+        ssimsr = None
+        if self._scaler in _L.SSIMSR_SCALERS and (h, w) != (th, tw):
+            _L.check_ssimsr_size(tw, th, w, h)         # likewise
+            ssimsr = 1 if self._scaler == "ssim_superres" else 0
         down = None
         if self._downscaler is not None and (h, w) != (th, tw):      # hdrtv_post_rgb48_down; a hot-swap may have moved the ratio
             down = _L.down_options(self._downscaler, self._down_antiring, tw, th, w, h, self._scaler, self._antiring, self._cas)
@@ -402,14 +410,14 @@ class HeadlessPipelineWorker:
             """The frame into ``dst`` and, when measured, its light level record into the pinned record kept per ``key``, all on
             ``st``: whatever is recorded on ``st`` afterwards (the slot's ready event) covers both.  Returns that record."""
             if not self._light:
-                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, antiring=antiring, cas=cas, fsr=fsr, down=down)
+                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, antiring=antiring, cas=cas, fsr=fsr, down=down, ssimsr=ssimsr)
                 return None
             bufs = self._light_bufs.get(key)
             if bufs is None:
                 bufs = self._light_bufs[key] = (torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, device=p.device),
                                                 torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, pin_memory=True))
             p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", bufs[0].data_ptr(), self._light_rect,
-                        self._cleanup, antiring, cas, fsr, down)
+                        self._cleanup, antiring, cas, fsr, down, ssimsr)
             with torch.cuda.stream(st):
                 bufs[1].copy_(bufs[0], non_blocking=True)
             return bufs[1].numpy()

@@ -312,6 +312,63 @@ int hdrtv_post_rgb48_fsr(hdrtv_ctx *ctx, void *stream, const void *dev_out, int 
 int hdrtv_post_rgb48_down(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
                           uint16_t *dst, int dH, int dW, int antiring, int ssim);
 
+/* RGB48 enlarged by the reference's third upscaler: hdrtv_post_rgb48 (pq = 0; peak_nits ignored) or hdrtv_post_pq_rgb48 (pq != 0),
+ * then spline36 and the SSimSuperRes shader, in one kernel without a frame-sized intermediate in device memory.  For the choice
+ * "SSimSuperRes" of UPSCALER_CHOICES (gui_scaling.py:42-43) the reference hands mpv scale=spline36 with scale-antiring = 0 and
+ * cas = 0 (gui_mpv_widget.py:589-590, gui_scaling.py:101-102, 128-129) and appends assets/shaders/SSimSuperRes.glsl to the shader
+ * chain (_build_shader_paths).  Stage A is mpv's part: mpv is not in the reference tree, parity with its own spline36 arithmetic is
+ * UNPINNED, and the device is held to the integer rule below.  Stage B (ssim = 1) is the shader's, which IS in the reference tree:
+ * its arithmetic in float32, operation by operation (every multiply, add, subtract, divide and square root rounded on its own, no
+ * fused multiply-add, denormals kept).  UNPINNED there: the 16-bit float textures mpv keeps the shader's intermediates in (the rule
+ * keeps float32), a texture unit's fixed-point filter weights, what a display's GLSL compiler makes of the shader.
+ * tests/rgb48_ssimsr_ref.py restates both stages in NumPy and the GPU tests hold this entry point to it bit for bit.
+ * Sq(v) = (0.2126 (r r) + 0.7152 (g g)) + 0.0722 (b b), each square one rounded multiply: the shader's Luma, which squares first.
+ *  1. codes: c = exactly what hdrtv_post_rgb48 / hdrtv_post_pq_rgb48 writes at the processing size, [H][W][3]; the rule sees only
+ *     these integers.  Indices outside a frame read the clamped pixel, in every step below.
+ *  2. stage A, spline36: steps 2 and 3 of hdrtv_post_rgb48_scaled with another kernel and no anti-ringing.  Six taps k = -2..3,
+ *     c = (d + 0.5) n / m - 0.5, i0 = floor(c), t = c - i0, w_k = S(t - k) in double, summed in tap order to s,
+ *     q_k = floor(w_k / s * 16384 + 0.5), the remainder to the largest q_k (the lowest k on a tie); the horizontal pass (int32), the
+ *     vertical pass (int64), P = clamp((sum + 2^27) >> 28, 0, 65535).  S(x), x = |x|:
+ *       x < 1: ((13/11 x - 453/209) x - 3/209) x + 1;   x < 2, y = x - 1: ((-6/11 y + 270/209) y - 156/209) y;
+ *       x < 3, y = x - 2: ((1/11 y - 45/209) y + 26/209) y;   else 0
+ *     P [dH][dW][3] are the spline36 codes; with ssim = 0 they are the output.
+ *  3. samples: s = float32(c) / float32(65535), Ps = float32(P) / float32(65535), one correctly rounded division each (the shader's
+ *     POSTKERNEL is taken as a 16-bit texture, as hdrtv_post_rgb48_down takes it), so stage B is a pure function of (c, P).
+ *  4. low-resolution footprint, per axis with low extent n (H or W) and high extent m (dH or dW), in double for j = 0..n-1:
+ *       ctr = (j + 0.5) m / n;  hw = 2 m / n;  k_lo = ceil(ctr - hw - 0.5);  k_hi = floor(ctr + hw - 0.5);  x_k = (k + 0.5 - ctr) n / m
+ *     at most 9 taps, with the weight mn(|x_k|), B = 0.334, C = 0.333:
+ *       x < 1: ((2 - 1.5 B - C) x + (-3 + 2 B + C)) x x + (1 - B / 3);   else (((-B / 6 - C) x + (B + 5 C)) x + (-2 B - 8 C)) x + (4/3 B + 4 C)
+ *     summed in tap order, each divided by the sum in double, then rounded to float32 (the shader's division by W folded in).
+ *  5. pass I, vertical, to [H][dW], k ascending from acc = 0, acc = acc + wy_k * v:  A.rgb = sum wy_k Ps[k][x],
+ *     A.q = sum wy_k Sq(Ps[k][x]);  e1 = max(|A.q - Sq(A.rgb)|, float32(5e-7)).
+ *  6. pass II, horizontal, on A.rgb, to [H][W]:  Lr.rgb = sum wx_k A.rgb[y][k],  q2 = sum wx_k Sq(A.rgb[y][k]),
+ *     e2 = max(|q2 - Sq(Lr.rgb)|, 5e-7).  The linear fetch of pass I's fourth component at this pixel: u = (i + 0.5) dW / W - 0.5,
+ *     b0 = floor(u), f = float32(u - b0) in double on the host;  e1i = ((1 - f) * e1[y][b0]) + (f * e1[y][b0 + 1]);  Lr.a = e2 + e1i.
+ *  7. var, at [H][W], the cross neighbours in the order (x-1, y), (x+1, y), (x, y-1), (x, y+1):
+ *       mL = ((((s0 + 0.25 s1) + 0.25 s2) + 0.25 s3) + 0.25 s4) / 2 per channel, mH the same on Lr.rgb;
+ *       vL = max(((((Sq(s0 - mL) + 0.25 Sq(s1 - mL)) + 0.25 Sq(s2 - mL)) + 0.25 Sq(s3 - mL)) + 0.25 Sq(s4 - mL)) / 2, float32(1e-6)),
+ *       vH likewise from Lr.rgb and mH.
+ *  8. final, per output pixel.  Per axis, in double on the host: p = (d + 0.5) n / m - 0.5, ip = floor(p + 0.5) (GLSL's round leaves
+ *     the tie open; the rule takes it up), off = p - ip, kern[d][t] = float32(cos(pi (t - off) / 3)) for t = -1, 0, 1 (the Hann
+ *     window; no cosine is evaluated on the device).  c0 = Ps at the pixel.  With X outer and Y inner, both -1..1, w = 1, 0.5 for
+ *     offset 0, +-1 and accumulation from 0:  mV = (sum (wX wY) * Lr.a[ip_y + Y][ip_x + X]) / 4.  Then, in the same order, at the
+ *     low-resolution pixel g = (ip_y + Y, ip_x + X):
+ *       R = -1.5 * sqrt(vL[g] / (vH[g] + mV))                                   (oversharp = 0.5)
+ *       wt = (kx[X] * ky[Y]) / (Sq(c0 - Lr.rgb[g]) + Lr.a[g])
+ *       term = (s[g] + Lr.rgb[g] * R) + ((-1 - R) * c0);   D = D + wt * term;   Ws = Ws + wt
+ *     pix = sat(c0 + D / Ws); the output code is (int)(pix * 65535 + 0.5), the quantiser of the unscaled entry point.  Every
+ *     denominator is positive: Lr.a >= 1e-6 (up to the roundings of the linear fetch), vH + mV >= 2e-6, the centre Hann weight at
+ *     least cos^2(pi / 6).  A flat frame returns its code.
+ * Sizes: equal sizes (dH == H && dW == W) delegate to the unscaled kernel and write its bytes, whatever ssim.  Otherwise both axes
+ * are strictly enlarged, by at most 2x: H < dH <= 2 H and W < dW <= 2 W (the reference calls it an upscale only when both axes grow,
+ * _is_upscale_required).  Out of scope: more than 2x and the residual mpv pass behind it, the shader's partial chains when only one
+ * axis grows.  Stream-ordered, needs no reservation; the tables are built at the first call with a geometry -- that call allocates
+ * and copies -- and kept in the context beside the other tap tables.  HDRTV_EINVAL, before any device call and with dst untouched,
+ * for a NULL pointer, an unknown dtype, H, W, dH or dW < 1, pq with peak_nits <= 0, one axis at identity, a smaller axis, more than
+ * 2x on an axis, ssim outside {0, 1}. */
+int hdrtv_post_rgb48_ssimsr(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
+                            uint16_t *dst, int dH, int dW, int ssim);
+
 /* 10-bit limited-range Y'CbCr for an encoder (HEVC Main10, hardware encoders, ProRes): P010 and yuv420p10le are 3 bytes per pixel,
  * yuv422p10le 4, against the 6 of RGB48.  The reference's export converts on the CPU: it pipes rgb48le into ffmpeg, zscale goes to
  * BT.2020nc limited range and format=yuv422p10le feeds prores_ks (gui_export.py:948-1005).  The network's output is PQ-encoded BT.2020
