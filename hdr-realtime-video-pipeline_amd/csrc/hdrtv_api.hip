@@ -1029,6 +1029,59 @@ int hdrtv_letterbox_u8(hdrtv_ctx *c, void *stream, const uint8_t *src_bgr, int s
     return launched(c, "letterbox", letterbox_launch(p, (hipStream_t)stream));
 }
 
+// The letterbox of a 10-bit Y'CbCr frame (letterbox10.hip): the argument rule of both entry points, then the tables of this geometry
+// (the ones hdrtv_letterbox_u8 uses: they do not depend on bit depth).  Nothing is enqueued before every check has passed.
+static int letterbox10_args(hdrtv_ctx *c, const char *what, const uint16_t *y, int y_pitch, const uint16_t *u, const uint16_t *v, int c_pitch,
+                            int fmt, int matrix, int full_range, int sh, int sw, int dh, int dw, bool reserved, Ycc10Src *src)
+{
+    if (const int rc = ycc10_args(c, what, y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, sh, sw, src)) return rc;
+    if (dh <= 0 || dw <= 0) return fail(c, HDRTV_EINVAL, "%s: destination %dx%d is not positive", what, dw, dh);
+    if (reserved && (c->H != dh || c->W != dw || c->lane_ws.empty())) return fail(c, HDRTV_ESTATE, "call hdrtv_reserve(%d,%d) first", dh, dw);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!letterbox_setup(c, sh, sw, dh, dw)) {
+        c->lb_key[0] = 0;
+        return fail(c, HDRTV_ENOMEM, "%s: table allocation failed", what);
+    }
+    if (!letterbox10_size_ok(c->lb))
+        return fail(c, HDRTV_EINVAL, "%s: %dx%d -> %dx%d shrinks by more than %dx on an axis", what, sw, sh, c->lb.new_w, c->lb.new_h, LB10_MAX_SHRINK);
+    return HDRTV_OK;
+}
+
+int hdrtv_letterbox_ycbcr10(hdrtv_ctx *c, void *stream, const uint16_t *y, int y_pitch, const uint16_t *u, const uint16_t *v, int c_pitch,
+                            int fmt, int matrix, int full_range, int sh, int sw, uint16_t *rgb, int dh, int dw)
+{
+    if (!c || !rgb) return fail(c, HDRTV_EINVAL, "null argument");
+    Ycc10Src src;
+    if (const int rc = letterbox10_args(c, "letterbox_ycbcr10", y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, sh, sw, dh, dw, false, &src))
+        return rc;
+    return launched(c, "letterbox_ycbcr10", letterbox10_launch(src, c->lb, LB10_U16_HWC, rgb, (hipStream_t)stream));
+}
+
+int hdrtv_preprocess_ycbcr10_letterboxed(hdrtv_ctx *c, void *stream, const uint16_t *y, int y_pitch, const uint16_t *u, const uint16_t *v,
+                                         int c_pitch, int fmt, int matrix, int full_range, int sh, int sw, int H, int W, void *rgb, void *cond)
+{
+    if (!c || !rgb || !cond) return fail(c, HDRTV_EINVAL, "null argument");
+    Ycc10Src src;
+    if (const int rc = letterbox10_args(c, "preprocess_ycbcr10_letterboxed", y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, sh, sw, H, W,
+                                        true, &src))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Seq q{c, s, c->lane_ws[0]};          // lane 0's resize tables, as hdrtv_preprocess
+    const Shapes shp = shapes_for(H, W);
+    // the tensor in one launch; the condition map is computed from the tensor that launch wrote
+    q.chk(letterbox10_launch(src, c->lb, c->fp32 ? LB10_F32_CHW : LB10_F16_CHW, rgb, s), "letterbox10");
+    if (c->fp32)
+        q.chk(cond_resize_f32_launch((const float *)rgb, (float *)cond, H, W, shp.h4, shp.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
+                                     q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"),
+                                     c->cond_mode, s), "cond_resize_f32");
+    else if (c->cond_mode == 0)
+        q.chk(cond_resize_launch((const f16 *)rgb, (f16 *)cond, H, W, shp.h4, shp.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
+                                 q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"), s), "cond_resize");
+    else
+        q.chk(cond_quarter_f16_launch((const f16 *)rgb, (f16 *)cond, H, W, c->cond_mode, s), "cond_quarter_f16");
+    return q.rc;
+}
+
 // --------------------------------------------------------------------------------- metrics
 int hdrtv_metrics(hdrtv_ctx *c, void *stream, const void *a, const void *b, int dtype, int H, int W, float peak_nits,
                   double *out3)

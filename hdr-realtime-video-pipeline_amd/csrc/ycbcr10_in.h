@@ -84,6 +84,16 @@ __device__ __forceinline__ void ycc10_rule(int Y, int c8u, int c8v, const Ycc10C
 // ycbcr10_in.hip
 hipError_t ycbcr10_to_rgb10_launch(const Ycc10Src &src, int H, int W, uint16_t *rgb, hipStream_t s);
 hipError_t pre_unpack_ycbcr10_f32_launch(const Ycc10Src &src, int H, int W, float *rgb, hipStream_t s);
+// letterbox10.hip: planes at the source size p.sh x p.sw -> the letterboxed frame p.dh x p.dw (p: letterbox_setup's geometry and tables;
+// its src / dst are not read), converted and resampled in one launch.  store: u16 [dh][dw][3] codes, or the f16 / f32 [3][dh][dw]
+// tensor of those codes.  hipErrorInvalidValue, nothing enqueued, for planes ycc10_check refuses at the source size, a null dst or a
+// shrink beyond LB10_MAX_SHRINK on an axis (letterbox10_size_ok).
+enum { LB10_U16_HWC = 0, LB10_F16_CHW = 1, LB10_F32_CHW = 2 };
+constexpr int LB10_MAX_SHRINK = 4;
+bool letterbox10_size_ok(const LetterboxParams &p);
+hipError_t letterbox10_launch(const Ycc10Src &src, const LetterboxParams &p, int store, void *dst, hipStream_t s);
+// ... and the 0.25x condition map of an f16 tensor [3][H][W] in condition modes 1 and 2 (mode 0: cond_resize_launch)
+hipError_t cond_quarter_f16_launch(const f16 *in, f16 *out, int H, int W, int mode, hipStream_t s);
 // prepost.hip: pre_fused with the 10-bit staging step (same tables, modes and outputs as pre_fused_launch)
 hipError_t pre_fused_ycbcr10_launch(const Ycc10Src &src, f16 *out, f16 *cond, int H, int W, int Ho, int Wo, const float *wx,
                                     const int *xmn, const int *xns, const float *wy, const int *ymn, const int *yns, int mode,

@@ -63,6 +63,8 @@ SYMBOLS = [
     ("hdrtv_preprocess_yuv420", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP]),
     ("hdrtv_ycbcr10_to_rgb10", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     ("hdrtv_preprocess_ycbcr10", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP]),
+    ("hdrtv_letterbox_ycbcr10", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I, _I]),
+    ("hdrtv_preprocess_ycbcr10_letterboxed", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP]),
     ("hdrtv_metrics", _I, [_VP, _VP, _VP, _VP, _I, _I, _I, C.c_float, C.POINTER(C.c_double)]),
     ("hdrtv_ring_create", _I, [_VP, _I, _I, _I]),
     ("hdrtv_ring_acquire", _I, [_VP, _I, C.POINTER(_VP), C.POINTER(_VP)]),

@@ -171,8 +171,8 @@ class RawVideoSource:
     """Headerless rawvideo file (what ``ffmpeg -f rawvideo -pix_fmt <pix_fmt>`` writes), memory-mapped.  ``pix_fmt``:
     ``bgr24`` frames are u8 ``(H, W, 3)``; ``yuv420p`` (I420) and ``nv12`` frames are u8 ``(H*3//2, W)``, the planes back to back
     (``HDRTVNetMI355X.preprocess_yuv420``), even sizes only; ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` frames are little-endian
-    u16 ``(H*3//2, W)``, or ``(2*H, W)`` for 4:2:2 (``HDRTVNetMI355X.preprocess_ycbcr10``; at the processing size only: 10-bit input
-    has no letterbox).  ``yuv_matrix`` (601 / 709 / 2020) and ``yuv_full_range`` say how
+    u16 ``(H*3//2, W)``, or ``(2*H, W)`` for 4:2:2 (``HDRTVNetMI355X.preprocess_ycbcr10``; a size other than the processing size needs
+    the worker's 10-bit letterbox, ``RealtimePlayback(letterbox=True)``).  ``yuv_matrix`` (601 / 709 / 2020) and ``yuv_full_range`` say how
     the 4:2:0 frames convert to RGB (the stream's ``color_space`` / ``color_range``)."""
 
     PIX_FMTS = ("bgr24", "yuv420p", "nv12") + tuple(_lib.YCBCR10_IN_FORMATS)
@@ -352,7 +352,7 @@ class RealtimePlayback:
 
     def __init__(self, worker, source, *, sink=True, frame_stride=1, realtime=True, metrics_cb=None, csv_path=None,
                  metrics_interval_s=0.20, metrics_window=120, clock=time.perf_counter, sleep=None, status_cb=None,
-                 gt_source=None, objective_every=10):
+                 gt_source=None, objective_every=10, letterbox=False):
         self.w, self.source = worker, source
         self.sink = sink
         self.frame_stride = max(1, int(frame_stride))
@@ -366,9 +366,15 @@ class RealtimePlayback:
         # optional ground-truth HDR frames ([3,H,W] or [1,3,H,W] unit-range tensors from ``gt_source.read()``): every
         # ``objective_every``-th processed frame is scored on the device (gui_pipeline_worker_objective.py role)
         self.gt_source, self.objective_every = gt_source, max(1, int(objective_every))
-        # a 4:2:0 source (RawVideoSource pix_fmt yuv420p / nv12): the worker converts its 2-D frames on the device
+        # a 4:2:0 source (RawVideoSource pix_fmt yuv420p / nv12): the worker converts its 2-D frames on the device.  ``letterbox``: a
+        # 10-bit source of another size than the processing size is letterboxed there too (the worker's opt-in; bgr24, yuv420p and
+        # nv12 frames are letterboxed without it)
         if getattr(source, "pix_fmt", "bgr24") != "bgr24" and hasattr(worker, "set_input_format"):
-            worker.set_input_format(source.pix_fmt, getattr(source, "yuv_matrix", 709), getattr(source, "yuv_full_range", False))
+            fmt = (source.pix_fmt, getattr(source, "yuv_matrix", 709), getattr(source, "yuv_full_range", False))
+            if letterbox and source.pix_fmt in _lib.YCBCR10_IN_FORMATS:
+                worker.set_input_format(*fmt, letterbox=True)
+            else:
+                worker.set_input_format(*fmt)
         self._objective = {"psnr_db": None, "sssim": None, "delta_e_itp": None}
         self._pending_precision = None
         self._pending_resolution = None
@@ -568,8 +574,8 @@ class RealtimePlayback:
 
 
 def parse_args(argv=None):
-    """The command line of ``main`` -> the argparse namespace, checked (a bad value ends in ``ap.error``): ``.proc_wh`` and ``.out_wh``
-    hold the two sizes as ``(w, h)``, ``.cleanup`` the ``lib.OutputCleanup`` of --deband / --dither, ``.antiring`` and ``.cas`` ``"auto"`` or the
+    """The command line of ``main`` -> the argparse namespace, checked (a bad value ends in ``ap.error``): ``.proc_wh``, ``.out_wh`` and
+    ``.src_wh`` hold the three sizes as ``(w, h)``, ``.cleanup`` the ``lib.OutputCleanup`` of --deband / --dither, ``.antiring`` and ``.cas`` ``"auto"`` or the
     strength as a float (0.0: off; both 0.0 under any ``--scaler`` but lanczos), ``.scaler`` one of ``lib.UPSCALERS``, ``.fsr_sharpness`` the RCAS
     sharpness as a float or None (EASU alone), ``.downscaler`` None, ``"mitchell"`` or ``"ssim"``, ``.down_antiring`` its anti-ringing
     strength as a float (``auto`` resolved to the reference's 0.20)."""
@@ -581,9 +587,12 @@ def parse_args(argv=None):
     ap.add_argument("--size", default="3840x2160", help="processing size WxH: the size the network runs at")
     ap.add_argument("--out-size", default=None, help="size WxH the sink receives frames at (default: --size; not below it on either "
                     "axis unless --downscaler is given): the RGB48 conversion upscales on the device (hdrtv_post_rgb48_scaled)")
+    ap.add_argument("--src-size", default=None, help="size WxH of the source frames (default: --size): a source of another size is "
+                    "letterboxed to --size on the device, 10-bit formats at ten bits (hdrtv_preprocess_ycbcr10_letterboxed: a shrink "
+                    "of at most 4x per axis)")
     ap.add_argument("--fps", type=float, default=60.0)
     ap.add_argument("--frames", type=int, default=240)
-    ap.add_argument("--input", help="rawvideo file at --size in --pix-fmt (default: synthetic frames)")
+    ap.add_argument("--input", help="rawvideo file at --src-size in --pix-fmt (default: synthetic frames)")
     ap.add_argument("--pix-fmt", choices=RawVideoSource.PIX_FMTS, default="bgr24", help="pixel format of --input")
     ap.add_argument("--yuv-matrix", type=int, choices=(601, 709, 2020), default=709, help="Y'CbCr matrix of a yuv420p / nv12 / 10-bit input")
     ap.add_argument("--yuv-range", choices=("limited", "full"), default="limited", help="Y'CbCr range of a yuv420p / nv12 / 10-bit input")
@@ -630,6 +639,12 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     wd, ht = (int(v) for v in a.size.lower().split("x", 1))
     owd, oht = (int(v) for v in a.out_size.lower().split("x", 1)) if a.out_size else (wd, ht)
+    try:
+        swd, sht = (int(v) for v in a.src_size.lower().split("x", 1)) if a.src_size else (wd, ht)
+    except ValueError:
+        ap.error(f"--src-size {a.src_size}: expected WxH")
+    if swd <= 0 or sht <= 0:
+        ap.error(f"--src-size {swd}x{sht} is not positive")
     if a.downscaler is None and (owd < wd or oht < ht):
         ap.error(f"--out-size {owd}x{oht} is below --size {wd}x{ht}: the output stage only enlarges unless --downscaler is given")
     if a.down_antiring is not None and a.downscaler is None:
@@ -689,7 +704,7 @@ def parse_args(argv=None):
         _lib.down_options(a.downscaler, a.down_antiring, wd, ht, owd, oht, a.scaler, a.antiring, a.cas)
     except ValueError as exc:
         ap.error(f"--downscaler: {exc}")
-    a.proc_wh, a.out_wh = (wd, ht), (owd, oht)
+    a.proc_wh, a.out_wh, a.src_wh = (wd, ht), (owd, oht), (swd, sht)
     return a
 
 
@@ -700,11 +715,11 @@ def main(argv=None):
     from .worker import HeadlessPipelineWorker
 
     a = parse_args(argv)
-    (wd, ht), (owd, oht) = a.proc_wh, a.out_wh
+    (wd, ht), (owd, oht), (swd, sht) = a.proc_wh, a.out_wh, a.src_wh
     if a.input:
-        src = RawVideoSource(a.input, wd, ht, a.fps, pix_fmt=a.pix_fmt, yuv_matrix=a.yuv_matrix, yuv_full_range=a.yuv_range == "full")
+        src = RawVideoSource(a.input, swd, sht, a.fps, pix_fmt=a.pix_fmt, yuv_matrix=a.yuv_matrix, yuv_full_range=a.yuv_range == "full")
     else:
-        src = SyntheticSource(wd, ht, a.fps, a.frames)
+        src = SyntheticSource(swd, sht, a.fps, a.frames)
     if not a.no_prefetch:
         src = PinnedPrefetch(src)
     worker = HeadlessPipelineWorker(a.weights_dir, use_hg=not a.no_hg, proc_w=wd, proc_h=ht, hg_weights=a.hg_weights,
@@ -720,7 +735,8 @@ def main(argv=None):
     if a.out:
         sink = RawVideoSink(a.out, owd, oht, a.fps, a.out_pix_fmt, a.out_siting)      # the sink, mpv_args() and ffmpeg_input_args() speak of the output size
         worker._start_hdr_feeder(sink)
-    pb = RealtimePlayback(worker, src, sink=bool(sink), frame_stride=a.stride, realtime=not a.max_throughput, csv_path=a.csv)
+    pb = RealtimePlayback(worker, src, sink=bool(sink), frame_stride=a.stride, realtime=not a.max_throughput, csv_path=a.csv,
+                          letterbox=a.src_wh != a.proc_wh)
     res = pb.run(max_frames=a.frames)
     if sink:
         deadline = time.perf_counter() + 5.0
@@ -733,6 +749,8 @@ def main(argv=None):
     worker.close()
     lm = res.pop("last_metrics") or {}
     res.update({k: lm.get(k) for k in ("latency_ms", "model_latency_ms", "fps_1p_low", "proc_res", "precision")})
+    if a.src_wh != a.proc_wh:
+        res["src_res"] = f"{swd}x{sht}"
     if a.out_size:
         res["out_res"] = f"{owd}x{oht}"
     if a.out_pix_fmt != "rgb48le":

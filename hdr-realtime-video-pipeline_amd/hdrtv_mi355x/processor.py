@@ -703,6 +703,24 @@ class HDRTVNetMI355X:
         return self._gpu_input, self._gpu_cond
 
     @torch.inference_mode()
+    def preprocess_ycbcr10_letterboxed(self, frame, out_w, out_h, *, pix_fmt, matrix=709, full_range=False):
+        """``preprocess_letterboxed`` of a 10-bit Y'CbCr frame, at ten bits: the planes are uploaded at THEIR size and one kernel
+        (``hdrtv_preprocess_ycbcr10_letterboxed``) converts, resizes and pastes them into the ``out_h x out_w`` tensor, which holds
+        ``fp16(code / 1023)`` of the letterboxed codes (include/hdrtv_mi355x.h states the rule; a shrink beyond 4x on an axis is
+        refused).  Equal sizes: ``preprocess_ycbcr10``."""
+        sh, sw = ycbcr10_frame_hw(frame, pix_fmt)
+        out_w, out_h = int(out_w), int(out_h)
+        if (sw, sh) == (out_w, out_h):
+            return self.preprocess_ycbcr10(frame, pix_fmt=pix_fmt, matrix=matrix, full_range=full_range)
+        ptr = self._upload("ycbcr10", np.ascontiguousarray(frame).view(np.uint8))
+        planes = _ycbcr10_planes(ptr, sh, sw, pix_fmt, matrix, full_range)
+        self._ensure_buffers(out_h, out_w)
+        self._chk(self._lib.hdrtv_preprocess_ycbcr10_letterboxed(self._ctx, self._stream(), *planes, sh, sw, out_h, out_w,
+                                                                 self._gpu_input.data_ptr(), self._gpu_cond.data_ptr()),
+                  "hdrtv_preprocess_ycbcr10_letterboxed")
+        return self._gpu_input, self._gpu_cond
+
+    @torch.inference_mode()
     def infer(self, input_cond):
         """hdrtvnet_torch.py:2301-2346.  Returns ``(out, agcm_out)`` like the eager model; both are
         processor-owned and overwritten by the next call (as HDRTVNetTensorRT's output is)."""

@@ -9,7 +9,8 @@
 Same names, argument meaning and error behaviour (``_load_model`` swallows backend exceptions
 into a status message and returns False), without PyQt/cv2/mpv: status messages go to a list
 or callback, the display sink is any callable taking a ``PinnedFrame``.  Frames that are not at
-the processing size are letterboxed on the device (``preprocess_letterboxed``).
+the processing size are letterboxed on the device (``preprocess_letterboxed``; 10-bit Y'CbCr frames
+where ``set_input_format(..., letterbox=True)`` asked for it).
 """
 from __future__ import annotations
 
@@ -193,11 +194,15 @@ class HeadlessPipelineWorker:
         self._fallback = None              # (pinned host u16 tensor, device u16 tensor) of the ring-exhaustion fallback
         self.ring_fallbacks = 0
         self._yuv_format = dict(layout="i420", matrix=709, full_range=False)     # how 2-D (4:2:0) frames convert
+        self._letterbox10 = False          # set_input_format(letterbox=True): 10-bit frames of another size are letterboxed on the device
 
-    def set_input_format(self, pix_fmt, yuv_matrix=709, yuv_full_range=False):
+    def set_input_format(self, pix_fmt, yuv_matrix=709, yuv_full_range=False, *, letterbox=False):
         """How ``_process_frame`` reads a 2-D frame: u8 ``(H*3//2, W)`` with ``pix_fmt`` ``yuv420p`` or ``nv12``
-        (``HDRTVNetMI355X.preprocess_yuv420``), or u16 with ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` (``preprocess_ycbcr10``; at
-        the processing size only: 10-bit input has no letterbox), and its matrix and range.  3-D frames are BGR whatever is set here."""
+        (``HDRTVNetMI355X.preprocess_yuv420``), or u16 with ``p010le`` / ``yuv420p10le`` / ``yuv422p10le`` (``preprocess_ycbcr10``),
+        and its matrix and range.  A 10-bit frame is taken at the processing size only unless ``letterbox=True``: then a frame of
+        another size is letterboxed to the processing size on the device, at ten bits (``preprocess_ycbcr10_letterboxed``; 8-bit
+        frames are letterboxed whatever the flag says).  3-D frames are BGR whatever is set here."""
+        self._letterbox10 = bool(letterbox)
         if pix_fmt in YCBCR10_IN_FORMATS:      # 2-D u16 frames: HDRTVNetMI355X.preprocess_ycbcr10
             self._yuv_format = dict(pix_fmt=pix_fmt, matrix=int(yuv_matrix), full_range=bool(yuv_full_range))
             return
@@ -321,14 +326,19 @@ class HeadlessPipelineWorker:
             raise ValueError(f"output size {ow}x{oh} is below the processing size {pw}x{ph} (enlarging only)")
         with torch.inference_mode():
             if frame.ndim == 2 and frame.dtype == np.uint16:
-                # 10-bit Y'CbCr planes (set_input_format): converted inside the preprocess kernel; there is no 10-bit letterbox
+                # 10-bit Y'CbCr planes (set_input_format): converted inside the preprocess kernel; letterboxed there, at ten bits,
+                # only where set_input_format(letterbox=True) asked for it
                 if "pix_fmt" not in self._yuv_format:
                     raise ValueError("a uint16 frame needs set_input_format('p010le' | 'yuv420p10le' | 'yuv422p10le')")
                 fh, fw = ycbcr10_frame_hw(frame, self._yuv_format["pix_fmt"])
-                if fw != pw or fh != ph:
+                if fw == pw and fh == ph:
+                    tensor, cond = self._processor.preprocess_ycbcr10(frame, **self._yuv_format)
+                elif self._letterbox10:
+                    tensor, cond = self._processor.preprocess_ycbcr10_letterboxed(frame, pw, ph, **self._yuv_format)
+                else:
                     raise ValueError(f"a {self._yuv_format['pix_fmt']} source of {fw}x{fh} differs from the processing size {pw}x{ph}: "
-                                     "10-bit input has no letterbox (out of scope), feed it at the processing size")
-                tensor, cond = self._processor.preprocess_ycbcr10(frame, **self._yuv_format)
+                                     "the 10-bit letterbox is off, ask for it with set_input_format(..., letterbox=True) or feed the "
+                                     "frame at the processing size")
             elif frame.ndim == 2:
                 # 8-bit 4:2:0 planes: converted on the device (set_input_format), letterboxed there when the sizes differ
                 fh = frame.shape[0] // 3 * 2

@@ -573,6 +573,42 @@ int hdrtv_preprocess_ycbcr10(hdrtv_ctx *ctx, void *stream, const uint16_t *dev_y
                              const uint16_t *dev_u, const uint16_t *dev_v, int c_pitch, int fmt,
                              int matrix, int full_range, int H, int W, void *dev_rgb_chw, void *dev_cond);
 
+/* Letterbox of a 10-bit Y'CbCr frame at ten bits: the reference's "lower-resolution processing" (a 3840x2160 source letterboxed to a
+ * 1920x1080 processing size, _letterbox_bgr(frame, proc_w, proc_h) in src/gui_pipeline_worker_frame_processing.py:207-210) without
+ * a pass through 8 bits.  The planes (layouts, pitches, matrix and range as above) are read at the SOURCE size sh x sw and the result
+ * is written at dh x dw by one kernel; no source-sized RGB frame exists in device memory.  The rule is the reference's order of
+ * operations, decode then letterbox:
+ *  1. the R, G, B codes 0..1023 of every source pixel by the rule of hdrtv_ycbcr10_to_rgb10, chroma clamps at the edges of the
+ *     source frame;
+ *  2. the geometry of hdrtv_letterbox_u8 (oracle/letterbox_oracle.py geometry: new_w x new_h centred at (x0, y0), Python's round());
+ *     pixels outside that rectangle are code 0 in all three channels;
+ *  3. the resize of the codes by hdrtv_letterbox_u8's algorithms with 1023 in the place of 255:
+ *       new == source size: the codes themselves;
+ *       shrinking, integer ratio ix x iy: int32 box sums; 2 x 2 is (sum + 2) >> 2, any other ratio
+ *         rint(float32(sum) * (float32(1) / float32(ix * iy))), half to even, clamped to [0, 1023];
+ *       shrinking, fractional ratio: computeResizeAreaTab's float32 weights; the horizontal sums of a source row accumulated from 0
+ *         in table order, multiply and add separate; vertically beta * buf for the first entry and sum + beta * buf after it; rint,
+ *         then the clamp;
+ *       enlarging: the 11-bit Keys coefficients (A = -0.75) and offsets of the 8-bit path, horizontal then vertical integer passes
+ *         with replicated borders in 64 bits, (v + 2^21) >> 22, clamped to [0, 1023].
+ * Parity with OpenCV's own 16-bit resize is UNPINNED and not claimed: OpenCV is not part of the reference tree and its u16 cubic path
+ * is a float one.  tests/letterbox10_ref.py restates the rule in numpy; the GPU tests hold both entry points to it bit for bit.
+ * A shrink beyond 4x on an axis (sw > 4 new_w or sh > 4 new_h) is HDRTV_EINVAL, the cap of hdrtv_post_rgb48_down; enlargement has
+ * no cap.
+ * hdrtv_letterbox_ycbcr10 writes the codes as u16 [dh][dw][3] R, G, B and needs no reservation.
+ * hdrtv_preprocess_ycbcr10_letterboxed writes the tensor fp16(float(code) * fp32(1/1023)) of those codes at H x W (the same
+ * expression in fp32 for an fp32 context), then the condition map of that tensor in a second launch; same reservation rule as
+ * hdrtv_preprocess: HDRTV_ESTATE before hdrtv_reserve(H, W).  With sh x sw == H x W the tensor is that of hdrtv_preprocess_ycbcr10.
+ * HDRTV_EINVAL, the destinations untouched, for a NULL pointer, a non-positive size, a shrink beyond 4x on an axis and everything
+ * hdrtv_ycbcr10_to_rgb10 refuses at the source size. */
+int hdrtv_letterbox_ycbcr10(hdrtv_ctx *ctx, void *stream, const uint16_t *dev_y, int y_pitch,
+                            const uint16_t *dev_u, const uint16_t *dev_v, int c_pitch, int fmt,
+                            int matrix, int full_range, int sh, int sw, uint16_t *dev_rgb10_hwc, int dh, int dw);
+int hdrtv_preprocess_ycbcr10_letterboxed(hdrtv_ctx *ctx, void *stream, const uint16_t *dev_y, int y_pitch,
+                                         const uint16_t *dev_u, const uint16_t *dev_v, int c_pitch, int fmt,
+                                         int matrix, int full_range, int sh, int sw, int H, int W,
+                                         void *dev_rgb_chw, void *dev_cond);
+
 /* Objective metrics of the reference's metrics dict between two device images [3][H][W]
  * (R, G, B planes, unit range, f16 or f32): out3 = { PSNR dB, SSIM, dE-ITP } as _psnr_bgr / _ssim_bgr /
  * _delta_e_itp_bgr compute them (src/gui_objective_metrics.py:438-528; peak_nits = HDRTVNET_OBJECTIVE_HDR_PEAK_NITS,
