@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "launchers.h"
+#include "scale_tables.h"
 
 namespace hdrtv_host {
 
@@ -262,17 +263,15 @@ struct hdrtv_ctx {
     void *lb_dev = nullptr;
     size_t lb_cap = 0;
     float *pq_bnd = nullptr;              // hdrtv_post_pq_rgb48: the 65536 code boundaries of the PQ quantiser (built on first use)
-    // hdrtv_post_rgb48_scaled: device tap tables per (H, W, dH, dW), xtab [dW] then ytab [dH]; built on first use of a geometry
-    std::map<std::array<int, 4>, int4 *> ps_tabs;
-    // hdrtv_post_rgb48_fsr: device position tables per (H, W, dH, dW), xtab [dW] then ytab [dH]; built on first use of a geometry
-    std::map<std::array<int, 4>, int2 *> fsr_tabs;
-    // hdrtv_post_rgb48_down: device tables per (H, W, dH, dW) in one allocation -- info [dW + dH] int4, then the integer coefficients
-    // [dW * ntx + dH * nty], then as many float32 L2 weights; built on first use of a geometry
-    struct DownTabs { int4 *dev; int ntx, nty; };
-    std::map<std::array<int, 4>, DownTabs> down_tabs;
-    // hdrtv_post_rgb48_ssimsr: device tables per (H, W, dH, dW) in one allocation -- int4 [2 (dW + dH) + W + H] (xsp, ysp, xfin, yfin,
-    // xlow, ylow), then SR_NT float32 weights per source index [W + H]; built on first use of a geometry
-    std::map<std::array<int, 4>, int4 *> ssimsr_tabs;
+    // the RGB48 scalers' device tables, per kind (scale_tables::Kind) and per geometry (H, W, dH, dW): one allocation in the kind's
+    // layout (scale_tables.h) and the downscaler's taps per index; built on first use of a geometry
+    struct ScaleTab {
+        char *dev;
+        int ntx, nty;
+        template <class T>
+        const T *at(size_t bytes = 0) const { return reinterpret_cast<const T *>(dev + bytes); }     // a table at a byte offset of the layout
+    };
+    std::array<std::map<std::array<int, 4>, ScaleTab>, scale_tables::NKINDS> scale_tabs;
     // objective metrics partial sums
     double *mt_dev = nullptr;
     size_t mt_cap = 0;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "tile_run.h"
+#include "scale_tiles.h"
 
 typedef _Float16 f16;
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -402,7 +403,7 @@ struct LetterboxParams {
 // Fused quantise + Lanczos upscale (post_scale.hip): planar [3][H][W] f16 / f32 -> u16 [dH][dW][3] RGB, dH >= H and dW >= W.
 // xtab [dW] / ytab [dH]: per destination index {first of six source taps (unclamped), q0 | q1 << 16, q2 | q3 << 16, q4 | q5 << 16},
 // the six coefficients as int16 with sum 16384 (include/hdrtv_mi355x.h states the rule).
-constexpr int PS_TW = 64, PS_TH = 32;            // output pixels per workgroup
+// PS_TW x PS_TH output pixels per workgroup (scale_tiles.h)
 struct PostScaleParams {
     const void *in;
     uint16_t *dst;
@@ -428,7 +429,6 @@ struct PostFsrParams {
 // xinfo [dW] / yinfo [dH]: per destination index {first source tap (unclamped), tap count, the two inner taps of the pull}; xq / yq:
 // ntx / nty integer coefficients per index (sum 16384, zero-padded); xw / yw: as many float32 L2 weights (include/hdrtv_mi355x.h
 // states the rule).  A workgroup owns DN_TH2 x DN_TW output pixels up to a ratio of 2 on both axes, DN_TH4 x DN_TW up to 4.
-constexpr int DN_TW = 32, DN_TH2 = 16, DN_TH4 = 8;
 struct PostDownParams {
     const void *in;
     uint16_t *dst;
@@ -445,11 +445,7 @@ struct PostDownParams {
 // three float32 Hann weights at -1, 0, 1}.  Per source index, xlow [W] / ylow [H]: {first high-resolution tap (unclamped), tap count,
 // b0, the bits of the float32 f of pass II's linear fetch}; xw / yw: SR_NT float32 weights per source index, zero-padded
 // (include/hdrtv_mi355x.h states the rule).  A workgroup owns SR_TH x SR_TW output pixels; the extents of the regions it keeps in
-// LDS (post_ssimsr.hip's header derives them): low-resolution positions, spline36 codes and source codes, with stage B / without.
-constexpr int SR_TW = 32, SR_TH = 16, SR_NT = 9;
-constexpr int sr_nl(int t) { return t + 4; }                                  // low-resolution pixels: Lr
-constexpr int sr_np(bool ssim, int t) { return ssim ? t + 18 : t; }           // spline36 codes
-constexpr int sr_nc(bool ssim, int t) { return ssim ? t + 14 : t + 5; }       // source codes
+// LDS are sr_nl, sr_np and sr_nc (scale_tiles.h, as are DN_* and SR_*).
 struct PostSsimsrParams {
     const void *in;
     uint16_t *dst;

@@ -75,10 +75,8 @@ int hdrtv_destroy(hdrtv_ctx *c)
     for (hipEvent_t ev : c->prof_ev) (void)hipEventDestroy(ev);
     if (c->pq_bnd) (void)hipFree(c->pq_bnd);
     if (c->lb_dev) (void)hipFree(c->lb_dev);
-    for (auto &kv : c->ps_tabs) (void)hipFree(kv.second);
-    for (auto &kv : c->fsr_tabs) (void)hipFree(kv.second);
-    for (auto &kv : c->down_tabs) (void)hipFree(kv.second.dev);
-    for (auto &kv : c->ssimsr_tabs) (void)hipFree(kv.second);
+    for (auto &tabs : c->scale_tabs)
+        for (auto &kv : tabs) (void)hipFree(kv.second.dev);
     if (c->mt_dev) (void)hipFree(c->mt_dev);
     free_workspaces(c);
     if (c->wts.dev) (void)hipFree(c->wts.dev);
@@ -511,74 +509,83 @@ int hdrtv_rgb48_light_stats(hdrtv_ctx *c, void *stream, const uint16_t *src, int
     return launched(c, "rgb48_light_stats", rgb48_light_stats_launch(p, c->var.at("light_wgs") * c->n_cu, (hipStream_t)stream));
 }
 
-// ------------------------------------------------------------------- RGB48 at the display size
-// Tap table of one axis of hdrtv_post_rgb48_scaled (the rule: include/hdrtv_mi355x.h), n source -> m >= n destination samples:
-// per destination index the first of six source taps (i0 - 2, unclamped) and six int16 coefficients that sum to 16384.
-static void lanczos_taps(int n, int m, int4 *out)
+// ------------------------------------------------------------------- RGB48 at another size than the processing size
+// Four families -- Lanczos (plain, anti-ringing, CAS), FSR, Mitchell / SSimDownscaler, spline36 / SSimSuperRes -- share everything
+// but their ratio limits, their options, their tables (scale_tables.h) and their launch.
+namespace st = scale_tables;
+static_assert(sizeof(st::I4) == sizeof(int4) && sizeof(st::I2) == sizeof(int2), "scale_tables.h's elements are uploaded as int4 / int2");
+
+// The checks every family makes, in their order: pointers and sizes, the family's ratio limit (ratio_err: what is wrong with
+// W x H -> dW x dH, or null), dtype, pq.
+static int scale_common_args(hdrtv_ctx *c, const char *what, const void *in, int dtype, int H, int W, int pq, float peak_nits,
+                             const uint16_t *dst, int dH, int dW, const char *ratio_err)
 {
-    const double PI = 3.14159265358979323846;
-    auto sinc = [&](double x) { return x == 0.0 ? 1.0 : std::sin(PI * x) / (PI * x); };
-    for (int d = 0; d < m; ++d) {
-        const double c = (d + 0.5) * n / m - 0.5, f = std::floor(c), t = c - f;
-        double w[6], sum = 0.0;
-        for (int k = 0; k < 6; ++k) {
-            const double x = t - (k - 2);
-            w[k] = std::fabs(x) < 3.0 ? sinc(x) * sinc(x / 3.0) : 0.0;
-            sum += w[k];
+    if (!c || !in || !dst || H <= 0 || W <= 0 || dH <= 0 || dW <= 0) return fail(c, HDRTV_EINVAL, "%s: bad argument", what);
+    if (ratio_err) return fail(c, HDRTV_EINVAL, "%s: %dx%d -> %dx%d %s", what, W, H, dW, dH, ratio_err);
+    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "%s: bad dtype %d", what, dtype);
+    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "%s: pq needs peak_nits > 0", what);
+    return HDRTV_OK;
+}
+
+// Device and PQ table; equal sizes are the unscaled kernel's bytes whatever the options (every family's tables would be the
+// identity, and the reference's scalers run only when the size changes): launched here, *done set.
+static int scale_begin(hdrtv_ctx *c, const char *what, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
+                       uint16_t *dst, int dH, int dW, bool *done)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = pq ? ensure_pq_table(c, what) : HDRTV_OK) return rc;
+    *done = dH == H && dW == W;
+    if (!*done) return HDRTV_OK;
+    return launched(c, what, post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd));
+}
+
+// The device tables of a geometry: first use builds them (allocates, copies), every later call finds them and only launches.  A
+// service cycles through a handful of sizes: at 16 geometries the kind's tables are freed (hipFree waits for kernels in flight).
+// A geometry whose tables do not fit the kernel (build returns false) is refused before anything is evicted.
+static int scale_tables_for(hdrtv_ctx *c, st::Kind kind, const char *what, int H, int W, int dH, int dW,
+                            bool (*build)(int, int, int, int, st::Built &), const hdrtv_ctx::ScaleTab **out)
+{
+    auto &tabs = c->scale_tabs[kind];
+    const std::array<int, 4> key{H, W, dH, dW};
+    auto it = tabs.find(key);
+    if (it == tabs.end()) {
+        st::Built b;
+        if (!build(H, W, dH, dW, b)) return fail(c, HDRTV_EINVAL, "%s: the tables of %dx%d -> %dx%d leave the kernel's tile bounds", what, W, H, dW, dH);
+        if (tabs.size() >= 16) {
+            for (auto &kv : tabs) (void)hipFree(kv.second.dev);
+            tabs.clear();
         }
-        int q[6], tot = 0, big = 0;
-        for (int k = 0; k < 6; ++k) {
-            q[k] = (int)std::floor(w[k] / sum * 16384.0 + 0.5);
-            tot += q[k];
-            if (q[k] > q[big]) big = k;          // the lowest k on a tie
+        char *dev = nullptr;
+        if (hipMalloc((void **)&dev, b.blob.size()) != hipSuccess) return fail(c, HDRTV_ENOMEM, "%s: table allocation failed", what);
+        if (hipMemcpy(dev, b.blob.data(), b.blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(dev);
+            return fail(c, HDRTV_EHIP, "%s: table upload failed", what);
         }
-        q[big] += 16384 - tot;
-        auto pack = [](int lo, int hi) { return (int)(((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16)); };
-        out[d] = make_int4((int)f - 2, pack(q[0], q[1]), pack(q[2], q[3]), pack(q[4], q[5]));
+        it = tabs.emplace(key, hdrtv_ctx::ScaleTab{dev, b.ntx, b.nty}).first;
     }
+    *out = &it->second;
+    return HDRTV_OK;
 }
 
 // The three entry points: antiring 0 = the plain rule (post_scale.hip's kernels), 1 .. 256 = post_scale_ar.hip's; cas 0 = those,
-// 1032 .. 4096 = post_scale_cas.hip's with either kind of pass; one tap-table cache.
+// 1032 .. 4096 = post_scale_cas.hip's with either kind of pass; one tap-table cache.  Anti-ringing leaves an identity alone (the sum
+// lies between its inner taps) and sharpening belongs to an upscale (the reference's chain): equal sizes are not sharpened.
 static int post_rgb48_scaled(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
                              uint16_t *dst, int dH, int dW, int antiring, int cas)
 {
-    if (!c || !in || !dst || H <= 0 || W <= 0 || dH <= 0 || dW <= 0) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: bad argument");
-    if (dH < H || dW < W) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: %dx%d -> %dx%d shrinks (enlarging only)", W, H, dW, dH);
-    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: bad dtype %d", dtype);
-    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled: pq needs peak_nits > 0");
+    const char *what = "post_rgb48_scaled";
+    const char *ratio = dH < H || dW < W ? "shrinks (enlarging only)" : nullptr;
+    if (int rc = scale_common_args(c, what, in, dtype, H, W, pq, peak_nits, dst, dH, dW, ratio)) return rc;
     if (antiring < 0 || antiring > 256) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled_ex: antiring %d is outside 0 .. 256", antiring);
     if (cas != 0 && (cas < 1032 || cas > 4096)) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled_cas: cas %d is neither 0 nor in 1032 .. 4096", cas);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = pq ? ensure_pq_table(c, "post_rgb48_scaled") : HDRTV_OK) return rc;
-    // every tap table would be the identity, and anti-ringing leaves an identity alone (the sum lies between its inner taps): the
-    // unscaled kernel writes the same bytes.  Sharpening belongs to an upscale (the reference's chain): equal sizes are not sharpened
-    if (dH == H && dW == W) {
-        return launched(c, "post_rgb48_scaled", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd));
-    }
-    // first use of a geometry builds its tables (allocates, copies); every later call finds them and only launches
-    const std::array<int, 4> key{H, W, dH, dW};
-    auto it = c->ps_tabs.find(key);
-    if (it == c->ps_tabs.end()) {
-        if (c->ps_tabs.size() >= 16) {            // a service cycles through a handful of sizes; hipFree waits for kernels in flight
-            for (auto &kv : c->ps_tabs) (void)hipFree(kv.second);
-            c->ps_tabs.clear();
-        }
-        std::vector<int4> tab((size_t)dW + dH);
-        lanczos_taps(W, dW, tab.data());
-        lanczos_taps(H, dH, tab.data() + dW);
-        int4 *dev = nullptr;
-        if (hipMalloc((void **)&dev, tab.size() * sizeof(int4)) != hipSuccess) return fail(c, HDRTV_ENOMEM, "post_rgb48_scaled: table allocation failed");
-        if (hipMemcpy(dev, tab.data(), tab.size() * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(dev);
-            return fail(c, HDRTV_EHIP, "post_rgb48_scaled: table upload failed");
-        }
-        it = c->ps_tabs.emplace(key, dev).first;
-    }
-    PostScaleParams p{in, dst, it->second, it->second + dW, c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
+    bool done;
+    if (int rc = scale_begin(c, what, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, &done); rc || done) return rc;
+    const hdrtv_ctx::ScaleTab *t;
+    if (int rc = scale_tables_for(c, st::LANCZOS, what, H, W, dH, dW, st::build_lanczos, &t)) return rc;
+    PostScaleParams p{in, dst, t->at<int4>(), t->at<int4>(st::lanczos_ytab(dW)), c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
     if (cas) return launched(c, "post_rgb48_scaled_cas", post_scale_cas_launch(p, antiring, cas, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
     if (antiring) return launched(c, "post_rgb48_scaled_ex", post_scale_ar_launch(p, antiring, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
-    return launched(c, "post_rgb48_scaled", post_scale_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
+    return launched(c, what, post_scale_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
 int hdrtv_post_rgb48_scaled(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
@@ -599,332 +606,63 @@ int hdrtv_post_rgb48_scaled_cas(hdrtv_ctx *c, void *stream, const void *in, int 
     return post_rgb48_scaled(c, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, antiring, cas);
 }
 
-// Position table of one axis of hdrtv_post_rgb48_fsr (the rule: include/hdrtv_mi355x.h), n source -> m destination samples: per
-// destination index fp = floor(p) and the bits of the float32 pp = p - fp.
-static void fsr_positions(int n, int m, int2 *out)
-{
-    for (int d = 0; d < m; ++d) {
-        const double p = (d + 0.5) * n / m - 0.5, f = std::floor(p);
-        const float pp = (float)(p - f);
-        int bits;
-        memcpy(&bits, &pp, sizeof bits);
-        out[d] = make_int2((int)f, bits);
-    }
-}
-
 int hdrtv_post_rgb48_fsr(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
                          uint16_t *dst, int dH, int dW, int rcas, float sharpness)
 {
-    if (!c || !in || !dst || H <= 0 || W <= 0 || dH <= 0 || dW <= 0) return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: bad argument");
-    if (dH < H || dW < W) return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: %dx%d -> %dx%d shrinks (enlarging only)", W, H, dW, dH);
-    if (dH > 2 * (long long)H || dW > 2 * (long long)W)
-        return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: %dx%d -> %dx%d is more than 2x on an axis", W, H, dW, dH);
-    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: bad dtype %d", dtype);
-    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: pq needs peak_nits > 0");
+    const char *what = "post_rgb48_fsr";
+    const char *ratio = dH < H || dW < W                             ? "shrinks (enlarging only)"
+                        : dH > 2 * (long long)H || dW > 2 * (long long)W ? "is more than 2x on an axis"
+                                                                         : nullptr;
+    if (int rc = scale_common_args(c, what, in, dtype, H, W, pq, peak_nits, dst, dH, dW, ratio)) return rc;
     if (rcas != 0 && rcas != 1) return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: rcas %d is neither 0 nor 1", rcas);
     if (rcas && !(sharpness >= 0.f && sharpness <= 2.f))          // NaN fails both comparisons
         return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: sharpness %g is outside 0 .. 2", (double)sharpness);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = pq ? ensure_pq_table(c, "post_rgb48_fsr") : HDRTV_OK) return rc;
-    // the shader runs only when the frame is enlarged: equal sizes are the unscaled kernel's bytes, whatever rcas
-    if (dH == H && dW == W) {
-        return launched(c, "post_rgb48_fsr", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd));
-    }
-    // first use of a geometry builds its tables (allocates, copies); every later call finds them and only launches
-    const std::array<int, 4> key{H, W, dH, dW};
-    auto it = c->fsr_tabs.find(key);
-    if (it == c->fsr_tabs.end()) {
-        if (c->fsr_tabs.size() >= 16) {
-            for (auto &kv : c->fsr_tabs) (void)hipFree(kv.second);
-            c->fsr_tabs.clear();
-        }
-        std::vector<int2> tab((size_t)dW + dH);
-        fsr_positions(W, dW, tab.data());
-        fsr_positions(H, dH, tab.data() + dW);
-        int2 *dev = nullptr;
-        if (hipMalloc((void **)&dev, tab.size() * sizeof(int2)) != hipSuccess) return fail(c, HDRTV_ENOMEM, "post_rgb48_fsr: table allocation failed");
-        if (hipMemcpy(dev, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(dev);
-            return fail(c, HDRTV_EHIP, "post_rgb48_fsr: table upload failed");
-        }
-        it = c->fsr_tabs.emplace(key, dev).first;
-    }
-    PostFsrParams p{in, dst, it->second, it->second + dW, c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
+    bool done;
+    if (int rc = scale_begin(c, what, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, &done); rc || done) return rc;
+    const hdrtv_ctx::ScaleTab *t;
+    if (int rc = scale_tables_for(c, st::FSR, what, H, W, dH, dW, st::build_fsr, &t)) return rc;
+    PostFsrParams p{in, dst, t->at<int2>(), t->at<int2>(st::fsr_ytab(dW)), c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
     const float sharp = rcas ? (float)std::exp2(-(double)sharpness) : 0.f;
-    return launched(c, "post_rgb48_fsr", post_fsr_launch(p, rcas, sharp, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
-}
-
-// Tables of one axis of hdrtv_post_rgb48_down (the rule: include/hdrtv_mi355x.h), n source -> m destination samples, m <= n <= 4 m:
-// per destination index {first tap, tap count, the two inner taps of the pull}, the Mitchell coefficients (int, sum 16384) and the
-// Catmull-Rom weights of the L2 passes (divided by their sum in double, then float32), both padded with zeros to nt = the largest count.
-struct DownAxis {
-    std::vector<int4> info;
-    std::vector<int> q;
-    std::vector<float> w;
-    int nt = 1;
-};
-static void down_axis(int n, int m, DownAxis &t)
-{
-    t.info.resize(m);
-    if (m == n) {                                 // one tap, k = d, weight one; the pull of an identity is a no-op on any pair of taps
-        t.nt = 1;
-        t.q.assign(m, 16384);
-        t.w.assign(m, 1.f);
-        for (int d = 0; d < m; ++d) t.info[d] = make_int4(d, 1, d, d);
-        return;
-    }
-    auto mitchell = [](double x) {
-        x = std::fabs(x);
-        if (x < 1.0) return ((7.0 * x - 12.0) * x * x + 16.0 / 3.0) / 6.0;
-        if (x < 2.0) return ((((-7.0 / 3.0) * x + 12.0) * x - 20.0) * x + 32.0 / 3.0) / 6.0;
-        return 0.0;
-    };
-    auto catrom = [](double x) {
-        x = std::fabs(x);
-        if (x < 1.0) return (1.5 * x - 2.5) * x * x + 1.0;
-        return ((-0.5 * x + 2.5) * x - 4.0) * x + 2.0;
-    };
-    const double hw = 2.0 * n / m;
-    int nt = 1;
-    for (int d = 0; d < m; ++d) {
-        const double ctr = (d + 0.5) * n / m;
-        const int lo = (int)std::ceil(ctr - hw - 0.5), hi = (int)std::floor(ctr + hw - 0.5), k2 = (int)std::floor(ctr - 0.5);
-        t.info[d] = make_int4(lo, hi - lo + 1, k2, k2 + 1);
-        nt = std::max(nt, hi - lo + 1);
-    }
-    t.nt = nt;
-    t.q.assign((size_t)m * nt, 0);
-    t.w.assign((size_t)m * nt, 0.f);
-    for (int d = 0; d < m; ++d) {
-        const double ctr = (d + 0.5) * n / m;
-        const int lo = t.info[d].x, cnt = t.info[d].y;
-        double v[17], cr[17], s = 0.0, cs = 0.0;
-        for (int k = 0; k < cnt; ++k) {
-            const double x = (lo + k + 0.5 - ctr) * m / n;
-            v[k] = mitchell(x);
-            cr[k] = catrom(x);
-            s += v[k];
-            cs += cr[k];
-        }
-        int *q = &t.q[(size_t)d * nt], tot = 0, big = 0;
-        for (int k = 0; k < cnt; ++k) {
-            q[k] = (int)std::floor(v[k] / s * 16384.0 + 0.5);
-            tot += q[k];
-            if (q[k] > q[big]) big = k;           // the lowest k on a tie
-            t.w[(size_t)d * nt + k] = (float)(cr[k] / cs);
-        }
-        q[big] += 16384 - tot;
-    }
+    return launched(c, what, post_fsr_launch(p, rcas, sharp, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
 int hdrtv_post_rgb48_down(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
                           uint16_t *dst, int dH, int dW, int antiring, int ssim)
 {
-    if (!c || !in || !dst || H <= 0 || W <= 0 || dH <= 0 || dW <= 0) return fail(c, HDRTV_EINVAL, "post_rgb48_down: bad argument");
-    if (dH > H || dW > W) return fail(c, HDRTV_EINVAL, "post_rgb48_down: %dx%d -> %dx%d enlarges (shrinking only)", W, H, dW, dH);
-    if (4 * (long long)dH < H || 4 * (long long)dW < W)
-        return fail(c, HDRTV_EINVAL, "post_rgb48_down: %dx%d -> %dx%d is more than 4x on an axis", W, H, dW, dH);
-    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_rgb48_down: bad dtype %d", dtype);
-    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_rgb48_down: pq needs peak_nits > 0");
+    const char *what = "post_rgb48_down";
+    const char *ratio = dH > H || dW > W                             ? "enlarges (shrinking only)"
+                        : 4 * (long long)dH < H || 4 * (long long)dW < W ? "is more than 4x on an axis"
+                                                                         : nullptr;
+    if (int rc = scale_common_args(c, what, in, dtype, H, W, pq, peak_nits, dst, dH, dW, ratio)) return rc;
     if (antiring < 0 || antiring > 256) return fail(c, HDRTV_EINVAL, "post_rgb48_down: antiring %d is outside 0 .. 256", antiring);
     if (ssim != 0 && ssim != 1) return fail(c, HDRTV_EINVAL, "post_rgb48_down: ssim %d is neither 0 nor 1", ssim);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = pq ? ensure_pq_table(c, "post_rgb48_down") : HDRTV_OK) return rc;
-    // the reference's downscaler runs only when the output is smaller: equal sizes are the unscaled kernel's bytes, whatever the options
-    if (dH == H && dW == W) {
-        return launched(c, "post_rgb48_down", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd));
-    }
-    // first use of a geometry builds its tables (allocates, copies); every later call finds them and only launches
-    const std::array<int, 4> key{H, W, dH, dW};
-    auto it = c->down_tabs.find(key);
-    if (it == c->down_tabs.end()) {
-        if (c->down_tabs.size() >= 16) {
-            for (auto &kv : c->down_tabs) (void)hipFree(kv.second.dev);
-            c->down_tabs.clear();
-        }
-        DownAxis ax, ay;
-        down_axis(W, dW, ax);
-        down_axis(H, dH, ay);
-        const size_t ni = (size_t)dW + dH, nq = ax.q.size() + ay.q.size();
-        std::vector<char> host(ni * sizeof(int4) + nq * (sizeof(int) + sizeof(float)));
-        char *h = host.data();
-        memcpy(h, ax.info.data(), dW * sizeof(int4));
-        memcpy(h + dW * sizeof(int4), ay.info.data(), dH * sizeof(int4));
-        h += ni * sizeof(int4);
-        memcpy(h, ax.q.data(), ax.q.size() * sizeof(int));
-        memcpy(h + ax.q.size() * sizeof(int), ay.q.data(), ay.q.size() * sizeof(int));
-        h += nq * sizeof(int);
-        memcpy(h, ax.w.data(), ax.w.size() * sizeof(float));
-        memcpy(h + ax.w.size() * sizeof(float), ay.w.data(), ay.w.size() * sizeof(float));
-        int4 *dev = nullptr;
-        if (hipMalloc((void **)&dev, host.size()) != hipSuccess) return fail(c, HDRTV_ENOMEM, "post_rgb48_down: table allocation failed");
-        if (hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(dev);
-            return fail(c, HDRTV_EHIP, "post_rgb48_down: table upload failed");
-        }
-        it = c->down_tabs.emplace(key, hdrtv_ctx::DownTabs{dev, ax.nt, ay.nt}).first;
-    }
-    const hdrtv_ctx::DownTabs &t = it->second;
-    const int *q = reinterpret_cast<const int *>(t.dev + dW + dH);
-    const size_t nqx = (size_t)dW * t.ntx, nq = nqx + (size_t)dH * t.nty;
-    const float *w = reinterpret_cast<const float *>(q + nq);
-    PostDownParams p{in, dst, t.dev, t.dev + dW, q, q + nqx, w, w + nqx, c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW, t.ntx, t.nty};
-    return launched(c, "post_rgb48_down", post_down_launch(p, antiring, ssim, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
-}
-
-// Tables of one axis of hdrtv_post_rgb48_ssimsr (the rule: include/hdrtv_mi355x.h), n source -> m destination samples, n < m <= 2 n.
-// Per destination index: sp, the spline36 taps in lanczos_taps' form; fin, {ip, the bits of the Hann weights at -1, 0, 1}.  Per
-// source index: low, {first tap of the step-4 footprint (unclamped), tap count, b0, the bits of f}; w, SR_NT weights (divided by their
-// sum in double, then float32, zero-padded).
-struct SsimsrAxis {
-    std::vector<int4> sp, fin, low;
-    std::vector<float> w;
-};
-static int float_bits(float v)
-{
-    int b;
-    memcpy(&b, &v, sizeof b);
-    return b;
-}
-static bool ssimsr_axis(int n, int m, SsimsrAxis &t)
-{
-    const double PI = 3.14159265358979323846;
-    auto spline36 = [](double x) {
-        x = std::fabs(x);
-        if (x < 1.0) return ((13.0 / 11.0 * x - 453.0 / 209.0) * x - 3.0 / 209.0) * x + 1.0;
-        if (x < 2.0) { const double y = x - 1.0; return ((-6.0 / 11.0 * y + 270.0 / 209.0) * y - 156.0 / 209.0) * y; }
-        if (x < 3.0) { const double y = x - 2.0; return ((1.0 / 11.0 * y - 45.0 / 209.0) * y + 26.0 / 209.0) * y; }
-        return 0.0;
-    };
-    auto mn = [](double x) {
-        const double b = 0.334, c = 0.333;
-        x = std::fabs(x);
-        if (x < 1.0) return ((2.0 - 1.5 * b - c) * x + (-3.0 + 2.0 * b + c)) * x * x + (1.0 - b / 3.0);
-        return (((-b / 6.0 - c) * x + (b + 5.0 * c)) * x + (-2.0 * b - 8.0 * c)) * x + (4.0 / 3.0 * b + 4.0 * c);
-    };
-    t.sp.resize(m);
-    t.fin.resize(m);
-    for (int d = 0; d < m; ++d) {
-        const double c = (d + 0.5) * n / m - 0.5, f = std::floor(c), tt = c - f;
-        double w[6], sum = 0.0;
-        for (int k = 0; k < 6; ++k) {
-            w[k] = spline36(tt - (k - 2));
-            sum += w[k];
-        }
-        int q[6], tot = 0, big = 0;
-        for (int k = 0; k < 6; ++k) {
-            q[k] = (int)std::floor(w[k] / sum * 16384.0 + 0.5);
-            tot += q[k];
-            if (q[k] > q[big]) big = k;          // the lowest k on a tie
-        }
-        q[big] += 16384 - tot;
-        auto pack = [](int lo, int hi) { return (int)(((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16)); };
-        t.sp[d] = make_int4((int)f - 2, pack(q[0], q[1]), pack(q[2], q[3]), pack(q[4], q[5]));
-        const double ip = std::floor(c + 0.5), off = c - ip;           // GLSL's round with the tie going up
-        t.fin[d] = make_int4((int)ip, float_bits((float)std::cos(PI * (-1.0 - off) / 3.0)), float_bits((float)std::cos(PI * (0.0 - off) / 3.0)),
-                             float_bits((float)std::cos(PI * (1.0 - off) / 3.0)));
-    }
-    t.low.resize(n);
-    t.w.assign((size_t)n * SR_NT, 0.f);
-    const double hw = 2.0 * m / n;
-    for (int j = 0; j < n; ++j) {
-        const double ctr = (j + 0.5) * m / n;
-        const int lo = (int)std::ceil(ctr - hw - 0.5), hi = (int)std::floor(ctr + hw - 0.5), cnt = hi - lo + 1;
-        if (cnt < 1 || cnt > SR_NT) return false;
-        double v[SR_NT], s = 0.0;
-        for (int k = 0; k < cnt; ++k) {
-            v[k] = mn((lo + k + 0.5 - ctr) * n / m);
-            s += v[k];
-        }
-        for (int k = 0; k < cnt; ++k) t.w[(size_t)j * SR_NT + k] = (float)(v[k] / s);
-        const double u = ctr - 0.5, b0 = std::floor(u);
-        t.low[j] = make_int4(lo, cnt, (int)b0, float_bits((float)(u - b0)));
-    }
-    return true;
-}
-
-// What post_ssimsr.hip's header derives, checked on the tables themselves: along one axis, every tile's regions fit the kernel's
-// arrays and every index a phase reads lies in the region the phase before it filled.
-static bool ssimsr_axis_fits(const SsimsrAxis &t, int n, int m, int T, bool ssim)
-{
-    auto cl = [](int v, int hi) { return std::min(std::max(v, 0), hi); };
-    for (int d0 = 0; d0 < m; d0 += T) {
-        const int d1 = std::min(d0 + T, m) - 1;
-        int fa = 0, fb = 0, la = 0, lb = 0, pa = d0, pb = d1;
-        if (ssim) {
-            fa = std::max(t.fin[d0].x - 1, 0), fb = std::min(t.fin[d1].x + 1, n - 1);
-            la = std::max(fa - 1, 0), lb = std::min(fb + 1, n - 1);
-            pa = std::max(t.low[la].x, 0), pb = std::min(t.low[lb].x + t.low[lb].y - 1, m - 1);
-        }
-        const int ca = std::max(t.sp[pa].x, 0), cb = std::min(t.sp[pb].x + 5, n - 1);
-        if (pa > pb || ca > cb || pb - pa + 1 > sr_np(ssim, T) || cb - ca + 1 > sr_nc(ssim, T)) return false;
-        for (int d = pa; d <= pb; ++d)
-            if (cl(t.sp[d].x, n - 1) < ca || cl(t.sp[d].x + 5, n - 1) > cb) return false;
-        if (!ssim) continue;
-        if (fa > fb || lb - la + 1 > sr_nl(T) || fb - fa + 1 > T + 2 || la < ca || lb > cb || d0 < pa || d1 > pb) return false;
-        for (int j = la; j <= lb; ++j) {
-            const int4 e = t.low[j];
-            if (cl(e.x, m - 1) < pa || cl(e.x + e.y - 1, m - 1) > pb || cl(e.z, m - 1) < pa || cl(e.z + 1, m - 1) > pb) return false;
-        }
-        for (int d = d0; d <= d1; ++d)
-            if (cl(t.fin[d].x - 1, n - 1) < fa || cl(t.fin[d].x + 1, n - 1) > fb || t.fin[d].x < 0 || t.fin[d].x > n - 1) return false;
-    }
-    return true;
+    bool done;
+    if (int rc = scale_begin(c, what, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, &done); rc || done) return rc;
+    const hdrtv_ctx::ScaleTab *t;
+    if (int rc = scale_tables_for(c, st::DOWN, what, H, W, dH, dW, st::build_down, &t)) return rc;
+    const st::DownLayout l = st::down_layout(dH, dW, t->ntx, t->nty);
+    PostDownParams p{in, dst, t->at<int4>(), t->at<int4>(l.yinfo), t->at<int>(l.xq), t->at<int>(l.yq), t->at<float>(l.xw),
+                     t->at<float>(l.yw), c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW, t->ntx, t->nty};
+    return launched(c, what, post_down_launch(p, antiring, ssim, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
 int hdrtv_post_rgb48_ssimsr(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
                             uint16_t *dst, int dH, int dW, int ssim)
 {
-    if (!c || !in || !dst || H <= 0 || W <= 0 || dH <= 0 || dW <= 0) return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: bad argument");
-    const bool same = dH == H && dW == W;
-    if (!same && (dH <= H || dW <= W))
-        return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: %dx%d -> %dx%d does not enlarge both axes", W, H, dW, dH);
-    if (dH > 2 * (long long)H || dW > 2 * (long long)W)
-        return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: %dx%d -> %dx%d is more than 2x on an axis", W, H, dW, dH);
-    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: bad dtype %d", dtype);
-    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: pq needs peak_nits > 0");
+    const char *what = "post_rgb48_ssimsr";
+    const char *ratio = !(dH == H && dW == W) && (dH <= H || dW <= W) ? "does not enlarge both axes"
+                        : dH > 2 * (long long)H || dW > 2 * (long long)W ? "is more than 2x on an axis"
+                                                                         : nullptr;
+    if (int rc = scale_common_args(c, what, in, dtype, H, W, pq, peak_nits, dst, dH, dW, ratio)) return rc;
     if (ssim != 0 && ssim != 1) return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: ssim %d is neither 0 nor 1", ssim);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = pq ? ensure_pq_table(c, "post_rgb48_ssimsr") : HDRTV_OK) return rc;
-    // the reference's upscaler runs only when the frame is enlarged: equal sizes are the unscaled kernel's bytes, whatever ssim
-    if (same) {
-        return launched(c, "post_rgb48_ssimsr", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd));
-    }
-    // first use of a geometry builds its tables (allocates, copies); every later call finds them and only launches
-    const std::array<int, 4> key{H, W, dH, dW};
-    auto it = c->ssimsr_tabs.find(key);
-    if (it == c->ssimsr_tabs.end()) {
-        SsimsrAxis ax, ay;
-        if (!ssimsr_axis(W, dW, ax) || !ssimsr_axis(H, dH, ay) || !ssimsr_axis_fits(ax, W, dW, SR_TW, false) ||
-            !ssimsr_axis_fits(ax, W, dW, SR_TW, true) || !ssimsr_axis_fits(ay, H, dH, SR_TH, false) || !ssimsr_axis_fits(ay, H, dH, SR_TH, true))
-            return fail(c, HDRTV_EINVAL, "post_rgb48_ssimsr: the tables of %dx%d -> %dx%d leave the kernel's tile bounds", W, H, dW, dH);
-        if (c->ssimsr_tabs.size() >= 16) {
-            for (auto &kv : c->ssimsr_tabs) (void)hipFree(kv.second);
-            c->ssimsr_tabs.clear();
-        }
-        const size_t ni = 2 * ((size_t)dW + dH) + W + H, nw = ((size_t)W + H) * SR_NT;
-        std::vector<char> host(ni * sizeof(int4) + nw * sizeof(float));
-        int4 *h = reinterpret_cast<int4 *>(host.data());
-        for (const std::vector<int4> *v : {&ax.sp, &ay.sp, &ax.fin, &ay.fin, &ax.low, &ay.low}) {
-            memcpy(h, v->data(), v->size() * sizeof(int4));
-            h += v->size();
-        }
-        float *hwt = reinterpret_cast<float *>(h);
-        memcpy(hwt, ax.w.data(), ax.w.size() * sizeof(float));
-        memcpy(hwt + ax.w.size(), ay.w.data(), ay.w.size() * sizeof(float));
-        int4 *dev = nullptr;
-        if (hipMalloc((void **)&dev, host.size()) != hipSuccess) return fail(c, HDRTV_ENOMEM, "post_rgb48_ssimsr: table allocation failed");
-        if (hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(dev);
-            return fail(c, HDRTV_EHIP, "post_rgb48_ssimsr: table upload failed");
-        }
-        it = c->ssimsr_tabs.emplace(key, dev).first;
-    }
-    const int4 *t = it->second;
-    const float *w = reinterpret_cast<const float *>(t + 2 * ((size_t)dW + dH) + W + H);
-    PostSsimsrParams p{in, dst, t, t + dW, t + dW + dH, t + 2 * (size_t)dW + dH, t + 2 * ((size_t)dW + dH), t + 2 * ((size_t)dW + dH) + W,
-                       w, w + (size_t)W * SR_NT, c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
-    return launched(c, "post_rgb48_ssimsr", post_ssimsr_launch(p, ssim, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
+    bool done;
+    if (int rc = scale_begin(c, what, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, &done); rc || done) return rc;
+    const hdrtv_ctx::ScaleTab *t;
+    if (int rc = scale_tables_for(c, st::SSIMSR, what, H, W, dH, dW, st::build_ssimsr, &t)) return rc;
+    const st::SsimsrLayout l = st::ssimsr_layout(H, W, dH, dW);
+    PostSsimsrParams p{in, dst, t->at<int4>(), t->at<int4>(l.ysp), t->at<int4>(l.xfin), t->at<int4>(l.yfin), t->at<int4>(l.xlow),
+                       t->at<int4>(l.ylow), t->at<float>(l.xw), t->at<float>(l.yw), c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
+    return launched(c, what, post_ssimsr_launch(p, ssim, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
 // ------------------------------------------------------------------------------- letterbox

@@ -77,17 +77,9 @@ class _Mi355xWorker:
         # deband / dither of the delivered frames (lib.OutputCleanup, validated by the dispatcher): a plain tuple in init_args
         cleanup = kw.pop("cleanup", None)
         self.cleanup = None if cleanup is None else L.OutputCleanup(*cleanup)
-        # anti-ringing of enlarged frames (a strength in [0, 1] or "auto", validated by the dispatcher); absent: off
-        self.antiring = kw.pop("antiring", 0.0)
-        # contrast-adaptive sharpening in front of that upscale (likewise); absent: off
-        self.cas = kw.pop("cas", 0.0)
-        # the scaler of enlarged frames ("fsr" = hdrtv_post_rgb48_fsr with its RCAS sharpness, or None = EASU alone); absent: Lanczos
-        self.scaler = kw.pop("scaler", "lanczos")
-        self.fsr_sharpness = kw.pop("fsr_sharpness", L.FSR_SHARPNESS)
-        # what shrinks frames delivered below the processing size ("mitchell" / "ssim" = hdrtv_post_rgb48_down) and its anti-ringing
-        # strength (validated by the dispatcher); absent: none
-        self.downscaler = kw.pop("downscaler", None)
-        self.down_antiring = kw.pop("down_antiring", 0.0)
+        # how frames of another size than the processing size are resized (lib.ScaleOptions; validated by the dispatcher, which hands
+        # on what is not the default): enqueue_frame's six keywords
+        self.scale = L.scale_options(**{name: kw.pop(name) for name in L.ScaleOptions._fields if name in kw})
         torch.cuda.set_device(device_index)
         with contextlib.redirect_stdout(sys.stderr):   # a worker's banner must not land on the parent's stdout (bench.py's one JSON line)
             self.proc = HDRTVNetMI355X(model, device=f"cuda:{device_index}", warmup_passes=0, **kw)
@@ -135,15 +127,7 @@ class _Mi355xWorker:
         else:
             h, w = (frame.shape[0], frame.shape[1]) if frame.ndim == 3 else (frame.shape[0] * 2 // 3, frame.shape[1])
         fmt = self.output_format
-        out_fmt = dict(out_hw=(fmt.h, fmt.w), out_pix_fmt=fmt.pix_fmt, out_siting=fmt.siting, cleanup=self.cleanup)
-        if self.antiring:
-            out_fmt["antiring"] = self.antiring
-        if self.cas:
-            out_fmt["cas"] = self.cas
-        if self.scaler != "lanczos":
-            out_fmt["scaler"], out_fmt["fsr_sharpness"] = self.scaler, self.fsr_sharpness
-        if self.downscaler is not None:
-            out_fmt["downscaler"], out_fmt["down_antiring"] = self.downscaler, self.down_antiring
+        out_fmt = dict(out_hw=(fmt.h, fmt.w), out_pix_fmt=fmt.pix_fmt, out_siting=fmt.siting, cleanup=self.cleanup, **self.scale._asdict())
         self._buffers(h, w, tuple(frame.shape) + ((2,) if ten else ()), fmt)       # _raw is bytes: a u16 sample is two
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
@@ -406,25 +390,13 @@ class FrameDispatcher:
         ``hdrtv_ycbcr10_bytes`` bytes, the planes back to back -- half the slot bytes and D2H copy of RGB48 for 4:2:0.
         ``deband`` / ``deband_range`` / ``deband_threshold`` / ``dither``: the output cleanup of ``lib.output_cleanup``
         (INTEGRATION.md 5f); when one is on, the tuple travels to the workers as ``init_args["cleanup"]`` and the product's worker
-        hands it to ``enqueue_frame(..., cleanup=)``.  Slot sizes do not depend on it.  ``antiring``: the anti-ringing strength of
-        enlarged frames, 0 .. 1, or ``"auto"`` = ``lib.scale_antiring`` of the processing and the output size,
-        kept as ``.antiring``; when it is not off it travels as ``init_args["antiring"]`` and the product's worker hands it to
-        ``enqueue_frame(..., antiring=)``.  Off (0.0, the default): the ``init_args`` of before.  ``cas``: the strength of the
-        contrast-adaptive sharpening in front of that upscale, 0 .. 1, or ``"auto"`` = ``lib.scale_cas`` of the two sizes
-        (INTEGRATION.md 5c), kept as ``.cas`` and handed on as ``init_args["cas"]`` under the same condition.  ``scaler``: ``"lanczos"``
-        (the default) or ``"fsr"`` = the product's worker enlarges through ``hdrtv_post_rgb48_fsr``, the reference's default upscaler
-        (INTEGRATION.md 5c): the output size is then at most twice the processing size per axis, ``antiring`` and ``cas`` are 0
-        (``"auto"`` resolves to 0, an explicit nonzero value is a ``ValueError``), and ``fsr_sharpness`` is its RCAS sharpness, 0 .. 2,
-        or None = EASU alone; ``"spline36"`` / ``"ssim_superres"`` = ``hdrtv_post_rgb48_ssimsr`` without / with the reference's
-        SSimSuperRes shader stage (both axes enlarged, by at most 2x; ``antiring`` and ``cas`` 0 likewise); kept as ``.scaler`` / ``.fsr_sharpness`` and handed on as ``init_args["scaler"]`` /
-        ``init_args["fsr_sharpness"]`` only when the scaler is not the default: otherwise the ``init_args`` of before.
-        ``downscaler``: None (the default: an output size below the processing size is a ``ValueError``, as before), ``"mitchell"``
-        or ``"ssim"`` = the output size lies below the processing size, by at most 4x per axis, and the product's worker shrinks
-        through ``hdrtv_post_rgb48_down`` with the anti-ringing strength ``down_antiring``, 0 .. 1 (``"auto"`` =
-        the reference's 0.20, resolved here); ``lib.down_options`` has the refusals (a mixed request, more than 4x, ``scaler="fsr"``
-        or a nonzero ``antiring`` / ``cas``, nothing to shrink).  Kept as ``.downscaler`` / ``.down_antiring`` and handed on as
-        ``init_args["downscaler"]`` / ``init_args["down_antiring"]`` only when a downscaler is given; stand-in workers fill slots of
-        the smaller size."""
+        hands it to ``enqueue_frame(..., cleanup=)``.  Slot sizes do not depend on it.  ``antiring``, ``cas``, ``scaler``,
+        ``fsr_sharpness``, ``downscaler``, ``down_antiring``: how the product's worker resizes a frame whose output size is not the
+        processing size (``lib.ScaleOptions`` describes the six).  They are checked here, against the two sizes
+        too (``ValueError``), and kept under these names (``"auto"`` of ``down_antiring`` resolved) and as ``.scale``.  Each travels
+        in ``init_args`` under its name only when it is not the default -- ``fsr_sharpness`` with ``scaler="fsr"``,
+        ``down_antiring`` with a downscaler -- and the product's worker hands them to ``enqueue_frame``; stand-in workers fill
+        slots of the output size."""
         if n_workers < 1 or slots < 2:
             raise ValueError("n_workers >= 1 and slots >= 2")
         from . import lib as _L
@@ -436,31 +408,24 @@ class FrameDispatcher:
             raise ValueError("yuv_matrix must be 601, 709 or 2020")
         self.n, self.h, self.w, self.slots = int(n_workers), int(height), int(width), int(slots)
         self.out_h, self.out_w = int(out_height or height), int(out_width or width)
-        self.downscaler = _L.check_downscaler(downscaler)
-        self.down_antiring = _L.check_down_antiring(down_antiring)
-        if _L.down_options(self.downscaler, down_antiring, self.w, self.h, self.out_w, self.out_h, scaler, antiring, cas) is not None:
-            antiring = cas = 0.0                # checked to be 0 or "auto", which is 0 where nothing is enlarged
-        if self.downscaler is None and (self.out_h < self.h or self.out_w < self.w):
-            raise ValueError(f"output size {self.out_w}x{self.out_h} is below the processing size {self.w}x{self.h} (enlarging only)")
+        self.scale = _L.scale_options(antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
+        self.scale.plan(self.w, self.h, self.out_w, self.out_h)                    # raises for sizes the options do not go with
+        self.antiring, self.cas, self.scaler, self.fsr_sharpness, self.downscaler, self.down_antiring = self.scale
         out = _L.output_format(out_pix_fmt, out_siting, self.out_h, self.out_w)    # raises for an odd size of a Y'CbCr layout
         self.out_pix_fmt, self.out_siting, self._out_shape = out.pix_fmt, out.siting, out.shape
         self.cleanup = _L.output_cleanup(deband, deband_range, deband_threshold, dither, pix_fmt=out.pix_fmt)
         init_args = dict(init_args or {})
         if self.cleanup.active:
             init_args["cleanup"] = tuple(self.cleanup)
-        self.scaler = _L.check_scaler(scaler)
-        self.antiring, self.cas = _L.scaler_options(self.scaler, antiring, cas)
-        self.fsr_sharpness = _L.check_fsr_sharpness(fsr_sharpness)
+        # an option travels only when it is not the default: otherwise the init_args of before
         if self.antiring:
             init_args["antiring"] = self.antiring
         if self.cas:
             init_args["cas"] = self.cas
-        if self.scaler == "fsr":
-            _L.check_fsr_size(self.w, self.h, self.out_w, self.out_h)
-            init_args["scaler"], init_args["fsr_sharpness"] = self.scaler, self.fsr_sharpness
-        if self.scaler in _L.SSIMSR_SCALERS:
-            _L.check_ssimsr_size(self.w, self.h, self.out_w, self.out_h)
+        if self.scaler != "lanczos":
             init_args["scaler"] = self.scaler
+        if self.scaler == "fsr":
+            init_args["fsr_sharpness"] = self.fsr_sharpness
         if self.downscaler is not None:
             init_args["downscaler"], init_args["down_antiring"] = self.downscaler, self.down_antiring
         self.pix_fmt = pix_fmt

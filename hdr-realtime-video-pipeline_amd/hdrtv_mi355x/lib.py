@@ -465,6 +465,77 @@ def down_options(downscaler, down_antiring, proc_w, proc_h, out_w, out_h, scaler
     return antiring_code(strength), 1 if downscaler == "ssim" else 0
 
 
+class ScalePlan(NamedTuple):
+    """How one frame geometry is resized: ``entry``, the C symbol (one of the six ``hdrtv_post_rgb48_scaled*`` / ``_fsr`` / ``_down`` /
+    ``_ssimsr``), and ``args``, the tuple that follows ``dH, dW`` in its signature."""
+    entry: str
+    args: tuple
+
+
+class ScaleOptions(NamedTuple):
+    """The six options of a frame delivered at another size than the processing size, checked
+    (``scale_options`` builds one); the processor, the worker, the dispatcher and the command line all take them by these names.
+
+    ``scaler``: what enlarges.  ``"lanczos"`` (the default): the fused Lanczos passes, ``hdrtv_post_rgb48_scaled``, with
+    ``antiring``, the anti-ringing strength 0 .. 1 or ``"auto"`` = ``scale_antiring`` of the two sizes (nonzero:
+    ``hdrtv_post_rgb48_scaled_ex``), and ``cas``, the strength of the contrast-adaptive sharpening in front of the upscale, 0 .. 1
+    or ``"auto"`` = ``scale_cas`` of the two sizes (nonzero: ``hdrtv_post_rgb48_scaled_cas``).  ``"fsr"``: ``hdrtv_post_rgb48_fsr``,
+    the reference's default upscaler, at most 2x per axis, with RCAS at ``fsr_sharpness`` (0 .. 2, 0 = the sharpest; the reference's
+    0.2) or, with None, EASU alone.  ``"spline36"`` / ``"ssim_superres"``: ``hdrtv_post_rgb48_ssimsr`` without / with the
+    reference's SSimSuperRes shader stage, both axes enlarged, by at most 2x.  Under the last three ``antiring`` and ``cas`` are 0:
+    ``"auto"`` resolves to 0, as the reference's schedules do, and an explicit nonzero value is a ``ValueError``.
+    ``downscaler``: what shrinks a frame delivered BELOW the processing size.  None (the default): such a size is a
+    ``ValueError``.  ``"mitchell"`` / ``"ssim"``: ``hdrtv_post_rgb48_down`` without / with the reference's SSimDownscaler stage, at
+    most 4x per axis, with the anti-ringing strength ``down_antiring`` (0 .. 1; ``"auto"`` = the reference's 0.20, resolved in the
+    record); ``down_options`` has the refusals (a mixed or enlarging request, an enlarging ``scaler``, a nonzero ``antiring`` /
+    ``cas``, nothing to shrink).  A frame delivered at the processing size is untouched by all of them."""
+    antiring: object
+    cas: object
+    scaler: str
+    fsr_sharpness: object
+    downscaler: object
+    down_antiring: float
+
+    def plan(self, proc_w, proc_h, out_w, out_h):
+        """The ``ScalePlan`` of a frame processed at ``proc_w`` x ``proc_h`` and delivered at ``out_w`` x ``out_h``, or None when
+        nothing is scaled; everything that depends on the sizes is checked (``ValueError``) and ``"auto"`` resolved here."""
+        if self.downscaler is not None:
+            return ScalePlan("hdrtv_post_rgb48_down", down_options(self.downscaler, self.down_antiring, proc_w, proc_h, out_w, out_h,
+                                                                   self.scaler, self.antiring, self.cas))
+        if out_w == proc_w and out_h == proc_h:
+            return None
+        if out_w < proc_w or out_h < proc_h:
+            raise ValueError(f"output size {out_w}x{out_h} is below the processing size {proc_w}x{proc_h} (enlarging only)")
+        if self.scaler == "fsr":
+            check_fsr_size(proc_w, proc_h, out_w, out_h)
+            return ScalePlan("hdrtv_post_rgb48_fsr", (0, 0.0) if self.fsr_sharpness is None else (1, self.fsr_sharpness))
+        if self.scaler in SSIMSR_SCALERS:
+            check_ssimsr_size(proc_w, proc_h, out_w, out_h)
+            return ScalePlan("hdrtv_post_rgb48_ssimsr", (1 if self.scaler == "ssim_superres" else 0,))
+        antiring = antiring_code(resolve_antiring(self.antiring, proc_w, proc_h, out_w, out_h))
+        cas = cas_code(resolve_cas(self.cas, proc_w, proc_h, out_w, out_h))
+        if cas:
+            return ScalePlan("hdrtv_post_rgb48_scaled_cas", (antiring, cas))
+        return ScalePlan("hdrtv_post_rgb48_scaled_ex", (antiring,)) if antiring else ScalePlan("hdrtv_post_rgb48_scaled", ())
+
+
+def scale_options(antiring=0.0, cas=0.0, scaler="lanczos", fsr_sharpness=FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
+    """The six options -> a ``ScaleOptions``, after every check that does not depend on the sizes (``ValueError``)."""
+    scaler = check_scaler(scaler)
+    antiring, cas = scaler_options(scaler, antiring, cas)
+    fsr_sharpness = check_fsr_sharpness(fsr_sharpness)
+    downscaler, strength = check_downscaler(downscaler), check_down_antiring(down_antiring)
+    if downscaler is None:
+        if strength != 0:
+            down_options(None, down_antiring, 0, 0, 0, 0)        # an explicit strength without a downscaler is refused there
+    else:                                                        # nothing is enlarged: "auto" is 0 (an explicit value: down_options)
+        antiring, cas = (0.0 if v == "auto" else v for v in (antiring, cas))
+    return ScaleOptions(antiring, cas, scaler, fsr_sharpness, downscaler, strength)
+
+
+SCALE_OFF = scale_options()                # the defaults: a frame at the processing size, or plain Lanczos to a larger one
+
+
 _libs = {}
 
 

@@ -341,8 +341,7 @@ class HDRTVNetMI355X:
             scratch = self._ycc_scratch[key] = torch.empty((out.h, out.w, 3), dtype=torch.uint16, device=self.device)
         return scratch.data_ptr()
 
-    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None, antiring=0, cas=0,
-                  fsr=None, down=None, ssimsr=None):
+    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None, scale=None):
         """The output conversion of a frame whose planar tensor lies at ``src_ptr``, to the ``lib.OutputFormat`` ``out`` at
         ``dst_ptr``: ``rgb48le`` at the processing size (``hdrtv_post_rgb48``) or enlarged to ``out.h`` x ``out.w``
         (``hdrtv_post_rgb48_scaled``); a 10-bit Y'CbCr layout in one kernel at the processing size (``hdrtv_post_ycbcr10``), or,
@@ -356,19 +355,10 @@ class HDRTVNetMI355X:
         (``rgb48le``), or into a second scratch and through the conversion from codes; the light level record is then taken from
         the debanded codes, which are what is delivered.  Dither alone: ``hdrtv_post_ycbcr10_ex`` at the processing size, the
         ``_ex`` conversion behind the scaled codes otherwise; it does not enter the record, which is defined on RGB48 codes.
-        ``antiring``: the anti-ringing code of an enlarged frame, 0 .. 256 (``lib.antiring_code``).  Nonzero and
-        enlarged: ``hdrtv_post_rgb48_scaled_ex`` replaces ``hdrtv_post_rgb48_scaled``, and everything behind the scaler -- deband,
-        the conversion from codes, the record -- works on the anti-ringed codes.  0, or an unscaled frame: the launches above.
-        ``cas``: the CAS code of an enlarged frame, 0 or 1032 .. 4096 (``lib.cas_code``).  Nonzero and enlarged:
-        ``hdrtv_post_rgb48_scaled_cas`` (which takes ``antiring`` too) sharpens the codes in front of the scaler, and everything
-        behind it sees the sharpened, scaled codes.  0, or an unscaled frame: the launches above.  ``fsr``: None, or ``(rcas,
-        sharpness)`` = the enlarged frame goes through ``hdrtv_post_rgb48_fsr`` instead (``_fsr_for``; ``antiring`` and ``cas`` are 0
-        then), and everything behind the scaler sees the FSR codes.  ``down``: None, or ``(antiring code, ssim)`` = a frame delivered
-        BELOW the processing size goes through ``hdrtv_post_rgb48_down`` (``lib.down_options``; the other three are off then), and
-        everything behind it -- deband, the conversion from codes, the record -- sees the shrunk codes.  ``ssimsr``: None, or 0 / 1 = the
-        enlarged frame goes through ``hdrtv_post_rgb48_ssimsr`` with that ``ssim`` (``_ssimsr_for``: spline36 alone, or the
-        reference's SSimSuperRes chain; the other four are off then), and everything behind the scaler sees its codes.  This is the
-        one place that chooses among the six entry points."""
+        ``scale``: the ``lib.ScalePlan`` of a frame delivered at another size (``lib.ScaleOptions.plan`` of the two sizes, which is
+        the one place that chooses among the six entry points): its entry point replaces
+        ``hdrtv_post_rgb48_scaled``, and everything behind it -- deband, the conversion from codes, the record -- sees its codes.
+        A frame delivered at the processing size has none."""
         scaled = (out.h, out.w) != (h, w)
         rect = (0, 0, out.w, out.h) if light_rect is None else tuple(int(v) for v in light_rect)
         active = cleanup is not None and cleanup.active
@@ -387,24 +377,8 @@ class HDRTVNetMI355X:
             return
         rgb_ptr = dst_ptr if out.is_rgb48 else self._scratch(scratch_key, out)
         raw_ptr = self._scratch((scratch_key, "raw"), out) if deband else rgb_ptr       # deband never works in place
-        if scaled and down is not None:
-            self._chk(self._lib.hdrtv_post_rgb48_down(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, down[0], down[1]),
-                      "hdrtv_post_rgb48_down")
-        elif scaled and fsr is not None:
-            self._chk(self._lib.hdrtv_post_rgb48_fsr(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, fsr[0], fsr[1]),
-                      "hdrtv_post_rgb48_fsr")
-        elif scaled and ssimsr is not None:
-            self._chk(self._lib.hdrtv_post_rgb48_ssimsr(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, int(ssimsr)),
-                      "hdrtv_post_rgb48_ssimsr")
-        elif scaled and cas:
-            self._chk(self._lib.hdrtv_post_rgb48_scaled_cas(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, int(antiring),
-                                                            int(cas)), "hdrtv_post_rgb48_scaled_cas")
-        elif scaled and antiring:
-            self._chk(self._lib.hdrtv_post_rgb48_scaled_ex(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, int(antiring)),
-                      "hdrtv_post_rgb48_scaled_ex")
-        elif scaled:
-            self._chk(self._lib.hdrtv_post_rgb48_scaled(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w),
-                      "hdrtv_post_rgb48_scaled")
+        if scaled:
+            self._chk(getattr(self._lib, scale.entry)(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, *scale.args), scale.entry)
         else:
             self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, src_ptr, dt, h, w, raw_ptr), "hdrtv_post_rgb48")
         if deband:
@@ -449,66 +423,17 @@ class HDRTVNetMI355X:
         return _L.output_cleanup(*cleanup, pix_fmt=out.pix_fmt)
 
     @staticmethod
-    def _antiring_for(antiring, h, w, out):
-        """The ``antiring`` argument of ``enqueue_frame*`` (a strength in [0, 1], or ``"auto"``: ``lib.scale_antiring`` of the two
-        sizes) -> the code ``_post_out`` takes."""
-        if type(antiring) in (float, int) and antiring == 0:          # off, the default: nothing to resolve on the hot path
-            return 0
-        return _L.antiring_code(_L.resolve_antiring(antiring, w, h, out.w, out.h))
+    def _plan_for(h, w, out, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring):
+        """The six scaler arguments of ``enqueue_frame*`` (``lib.ScaleOptions``) -> the ``lib.ScalePlan`` of the frame, or None."""
+        def off(v):
+            return type(v) in (float, int) and v == 0
+        if scaler == "lanczos" and downscaler is None and off(antiring) and off(cas) and off(down_antiring):
+            opts = _L.SCALE_OFF                                       # the default: nothing to check on the hot path
+        else:
+            opts = _L.scale_options(antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
+        return opts.plan(w, h, out.w, out.h)
 
-    @staticmethod
-    def _cas_for(cas, h, w, out):
-        """The ``cas`` argument of ``enqueue_frame*`` (a strength in [0, 1], or ``"auto"``: ``lib.scale_cas`` of the two sizes) -> the
-        code ``_post_out`` takes."""
-        if type(cas) in (float, int) and cas == 0:                    # off, the default: nothing to resolve on the hot path
-            return 0
-        return _L.cas_code(_L.resolve_cas(cas, w, h, out.w, out.h))
-
-    @staticmethod
-    def _fsr_for(scaler, fsr_sharpness, antiring, cas, h, w, out_h, out_w):
-        """The ``scaler`` / ``fsr_sharpness`` arguments of ``enqueue_frame*`` and ``postprocess_rgb48_scaled`` -> what ``_post_out``
-        takes as ``fsr``: None for ``"lanczos"``; for ``"fsr"`` ``(rcas, sharpness)`` after the checks -- ``antiring`` and ``cas`` must
-        be 0 or ``"auto"`` (``lib.scaler_options``), the delivered size at most twice the processing size (``lib.check_fsr_size``)."""
-        if scaler == "lanczos":                                       # the default: nothing to resolve on the hot path
-            return None
-        if _L.check_scaler(scaler) != "fsr":
-            return None
-        _L.scaler_options("fsr", antiring, cas)
-        _L.check_fsr_size(w, h, out_w, out_h)
-        sharp = _L.check_fsr_sharpness(fsr_sharpness)
-        return (0, 0.0) if sharp is None else (1, sharp)
-
-    @staticmethod
-    def _ssimsr_for(scaler, antiring, cas, h, w, out_h, out_w):
-        """The ``scaler`` argument of ``enqueue_frame*`` and ``postprocess_rgb48_scaled`` -> what ``_post_out`` takes as ``ssimsr``:
-        None unless it is ``"spline36"`` (0) or ``"ssim_superres"`` (1), after the checks -- ``antiring`` and ``cas`` must be 0 or
-        ``"auto"`` (``lib.scaler_options``), the delivered size the processing size or above it on both axes, by at most 2x
-        (``lib.check_ssimsr_size``)."""
-        if scaler == "lanczos":                                       # the default: nothing to resolve on the hot path
-            return None
-        scaler = _L.check_scaler(scaler)
-        if scaler not in _L.SSIMSR_SCALERS:
-            return None
-        _L.scaler_options(scaler, antiring, cas)
-        _L.check_ssimsr_size(w, h, out_w, out_h)
-        return 1 if scaler == "ssim_superres" else 0
-
-    def _scale_for(self, antiring, cas, scaler, fsr_sharpness, h, w, out, downscaler=None, down_antiring=0.0):
-        """The scaler arguments of ``enqueue_frame*`` -> ``(antiring code, CAS code, fsr, down, ssimsr)`` as ``_post_out`` takes them."""
-        if downscaler is not None or not (type(down_antiring) in (float, int) and down_antiring == 0):
-            down = _L.down_options(downscaler, down_antiring, w, h, out.w, out.h, scaler, antiring, cas)
-            if down is not None:
-                return 0, 0, None, down, None
-        fsr = self._fsr_for(scaler, fsr_sharpness, antiring, cas, h, w, out.h, out.w)
-        if fsr is not None:
-            return 0, 0, fsr, None, None
-        ssimsr = self._ssimsr_for(scaler, antiring, cas, h, w, out.h, out.w)
-        if ssimsr is not None:
-            return 0, 0, None, None, ssimsr
-        return self._antiring_for(antiring, h, w, out), self._cas_for(cas, h, w, out), None, None, None
-
-    def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out, light_ptr=None, light_rect=None, cleanup=None, antiring=0,
-                 cas=0, fsr=None, down=None, ssimsr=None):
+    def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out, light_ptr=None, light_rect=None, cleanup=None, scale=None):
         """The body of ``enqueue_frame*``: the preprocess entry point ``pre`` (named ``what``) on its source arguments ``src``,
         ``hdrtv_infer_lane`` and ``_post_out``, all on the lane's buffers and ``stream`` (default: the lane's own)."""
         self._ensure_buffers(h, w)
@@ -517,7 +442,7 @@ class HDRTVNetMI355X:
         self._chk(pre(self._ctx, st, *src, h, w, tin.data_ptr(), tcond.data_ptr()), what)
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), self._out_dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, antiring, cas, fsr, down, ssimsr)
+        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, scale)
 
     def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le",
                       out_siting="left", light_ptr=None, light_rect=None, cleanup=None, antiring=0.0, cas=0.0,
@@ -533,24 +458,13 @@ class HDRTVNetMI355X:
         the processing size, with ``out_hw`` two launches through a per-lane RGB48 scratch.  ``light_ptr`` / ``light_rect``: the
         delivered frame's content light level record, behind the frame on the same stream (``_post_out``).
         ``cleanup``: a ``lib.OutputCleanup`` (``lib.output_cleanup``): deband and / or ordered dither of the delivered frame
-        (``_post_out``); None: neither, and the bytes of before.  ``antiring``: the anti-ringing strength of an
-        enlarged frame, 0 .. 1, or ``"auto"`` = ``lib.scale_antiring`` of the two sizes (``hdrtv_post_rgb48_scaled_ex``;
-        INTEGRATION.md 5c); 0.0, or a frame delivered at the processing size: the launches and bytes of before.  ``cas``: the strength
-        of the contrast-adaptive sharpening in front of that upscale, 0 .. 1, or ``"auto"`` = ``lib.scale_cas`` of the two sizes
-        (``hdrtv_post_rgb48_scaled_cas``); 0.0, or a frame at the processing size: the launches and bytes of before.
-        ``scaler``: ``"lanczos"`` (the default: all of the above) or ``"fsr"``: an enlarged frame goes through ``hdrtv_post_rgb48_fsr``,
-        the reference's default upscaler, at most 2x per axis; ``antiring`` and ``cas`` must then be 0 or ``"auto"``
-        (which is 0 there).  ``fsr_sharpness``: its RCAS sharpness, 0 .. 2 (0 = the sharpest; the reference's 0.2), or None = EASU
-        alone.  ``"spline36"`` / ``"ssim_superres"``: ``hdrtv_post_rgb48_ssimsr`` without / with the reference's SSimSuperRes shader
-        stage, both axes enlarged, by at most 2x; ``antiring`` and ``cas`` 0 or ``"auto"`` there too.  A frame at the processing size is
-        not touched by any of them.  ``downscaler``: None (the default: an ``out_hw`` below the
-        processing size is refused, as before), ``"mitchell"`` or ``"ssim"``: a frame delivered below the processing size, by at most
-        4x per axis, goes through ``hdrtv_post_rgb48_down`` with the anti-ringing strength ``down_antiring``, 0 .. 1
-        or ``"auto"`` = the reference's 0.20; ``scaler`` must then be ``"lanczos"`` and ``antiring`` / ``cas`` 0 or ``"auto"``, and an
-        ``out_hw`` with nothing to shrink is a ``ValueError`` (``lib.down_options``)."""
+        (``_post_out``); None: neither, and the bytes of before.  ``antiring``, ``cas``, ``scaler``,
+        ``fsr_sharpness``, ``downscaler``, ``down_antiring``: how a frame with an ``out_hw`` other than the processing size is resized
+        (``lib.ScaleOptions`` describes the six).  The defaults: plain Lanczos to a larger size, a smaller one is a
+        ``ValueError``, and a frame at the processing size is touched by none of them."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         self._enqueue(lane, self._lib.hdrtv_preprocess, "hdrtv_preprocess", (src_bgr_ptr,), h, w, dst_rgb48_ptr, stream, out,
-                      light_ptr, light_rect, self._cleanup_for(cleanup, out), *self._scale_for(antiring, cas, scaler, fsr_sharpness, h, w, out, downscaler, down_antiring))
+                      light_ptr, light_rect, self._cleanup_for(cleanup, out), self._plan_for(h, w, out, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring))
 
     def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None,
                              out_hw=None, out_pix_fmt="rgb48le", out_siting="left", light_ptr=None, light_rect=None, cleanup=None,
@@ -560,7 +474,7 @@ class HDRTVNetMI355X:
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         planes = _yuv_planes(src_ptr, int(h), int(w), layout, matrix, full_range)
         self._enqueue(lane, self._lib.hdrtv_preprocess_yuv420, "hdrtv_preprocess_yuv420", planes, h, w, dst_rgb48_ptr, stream, out,
-                      light_ptr, light_rect, self._cleanup_for(cleanup, out), *self._scale_for(antiring, cas, scaler, fsr_sharpness, h, w, out, downscaler, down_antiring))
+                      light_ptr, light_rect, self._cleanup_for(cleanup, out), self._plan_for(h, w, out, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring))
 
     def enqueue_frame_ycbcr10(self, lane, src_ptr, h, w, dst_ptr, *, pix_fmt, matrix=709, full_range=False, stream=None, out_hw=None,
                               out_pix_fmt="rgb48le", out_siting="left", cleanup=None, antiring=0.0, cas=0.0, scaler="lanczos",
@@ -571,7 +485,7 @@ class HDRTVNetMI355X:
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         planes = _ycbcr10_planes(src_ptr, int(h), int(w), pix_fmt, matrix, full_range)
         self._enqueue(lane, self._lib.hdrtv_preprocess_ycbcr10, "hdrtv_preprocess_ycbcr10", planes, h, w, dst_ptr, stream, out,
-                      None, None, self._cleanup_for(cleanup, out), *self._scale_for(antiring, cas, scaler, fsr_sharpness, h, w, out, downscaler, down_antiring))
+                      None, None, self._cleanup_for(cleanup, out), self._plan_for(h, w, out, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring))
 
     def _upload(self, key, src, staged=None):
         """Device pointer of the host u8 array ``src``, uploaded through the staging slot kept per ``key`` in ``_staging``: a
@@ -811,51 +725,22 @@ class HDRTVNetMI355X:
                                  fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
         """RGB48 at the display size: the u16 codes of ``hdrtv_post_rgb48`` (``pq=True``: of
         ``hdrtv_post_pq_rgb48`` at ``peak_nits``) upscaled to ``out_h`` x ``out_w`` by ``hdrtv_post_rgb48_scaled`` in one kernel.
-        ``antiring``: the anti-ringing strength, 0 .. 1, or ``"auto"`` = ``lib.scale_antiring`` of the two sizes; nonzero:
-        ``hdrtv_post_rgb48_scaled_ex``.  ``cas``: the strength of the contrast-adaptive sharpening in front of the upscale, 0 .. 1, or
-        ``"auto"`` = ``lib.scale_cas`` of the two sizes; nonzero: ``hdrtv_post_rgb48_scaled_cas``.  ``scaler="fsr"``: ``hdrtv_post_rgb48_fsr`` instead, the reference's default upscaler, at most 2x
-        per axis (more is a ``ValueError``); ``antiring`` and ``cas`` must then be 0 or ``"auto"`` (which is 0 there); ``fsr_sharpness``:
-        the RCAS sharpness, 0 .. 2 (the reference's 0.2), or None = EASU alone.  ``scaler="spline36"`` / ``"ssim_superres"``:
-        ``hdrtv_post_rgb48_ssimsr`` with ``ssim`` 0 / 1, the reference's third upscaler: both axes enlarged, by at most 2x (anything else
-        but equal sizes is a ``ValueError``), ``antiring`` and ``cas`` 0 or ``"auto"``.  ``downscaler``: None (a size below the processing size is a ``ValueError``, as before),
-        ``"mitchell"`` or ``"ssim"``: ``hdrtv_post_rgb48_down`` shrinks to a size below the processing size, by at most 4x per axis, with
-        the anti-ringing strength ``down_antiring`` (0 .. 1, or ``"auto"`` = the reference's 0.20); ``lib.down_options`` has the refusals
-        (a mixed or larger request, ``scaler="fsr"``, a nonzero ``antiring`` / ``cas``, nothing to shrink).  Returns a new device u16 ``(out_h, out_w, 3)`` tensor; stream-ordered on the current stream,
-        no synchronisation."""
+        The six options after ``peak_nits`` choose another scaler, or one for a size below the processing size (``lib.ScaleOptions``
+        describes them; its ``plan`` has the refusals, each a ``ValueError``).  Returns a new device u16 ``(out_h, out_w, 3)``
+        tensor; stream-ordered on the current stream, no synchronisation."""
         if isinstance(output, (tuple, list)):
             output = output[0]
         if output.dtype not in (torch.float16, torch.float32):
             raise ValueError("postprocess_rgb48_scaled expects an fp16 or fp32 tensor")
         h, w = int(output.shape[-2]), int(output.shape[-1])
         out_w, out_h = int(out_w), int(out_h)
-        down = _L.down_options(downscaler, down_antiring, w, h, out_w, out_h, scaler, antiring, cas)
-        if down is not None:
-            output = output.contiguous()
-            dst = torch.empty((out_h, out_w, 3), dtype=torch.uint16, device=self.device)
-            self._chk(self._lib.hdrtv_post_rgb48_down(self._ctx, self._stream(), output.data_ptr(), _dtype_code(output), h, w, 1 if pq else 0,
-                                                      float(peak_nits), dst.data_ptr(), out_h, out_w, *down), "hdrtv_post_rgb48_down")
-            return dst
-        if out_w < w or out_h < h:
-            raise ValueError(f"output size {out_w}x{out_h} is below the processing size {w}x{h} (enlarging only)")
-        fsr = self._fsr_for(scaler, fsr_sharpness, antiring, cas, h, w, out_h, out_w)
-        ssimsr = None if fsr is not None else self._ssimsr_for(scaler, antiring, cas, h, w, out_h, out_w)
-        other = fsr is not None or ssimsr is not None
-        code = 0 if other else _L.antiring_code(_L.resolve_antiring(antiring, w, h, out_w, out_h))
-        kcas = 0 if other else _L.cas_code(_L.resolve_cas(cas, w, h, out_w, out_h))
+        opts = _L.scale_options(antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
+        # equal sizes: the entry point itself writes the unscaled kernel's bytes (and takes pq, which hdrtv_post_rgb48 does not)
+        plan = opts.plan(w, h, out_w, out_h) or _L.ScalePlan("hdrtv_post_rgb48_scaled", ())
         output = output.contiguous()
         dst = torch.empty((out_h, out_w, 3), dtype=torch.uint16, device=self.device)
-        args = (self._ctx, self._stream(), output.data_ptr(), _dtype_code(output), h, w, 1 if pq else 0, float(peak_nits), dst.data_ptr(),
-                out_h, out_w)
-        if fsr is not None:
-            self._chk(self._lib.hdrtv_post_rgb48_fsr(*args, *fsr), "hdrtv_post_rgb48_fsr")
-        elif ssimsr is not None:
-            self._chk(self._lib.hdrtv_post_rgb48_ssimsr(*args, ssimsr), "hdrtv_post_rgb48_ssimsr")
-        elif kcas:
-            self._chk(self._lib.hdrtv_post_rgb48_scaled_cas(*args, code, kcas), "hdrtv_post_rgb48_scaled_cas")
-        elif code:
-            self._chk(self._lib.hdrtv_post_rgb48_scaled_ex(*args, code), "hdrtv_post_rgb48_scaled_ex")
-        else:
-            self._chk(self._lib.hdrtv_post_rgb48_scaled(*args), "hdrtv_post_rgb48_scaled")
+        self._chk(getattr(self._lib, plan.entry)(self._ctx, self._stream(), output.data_ptr(), _dtype_code(output), h, w, 1 if pq else 0,
+                                                 float(peak_nits), dst.data_ptr(), out_h, out_w, *plan.args), plan.entry)
         return dst
 
     @torch.inference_mode()

@@ -121,6 +121,10 @@ class HostFrame:
 
 
 class HeadlessPipelineWorker:
+    # the six checked scaler options, read from the record they are kept in
+    _antiring, _cas, _scaler, _fsr_sharpness, _downscaler, _down_antiring = (
+        property(lambda self, name=name: getattr(self._scale, name)) for name in _L.ScaleOptions._fields)
+
     def __init__(self, weights_dir, use_hg=True, proc_w=1920, proc_h=1080, hg_weights=None,
                  status_cb=None, buffer_frames=1, out_w=None, out_h=None, out_pix_fmt="rgb48le", out_siting="left",
                  light_stats=False, light_rect=None, deband=False, deband_range=_L.DEBAND_RANGE,
@@ -139,34 +143,13 @@ class HeadlessPipelineWorker:
         # deband / ordered dither of the delivered frames, one lib.OutputCleanup; off: nothing more is launched
         # or allocated and the bytes are those of before.  With light_stats the record describes the debanded codes.
         self._cleanup = _L.output_cleanup(deband, deband_range, deband_threshold, dither, pix_fmt=self._out.pix_fmt)
-        # anti-ringing of an enlarged frame: a strength in [0, 1], or "auto" = lib.scale_antiring of each frame's
-        # processing and delivered size (what the reference hands mpv), so a hot-swap of the processing resolution changes it.  Off
-        # (0.0, the default), or a frame delivered at the processing size: the launches and bytes of before.
-        self._antiring = _L.check_antiring(antiring)
-        # contrast-adaptive sharpening in front of that upscale: a strength in [0, 1], or "auto" = lib.scale_cas of
-        # each frame's two sizes (what the reference appends to its filter chain as cas=), resolved per frame like the anti-ringing.
-        # Off (0.0, the default), or a frame delivered at the processing size: the launches and bytes of before.
-        self._cas = _L.check_cas(cas)
-        # what enlarges a frame: "lanczos" (the default: the fused Lanczos upscale with the two options above), or
-        # "fsr" = hdrtv_post_rgb48_fsr, the reference's default upscaler, at most 2x per axis, with RCAS at fsr_sharpness (0 .. 2, the
-        # reference's 0.2) or, with None, EASU alone.  Under "fsr" antiring and cas are 0 ("auto" resolves to 0, as the reference's
-        # schedules do; an explicit nonzero value is refused).  "spline36" / "ssim_superres" = hdrtv_post_rgb48_ssimsr without / with the
-        # reference's SSimSuperRes shader stage: both axes enlarged, by at most 2x, antiring and cas 0 likewise.  A frame delivered at
-        # the processing size is untouched by any of them.
-        self._scaler = _L.check_scaler(scaler)
-        self._antiring, self._cas = _L.scaler_options(self._scaler, self._antiring, self._cas)
-        self._fsr_sharpness = _L.check_fsr_sharpness(fsr_sharpness)
-        if self._scaler == "fsr":
-            _L.check_fsr_size(self._proc_w, self._proc_h, self._out.w, self._out.h)
-        if self._scaler in _L.SSIMSR_SCALERS:
-            _L.check_ssimsr_size(self._proc_w, self._proc_h, self._out.w, self._out.h)
-        # what shrinks a frame delivered BELOW the processing size: None (the default: such a size is refused, as
-        # before), "mitchell" or "ssim" = hdrtv_post_rgb48_down, at most 4x per axis, with the anti-ringing strength down_antiring
-        # (0 .. 1, or "auto" = the reference's 0.20).  lib.down_options has the refusals: a mixed request, an enlarging scaler option,
-        # a downscaler with nothing to shrink.
-        self._downscaler, self._down_antiring = _L.check_downscaler(downscaler), down_antiring
-        _L.down_options(self._downscaler, self._down_antiring, self._proc_w, self._proc_h, self._out.w, self._out.h, self._scaler,
-                        self._antiring, self._cas)
+        # how a frame delivered at another size than the processing size is resized: one lib.ScaleOptions, which
+        # describes the six options.  "auto" strengths are resolved per frame from its two sizes (_tensor_to_rgb48_bytes), so a
+        # hot-swap of the processing resolution changes them.  The limits of a scaler or downscaler are checked here against the
+        # sizes known now; plain Lanczos has none, and a size below the processing size without a downscaler is refused per frame.
+        self._scale = _L.scale_options(antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
+        if self._scale.scaler != "lanczos" or self._scale.downscaler is not None:
+            self._scale.plan(self._proc_w, self._proc_h, self._out.w, self._out.h)
         # HDR10 content light level: every delivered frame carries its record (``.light``), measured on the
         # device from the codes the sink receives over ``light_rect = (x0, y0, rw, rh)`` in delivered-frame coordinates (None: the
         # whole frame), and ``content_light`` accumulates MaxCLL / MaxFALL in delivery order.  Off: nothing is launched or allocated.
@@ -383,10 +366,8 @@ class HeadlessPipelineWorker:
         return a ``PinnedFrame`` guarded by the slot's ready event.  Ring exhaustion (no slot free
         within 250 ms, feeders.py:166-167) falls back to one blocking pinned buffer as the reference
         does (209-235): convert, copy, synchronise the stream, hand the finished frame over.  ``out_hw = (out_h, out_w)``: the
-        ring, the fallback buffer and the frame are at that size and the conversion is ``hdrtv_post_rgb48_scaled`` (with the
-        worker's ``antiring``, resolved here from the tensor's and the delivered size: ``hdrtv_post_rgb48_scaled_ex``; with its ``cas``, resolved alike:
-        ``hdrtv_post_rgb48_scaled_cas``; with ``scaler="fsr"`` ``hdrtv_post_rgb48_fsr`` does the enlargement, with ``"spline36"`` / ``"ssim_superres"`` ``hdrtv_post_rgb48_ssimsr``; with a ``downscaler`` and a size below the tensor's
-        ``hdrtv_post_rgb48_down`` shrinks).  With a
+        ring, the fallback buffer and the frame are at that size and the conversion is the ``lib.ScalePlan`` of the worker's scaler
+        options for the tensor's and the delivered size (``hdrtv_post_rgb48_scaled`` by default).  With a
         Y'CbCr ``out_pix_fmt`` the slot (an RGB48 slot holds any of the layouts) receives the planes, only the frame's bytes are
         committed (``hdrtv_ring_commit_bytes``) and the frame is a 1-D u16 view of them."""
         p = self._processor
@@ -401,33 +382,21 @@ class HeadlessPipelineWorker:
 
         out = self._out.at(h, w)
         shape = out.shape
-        antiring = _L.antiring_code(_L.resolve_antiring(self._antiring, tw, th, w, h)) if self._antiring else 0
-        cas = _L.cas_code(_L.resolve_cas(self._cas, tw, th, w, h)) if self._cas else 0
-        fsr = None
-        if self._scaler == "fsr" and (h, w) != (th, tw):
-            _L.check_fsr_size(tw, th, w, h)            # a hot-swap of the processing resolution may have moved the ratio past 2x
-            fsr = (0, 0.0) if self._fsr_sharpness is None else (1, self._fsr_sharpness)
-        ssimsr = None
-        if self._scaler in _L.SSIMSR_SCALERS and (h, w) != (th, tw):
-            _L.check_ssimsr_size(tw, th, w, h)         # likewise
-            ssimsr = 1 if self._scaler == "ssim_superres" else 0
-        down = None
-        if self._downscaler is not None and (h, w) != (th, tw):      # hdrtv_post_rgb48_down; a hot-swap may have moved the ratio
-            down = _L.down_options(self._downscaler, self._down_antiring, tw, th, w, h, self._scaler, self._antiring, self._cas)
-            antiring = cas = 0
+        # a hot-swap of the processing resolution may have moved the ratio past a scaler's limit: checked again here
+        scale = self._scale.plan(tw, th, w, h) if (h, w) != (th, tw) else None
 
         def convert(dst, key):
             """The frame into ``dst`` and, when measured, its light level record into the pinned record kept per ``key``, all on
             ``st``: whatever is recorded on ``st`` afterwards (the slot's ready event) covers both.  Returns that record."""
             if not self._light:
-                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, antiring=antiring, cas=cas, fsr=fsr, down=down, ssimsr=ssimsr)
+                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, scale=scale)
                 return None
             bufs = self._light_bufs.get(key)
             if bufs is None:
                 bufs = self._light_bufs[key] = (torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, device=p.device),
                                                 torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, pin_memory=True))
             p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", bufs[0].data_ptr(), self._light_rect,
-                        self._cleanup, antiring, cas, fsr, down, ssimsr)
+                        self._cleanup, scale)
             with torch.cuda.stream(st):
                 bufs[1].copy_(bufs[0], non_blocking=True)
             return bufs[1].numpy()
