@@ -275,6 +275,12 @@ struct hdrtv_ctx {
     // objective metrics partial sums
     double *mt_dev = nullptr;
     size_t mt_cap = 0;
+    // the full-reference chain (hdrtv_full_reference_metrics and its pieces), allocated on first use: the border counts, the six
+    // histograms, the two evaluation frames, and the area tables per (sh, sw, nh, nw)
+    struct FrBuf { void *dev = nullptr; size_t cap = 0; } fr_counts, fr_hist, fr_eval;
+    uint32_t *fr_hist_host = nullptr;     // pinned: the histograms' landing place on the host
+    struct AreaTab { char *dev; size_t o_xbeg, o_ybeg, o_xsrc, o_ysrc, o_xw, o_yw; };
+    std::map<std::array<int, 4>, AreaTab> fr_tabs;
     // ring
     std::vector<hdrtv_host::RingSlot> ring;
     int ring_next = 0, ring_H = 0, ring_W = 0, ring_waiters = 0;   // ring_waiters: threads blocked on a slot's event outside ring_mu

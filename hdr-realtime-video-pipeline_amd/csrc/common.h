@@ -492,4 +492,34 @@ struct MetricsParams {
     int is_f32, H, W;
     float peak_nits;
     double *partials;   // [workgroups][3]
+    // metrics_u16_launch: a, b = u16 [H][W][3] R, G, B codes, `pitch` u16 elements from one row to the next (a crop is an offset
+    // into a wider frame), read as float32(code) / 65535.  norm != 0: a's codes pass through the grade match at load
+    // (include/hdrtv_mi355x.h, R6): gain / bias on the codes for PSNR and SSIM, gain_abs / bias_abs on absolute RGB for dE-ITP.
+    int pitch, norm;
+    float gain[3], bias[3], gain_abs[3], bias_abs[3];
+};
+
+// The full-reference chain in front of the metric kernel (metrics_full.hip; include/hdrtv_mi355x.h states rules R1 .. R6).
+constexpr int FR_SIGNAL_MIN = 132;   // a pixel is signal when max(R, G, B) >= this
+constexpr int FR_MAX_SHRINK = 16;    // the area reduction's largest ratio per axis
+constexpr int FR_STRIP = 64;         // output columns per workgroup of the area reduction
+enum { FR_AREA_2X2 = 0, FR_AREA_INT = 1, FR_AREA_TAB = 2 };
+struct BorderCountsParams {
+    const uint16_t *frame[2];        // u16 [H][W][3]
+    uint32_t *counts;                // u32 [2][H + W]: per frame H row counts, then W column counts; zeroed by the launcher
+    int H, W;
+};
+struct AreaReduceParams {
+    const uint16_t *src[2];          // the rectangle's first pixel in each frame (the crop is this offset); src[1] may be null
+    uint16_t *dst[2];                // u16 [nh][nw][3], contiguous
+    int pitch;                       // u16 elements from one source row to the next
+    int sh, sw, nh, nw, mode, ix, iy;
+    // FR_AREA_TAB: computeResizeAreaTab's runs, as LetterboxParams holds them
+    const int *xbeg, *ybeg, *xsrc, *ysrc;
+    const float *xw, *yw;
+};
+struct ChannelHistParams {
+    const uint16_t *frame[2];        // u16 [H][W][3] with `pitch`
+    uint32_t *hist;                  // u32 [2][3][65536]; zeroed by the launcher
+    int H, W, pitch;
 };

@@ -78,6 +78,10 @@ int hdrtv_destroy(hdrtv_ctx *c)
     for (auto &tabs : c->scale_tabs)
         for (auto &kv : tabs) (void)hipFree(kv.second.dev);
     if (c->mt_dev) (void)hipFree(c->mt_dev);
+    for (hdrtv_ctx::FrBuf *b : {&c->fr_counts, &c->fr_hist, &c->fr_eval})
+        if (b->dev) (void)hipFree(b->dev);
+    for (auto &kv : c->fr_tabs) (void)hipFree(kv.second.dev);
+    if (c->fr_hist_host) (void)hipHostFree(c->fr_hist_host);
     free_workspaces(c);
     if (c->wts.dev) (void)hipFree(c->wts.dev);
     delete c;
@@ -821,12 +825,11 @@ int hdrtv_preprocess_ycbcr10_letterboxed(hdrtv_ctx *c, void *stream, const uint1
 }
 
 // --------------------------------------------------------------------------------- metrics
-int hdrtv_metrics(hdrtv_ctx *c, void *stream, const void *a, const void *b, int dtype, int H, int W, float peak_nits,
-                  double *out3)
+// One launch of the metric kernel (planar tensors or, with u16, RGB48 codes), its partial sums brought back and added in index order
+// -> out3 = {PSNR dB, SSIM, dE-ITP}.  Synchronises `s`.
+static int metrics_run(hdrtv_ctx *c, MetricsParams &p, bool u16, hipStream_t s, double *out3)
 {
-    if (!c || !a || !b || !out3 || H <= 0 || W <= 0 || !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "metrics: bad argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nblk = (size_t)metrics_blocks(H, W);
+    const size_t nblk = (size_t)metrics_blocks(p.H, p.W);
     if (nblk > c->mt_cap) {
         if (c->mt_dev) (void)hipFree(c->mt_dev);
         c->mt_dev = nullptr; c->mt_cap = 0;
@@ -836,21 +839,235 @@ int hdrtv_metrics(hdrtv_ctx *c, void *stream, const void *a, const void *b, int 
         }
         c->mt_cap = nblk;
     }
-    MetricsParams p;
-    p.a = a; p.b = b; p.is_f32 = dtype == HDRTV_F32; p.H = H; p.W = W; p.peak_nits = peak_nits; p.partials = c->mt_dev;
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = metrics_launch(p, s);
+    p.partials = c->mt_dev;
+    hipError_t e = u16 ? metrics_u16_launch(p, s) : metrics_launch(p, s);
     if (e != hipSuccess) return fail(c, HDRTV_EHIP, "metrics: %s", hipGetErrorString(e));
     std::vector<double> host(nblk * 3);
     HIPCHK(c, hipMemcpyAsync(host.data(), c->mt_dev, host.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     double se = 0.0, ss = 0.0, de = 0.0;
     for (size_t i = 0; i < nblk; ++i) { se += host[3 * i]; ss += host[3 * i + 1]; de += host[3 * i + 2]; }
-    const double npx = (double)H * W;
+    const double npx = (double)p.H * p.W;
     const double mse = se / (3.0 * npx);
     out3[0] = mse <= 1e-12 ? 99.0 : 10.0 * std::log10(1.0 / mse);      // _psnr_bgr
     out3[1] = ss / (3.0 * npx);                                         // _ssim_bgr
     out3[2] = de / npx;                                                 // _delta_e_itp
+    return HDRTV_OK;
+}
+
+int hdrtv_metrics(hdrtv_ctx *c, void *stream, const void *a, const void *b, int dtype, int H, int W, float peak_nits,
+                  double *out3)
+{
+    if (!c || !a || !b || !out3 || H <= 0 || W <= 0 || !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "metrics: bad argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    MetricsParams p{};
+    p.a = a; p.b = b; p.is_f32 = dtype == HDRTV_F32; p.H = H; p.W = W; p.peak_nits = peak_nits;
+    return metrics_run(c, p, false, (hipStream_t)stream, out3);
+}
+
+// ------------------------------------------------------------------- full-reference metrics (include/hdrtv_mi355x.h, R1 .. R6)
+static bool fr_ensure(hdrtv_ctx::FrBuf &b, size_t bytes)
+{
+    if (bytes <= b.cap) return true;
+    if (b.dev) (void)hipFree(b.dev);
+    b.dev = nullptr; b.cap = 0;
+    if (hipMalloc(&b.dev, bytes) != hipSuccess) { b.dev = nullptr; return false; }
+    b.cap = bytes;
+    return true;
+}
+
+// R3's case and, for the table path, computeResizeAreaTab's tables (built in double as oracle/letterbox_oracle.area_tab does, kept
+// per geometry); the sizes have passed area_reduce_size_ok
+static int fr_area_setup(hdrtv_ctx *c, const char *what, int sh, int sw, int nh, int nw, AreaReduceParams &p)
+{
+    p.sh = sh; p.sw = sw; p.nh = nh; p.nw = nw; p.ix = p.iy = 0;
+    if (sw % nw == 0 && sh % nh == 0) {
+        p.ix = sw / nw; p.iy = sh / nh;
+        p.mode = p.ix == 2 && p.iy == 2 ? FR_AREA_2X2 : FR_AREA_INT;
+        return HDRTV_OK;
+    }
+    p.mode = FR_AREA_TAB;
+    const std::array<int, 4> key{sh, sw, nh, nw};
+    auto it = c->fr_tabs.find(key);
+    if (it == c->fr_tabs.end()) {
+        std::vector<int> ints;
+        std::vector<float> flts;
+        hdrtv_ctx::AreaTab t{};
+        auto tab = [&](int ssize, int dsize, size_t &o_beg, size_t &o_src, size_t &o_w) {
+            const double sc = ssize / (double)dsize;
+            std::vector<int> beg(dsize + 1), src;
+            std::vector<float> w;
+            for (int dx = 0; dx < dsize; ++dx) {
+                beg[dx] = (int)src.size();
+                const double f1 = dx * sc, f2 = f1 + sc, cell = std::min(sc, ssize - f1);
+                int s1 = (int)std::ceil(f1), s2 = (int)std::floor(f2);
+                s2 = std::min(s2, ssize - 1); s1 = std::min(s1, s2);
+                if (s1 - f1 > 1e-3) { src.push_back(s1 - 1); w.push_back((float)((s1 - f1) / cell)); }
+                for (int q = s1; q < s2; ++q) { src.push_back(q); w.push_back((float)(1.0 / cell)); }
+                if (f2 - s2 > 1e-3) { src.push_back(s2); w.push_back((float)(std::min(std::min(f2 - s2, 1.0), cell) / cell)); }
+            }
+            beg[dsize] = (int)src.size();
+            o_beg = ints.size(); ints.insert(ints.end(), beg.begin(), beg.end());
+            o_src = ints.size(); ints.insert(ints.end(), src.begin(), src.end());
+            o_w = flts.size(); flts.insert(flts.end(), w.begin(), w.end());
+        };
+        tab(sw, nw, t.o_xbeg, t.o_xsrc, t.o_xw);
+        tab(sh, nh, t.o_ybeg, t.o_ysrc, t.o_yw);
+        // a run that is empty or leaves the source would send the kernel outside its segment: refuse the geometry instead
+        for (int axis = 0; axis < 2; ++axis) {
+            const int d = axis ? nh : nw, n = axis ? sh : sw;
+            const int *beg = ints.data() + (axis ? t.o_ybeg : t.o_xbeg), *src = ints.data() + (axis ? t.o_ysrc : t.o_xsrc);
+            for (int i = 0; i < d; ++i) {
+                if (beg[i + 1] <= beg[i]) return fail(c, HDRTV_EINVAL, "%s: empty area run", what);
+                for (int k = beg[i]; k < beg[i + 1]; ++k)
+                    if (src[k] < 0 || src[k] >= n || (k > 0 && k > beg[0] && src[k] < src[k - 1]))
+                        return fail(c, HDRTV_EINVAL, "%s: area run leaves the source", what);
+            }
+        }
+        const size_t bytes = (ints.size() + flts.size()) * 4;
+        if (hipMalloc((void **)&t.dev, bytes) != hipSuccess) return fail(c, HDRTV_ENOMEM, "%s: table allocation failed", what);
+        if (hipMemcpy(t.dev, ints.data(), ints.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(t.dev + ints.size() * 4, flts.data(), flts.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(t.dev);
+            return fail(c, HDRTV_EHIP, "%s: table upload failed", what);
+        }
+        t.o_xw += ints.size(); t.o_yw += ints.size();         // word offsets into the one allocation
+        it = c->fr_tabs.emplace(key, t).first;
+    }
+    const hdrtv_ctx::AreaTab &t = it->second;
+    const int *di = (const int *)t.dev;
+    p.xbeg = di + t.o_xbeg; p.ybeg = di + t.o_ybeg; p.xsrc = di + t.o_xsrc; p.ysrc = di + t.o_ysrc;
+    p.xw = (const float *)di + t.o_xw; p.yw = (const float *)di + t.o_yw;
+    return HDRTV_OK;
+}
+
+int hdrtv_rgb48_border_counts(hdrtv_ctx *c, void *stream, const uint16_t *pred, const uint16_t *ref, int H, int W, uint32_t *counts)
+{
+    if (!c || !pred || !ref || !counts || H <= 0 || W <= 0) return fail(c, HDRTV_EINVAL, "rgb48_border_counts: bad argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    BorderCountsParams p{{pred, ref}, counts, H, W};
+    return launched(c, "rgb48_border_counts", border_counts_launch(p, (hipStream_t)stream));
+}
+
+int hdrtv_rgb48_area_reduce(hdrtv_ctx *c, void *stream, const uint16_t *src, int H, int W, int x0, int y0, int rw, int rh,
+                            uint16_t *dst, int nh, int nw)
+{
+    const char *what = "rgb48_area_reduce";
+    if (!c || !src || !dst || H <= 0 || W <= 0) return fail(c, HDRTV_EINVAL, "%s: bad argument", what);
+    if (x0 < 0 || y0 < 0 || rw < 1 || rh < 1 || x0 > W - rw || y0 > H - rh)
+        return fail(c, HDRTV_EINVAL, "%s: rectangle %dx%d at (%d, %d) leaves the %dx%d frame", what, rw, rh, x0, y0, W, H);
+    if (!area_reduce_size_ok(rh, rw, nh, nw))
+        return fail(c, HDRTV_EINVAL, "%s: %dx%d -> %dx%d is not a shrink of at most %dx per axis", what, rw, rh, nw, nh, FR_MAX_SHRINK);
+    HIPCHK(c, hipSetDevice(c->device));
+    AreaReduceParams p{};
+    if (int rc = fr_area_setup(c, what, rh, rw, nh, nw, p)) return rc;
+    p.src[0] = src + ((size_t)y0 * W + x0) * 3; p.dst[0] = dst; p.pitch = 3 * W;
+    return launched(c, what, area_reduce_launch(p, (hipStream_t)stream));
+}
+
+// the six histograms of two frames read with `pitch`, brought to the host (synchronises) -> R5's gains and biases
+static int fr_grade_match(hdrtv_ctx *c, const char *what, hipStream_t s, const uint16_t *pred, const uint16_t *ref, int H, int W, int pitch,
+                          float peak_nits, float *out12)
+{
+    const size_t bytes = (size_t)6 * 65536 * sizeof(uint32_t);
+    if (!fr_ensure(c->fr_hist, bytes)) return fail(c, HDRTV_ENOMEM, "%s: histogram allocation failed", what);
+    ChannelHistParams p{{pred, ref}, (uint32_t *)c->fr_hist.dev, H, W, pitch};
+    if (int rc = launched(c, what, channel_hist_launch(p, s))) return rc;
+    if (!c->fr_hist_host && hipHostMalloc((void **)&c->fr_hist_host, bytes, hipHostMallocDefault) != hipSuccess) {
+        c->fr_hist_host = nullptr;
+        return fail(c, HDRTV_ENOMEM, "%s: pinned histogram allocation failed", what);
+    }
+    HIPCHK(c, hipMemcpyAsync(c->fr_hist_host, c->fr_hist.dev, bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    grade_match_host(c->fr_hist_host, (double)H * W, peak_nits, out12);
+    return HDRTV_OK;
+}
+
+int hdrtv_rgb48_grade_match(hdrtv_ctx *c, void *stream, const uint16_t *pred, const uint16_t *ref, int H, int W, float peak_nits,
+                            float *out12)
+{
+    if (!c || !pred || !ref || !out12 || H <= 0 || W <= 0 || !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "rgb48_grade_match: bad argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    return fr_grade_match(c, "rgb48_grade_match", (hipStream_t)stream, pred, ref, H, W, 3 * W, peak_nits, out12);
+}
+
+// R1's host half: first / last row and column with signal -> {top, bottom, left, right}, false for "none"
+static bool fr_bounds(const uint32_t *cnt, int H, int W, int b[4])
+{
+    const uint32_t min_row = (uint32_t)std::max(4, (int)std::nearbyint(W * 0.01));      // Python round(): half to even
+    const uint32_t min_col = (uint32_t)std::max(4, (int)std::nearbyint(H * 0.01));
+    int top = -1, bottom = -1, left = -1, right = -1;
+    for (int y = 0; y < H; ++y)
+        if (cnt[y] >= min_row) { if (top < 0) top = y; bottom = y + 1; }
+    for (int x = 0; x < W; ++x)
+        if (cnt[H + x] >= min_col) { if (left < 0) left = x; right = x + 1; }
+    if (top < 0 || left < 0 || bottom - top < 2 || right - left < 2) return false;
+    b[0] = top; b[1] = bottom; b[2] = left; b[3] = right;
+    return true;
+}
+
+int hdrtv_full_reference_metrics(hdrtv_ctx *c, void *stream, const uint16_t *pred, const uint16_t *ref, int H, int W, int max_side,
+                                 float peak_nits, int flags, double *out6, int *info)
+{
+    const char *what = "full_reference_metrics";
+    if (!c || !pred || !ref || !out6 || !info || H <= 0 || W <= 0 || max_side < 2 || !(peak_nits > 0.f) ||
+        (flags & ~(HDRTV_FR_CROP | HDRTV_FR_NORMALIZED)))
+        return fail(c, HDRTV_EINVAL, "%s: bad argument", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    int b[4] = {0, H, 0, W};
+    if (flags & HDRTV_FR_CROP) {
+        const size_t words = (size_t)2 * (H + W);
+        if (!fr_ensure(c->fr_counts, words * sizeof(uint32_t))) return fail(c, HDRTV_ENOMEM, "%s: allocation failed", what);
+        BorderCountsParams bp{{pred, ref}, (uint32_t *)c->fr_counts.dev, H, W};
+        if (int rc = launched(c, what, border_counts_launch(bp, s))) return rc;
+        std::vector<uint32_t> cnt(words);
+        HIPCHK(c, hipMemcpyAsync(cnt.data(), c->fr_counts.dev, words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        int bp_[4], br_[4], r[4];
+        const bool hp = fr_bounds(cnt.data(), H, W, bp_), hr = fr_bounds(cnt.data() + H + W, H, W, br_);
+        if (hp || hr) {
+            if (hp && hr) { r[0] = std::max(bp_[0], br_[0]); r[1] = std::min(bp_[1], br_[1]); r[2] = std::max(bp_[2], br_[2]); r[3] = std::min(bp_[3], br_[3]); }
+            else memcpy(r, hp ? bp_ : br_, sizeof r);
+            const int margin = std::max(std::max(r[0], H - r[1]), std::max(r[2], W - r[3]));
+            if (margin >= 8 && r[1] - r[0] >= 2 && r[3] - r[2] >= 2) memcpy(b, r, sizeof b);
+        }
+    }
+    const int h = b[1] - b[0], w = b[3] - b[2];
+    int nh = h, nw = w;
+    if (std::max(h, w) > max_side) {                                                     // R2
+        const double scale = (double)max_side / (double)std::max(h, w);
+        nw = std::max(2, (int)std::nearbyint(w * scale));
+        nh = std::max(2, (int)std::nearbyint(h * scale));
+    }
+    const uint16_t *ep = pred + ((size_t)b[0] * W + b[2]) * 3, *er = ref + ((size_t)b[0] * W + b[2]) * 3;
+    int pitch = 3 * W;
+    if (nh != h || nw != w) {
+        if (!area_reduce_size_ok(h, w, nh, nw))
+            return fail(c, HDRTV_EINVAL, "%s: %dx%d -> %dx%d is not a shrink of at most %dx per axis", what, w, h, nw, nh, FR_MAX_SHRINK);
+        const size_t frame = ((size_t)nh * nw * 3 * sizeof(uint16_t) + 255) & ~(size_t)255;
+        if (!fr_ensure(c->fr_eval, 2 * frame)) return fail(c, HDRTV_ENOMEM, "%s: allocation failed", what);
+        AreaReduceParams ap{};
+        if (int rc = fr_area_setup(c, what, h, w, nh, nw, ap)) return rc;
+        ap.src[0] = ep; ap.src[1] = er; ap.pitch = pitch;
+        ap.dst[0] = (uint16_t *)c->fr_eval.dev; ap.dst[1] = (uint16_t *)((char *)c->fr_eval.dev + frame);
+        if (int rc = launched(c, what, area_reduce_launch(ap, s))) return rc;
+        ep = ap.dst[0]; er = ap.dst[1]; pitch = 3 * nw;
+    }
+    MetricsParams p{};
+    p.a = ep; p.b = er; p.H = nh; p.W = nw; p.pitch = pitch; p.peak_nits = peak_nits;
+    double out[6] = {0, 0, 0, 0, 0, 0};
+    if (int rc = metrics_run(c, p, true, s, out)) return rc;                             // R4
+    if (flags & HDRTV_FR_NORMALIZED) {
+        float g[12];
+        if (int rc = fr_grade_match(c, what, s, ep, er, nh, nw, pitch, peak_nits, g)) return rc;      // R5
+        p.norm = 1;
+        for (int k = 0; k < 3; ++k) { p.gain[k] = g[k]; p.bias[k] = g[3 + k]; p.gain_abs[k] = g[6 + k]; p.bias_abs[k] = g[9 + k]; }
+        if (int rc = metrics_run(c, p, true, s, out + 3)) return rc;                     // R6
+    }
+    memcpy(out6, out, sizeof out);
+    memcpy(info, b, sizeof b);
+    info[4] = nh; info[5] = nw;
     return HDRTV_OK;
 }
 

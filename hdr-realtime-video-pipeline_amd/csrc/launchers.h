@@ -174,6 +174,17 @@ hipError_t light_stats_launch(const LightStatsParams &p, int is_f32, int pq, int
 hipError_t rgb48_light_stats_launch(const LightStatsParams &p, int max_wgs, hipStream_t s);
 hipError_t metrics_launch(const MetricsParams &p, hipStream_t s);
 int metrics_blocks(int H, int W);
+// the same kernel on two u16 [H][W][3] RGB48 frames through its CodeLoad policy (p.pitch, p.norm and the gains; R4 / R6 of
+// include/hdrtv_mi355x.h); hipErrorInvalidValue, nothing enqueued, unless H, W >= 1 and pitch >= 3 W
+hipError_t metrics_u16_launch(const MetricsParams &p, hipStream_t s);
+// the full-reference chain (metrics_full.hip).  Each launcher returns hipErrorInvalidValue with nothing enqueued for a null pointer
+// or a size its kernel does not take; border_counts_launch and channel_hist_launch zero their record on `s` first
+hipError_t border_counts_launch(const BorderCountsParams &p, hipStream_t s);
+bool area_reduce_size_ok(int sh, int sw, int nh, int nw);     // 1 <= nh <= sh <= FR_MAX_SHRINK nh, likewise the widths
+hipError_t area_reduce_launch(const AreaReduceParams &p, hipStream_t s);
+hipError_t channel_hist_launch(const ChannelHistParams &p, hipStream_t s);
+// host side of R5: hist u32 [2][3][65536] of n samples each -> gain[3], bias[3], gain_abs[3], bias_abs[3] as float32
+void grade_match_host(const uint32_t *hist, double n, float peak_nits, float *out12);
 
 // precision="fp32" (fp32_ops.hip)
 hipError_t conv_f32_launch(const F32ConvParams &p, int ks, int stride, int n_cu, hipStream_t s);

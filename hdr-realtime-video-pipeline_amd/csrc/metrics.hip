@@ -3,6 +3,9 @@
 // [3][H][W] (R, G, B planes; f16 or f32) -- src/gui_objective_metrics.py:438-528 as restated in
 // oracle/metrics_oracle.py (parity unpinned: that module needs cv2).  One 16x16-pixel tile per workgroup,
 // per-workgroup fp64 partial sums, summed in index order on the host: results are reproducible bit for bit.
+// A load policy says where the two images come from: PlanarLoad<T> is the above; CodeLoad<NORM> reads two interleaved
+// u16 [H][W][3] RGB48 frames as float32(code) / 65535 (the full-reference chain, include/hdrtv_mi355x.h R4), and with NORM
+// passes the first frame's codes through the grade match while it loads them (R6): no normalised frame exists in memory.
 #include "launchers.h"
 
 namespace {
@@ -40,7 +43,53 @@ __device__ __forceinline__ void to_itp(const float rgb[3], float out[3])
     out[2] = (17933.0f * lp - 17390.0f * mp - 543.0f * sp) / 4096.0f;
 }
 
+// x * g + b as two float32 operations: the empty asm keeps the backend from contracting them into one FMA, which
+// -ffp-contract=fast (this file's setting, and what the planar instantiations' bits depend on) would otherwise do
+__device__ __forceinline__ float mul_then_add(float x, float g, float b)
+{
+    float t = x * g;
+    asm volatile("" : "+v"(t));
+    return t + b;
+}
+
+__device__ __forceinline__ float pick3(const float (&v)[3], int c) { return c == 0 ? v[0] : (c == 1 ? v[1] : v[2]); }
+
 template <typename T>
+struct PlanarLoad {
+    static constexpr bool NORM = false;
+    static __device__ __forceinline__ void load(const MetricsParams &p, int c, int y, int x, float &a, float &b)
+    {
+        const size_t idx = c * ((size_t)p.H * p.W) + (size_t)y * p.W + x;
+        a = ld<T>(p.a, idx);
+        b = ld<T>(p.b, idx);
+    }
+};
+
+template <bool NORM_>
+struct CodeLoad {
+    static constexpr bool NORM = NORM_;
+    static __device__ __forceinline__ void load(const MetricsParams &p, int c, int y, int x, float &a, float &b)
+    {
+        const size_t idx = (size_t)y * p.pitch + (size_t)x * 3 + c;
+        float fa = (float)reinterpret_cast<const uint16_t *>(p.a)[idx];
+        if (NORM)          // trunc(clip(code * gain + bias, 0, 65535)): the reference's .astype(uint16)
+            fa = (float)(int)fminf(fmaxf(mul_then_add(fa, pick3(p.gain, c), pick3(p.bias, c)), 0.f), 65535.f);
+        a = fa / 65535.0f;
+        b = (float)reinterpret_cast<const uint16_t *>(p.b)[idx] / 65535.0f;
+    }
+    // the first frame's absolute RGB after the grade match in cd/m^2, from its raw codes
+    static __device__ __forceinline__ void abs_norm(const MetricsParams &p, int y, int x, float out[3])
+    {
+        const uint16_t *px = reinterpret_cast<const uint16_t *>(p.a) + (size_t)y * p.pitch + (size_t)x * 3;
+        const float peak = fmaxf(1.0f, p.peak_nits);
+        for (int c = 0; c < 3; ++c) {
+            const float v = fminf(fmaxf((float)px[c] / 65535.0f, 0.f), 1.f) * p.peak_nits;
+            out[c] = fminf(fmaxf(mul_then_add(v, p.gain_abs[c], p.bias_abs[c]), 0.f), peak);
+        }
+    }
+};
+
+template <typename LD>
 __global__ __launch_bounds__(256) void metrics_kernel(MetricsParams p)
 {
     __shared__ float s_a[HT][HT + 1], s_b[HT][HT + 1];
@@ -50,16 +99,13 @@ __global__ __launch_bounds__(256) void metrics_kernel(MetricsParams p)
     const int x0 = blockIdx.x * MT, y0 = blockIdx.y * MT;
     const int x = x0 + tx, y = y0 + ty;
     const bool in = x < p.W && y < p.H;
-    const size_t plane = (size_t)p.H * p.W;
     double se = 0.0, ss = 0.0, de = 0.0;
     float ca[3], cb[3];
     for (int c = 0; c < 3; ++c) {
         __syncthreads();
         for (int e = tid; e < HT * HT; e += 256) {
             const int r = e / HT, q = e % HT;
-            const size_t idx = c * plane + (size_t)reflect101(y0 - R + r, p.H) * p.W + reflect101(x0 - R + q, p.W);
-            s_a[r][q] = ld<T>(p.a, idx);
-            s_b[r][q] = ld<T>(p.b, idx);
+            LD::load(p, c, reflect101(y0 - R + r, p.H), reflect101(x0 - R + q, p.W), s_a[r][q], s_b[r][q]);
         }
         __syncthreads();
         for (int e = tid; e < HT * MT; e += 256) {
@@ -94,6 +140,7 @@ __global__ __launch_bounds__(256) void metrics_kernel(MetricsParams p)
             ra[c] = fminf(fmaxf(ca[c], 0.f), 1.f) * p.peak_nits;
             rb[c] = fminf(fmaxf(cb[c], 0.f), 1.f) * p.peak_nits;
         }
+        if constexpr (LD::NORM) LD::abs_norm(p, y, x, ra);
         to_itp(ra, ia);
         to_itp(rb, ib);
         const float di = ia[0] - ib[0], dt = ia[1] - ib[1], dp = ia[2] - ib[2];
@@ -116,7 +163,7 @@ __global__ __launch_bounds__(256) void metrics_kernel(MetricsParams p)
 
 int metrics_blocks(int H, int W) { return ((W + MT - 1) / MT) * ((H + MT - 1) / MT); }
 
-hipError_t metrics_launch(const MetricsParams &p, hipStream_t s)
+static hipError_t gauss_init()
 {
     static bool init = false;
     if (!init) {
@@ -128,8 +175,24 @@ hipError_t metrics_launch(const MetricsParams &p, hipStream_t s)
         if (e != hipSuccess) return e;
         init = true;
     }
+    return hipSuccess;
+}
+
+hipError_t metrics_launch(const MetricsParams &p, hipStream_t s)
+{
+    if (hipError_t e = gauss_init(); e != hipSuccess) return e;
     const dim3 grid((p.W + MT - 1) / MT, (p.H + MT - 1) / MT);
-    if (p.is_f32) hipLaunchKernelGGL(metrics_kernel<float>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(metrics_kernel<f16>, grid, dim3(256), 0, s, p);
+    if (p.is_f32) hipLaunchKernelGGL(metrics_kernel<PlanarLoad<float>>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(metrics_kernel<PlanarLoad<f16>>, grid, dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t metrics_u16_launch(const MetricsParams &p, hipStream_t s)
+{
+    if (p.H < 1 || p.W < 1 || p.pitch < 3 * p.W) return hipErrorInvalidValue;
+    if (hipError_t e = gauss_init(); e != hipSuccess) return e;
+    const dim3 grid((p.W + MT - 1) / MT, (p.H + MT - 1) / MT);
+    if (p.norm) hipLaunchKernelGGL(metrics_kernel<CodeLoad<true>>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(metrics_kernel<CodeLoad<false>>, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }

@@ -24,6 +24,11 @@ SITING_LEFT, SITING_TOPLEFT = 0, 1
 DITHER_NONE, DITHER_ORDERED = 0, 1         # hdrtv_post_ycbcr10_ex / hdrtv_rgb48_to_ycbcr10_ex
 DEBAND_RANGE_MAX, DEBAND_RANGE, DEBAND_THRESHOLD = 16, 16, 1311     # hdrtv_rgb48_deband: the largest range and the defaults
 LIGHT_BINS, LIGHT_WORDS = 4096, 4104       # hdrtv_light_stats / hdrtv_rgb48_light_stats: the record, u32 words (lightlevel.py reads it)
+FR_CROP, FR_NORMALIZED = 1, 2              # hdrtv_full_reference_metrics flags
+FR_MAX_SIDE, FR_MAX_SHRINK = 512, 16       # the reference's evaluation size (_OBJECTIVE_METRIC_MAX_SIDE); the area reduction's largest ratio
+# _compute_full_reference_metrics' obj_note (gui_objective_metrics.py:659-664), without / with its crop suffix
+FR_NOTE = ("Computed (raw + normalized; PSNR/SSIM linear, DeltaEITP/HDR-VDP3 color-managed; DeltaEITP-N normalized pre-PQ{})")
+FR_NOTE_CROPPED = "; shared black borders cropped"
 
 # every symbol include/hdrtv_mi355x.h declares: (name, restype, argtypes)
 _VP, _I, _SZ = C.c_void_p, C.c_int, C.c_size_t
@@ -66,6 +71,10 @@ SYMBOLS = [
     ("hdrtv_letterbox_ycbcr10", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I, _I]),
     ("hdrtv_preprocess_ycbcr10_letterboxed", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP]),
     ("hdrtv_metrics", _I, [_VP, _VP, _VP, _VP, _I, _I, _I, C.c_float, C.POINTER(C.c_double)]),
+    ("hdrtv_full_reference_metrics", _I, [_VP, _VP, _VP, _VP, _I, _I, _I, C.c_float, _I, C.POINTER(C.c_double), C.POINTER(_I)]),
+    ("hdrtv_rgb48_border_counts", _I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
+    ("hdrtv_rgb48_area_reduce", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I, _I]),
+    ("hdrtv_rgb48_grade_match", _I, [_VP, _VP, _VP, _VP, _I, _I, C.c_float, C.POINTER(C.c_float)]),
     ("hdrtv_ring_create", _I, [_VP, _I, _I, _I]),
     ("hdrtv_ring_acquire", _I, [_VP, _I, C.POINTER(_VP), C.POINTER(_VP)]),
     ("hdrtv_ring_commit", _I, [_VP, _I, _VP]),

@@ -343,6 +343,31 @@ class CsvLogger:
 
 
 # ------------------------------------------------------------------------------- the loop
+OBJECTIVE_MODES = ("tensor", "reference")
+
+
+class Rgb48leSource:
+    """Ground-truth frames for ``RealtimePlayback(objective_mode="reference")``: a headerless little-endian ``rgb48le`` rawvideo file
+    at the delivered size, memory-mapped; ``read()`` yields u16 ``(H, W, 3)`` frames."""
+
+    def __init__(self, path, width, height):
+        self.width, self.height = int(width), int(height)
+        fb = self.width * self.height * 6
+        size = os.path.getsize(path)
+        if fb <= 0 or size < fb or size % fb:
+            raise ValueError(f"{path}: size {size} is not a whole number of {self.width}x{self.height} rgb48le frames")
+        self.frame_count = size // fb
+        self._mm = np.memmap(path, dtype=np.dtype("<u2"), mode="r", shape=(self.frame_count, self.height, self.width, 3))
+        self._i = 0
+
+    def read(self):
+        if self._i >= self.frame_count:
+            return False, None
+        f = np.ascontiguousarray(self._mm[self._i]).astype(np.uint16, copy=False)
+        self._i += 1
+        return True, f
+
+
 class RealtimePlayback:
     """The worker's ``run()`` loop for a file-like source (not live capture), headless.
 
@@ -352,7 +377,7 @@ class RealtimePlayback:
 
     def __init__(self, worker, source, *, sink=True, frame_stride=1, realtime=True, metrics_cb=None, csv_path=None,
                  metrics_interval_s=0.20, metrics_window=120, clock=time.perf_counter, sleep=None, status_cb=None,
-                 gt_source=None, objective_every=10, letterbox=False):
+                 gt_source=None, objective_every=10, letterbox=False, objective_mode="tensor"):
         self.w, self.source = worker, source
         self.sink = sink
         self.frame_stride = max(1, int(frame_stride))
@@ -366,6 +391,13 @@ class RealtimePlayback:
         # optional ground-truth HDR frames ([3,H,W] or [1,3,H,W] unit-range tensors from ``gt_source.read()``): every
         # ``objective_every``-th processed frame is scored on the device (gui_pipeline_worker_objective.py role)
         self.gt_source, self.objective_every = gt_source, max(1, int(objective_every))
+        # ``objective_mode``: "tensor" scores the model's float tensor at the processing size (``objective_metrics``); "reference"
+        # scores what the reference's live path scores (gui_pipeline_worker_objective.py:60-73): the delivered RGB48 codes against
+        # u16 ``(H, W, 3)`` ground-truth frames at the delivered size, both area-reduced to 512 on the longer side
+        # (``full_reference_metrics(crop=False, normalized=False)``)
+        if objective_mode not in OBJECTIVE_MODES:
+            raise ValueError(f"objective_mode must be one of {list(OBJECTIVE_MODES)} (got {objective_mode!r})")
+        self.objective_mode = objective_mode
         # a 4:2:0 source (RawVideoSource pix_fmt yuv420p / nv12): the worker converts its 2-D frames on the device.  ``letterbox``: a
         # 10-bit source of another size than the processing size is letterboxed there too (the worker's opt-in; bgr24, yuv420p and
         # nv12 frames are letterboxed without it)
@@ -489,7 +521,11 @@ class RealtimePlayback:
             if self.gt_source is not None:
                 ok_gt, gt = self.gt_source.read()
                 if ok_gt and prepared is not None and (self.frames_processed % self.objective_every) == 0:
-                    self._objective = w._processor.objective_metrics(prepared, gt)
+                    if self.objective_mode == "reference":
+                        self._objective = w._processor.full_reference_metrics(self._delivered_rgb48(prepared), gt, crop=False,
+                                                                              normalized=False)
+                    else:
+                        self._objective = w._processor.objective_metrics(prepared, gt)
             t1 = self._clock()
             next_frame_t += frame_interval_s
             frame_ms = (t1 - t0) * 1000.0
@@ -529,6 +565,18 @@ class RealtimePlayback:
                 "catchup_dropped_frames": self.realtime_drop_frames,
                 "fps_limiter_dropped_frames": self.fps_limiter_dropped_frames,
                 "fps": (self.frames_processed / elapsed) if elapsed > 0 else 0.0, "last_metrics": self.last_metrics}
+
+    def _delivered_rgb48(self, prepared):
+        """The RGB48 codes the sink receives for ``prepared``, as a device tensor: the worker's delivered size and scaler options
+        through the processor's own conversion (the bytes the feeder's ring slot gets, before any deband).  A worker delivering
+        10-bit Y'CbCr has no RGB48 frame to score."""
+        t = prepared[0] if isinstance(prepared, (tuple, list)) else prepared
+        out = getattr(self.w, "_out", None)
+        if out is not None and not out.is_rgb48:
+            raise ValueError(f"objective_mode='reference' scores RGB48 codes: the worker delivers {out.pix_fmt}")
+        oh, ow = (out.h, out.w) if out is not None else (int(t.shape[-2]), int(t.shape[-1]))
+        opts = getattr(self.w, "_scale", _lib.SCALE_OFF)
+        return self.w._processor.postprocess_rgb48_scaled(t, ow, oh, **opts._asdict())
 
     def _emit_metrics(self, frame_idx, frame_times, model_times, presented_times, fps_samples, proc_w, proc_h):
         avg = sum(frame_times) / len(frame_times)
@@ -636,7 +684,22 @@ def parse_args(argv=None):
     ap.add_argument("--no-prefetch", action="store_true", help="copy each frame into pinned memory on the processing thread, as the reference does")
     ap.add_argument("--stride", type=int, default=1)
     ap.add_argument("--csv")
+    ap.add_argument("--gt", metavar="PATH", help="ground-truth frames for --objective-mode reference: rgb48le rawvideo at the delivered "
+                    "size (--out-size), one frame per source frame")
+    ap.add_argument("--objective-every", type=int, default=6, help="score every N-th processed frame against --gt (the reference "
+                    "samples every sixth)")
+    ap.add_argument("--objective-mode", choices=OBJECTIVE_MODES, default="tensor", help="what the objective metrics score: tensor (the "
+                    "model's float tensor at the processing size) or reference (the delivered RGB48 codes against --gt, both "
+                    "area-reduced to 512 on the longer side, as the reference's live path reports them)")
     a = ap.parse_args(argv)
+    if a.objective_mode == "reference" and not a.gt:
+        ap.error("--objective-mode reference needs --gt")
+    if a.gt and a.objective_mode != "reference":
+        ap.error("--gt holds RGB48 frames: it goes with --objective-mode reference")
+    if a.gt and a.out_pix_fmt != "rgb48le":
+        ap.error("--objective-mode reference scores RGB48 codes: --out-pix-fmt must be rgb48le")
+    if a.objective_every < 1:
+        ap.error("--objective-every must be at least 1")
     wd, ht = (int(v) for v in a.size.lower().split("x", 1))
     owd, oht = (int(v) for v in a.out_size.lower().split("x", 1)) if a.out_size else (wd, ht)
     try:
@@ -736,7 +799,8 @@ def main(argv=None):
         sink = RawVideoSink(a.out, owd, oht, a.fps, a.out_pix_fmt, a.out_siting)      # the sink, mpv_args() and ffmpeg_input_args() speak of the output size
         worker._start_hdr_feeder(sink)
     pb = RealtimePlayback(worker, src, sink=bool(sink), frame_stride=a.stride, realtime=not a.max_throughput, csv_path=a.csv,
-                          letterbox=a.src_wh != a.proc_wh)
+                          letterbox=a.src_wh != a.proc_wh, gt_source=Rgb48leSource(a.gt, owd, oht) if a.gt else None,
+                          objective_every=a.objective_every, objective_mode=a.objective_mode)
     res = pb.run(max_frames=a.frames)
     if sink:
         deadline = time.perf_counter() + 5.0
@@ -749,6 +813,8 @@ def main(argv=None):
     worker.close()
     lm = res.pop("last_metrics") or {}
     res.update({k: lm.get(k) for k in ("latency_ms", "model_latency_ms", "fps_1p_low", "proc_res", "precision")})
+    if a.gt:
+        res.update({k: lm.get(k) for k in ("psnr_db", "sssim", "delta_e_itp")})
     if a.src_wh != a.proc_wh:
         res["src_res"] = f"{swd}x{sht}"
     if a.out_size:

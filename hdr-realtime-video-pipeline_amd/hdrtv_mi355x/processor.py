@@ -704,6 +704,82 @@ class HDRTVNetMI355X:
                   "hdrtv_metrics")
         return {"psnr_db": float(out[0]), "sssim": float(out[1]), "delta_e_itp": float(out[2])}
 
+    def _rgb48_on_device(self, frame, what):
+        """A u16 ``(H, W, 3)`` RGB48 frame (device tensor, host tensor or numpy array) as a contiguous device tensor."""
+        if not isinstance(frame, torch.Tensor):
+            frame = torch.from_numpy(np.ascontiguousarray(frame))
+        if frame.dtype != torch.uint16 or frame.ndim != 3 or frame.shape[2] != 3 or frame.shape[0] < 1 or frame.shape[1] < 1:
+            raise ValueError(f"{what} expects uint16 (H, W, 3) frames of RGB48 codes")
+        return frame.to(self.device).contiguous()
+
+    @torch.inference_mode()
+    def full_reference_metrics(self, pred_u16, ref_u16, max_side=_L.FR_MAX_SIDE, peak_nits=1000.0, crop=True, normalized=True):
+        """The metrics the reference's compare dialog, session log and quality benchmark report (``_compute_full_reference_metrics``,
+        gui_objective_metrics.py:617-677), between two RGB48 frames u16 ``(H, W, 3)`` of the same size -- the delivered codes and a
+        ground truth the caller has brought to that size: shared black borders cropped (``crop``), both frames reduced with
+        INTER_AREA until the longer side is ``max_side``, the three metrics on the u16 codes, and (``normalized``) the three again
+        after the prediction's per-channel mean and standard deviation are matched to the ground truth's.  All of it on the device
+        (``hdrtv_full_reference_metrics``; include/hdrtv_mi355x.h states the rules).  ``crop=False, normalized=False`` is the
+        reference's live path (gui_pipeline_worker_objective.py:60-73).  Returns a dict with the reference's keys (``psnr_db``,
+        ``sssim``, ``delta_e_itp``, ``psnr_norm_db``, ``sssim_norm``, ``delta_e_itp_norm``: the last three ``None`` without
+        ``normalized``), its ``obj_note``, and ``crop_rect`` = (top, bottom, left, right) and ``eval_size`` = (h, w).
+        Synchronises the current stream."""
+        a = self._rgb48_on_device(pred_u16, "full_reference_metrics")
+        b = self._rgb48_on_device(ref_u16, "full_reference_metrics")
+        if a.shape != b.shape:
+            raise ValueError("full_reference_metrics expects two frames of the same size")
+        h, w = int(a.shape[0]), int(a.shape[1])
+        flags = (_L.FR_CROP if crop else 0) | (_L.FR_NORMALIZED if normalized else 0)
+        out, info = (C.c_double * 6)(), (C.c_int * 6)()
+        self._chk(self._lib.hdrtv_full_reference_metrics(self._ctx, self._stream(), a.data_ptr(), b.data_ptr(), h, w, int(max_side),
+                                                         float(peak_nits), flags, out, info), "hdrtv_full_reference_metrics")
+        rect = tuple(int(v) for v in info[:4])
+        norm = [float(v) for v in out[3:6]] if normalized else [None] * 3
+        return {"psnr_db": float(out[0]), "sssim": float(out[1]), "delta_e_itp": float(out[2]),
+                "psnr_norm_db": norm[0], "sssim_norm": norm[1], "delta_e_itp_norm": norm[2],
+                "obj_note": _L.FR_NOTE.format(_L.FR_NOTE_CROPPED if rect != (0, h, 0, w) else ""),
+                "crop_rect": rect, "eval_size": (int(info[4]), int(info[5]))}
+
+    @torch.inference_mode()
+    def rgb48_border_counts(self, pred_u16, ref_u16):
+        """``hdrtv_rgb48_border_counts``: a device u32-as-int32 ``(2, H + W)`` tensor, per frame the signal pixels (max(R, G, B) >= 132)
+        of each row, then of each column.  Stream-ordered, no synchronisation."""
+        a, b = self._rgb48_on_device(pred_u16, "rgb48_border_counts"), self._rgb48_on_device(ref_u16, "rgb48_border_counts")
+        if a.shape != b.shape:
+            raise ValueError("rgb48_border_counts expects two frames of the same size")
+        h, w = int(a.shape[0]), int(a.shape[1])
+        counts = torch.empty((2, h + w), dtype=torch.int32, device=self.device)
+        self._chk(self._lib.hdrtv_rgb48_border_counts(self._ctx, self._stream(), a.data_ptr(), b.data_ptr(), h, w, counts.data_ptr()),
+                  "hdrtv_rgb48_border_counts")
+        return counts
+
+    @torch.inference_mode()
+    def rgb48_area_reduce(self, src_u16, out_w, out_h, rect=None):
+        """``hdrtv_rgb48_area_reduce``: the rows [top, bottom) and columns [left, right) of ``rect`` (default: the whole frame) of a
+        u16 ``(H, W, 3)`` frame reduced to ``out_h`` x ``out_w`` with the 16-bit INTER_AREA rule, at most 16x per axis.  Returns a
+        new device u16 tensor; stream-ordered, no synchronisation."""
+        src = self._rgb48_on_device(src_u16, "rgb48_area_reduce")
+        h, w = int(src.shape[0]), int(src.shape[1])
+        top, bottom, left, right = (0, h, 0, w) if rect is None else (int(v) for v in rect)
+        out_w, out_h = int(out_w), int(out_h)
+        dst = torch.empty((max(out_h, 1), max(out_w, 1), 3), dtype=torch.uint16, device=self.device)
+        self._chk(self._lib.hdrtv_rgb48_area_reduce(self._ctx, self._stream(), src.data_ptr(), h, w, left, top, right - left, bottom - top,
+                                                    dst.data_ptr(), out_h, out_w), "hdrtv_rgb48_area_reduce")
+        return dst
+
+    @torch.inference_mode()
+    def rgb48_grade_match(self, pred_u16, ref_u16, peak_nits=1000.0):
+        """``hdrtv_rgb48_grade_match``: the gains and biases that match the prediction's per-channel mean and standard deviation to the
+        ground truth's, from exact histograms -> a float32 numpy array [12]: gain[3], bias[3] on the codes, gain[3], bias[3] on
+        absolute RGB.  Synchronises the current stream."""
+        a, b = self._rgb48_on_device(pred_u16, "rgb48_grade_match"), self._rgb48_on_device(ref_u16, "rgb48_grade_match")
+        if a.shape != b.shape:
+            raise ValueError("rgb48_grade_match expects two frames of the same size")
+        out = (C.c_float * 12)()
+        self._chk(self._lib.hdrtv_rgb48_grade_match(self._ctx, self._stream(), a.data_ptr(), b.data_ptr(), int(a.shape[0]), int(a.shape[1]),
+                                                    float(peak_nits), out), "hdrtv_rgb48_grade_match")
+        return np.array(list(out), dtype=np.float32)
+
     @torch.inference_mode()
     def postprocess(self, output):
         """hdrtvnet_torch.py:2351-2368.  Returns a zero-copy view of processor-owned pinned memory."""

@@ -617,6 +617,62 @@ int hdrtv_preprocess_ycbcr10_letterboxed(hdrtv_ctx *ctx, void *stream, const uin
 int hdrtv_metrics(hdrtv_ctx *ctx, void *stream, const void *dev_a, const void *dev_b, int dtype, int H, int W,
                   float peak_nits, double *out3);
 
+/* Full-reference metrics as the reference reports them (_compute_full_reference_metrics, src/gui_objective_metrics.py:617-677; its
+ * live path, gui_pipeline_worker_objective.py:60-73, is the same without CROP and NORMALIZED): between two RGB48 frames in device
+ * memory, u16 [H][W][3] R, G, B -- the codes hdrtv_post_rgb48* writes -- of the same size.  Bringing the ground truth to that size
+ * and layout is the caller's.  Integer stages are rules the device meets bit for bit (tests/metrics_full_ref.py restates them in
+ * numpy); the float stages are hdrtv_metrics' arithmetic.
+ *  R1 (flag HDRTV_FR_CROP) shared border bounds.  A pixel is signal when max(R, G, B) >= 132 (the reference's threshold
+ *     max(2, 65535 * 0.002) = 131.07, compared with >).  hdrtv_rgb48_border_counts writes u32 [2][H + W]: per frame the signal
+ *     pixels of each row, then of each column (the record is zeroed on `stream` first; integer adds only).  On the host, with
+ *     round() Python's (half to even): a row has signal when its count >= max(4, round(0.01 * W)), a column when >=
+ *     max(4, round(0.01 * H)); a frame's bounds are its first and last such row and column, or none when there is none or fewer
+ *     than 2 remain on an axis; both present: the intersection, one: that one, neither: no crop.  The crop applies when the largest
+ *     of the four margins is >= 8 and at least 2 x 2 remains.
+ *  R2 evaluation size.  (h, w) the size after the crop; if max(h, w) > max_side: scale = max_side / max(h, w),
+ *     nw = max(2, round(w * scale)), nh = max(2, round(h * scale)); else the frames are read as they are.  The reference's
+ *     max_side is 512.
+ *  R3 16-bit INTER_AREA, hdrtv_rgb48_area_reduce: the rectangle (x0, y0, rw, rh) of src -> dst u16 [nh][nw][3]; the crop is an
+ *     offset into the source, no cropped copy exists.  It is oracle/letterbox_oracle.resize_area on 16-bit codes:
+ *       both ratios exactly 2: (a + b + c + d + 2) >> 2;
+ *       both ratios another integer: rint(float32(sum) * float32(1 / area)), clipped to 65535;
+ *       anything else (one integer and one fractional axis included): computeResizeAreaTab's float32 weights, built in double;
+ *         horizontal sums buf = buf + s * alpha from 0 in table order, vertically out = beta * buf for the first entry and
+ *         out = out + beta * buf after it, float32 with multiply and add separate; rint (half to even), clipped to 0 .. 65535.
+ *     1 <= nh <= rh <= 16 nh and 1 <= nw <= rw <= 16 nw (7680 -> 512 is 15x; up to 16x an integer block sum stays below 2^24 and
+ *     is the same number in int and in float32); anything else is HDRTV_EINVAL with nothing written.  Parity with OpenCV's own
+ *     16-bit resize is UNPINNED, as for the 8-bit rule: OpenCV is not part of the reference tree.
+ *  R4 raw metrics: hdrtv_metrics' three formulas on float32(code) / 65535.0f (a true division, _to_unit_float), read from the
+ *     interleaved evaluation frames -> out6[0..2].
+ *  R5 (flag HDRTV_FR_NORMALIZED) channel statistics, hdrtv_rgb48_grade_match: six exact histograms (2 frames x 3 channels x 65536
+ *     u32 bins, integer atomics); per histogram of N samples, in float64 and ascending code order,
+ *       mean = sum(h[c] * x_c) / N,  std = sqrt(sum(h[c] * (x_c - mean)^2) / N)
+ *     with x_c = c (codes) or x_c = v(c) = float32(clip(float32(c) / 65535, 0, 1) * peak_nits) (absolute RGB); per channel and
+ *     domain gain = 1 if std_pred < 1e-6 else std_ref / std_pred, bias = mean_ref - gain * mean_pred, both then rounded to
+ *     float32.  out12 = gain[3], bias[3] (codes), gain[3], bias[3] (absolute RGB).  This replaces the reference's float32
+ *     np.mean / np.std, whose pairwise summation order is numpy's own (DESIGN.md has the measured distance).
+ *  R6 normalised metrics -> out6[3..5] (zero without the flag): for PSNR and SSIM the prediction's code becomes
+ *     trunc(clip(float32(code) * gain + bias, 0, 65535)) (float32, multiply and add separate; the reference's .astype(uint16)),
+ *     then R4; for dE-ITP its absolute RGB becomes clip(v * gain + bias, 0, max(1, peak_nits)) with the second pair, before PQ.
+ *     Both happen where the metric kernel loads: one more launch, no normalised frame in memory.
+ * info = {top, bottom, left, right, eval_h, eval_w}: the rows [top, bottom) and columns [left, right) that were scored -- the whole
+ * frame when nothing was cropped -- and the evaluation size.  hdrtv_full_reference_metrics and hdrtv_rgb48_grade_match bring
+ * numbers to the host and synchronise `stream` (the bounds, the histograms and the partial sums each cost a round trip);
+ * hdrtv_rgb48_border_counts and hdrtv_rgb48_area_reduce are stream-ordered.  None needs a reservation; scratch and the area tables
+ * of a geometry are allocated in the context on first use.  HDRTV_EINVAL, with nothing written, for a NULL pointer, a non-positive
+ * size, max_side < 2, peak_nits <= 0, unknown flags, a rectangle that leaves the frame, or a shrink beyond 16x.  Out of scope:
+ * HDR-VDP3, pairing and resizing the ground truth, error bars over a stream. */
+#define HDRTV_FR_CROP 1
+#define HDRTV_FR_NORMALIZED 2
+int hdrtv_full_reference_metrics(hdrtv_ctx *ctx, void *stream, const uint16_t *pred_rgb48, const uint16_t *ref_rgb48, int H, int W,
+                                 int max_side, float peak_nits, int flags, double *out6, int *info);
+int hdrtv_rgb48_border_counts(hdrtv_ctx *ctx, void *stream, const uint16_t *pred_rgb48, const uint16_t *ref_rgb48, int H, int W,
+                              uint32_t *dev_counts);
+int hdrtv_rgb48_area_reduce(hdrtv_ctx *ctx, void *stream, const uint16_t *src_rgb48, int H, int W, int x0, int y0, int rw, int rh,
+                            uint16_t *dst_rgb48, int nh, int nw);
+int hdrtv_rgb48_grade_match(hdrtv_ctx *ctx, void *stream, const uint16_t *pred_rgb48, const uint16_t *ref_rgb48, int H, int W,
+                            float peak_nits, float *out12);
+
 /* ---- pinned host RGB48 ring: replaces _pinned_u16_host_ring / _acquire_pinned_u16_slot /
  * _PinnedMpvFrame (gui_pipeline_worker_feeders.py:38-70, 125-170).  `slots` in [2,8]
  * (HDRTVNET_FEEDER_GPU_RGB48_RING_FRAMES).  A slot cycles free -> acquired -> (kernel writes its device
