@@ -12,7 +12,6 @@
 // Both accumulate in the order (input channel, tap) from zero and add the bias behind the sum.
 #include "common.h"
 #include "launchers.h"
-#include "yuv420.h"
 
 namespace {
 
@@ -514,20 +513,16 @@ hipError_t hg_blend_f32_launch(const float *t, const float *img, const float *ma
     return hipGetLastError();
 }
 
-hipError_t pre_f32_launch(const uint8_t *bgr, float *rgb, float *cond, int H, int W, int Ho, int Wo, const float *wx,
-                          const int *xmn, const int *xns, const float *wy, const int *ymn, const int *yns, int mode, hipStream_t s)
+hipError_t pre_f32_launch(const uint8_t *bgr, float *rgb, float *cond, int H, int W, int Ho, int Wo, const AaTables &t, int mode, hipStream_t s)
 {
     hipLaunchKernelGGL(pre_unpack_f32_kernel, ew_grid_f32((size_t)H * W), dim3(256), 0, s, bgr, rgb, (size_t)H * W);
-    hipLaunchKernelGGL(cond_resize_f32_kernel, ew_grid_f32((size_t)3 * Ho * Wo), dim3(256), 0, s, rgb, cond, H, W, Ho, Wo, wx, xmn,
-                       xns, wy, ymn, yns, mode);
-    return hipGetLastError();
+    return cond_resize_f32_launch(rgb, cond, H, W, Ho, Wo, t, mode, s);
 }
 
-// the condition-map half of pre_f32_launch on its own: the fp32 preset's YUV route (yuv420.h) unpacks with its own kernel
-hipError_t cond_resize_f32_launch(const float *rgb, float *cond, int H, int W, int Ho, int Wo, const float *wx, const int *xmn,
-                                  const int *xns, const float *wy, const int *ymn, const int *yns, int mode, hipStream_t s)
+// the condition-map half of pre_f32_launch on its own: the fp32 preset's Y'CbCr routes (ycc_in.h) unpack with their own kernels
+hipError_t cond_resize_f32_launch(const float *rgb, float *cond, int H, int W, int Ho, int Wo, const AaTables &t, int mode, hipStream_t s)
 {
-    hipLaunchKernelGGL(cond_resize_f32_kernel, ew_grid_f32((size_t)3 * Ho * Wo), dim3(256), 0, s, rgb, cond, H, W, Ho, Wo, wx, xmn,
-                       xns, wy, ymn, yns, mode);
+    hipLaunchKernelGGL(cond_resize_f32_kernel, ew_grid_f32((size_t)3 * Ho * Wo), dim3(256), 0, s, rgb, cond, H, W, Ho, Wo, t.wx, t.xmn,
+                       t.xns, t.wy, t.ymn, t.yns, mode);
     return hipGetLastError();
 }

@@ -2,10 +2,60 @@
 // the RGB48 ring, letterbox / metrics / PQ tables.  Packing, workspace and launch sequencing are their own translation units
 // (api.h).  No kernel lives in this file.
 #include "api.h"
-#include "yuv420.h"
-#include "ycbcr10_in.h"
+#include "ycc_in.h"
 
 using namespace hdrtv_host;
+
+// =========================================================================== the input side's shared steps (templates: C++ linkage)
+// What the four preprocess entry points share: the reserved-size check, the device, a Seq on lane 0 (do_reserve uploads the resize
+// tables to lane 0 only), then the tensor step and the condition step.  tensor(q, sh, t) is the entry point's own: it enqueues the
+// tensor and returns whether the condition map is still to be computed from it (false: its launch wrote both, or it failed with q.rc).
+template <typename Step>
+static int preprocess_tail(hdrtv_ctx *c, void *stream, int H, int W, void *rgb, void *cond, Step tensor)
+{
+    if (c->H != H || c->W != W || c->lane_ws.empty()) return fail(c, HDRTV_ESTATE, "call hdrtv_reserve(%d,%d) first", H, W);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    Seq q{c, s, c->lane_ws[0]};
+    const Shapes sh = shapes_for(H, W);
+    const AaTables t{q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"), q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns")};
+    if (!tensor(q, sh, t)) return q.rc;
+    if (c->fp32) q.chk(cond_resize_f32_launch((const float *)rgb, (float *)cond, H, W, sh.h4, sh.w4, t, c->cond_mode, s), "cond_resize_f32");
+    else if (c->cond_mode == 0) q.chk(cond_resize_launch((const f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, t, s), "cond_resize");
+    else q.chk(cond_quarter_f16_launch((const f16 *)rgb, (f16 *)cond, H, W, c->cond_mode, s), "cond_quarter_f16");
+    return q.rc;
+}
+
+// The argument rule of every Y'CbCr input entry point (include/hdrtv_mi355x.h; ycc_check, then the matrix); fills `src` on success.
+template <int BITS>
+static int ycc_args(hdrtv_ctx *c, const char *what, const typename YccSrc<BITS>::sample *y, int y_pitch, const typename YccSrc<BITS>::sample *u,
+                    const typename YccSrc<BITS>::sample *v, int c_pitch, int layout, int matrix, int full_range, int H, int W, YccSrc<BITS> *src)
+{
+    if (const char *why = ycc_check(BITS, y, y_pitch, u, v, c_pitch, layout, H, W))
+        return fail(c, HDRTV_EINVAL, "%s: %s (layout %d, %dx%d, pitches %d / %d)", what, why, layout, W, H, y_pitch, c_pitch);
+    YccCoef k;
+    if (!ycc_coef(BITS, matrix, full_range, &k)) return fail(c, HDRTV_EINVAL, "%s: matrix %d / range %d (601, 709, 2020; 0 or 1)", what, matrix, full_range);
+    *src = YccSrc<BITS>{y, u, v, y_pitch, c_pitch, layout, k};
+    return HDRTV_OK;
+}
+
+// The tensor step of the plane entry points.  fp32: the unpack reading the planes, then the tail's cond_resize_f32 (pre_f32_launch's
+// two steps).  f16: pre_fused with the plane staging; the pre_split developer variant has no plane counterpart.
+template <typename Src>      // Yuv420Src | Ycc10Src
+static int preprocess_planes(hdrtv_ctx *c, void *stream, const Src &src, int H, int W, void *rgb, void *cond)
+{
+    return preprocess_tail(c, stream, H, W, rgb, cond, [&](Seq &q, const Shapes &sh, const AaTables &t) {
+        if constexpr (std::is_same<Src, Yuv420Src>::value) {
+            if (c->fp32) q.chk(pre_unpack_yuv_f32_launch(src, H, W, (float *)rgb, q.s), "pre_unpack_yuv_f32");
+            else q.chk(pre_fused_yuv_launch(src, (f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, t, c->cond_mode, q.s), "pre_fused_yuv");
+        } else {
+            if (c->fp32) q.chk(pre_unpack_ycbcr10_f32_launch(src, H, W, (float *)rgb, q.s), "pre_unpack_ycbcr10_f32");
+            else q.chk(pre_fused_ycbcr10_launch(src, (f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, t, c->cond_mode, q.s), "pre_fused_ycbcr10");
+        }
+        return c->fp32;
+    });
+}
+
 // =========================================================================== exported C ABI
 extern "C" {
 
@@ -143,47 +193,20 @@ int hdrtv_reserve(hdrtv_ctx *c, int H, int W)
 int hdrtv_preprocess(hdrtv_ctx *c, void *stream, const uint8_t *bgr, int H, int W, void *rgb, void *cond)
 {
     if (!c || !bgr || !rgb || !cond) return fail(c, HDRTV_EINVAL, "null argument");
-    if (c->H != H || c->W != W || c->lane_ws.empty()) return fail(c, HDRTV_ESTATE, "call hdrtv_reserve(%d,%d) first", H, W);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    Seq q{c, s, c->lane_ws[0]};          // the resize tables: do_reserve uploads them to lane 0 only
-    const Shapes sh = shapes_for(H, W);
-    if (c->fp32) {                       // precision="fp32": rgb / cond are fp32 tensors
-        q.chk(pre_f32_launch(bgr, (float *)rgb, (float *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
-                             q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"),
-                             c->cond_mode, s), "pre_f32");
-        return q.rc;
-    }
-    const bool split = c->var.at("pre_split") != 0;                       // developer A/B: the two-kernel form
-    if (H / 4 >= 1 && W / 4 >= 1 && !(split && c->cond_mode == 0)) {
-        q.chk(pre_fused_launch(bgr, (f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
-                               q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"), c->cond_mode, s),
-              "pre_fused");
-        return q.rc;
-    }
-    q.chk(pre_unpack_launch(bgr, (f16 *)rgb, H, W, s), "pre_unpack");
-    q.chk(cond_resize_launch((const f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
-                             q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"), s),
-          "cond_resize");
-    return q.rc;
-}
-
-// The argument rule of both YUV entry points (include/hdrtv_mi355x.h); fills `src` on success.
-static int yuv_args(hdrtv_ctx *c, const uint8_t *y, int y_pitch, const uint8_t *u, const uint8_t *v, int c_pitch, int layout,
-                    int matrix, int full_range, int H, int W, Yuv420Src *src)
-{
-    if (!y || !u) return fail(c, HDRTV_EINVAL, "yuv420: null plane");
-    if (layout != HDRTV_YUV_I420 && layout != HDRTV_YUV_NV12) return fail(c, HDRTV_EINVAL, "yuv420: unknown layout %d", layout);
-    if (layout == HDRTV_YUV_I420 && !v) return fail(c, HDRTV_EINVAL, "yuv420: I420 needs the Cr plane");
-    if (layout == HDRTV_YUV_NV12 && v) return fail(c, HDRTV_EINVAL, "yuv420: NV12 takes dev_v = NULL (CbCr interleaved in dev_u)");
-    if (H <= 0 || W <= 0 || (H & 1) || (W & 1)) return fail(c, HDRTV_EINVAL, "yuv420: frame %dx%d is not even-sized", W, H);
-    if (y_pitch < W) return fail(c, HDRTV_EINVAL, "yuv420: luma pitch %d < width %d", y_pitch, W);
-    const int cw = layout == HDRTV_YUV_NV12 ? W : W / 2;
-    if (c_pitch < cw) return fail(c, HDRTV_EINVAL, "yuv420: chroma pitch %d < %d", c_pitch, cw);
-    YuvCoef k;
-    if (!yuv_coef(matrix, full_range, &k)) return fail(c, HDRTV_EINVAL, "yuv420: matrix %d / range %d (601, 709, 2020; 0 or 1)", matrix, full_range);
-    *src = Yuv420Src{y, u, v, y_pitch, c_pitch, layout, k};
-    return HDRTV_OK;
+    return preprocess_tail(c, stream, H, W, rgb, cond, [&](Seq &q, const Shapes &sh, const AaTables &t) {
+        if (c->fp32) {                       // precision="fp32": rgb / cond are fp32 tensors; both launches in one launcher
+            q.chk(pre_f32_launch(bgr, (float *)rgb, (float *)cond, H, W, sh.h4, sh.w4, t, c->cond_mode, q.s), "pre_f32");
+            return false;
+        }
+        // the two-kernel form: the pre_split developer A/B (condition mode 0 only; hdrtv_reserve's 8 x 8 minimum puts every reserved
+        // size on the fused kernel's ground, H / 4 and W / 4 >= 1)
+        if (c->var.at("pre_split") != 0 && c->cond_mode == 0) {
+            q.chk(pre_unpack_launch(bgr, (f16 *)rgb, H, W, q.s), "pre_unpack");
+            return true;
+        }
+        q.chk(pre_fused_launch(bgr, (f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, t, c->cond_mode, q.s), "pre_fused");
+        return false;
+    });
 }
 
 int hdrtv_yuv420_to_bgr_u8(hdrtv_ctx *c, void *stream, const uint8_t *y, int y_pitch, const uint8_t *u, const uint8_t *v, int c_pitch,
@@ -191,46 +214,9 @@ int hdrtv_yuv420_to_bgr_u8(hdrtv_ctx *c, void *stream, const uint8_t *y, int y_p
 {
     if (!c || !bgr) return fail(c, HDRTV_EINVAL, "null argument");
     Yuv420Src src;
-    if (const int rc = yuv_args(c, y, y_pitch, u, v, c_pitch, layout, matrix, full_range, H, W, &src)) return rc;
+    if (const int rc = ycc_args(c, "yuv420_to_bgr", y, y_pitch, u, v, c_pitch, layout, matrix, full_range, H, W, &src)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     return launched(c, "yuv420_to_bgr", yuv420_to_bgr_launch(src, H, W, bgr, (hipStream_t)stream));
-}
-
-int hdrtv_preprocess_yuv420(hdrtv_ctx *c, void *stream, const uint8_t *y, int y_pitch, const uint8_t *u, const uint8_t *v, int c_pitch,
-                            int layout, int matrix, int full_range, int H, int W, void *rgb, void *cond)
-{
-    if (!c || !rgb || !cond) return fail(c, HDRTV_EINVAL, "null argument");
-    Yuv420Src src;
-    if (const int rc = yuv_args(c, y, y_pitch, u, v, c_pitch, layout, matrix, full_range, H, W, &src)) return rc;
-    if (c->H != H || c->W != W || c->lane_ws.empty()) return fail(c, HDRTV_ESTATE, "call hdrtv_reserve(%d,%d) first", H, W);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    Seq q{c, s, c->lane_ws[0]};          // lane 0's resize tables, as hdrtv_preprocess
-    const Shapes sh = shapes_for(H, W);
-    if (c->fp32) {                       // pre_f32_launch's two steps, the unpack reading the planes
-        q.chk(pre_unpack_yuv_f32_launch(src, H, W, (float *)rgb, s), "pre_unpack_yuv_f32");
-        q.chk(cond_resize_f32_launch((const float *)rgb, (float *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
-                                     q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"),
-                                     c->cond_mode, s), "cond_resize_f32");
-        return q.rc;
-    }
-    // hdrtv_reserve's 8 x 8 minimum puts every reserved size on the fused kernel's ground (H / 4, W / 4 >= 1); the pre_split
-    // developer variant (the two-kernel BGR form, bit-identical to pre_fused) has no YUV counterpart
-    q.chk(pre_fused_yuv_launch(src, (f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
-                               q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"), c->cond_mode, s),
-          "pre_fused_yuv");
-    return q.rc;
-}
-
-// The argument rule of both 10-bit input entry points (include/hdrtv_mi355x.h; ycc10_check); fills `src` on success.
-static int ycc10_args(hdrtv_ctx *c, const char *what, const uint16_t *y, int y_pitch, const uint16_t *u, const uint16_t *v, int c_pitch,
-                      int fmt, int matrix, int full_range, int H, int W, Ycc10Src *src)
-{
-    if (const char *why = ycc10_check(y, y_pitch, u, v, c_pitch, fmt, H, W)) return fail(c, HDRTV_EINVAL, "%s: %s (fmt %d, %dx%d, pitches %d / %d)", what, why, fmt, W, H, y_pitch, c_pitch);
-    Ycc10Coef k;
-    if (!ycc10_coef(matrix, full_range, &k)) return fail(c, HDRTV_EINVAL, "%s: matrix %d / range %d (601, 709, 2020; 0 or 1)", what, matrix, full_range);
-    *src = Ycc10Src{y, u, v, y_pitch, c_pitch, fmt, k};
-    return HDRTV_OK;
 }
 
 int hdrtv_ycbcr10_to_rgb10(hdrtv_ctx *c, void *stream, const uint16_t *y, int y_pitch, const uint16_t *u, const uint16_t *v, int c_pitch,
@@ -238,9 +224,18 @@ int hdrtv_ycbcr10_to_rgb10(hdrtv_ctx *c, void *stream, const uint16_t *y, int y_
 {
     if (!c || !rgb) return fail(c, HDRTV_EINVAL, "null argument");
     Ycc10Src src;
-    if (const int rc = ycc10_args(c, "ycbcr10_to_rgb10", y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, H, W, &src)) return rc;
+    if (const int rc = ycc_args(c, "ycbcr10_to_rgb10", y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, H, W, &src)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     return launched(c, "ycbcr10_to_rgb10", ycbcr10_to_rgb10_launch(src, H, W, rgb, (hipStream_t)stream));
+}
+
+int hdrtv_preprocess_yuv420(hdrtv_ctx *c, void *stream, const uint8_t *y, int y_pitch, const uint8_t *u, const uint8_t *v, int c_pitch,
+                            int layout, int matrix, int full_range, int H, int W, void *rgb, void *cond)
+{
+    if (!c || !rgb || !cond) return fail(c, HDRTV_EINVAL, "null argument");
+    Yuv420Src src;
+    if (const int rc = ycc_args(c, "preprocess_yuv420", y, y_pitch, u, v, c_pitch, layout, matrix, full_range, H, W, &src)) return rc;
+    return preprocess_planes(c, stream, src, H, W, rgb, cond);
 }
 
 int hdrtv_preprocess_ycbcr10(hdrtv_ctx *c, void *stream, const uint16_t *y, int y_pitch, const uint16_t *u, const uint16_t *v, int c_pitch,
@@ -248,23 +243,8 @@ int hdrtv_preprocess_ycbcr10(hdrtv_ctx *c, void *stream, const uint16_t *y, int 
 {
     if (!c || !rgb || !cond) return fail(c, HDRTV_EINVAL, "null argument");
     Ycc10Src src;
-    if (const int rc = ycc10_args(c, "preprocess_ycbcr10", y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, H, W, &src)) return rc;
-    if (c->H != H || c->W != W || c->lane_ws.empty()) return fail(c, HDRTV_ESTATE, "call hdrtv_reserve(%d,%d) first", H, W);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    Seq q{c, s, c->lane_ws[0]};          // lane 0's resize tables, as hdrtv_preprocess
-    const Shapes sh = shapes_for(H, W);
-    if (c->fp32) {                       // two launches, as hdrtv_preprocess_yuv420
-        q.chk(pre_unpack_ycbcr10_f32_launch(src, H, W, (float *)rgb, s), "pre_unpack_ycbcr10_f32");
-        q.chk(cond_resize_f32_launch((const float *)rgb, (float *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
-                                     q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"),
-                                     c->cond_mode, s), "cond_resize_f32");
-        return q.rc;
-    }
-    q.chk(pre_fused_ycbcr10_launch(src, (f16 *)rgb, (f16 *)cond, H, W, sh.h4, sh.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
-                                   q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"), c->cond_mode, s),
-          "pre_fused_ycbcr10");
-    return q.rc;
+    if (const int rc = ycc_args(c, "preprocess_ycbcr10", y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, H, W, &src)) return rc;
+    return preprocess_planes(c, stream, src, H, W, rgb, cond);
 }
 
 int hdrtv_set_lanes(hdrtv_ctx *c, int lanes)
@@ -771,15 +751,19 @@ int hdrtv_letterbox_u8(hdrtv_ctx *c, void *stream, const uint8_t *src_bgr, int s
     return launched(c, "letterbox", letterbox_launch(p, (hipStream_t)stream));
 }
 
-// The letterbox of a 10-bit Y'CbCr frame (letterbox10.hip): the argument rule of both entry points, then the tables of this geometry
-// (the ones hdrtv_letterbox_u8 uses: they do not depend on bit depth).  Nothing is enqueued before every check has passed.
+// The letterbox of a 10-bit Y'CbCr frame (letterbox10.hip).  Both entry points check the planes and the destination first
+// (letterbox10_args), then, with the device set, build the tables of this geometry (letterbox10_tables: the ones hdrtv_letterbox_u8
+// uses, they do not depend on bit depth).  Nothing is enqueued before every check has passed.
 static int letterbox10_args(hdrtv_ctx *c, const char *what, const uint16_t *y, int y_pitch, const uint16_t *u, const uint16_t *v, int c_pitch,
-                            int fmt, int matrix, int full_range, int sh, int sw, int dh, int dw, bool reserved, Ycc10Src *src)
+                            int fmt, int matrix, int full_range, int sh, int sw, int dh, int dw, Ycc10Src *src)
 {
-    if (const int rc = ycc10_args(c, what, y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, sh, sw, src)) return rc;
+    if (const int rc = ycc_args(c, what, y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, sh, sw, src)) return rc;
     if (dh <= 0 || dw <= 0) return fail(c, HDRTV_EINVAL, "%s: destination %dx%d is not positive", what, dw, dh);
-    if (reserved && (c->H != dh || c->W != dw || c->lane_ws.empty())) return fail(c, HDRTV_ESTATE, "call hdrtv_reserve(%d,%d) first", dh, dw);
-    HIPCHK(c, hipSetDevice(c->device));
+    return HDRTV_OK;
+}
+
+static int letterbox10_tables(hdrtv_ctx *c, const char *what, int sh, int sw, int dh, int dw)
+{
     if (!letterbox_setup(c, sh, sw, dh, dw)) {
         c->lb_key[0] = 0;
         return fail(c, HDRTV_ENOMEM, "%s: table allocation failed", what);
@@ -794,34 +778,25 @@ int hdrtv_letterbox_ycbcr10(hdrtv_ctx *c, void *stream, const uint16_t *y, int y
 {
     if (!c || !rgb) return fail(c, HDRTV_EINVAL, "null argument");
     Ycc10Src src;
-    if (const int rc = letterbox10_args(c, "letterbox_ycbcr10", y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, sh, sw, dh, dw, false, &src))
-        return rc;
+    if (const int rc = letterbox10_args(c, "letterbox_ycbcr10", y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, sh, sw, dh, dw, &src)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (const int rc = letterbox10_tables(c, "letterbox_ycbcr10", sh, sw, dh, dw)) return rc;
     return launched(c, "letterbox_ycbcr10", letterbox10_launch(src, c->lb, LB10_U16_HWC, rgb, (hipStream_t)stream));
 }
 
 int hdrtv_preprocess_ycbcr10_letterboxed(hdrtv_ctx *c, void *stream, const uint16_t *y, int y_pitch, const uint16_t *u, const uint16_t *v,
                                          int c_pitch, int fmt, int matrix, int full_range, int sh, int sw, int H, int W, void *rgb, void *cond)
 {
+    const char *what = "preprocess_ycbcr10_letterboxed";
     if (!c || !rgb || !cond) return fail(c, HDRTV_EINVAL, "null argument");
     Ycc10Src src;
-    if (const int rc = letterbox10_args(c, "preprocess_ycbcr10_letterboxed", y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, sh, sw, H, W,
-                                        true, &src))
-        return rc;
-    hipStream_t s = (hipStream_t)stream;
-    Seq q{c, s, c->lane_ws[0]};          // lane 0's resize tables, as hdrtv_preprocess
-    const Shapes shp = shapes_for(H, W);
+    if (const int rc = letterbox10_args(c, what, y, y_pitch, u, v, c_pitch, fmt, matrix, full_range, sh, sw, H, W, &src)) return rc;
     // the tensor in one launch; the condition map is computed from the tensor that launch wrote
-    q.chk(letterbox10_launch(src, c->lb, c->fp32 ? LB10_F32_CHW : LB10_F16_CHW, rgb, s), "letterbox10");
-    if (c->fp32)
-        q.chk(cond_resize_f32_launch((const float *)rgb, (float *)cond, H, W, shp.h4, shp.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
-                                     q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"),
-                                     c->cond_mode, s), "cond_resize_f32");
-    else if (c->cond_mode == 0)
-        q.chk(cond_resize_launch((const f16 *)rgb, (f16 *)cond, H, W, shp.h4, shp.w4, q.wsp<float>("aa.wx"), q.wsp<int>("aa.xmn"),
-                                 q.wsp<int>("aa.xns"), q.wsp<float>("aa.wy"), q.wsp<int>("aa.ymn"), q.wsp<int>("aa.yns"), s), "cond_resize");
-    else
-        q.chk(cond_quarter_f16_launch((const f16 *)rgb, (f16 *)cond, H, W, c->cond_mode, s), "cond_quarter_f16");
-    return q.rc;
+    return preprocess_tail(c, stream, H, W, rgb, cond, [&](Seq &q, const Shapes &, const AaTables &) {
+        if ((q.rc = letterbox10_tables(c, what, sh, sw, H, W)) != HDRTV_OK) return false;
+        q.chk(letterbox10_launch(src, c->lb, c->fp32 ? LB10_F32_CHW : LB10_F16_CHW, rgb, q.s), "letterbox10");
+        return true;
+    });
 }
 
 // --------------------------------------------------------------------------------- metrics

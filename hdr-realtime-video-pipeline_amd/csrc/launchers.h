@@ -41,10 +41,15 @@ hipError_t conv_q8_multi_launch(ConvQ8MultiParams p, int n_cu, hipStream_t strea
 hipError_t conv3x3s2_preg_launch(ConvParams p, int n_cu, hipStream_t stream);
 
 hipError_t pre_unpack_launch(const uint8_t *bgr, f16 *out, int H, int W, hipStream_t s);
-hipError_t cond_resize_launch(const f16 *in, f16 *out, int H, int W, int Ho, int Wo, const float *wx, const int *xmn,
-                              const int *xns, const float *wy, const int *ymn, const int *yns, hipStream_t s);
-hipError_t pre_fused_launch(const uint8_t *bgr, f16 *out, f16 *cond, int H, int W, int Ho, int Wo, const float *wx, const int *xmn,
-                            const int *xns, const float *wy, const int *ymn, const int *yns, int mode, hipStream_t s);
+// The six resize-table pointers of a reserved size (ATen's _upsample_bicubic2d_aa taps: lane 0's workspace entries "aa.*")
+struct AaTables {
+    const float *wx;
+    const int *xmn, *xns;
+    const float *wy;
+    const int *ymn, *yns;
+};
+hipError_t cond_resize_launch(const f16 *in, f16 *out, int H, int W, int Ho, int Wo, const AaTables &t, hipStream_t s);
+hipError_t pre_fused_launch(const uint8_t *bgr, f16 *out, f16 *cond, int H, int W, int Ho, int Wo, const AaTables &t, int mode, hipStream_t s);
 hipError_t post_u8_launch(const void *in, int is_f32, int H, int W, uint8_t *bgr, hipStream_t s);
 hipError_t post_rgb48_launch(const void *in, int is_f32, int H, int W, uint16_t *rgb, int pq, float peak, hipStream_t s,
                              const float *pq_bnd = nullptr);
@@ -199,5 +204,6 @@ hipError_t window_f32_launch(const float *x, float *y, int C, int H, int W, int 
 hipError_t hg_mask_f32_launch(const float *base, float *mask, size_t npix, float r, hipStream_t s);
 hipError_t hg_blend_f32_launch(const float *t, const float *img, const float *mask, float *out, int H, int W, int Hp, int Wp,
                                hipStream_t s);
-hipError_t pre_f32_launch(const uint8_t *bgr, float *rgb, float *cond, int H, int W, int Ho, int Wo, const float *wx,
-                          const int *xmn, const int *xns, const float *wy, const int *ymn, const int *yns, int mode, hipStream_t s);
+hipError_t pre_f32_launch(const uint8_t *bgr, float *rgb, float *cond, int H, int W, int Ho, int Wo, const AaTables &t, int mode, hipStream_t s);
+// the condition-map half of pre_f32_launch on its own (planar fp32 RGB -> cond): the Y'CbCr routes unpack with their own kernels
+hipError_t cond_resize_f32_launch(const float *rgb, float *cond, int H, int W, int Ho, int Wo, const AaTables &t, int mode, hipStream_t s);

@@ -6,7 +6,7 @@
 //
 //  letterbox10_kernel<STORE>  a 256-thread workgroup owns a 32 x 8 tile of destination pixels.  It stages the source patch the tile's
 //                             taps cover (raw luma words into the patch itself, the chroma rows and columns around it beside it),
-//                             converts every patch pixel ONCE with ycc10_rule into one packed 10:10:10 word in LDS, and resamples
+//                             converts every patch pixel ONCE with ycc_rule<10> into one packed 10:10:10 word in LDS, and resamples
 //                             its 256 pixels from there; pixels outside the rectangle are written as zeros by the same launch.
 //                             STORE: u16 HWC codes | f16 CHW planes fp16(float(code) * fp32(1/1023)) | f32 CHW planes, the same
 //                             expression without the last conversion.
@@ -15,9 +15,9 @@
 //
 // LDS: the patch is at most 130 x 34 (a 4x shrink per axis is the cap: 128 x 32, one more row and column for a fractional ratio,
 // rounded up to even), 17.4 KB at pitch 131; the chroma area 34 rows of 2 x 68 samples, 9.0 KB.  26.4 KB per workgroup.
-// Built with -ffp-contract=off (csrc/Makefile), as letterbox.hip: the area modes multiply and add separately in float32.
-#include "launchers.h"
-#include "ycbcr10_in.h"
+// The plane stager and the chroma walk are ycc_in.h's.  Built with -ffp-contract=off (csrc/Makefile), as letterbox.hip: the area modes
+// multiply and add separately in float32.
+#include "ycc_in.h"
 
 namespace {
 
@@ -27,47 +27,6 @@ constexpr int LB10_CW = 68, LB10_CROWS = 34;                   // chroma samples
 static_assert(LB10_TW * LB10_TH == 256, "one thread per destination pixel");
 static_assert(LB10_PW >= 4 * LB10_TW + 1 && LB10_PH >= 4 * LB10_TH + 1, "a 4x fractional shrink");
 static_assert(LB10_PW / 2 + 2 <= LB10_CW && LB10_PH <= LB10_CROWS, "the chroma columns / rows a full patch needs");
-
-__device__ __forceinline__ const uint16_t *row_of(const uint16_t *p, int row, int pitch_bytes)
-{
-    return reinterpret_cast<const uint16_t *>(reinterpret_cast<const uint8_t *>(p) + (size_t)row * pitch_bytes);
-}
-
-// Rows [row0, row0 + nrows) x samples [col0, col0 + len) of a plane -> dst[r * dst_pitch + k].  The load discipline of pf_stage10
-// (prepost.hip): planes and pitches are two-byte aligned and no more, so a row segment is read as the whole aligned dwords that hold
-// at least one of its samples, never a dword past its last byte; each half of a dword is kept or dropped.  Four loads in flight per
-// thread before the first is unpacked.
-template <typename T>
-__device__ __forceinline__ void lb10_stage(const uint16_t *plane, int pitch_bytes, int row0, int nrows, int col0, int len, T *dst,
-                                           int dst_pitch, int tid)
-{
-    const int ndw = len / 2 + 1, n = nrows * ndw;             // ceil((2 len + 2) / 4) dwords cover a segment at either alignment
-    for (int e0 = tid; e0 < n; e0 += 4 * 256) {
-        uint32_t word[4];
-        int rel[4], row[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = e0 + 256 * i;
-            rel[i] = -1000; row[i] = 0; word[i] = 0u;
-            if (e < n) {
-                const int r = e / ndw, d = e - r * ndw;
-                const uint16_t *seg = row_of(plane, row0 + r, pitch_bytes) + col0;
-                const uintptr_t a = ((uintptr_t)seg & ~(uintptr_t)3) + 4 * (uintptr_t)d;
-                if (a < (uintptr_t)seg + 2 * (uintptr_t)len) {
-                    rel[i] = (int)((long)a - (long)(uintptr_t)seg) >> 1;      // sample index of the dword's low half: -1 or even
-                    row[i] = r;
-                    word[i] = *reinterpret_cast<const uint32_t *>(a);
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            T *d = dst + row[i] * dst_pitch;
-            if (rel[i] >= 0 && rel[i] < len) d[rel[i]] = (T)(word[i] & 0xffffu);
-            if (rel[i] + 1 >= 0 && rel[i] + 1 < len) d[rel[i] + 1] = (T)(word[i] >> 16);
-        }
-    }
-}
 
 template <int STORE>
 __device__ __forceinline__ void lb10_store(void *__restrict__ dst, int dh, int dw, int y, int x, uint32_t r, uint32_t g, uint32_t b)
@@ -127,17 +86,17 @@ __global__ __launch_bounds__(256) void letterbox10_kernel(const Ycc10Src src, co
         pw = min(x1 - px0 + 1, LB10_PW); ph = min(y1 - py0 + 1, LB10_PH);      // (never cut: the launcher refuses a shrink beyond 4x)
         x1 = px0 + pw - 1; y1 = py0 + ph - 1;
         // ---- stage: luma words into the patch, the chroma rows / columns the patch's pixels use (clamped at the frame's edges)
-        const bool p010 = src.fmt == YCC10_P010, c422 = src.fmt == YCC10_YUV422P10;
+        const bool p010 = src.layout == YCC10_P010, c422 = src.layout == YCC10_YUV422P10;
         const int Hc = c422 ? p.sh : p.sh >> 1, Wc = p.sw >> 1;
         const int jlo = c422 ? py0 : max((py0 >> 1) - 1, 0), jhi = c422 ? y1 : min((y1 >> 1) + 1, Hc - 1);
         const int ilo = px0 >> 1, ihi = min((x1 >> 1) + 1, Wc - 1);
         const int nrow = min(jhi - jlo + 1, LB10_CROWS), ncol = min(ihi - ilo + 1, LB10_CW);
-        lb10_stage(src.y, src.y_pitch, py0, ph, px0, pw, &s_px[0][0], LB10_PITCH, tid);
+        ycc10_stage(src.y, src.y_pitch, py0, ph, px0, pw, &s_px[0][0], LB10_PITCH, tid);
         if (p010) {
-            lb10_stage(src.u, src.c_pitch, jlo, nrow, 2 * ilo, 2 * ncol, &s_c[0][0], 2 * LB10_CW, tid);
+            ycc10_stage(src.u, src.c_pitch, jlo, nrow, 2 * ilo, 2 * ncol, &s_c[0][0], 2 * LB10_CW, tid);
         } else {
-            lb10_stage(src.u, src.c_pitch, jlo, nrow, ilo, ncol, &s_c[0][0], 2 * LB10_CW, tid);
-            lb10_stage(src.v, src.c_pitch, jlo, nrow, ilo, ncol, &s_c[0][LB10_CW], 2 * LB10_CW, tid);
+            ycc10_stage(src.u, src.c_pitch, jlo, nrow, ilo, ncol, &s_c[0][0], 2 * LB10_CW, tid);
+            ycc10_stage(src.v, src.c_pitch, jlo, nrow, ilo, ncol, &s_c[0][LB10_CW], 2 * LB10_CW, tid);
         }
         __syncthreads();
         // ---- convert: one item = one chroma column of one row = the two patch pixels that share it; the item that reads a pixel's
@@ -146,19 +105,16 @@ __global__ __launch_bounds__(256) void letterbox10_kernel(const Ycc10Src src, co
         for (int e = tid; e < ph * ncol; e += 256) {
             const int r = e / ncol, c = e - r * ncol;
             const int y = py0 + r, i = ilo + c, q0 = 2 * i - px0;
-            const int j = c422 ? y : y >> 1, n = c422 ? y : (y & 1) ? min(j + 1, Hc - 1) : max(j - 1, 0);
-            const int i2 = min(min(i + 1, Wc - 1), ihi);
+            int j, n, u4a, u4b, v4a, v4b;
+            ycc_rows(y, Hc, c422, j, n);
             const uint16_t *cj = s_c[min(j - jlo, nrow - 1)], *cn = s_c[min(n - jlo, nrow - 1)];
-            const int k1 = cs * c, k2 = cs * min(i2 - ilo, ncol - 1);
-            const int u4a = 3 * ycc10_sample(cj[k1], sh) + ycc10_sample(cn[k1], sh), u4b = 3 * ycc10_sample(cj[k2], sh) + ycc10_sample(cn[k2], sh);
-            const int v4a = 3 * ycc10_sample(cj[k1 + co], sh) + ycc10_sample(cn[k1 + co], sh);
-            const int v4b = 3 * ycc10_sample(cj[k2 + co], sh) + ycc10_sample(cn[k2 + co], sh);
+            ycc_walk<10>(cj, cn, cs * c, cs * min(ycc_col2(i, ihi) - ilo, ncol - 1), co, sh, u4a, u4b, v4a, v4b);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int q = q0 + h;
                 if (q < 0 || q >= pw) continue;
                 uint32_t R, G, B;
-                ycc10_rule(ycc10_sample(s_px[r][q], sh), h ? u4a + u4b : 2 * u4a, h ? v4a + v4b : 2 * v4a, src.k, R, G, B);
+                ycc_rule<10>(ycc_sample<10>(s_px[r][q], sh), h ? u4a + u4b : 2 * u4a, h ? v4a + v4b : 2 * v4a, src.k, R, G, B);
                 s_px[r][q] = R | (G << 10) | (B << 20);
             }
         }
@@ -259,7 +215,7 @@ bool letterbox10_size_ok(const LetterboxParams &p)
 
 hipError_t letterbox10_launch(const Ycc10Src &src, const LetterboxParams &p, int store, void *dst, hipStream_t s)
 {
-    if (ycc10_check(src.y, src.y_pitch, src.u, src.v, src.c_pitch, src.fmt, p.sh, p.sw) || !dst || !letterbox10_size_ok(p))
+    if (!ycc_ok(src, p.sh, p.sw) || !dst || !letterbox10_size_ok(p))
         return hipErrorInvalidValue;
     if (p.mode == LB_AREA_INT && (p.ix < 1 || p.iy < 1 || p.ix > LB10_MAX_SHRINK || p.iy > LB10_MAX_SHRINK)) return hipErrorInvalidValue;
     const dim3 g((p.dw + LB10_TW - 1) / LB10_TW, (p.dh + LB10_TH - 1) / LB10_TH), b(256);

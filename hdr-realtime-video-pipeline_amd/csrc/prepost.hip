@@ -11,8 +11,7 @@
 // __fadd_rn: the reference rounds the multiply and the add separately.
 #include "launchers.h"
 #include "post_quant.h"
-#include "yuv420.h"
-#include "ycbcr10_in.h"
+#include "ycc_in.h"
 
 #include <type_traits>
 
@@ -118,8 +117,8 @@ constexpr int PF_PITCH = 144;
 // of patch pixel (ix0 + q, iy0 + r), for every r with iy0 + r < H and q with ix0 + q < W.  Everything after it is shared.
 //  PfBgr      u8 HWC BGR, the staging written out in the kernel body (its instruction sequence is that of the kernel before the
 //             template: an inlined helper let hipcc pick another division sequence for e / PF_ROWDW)
-//  Yuv420Src  I420 / NV12 planes: pf_stage below, the conversion rule of yuv420.h
-//  Ycc10Src   P010 / yuv420p10 / yuv422p10 planes: pf_stage10 below, the rule of ycbcr10_in.h, fp16(float(code) * fp32(1/1023))
+//  Yuv420Src  I420 / NV12 planes: pf_stage below, the conversion rule of ycc_in.h at 8 bits
+//  Ycc10Src   P010 / yuv420p10 / yuv422p10 planes: pf_stage10 below, the rule at 10 bits, fp16(float(code) * fp32(1/1023))
 typedef const uint8_t *__restrict__ PfBgr;
 
 // YUV staging.  Byte staging area: the horizontal pass's s_h (17.4 KB, unused until the barrier after staging), so the kernel's LDS
@@ -186,17 +185,16 @@ __device__ __forceinline__ void pf_stage(const Yuv420Src &src, f16 (*s_in)[PF_IH
         const int r = e / PFC_W, p = e - r * PFC_W;
         const int y = iy0 + r, i = ilo + p, q0 = 2 * i - ix0;
         if (y >= H || i > ihi) continue;          // (i <= ihi: a chroma column the patch uses)
-        const int j = y >> 1, n = (y & 1) ? min(j + 1, Hc - 1) : max(j - 1, 0), i2 = min(i + 1, Wc - 1);
+        int j, n, u4a, u4b, v4a, v4b;
+        ycc_rows(y, Hc, false, j, n);
         const uint8_t *cj = s_c + (j - jlo) * PFC_PITCH, *cn = s_c + (n - jlo) * PFC_PITCH;
-        const int k1 = cs * p, k2 = cs * (i2 - ilo);
-        const int u4a = 3 * cj[k1] + cn[k1], u4b = 3 * cj[k2] + cn[k2];
-        const int v4a = 3 * cj[k1 + co] + cn[k1 + co], v4b = 3 * cj[k2 + co] + cn[k2 + co];
+        ycc_walk<8>(cj, cn, cs * p, cs * (ycc_col2(i, ihi) - ilo), co, 0, u4a, u4b, v4a, v4b);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int q = q0 + h;
             if (q < 0 || q >= PF_IW || ix0 + q >= W) continue;
             uint32_t R, G, B;
-            yuv_rule(s_y[r * PFY_PITCH + q], h ? u4a + u4b : 2 * u4a, h ? v4a + v4b : 2 * v4a, src.k, R, G, B);
+            ycc_rule<8>(s_y[r * PFY_PITCH + q], h ? u4a + u4b : 2 * u4a, h ? v4a + v4b : 2 * v4a, src.k, R, G, B);
             s_in[0][r][q] = (f16)__fmul_rn((float)R, k255);
             s_in[1][r][q] = (f16)__fmul_rn((float)G, k255);
             s_in[2][r][q] = (f16)__fmul_rn((float)B, k255);
@@ -204,39 +202,24 @@ __device__ __forceinline__ void pf_stage(const Yuv420Src &src, f16 (*s_in)[PF_IH
     }
 }
 
-// 10-bit staging (Ycc10Src: P010 / yuv420p10 / yuv422p10, the rule of ycbcr10_in.h).  At two bytes per sample the byte layout above
+// 10-bit staging (Ycc10Src: P010 / yuv420p10 / yuv422p10).  At two bytes per sample the byte layout above
 // would need 19.9 KB, more than s_h holds, so the luma patch does not go there: its raw sample words are staged straight into
 // s_in[0] (an f16 slot is 16 bits; the convert step reads the word of a patch pixel and overwrites it with that pixel's R, the same
 // work item doing both).  s_h holds only the chroma rows, 288 bytes each: 25 rows for 4:2:0 (7.2 KB), 44 for 4:2:2 (12.7 KB), each
 // Cb at samples 0..71 and Cr at 72..143 (planar) or the CbCr pairs as they lie in memory (P010).  So the kernel's LDS is that of the
-// BGR form.  Loads keep pf_stage's discipline: whole aligned dwords that hold at least one sample of the segment, never a dword past
-// its last byte; segments are two-byte aligned, so a dword holds two samples, each kept or dropped.  LDS accesses of the staging go
+// BGR form.  Loads keep pf_stage's discipline through ycc_in.h's ycc10_load / ycc10_keep (shared with letterbox10.hip): whole aligned dwords that hold at
+// least one sample of the segment, never a dword past its last byte.  LDS accesses of the staging go
 // through a may_alias type: the same addresses are f16 / float to the rest of the kernel.
 typedef uint16_t __attribute__((may_alias)) pf_u16;
 constexpr int PF10_YDW = 71;                              // 71 dwords cover 140 samples (280 B) at either alignment
 constexpr int PF10_CPITCH = 144, PF10_CW = 72;            // u16 per staged chroma row / samples per plane in it
 constexpr int PF10_CDW1 = 37, PF10_CDW2 = 73;             // dwords covering 144 B (a planar row) / 288 B (a P010 row)
 
-// the dword d of the row segment [seg, seg + 2 len): loaded when it holds a sample of the segment; rel = the sample index of its low half
-__device__ __forceinline__ void pf10_load(const uint16_t *seg, int len, int d, uint32_t &word, int &rel)
-{
-    const uintptr_t a = ((uintptr_t)seg & ~(uintptr_t)3) + 4 * (uintptr_t)d;
-    const bool ok = seg != nullptr && a < (uintptr_t)seg + 2 * (uintptr_t)len;
-    rel = ok ? (int)((long)a - (long)(uintptr_t)seg) >> 1 : -1000;
-    word = ok ? *reinterpret_cast<const uint32_t *>(a) : 0u;
-}
-
-__device__ __forceinline__ void pf10_keep(pf_u16 *dst, int len, uint32_t word, int rel)
-{
-    if (rel >= 0 && rel < len) dst[rel] = (uint16_t)word;
-    if (rel + 1 >= 0 && rel + 1 < len) dst[rel + 1] = (uint16_t)(word >> 16);
-}
-
 __device__ __forceinline__ void pf_stage10(const Ycc10Src &src, f16 (*s_in)[PF_IH][PF_PITCH], pf_u16 *s_c, int tid, int H, int W,
                                            int ix0, int iy0)
 {
     pf_u16 *s_y = reinterpret_cast<pf_u16 *>(&s_in[0][0][0]);
-    const bool p010 = src.fmt == YCC10_P010, c422 = src.fmt == YCC10_YUV422P10;
+    const bool p010 = src.layout == YCC10_P010, c422 = src.layout == YCC10_YUV422P10;
     const int Hc = c422 ? H : H >> 1, Wc = W >> 1;
     const int ylast = min(iy0 + PF_IH, H) - 1, xlast = min(ix0 + PF_IW, W) - 1;
     const int jlo = c422 ? iy0 : max((iy0 >> 1) - 1, 0), jhi = c422 ? ylast : min((ylast >> 1) + 1, Hc - 1);
@@ -251,13 +234,13 @@ __device__ __forceinline__ void pf_stage10(const Ycc10Src &src, f16 (*s_in)[PF_I
             const int e = tid + 256 * i, r = e / PF10_YDW, d = e - r * PF10_YDW;
             const uint16_t *seg = nullptr;
             if (e < NY && iy0 + r < H)
-                seg = reinterpret_cast<const uint16_t *>(reinterpret_cast<const uint8_t *>(src.y) + (size_t)(iy0 + r) * src.y_pitch) + ix0;
-            pf10_load(seg, ylen, d, word[i], rel[i]);
+                seg = row_of(src.y, iy0 + r, src.y_pitch) + ix0;
+            ycc10_load(seg, ylen, d, word[i], rel[i]);
         }
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int r = (tid + 256 * i) / PF10_YDW;
-            pf10_keep(s_y + r * PF_PITCH, ylen, word[i], rel[i]);
+            ycc10_keep(s_y + r * PF_PITCH, ylen, word[i], rel[i]);
         }
     }
     {
@@ -272,16 +255,15 @@ __device__ __forceinline__ void pf_stage10(const Ycc10Src &src, f16 (*s_in)[PF_I
             const int plane = (!p010 && rem >= PF10_CDW1) ? 1 : 0, d = rem - plane * PF10_CDW1;
             const uint16_t *seg = nullptr;
             if (jlo + rr <= jhi)
-                seg = reinterpret_cast<const uint16_t *>(reinterpret_cast<const uint8_t *>(plane ? src.v : src.u) +
-                                                         (size_t)(jlo + rr) * src.c_pitch) + (ilo << (p010 ? 1 : 0));
-            pf10_load(seg, clen, d, word[i], rel[i]);
+                seg = row_of(plane ? src.v : src.u, jlo + rr, src.c_pitch) + (ilo << (p010 ? 1 : 0));
+            ycc10_load(seg, clen, d, word[i], rel[i]);
         }
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int e = tid + 256 * i;
             const int rr = p010 ? e / PF10_CDW2 : e / (2 * PF10_CDW1), rem = e - rr * (p010 ? PF10_CDW2 : 2 * PF10_CDW1);
             const int plane = (!p010 && rem >= PF10_CDW1) ? 1 : 0;
-            if (rel[i] > -1000) pf10_keep(s_c + rr * PF10_CPITCH + plane * PF10_CW, clen, word[i], rel[i]);
+            if (rel[i] > -1000) ycc10_keep(s_c + rr * PF10_CPITCH + plane * PF10_CW, clen, word[i], rel[i]);
         }
     }
     __syncthreads();
@@ -291,18 +273,16 @@ __device__ __forceinline__ void pf_stage10(const Ycc10Src &src, f16 (*s_in)[PF_I
         const int r = e / PF10_CW, p = e - r * PF10_CW;
         const int y = iy0 + r, i = ilo + p, q0 = 2 * i - ix0;
         if (y >= H || i > ihi) continue;          // (i <= ihi: a chroma column the patch uses)
-        const int j = c422 ? y : y >> 1, n = c422 ? y : (y & 1) ? min(j + 1, Hc - 1) : max(j - 1, 0), i2 = min(min(i + 1, Wc - 1), ihi);
+        int j, n, u4a, u4b, v4a, v4b;
+        ycc_rows(y, Hc, c422, j, n);
         const pf_u16 *cj = s_c + (j - jlo) * PF10_CPITCH, *cn = s_c + (n - jlo) * PF10_CPITCH;
-        const int k1 = cs * p, k2 = cs * (i2 - ilo);
-        const int u4a = 3 * ycc10_sample(cj[k1], sh) + ycc10_sample(cn[k1], sh), u4b = 3 * ycc10_sample(cj[k2], sh) + ycc10_sample(cn[k2], sh);
-        const int v4a = 3 * ycc10_sample(cj[k1 + co], sh) + ycc10_sample(cn[k1 + co], sh);
-        const int v4b = 3 * ycc10_sample(cj[k2 + co], sh) + ycc10_sample(cn[k2 + co], sh);
+        ycc_walk<10>(cj, cn, cs * p, cs * (ycc_col2(i, ihi) - ilo), co, sh, u4a, u4b, v4a, v4b);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int q = q0 + h;
             if (q < 0 || q >= PF_IW || ix0 + q >= W) continue;
             uint32_t R, G, B;
-            ycc10_rule(ycc10_sample(s_y[r * PF_PITCH + q], sh), h ? u4a + u4b : 2 * u4a, h ? v4a + v4b : 2 * v4a, src.k, R, G, B);
+            ycc_rule<10>(ycc_sample<10>(s_y[r * PF_PITCH + q], sh), h ? u4a + u4b : 2 * u4a, h ? v4a + v4b : 2 * v4a, src.k, R, G, B);
             s_in[0][r][q] = (f16)__fmul_rn((float)R, k1023);
             s_in[1][r][q] = (f16)__fmul_rn((float)G, k1023);
             s_in[2][r][q] = (f16)__fmul_rn((float)B, k1023);
@@ -628,44 +608,38 @@ hipError_t pre_unpack_launch(const uint8_t *bgr, f16 *out, int H, int W, hipStre
     return hipGetLastError();
 }
 
-hipError_t cond_resize_launch(const f16 *in, f16 *out, int H, int W, int Ho, int Wo, const float *wx, const int *xmn,
-                              const int *xns, const float *wy, const int *ymn, const int *yns, hipStream_t s)
+hipError_t cond_resize_launch(const f16 *in, f16 *out, int H, int W, int Ho, int Wo, const AaTables &t, hipStream_t s)
 {
     dim3 grid((Wo + RT_W - 1) / RT_W, (Ho + RT_H - 1) / RT_H, 3);
-    hipLaunchKernelGGL(cond_resize_kernel, grid, dim3(256), 0, s, in, out, H, W, Ho, Wo, wx, xmn, xns, wy, ymn, yns);
+    hipLaunchKernelGGL(cond_resize_kernel, grid, dim3(256), 0, s, in, out, H, W, Ho, Wo, t.wx, t.xmn, t.xns, t.wy, t.ymn, t.yns);
     return hipGetLastError();
 }
 
 // mode 0: 0.25x antialiased bicubic; 1: bilinear (fast_condition_resize); 2: zero condition.  Needs Ho = H / 4 >= 1, Wo = W / 4 >= 1.
-hipError_t pre_fused_launch(const uint8_t *bgr, f16 *out, f16 *cond, int H, int W, int Ho, int Wo, const float *wx, const int *xmn,
-                            const int *xns, const float *wy, const int *ymn, const int *yns, int mode, hipStream_t s)
+template <typename Src>
+static hipError_t pre_fused_any(const Src &src, f16 *out, f16 *cond, int H, int W, int Ho, int Wo, const AaTables &t, int mode, hipStream_t s)
 {
     if (Ho != H / 4 || Wo != W / 4 || Ho < 1 || Wo < 1) return hipErrorInvalidValue;
-    dim3 grid((Wo + PF_OW - 1) / PF_OW, (Ho + PF_OH - 1) / PF_OH, 1);
-    hipLaunchKernelGGL(pre_fused_kernel<PfBgr>, grid, dim3(256), 0, s, bgr, out, cond, H, W, Ho, Wo, wx, xmn, xns, wy, ymn, yns, mode);
+    const dim3 grid((Wo + PF_OW - 1) / PF_OW, (Ho + PF_OH - 1) / PF_OH, 1);
+    hipLaunchKernelGGL(pre_fused_kernel<Src>, grid, dim3(256), 0, s, src, out, cond, H, W, Ho, Wo, t.wx, t.xmn, t.xns, t.wy, t.ymn, t.yns, mode);
     return hipGetLastError();
 }
 
-hipError_t pre_fused_yuv_launch(const Yuv420Src &src, f16 *out, f16 *cond, int H, int W, int Ho, int Wo, const float *wx,
-                                const int *xmn, const int *xns, const float *wy, const int *ymn, const int *yns, int mode,
-                                hipStream_t s)
+hipError_t pre_fused_launch(const uint8_t *bgr, f16 *out, f16 *cond, int H, int W, int Ho, int Wo, const AaTables &t, int mode, hipStream_t s)
 {
-    if (Ho != H / 4 || Wo != W / 4 || Ho < 1 || Wo < 1 || (H & 1) || (W & 1)) return hipErrorInvalidValue;
-    dim3 grid((Wo + PF_OW - 1) / PF_OW, (Ho + PF_OH - 1) / PF_OH, 1);
-    hipLaunchKernelGGL(pre_fused_kernel<Yuv420Src>, grid, dim3(256), 0, s, src, out, cond, H, W, Ho, Wo, wx, xmn, xns, wy, ymn, yns,
-                       mode);
-    return hipGetLastError();
+    return pre_fused_any<PfBgr>(bgr, out, cond, H, W, Ho, Wo, t, mode, s);
 }
 
-hipError_t pre_fused_ycbcr10_launch(const Ycc10Src &src, f16 *out, f16 *cond, int H, int W, int Ho, int Wo, const float *wx,
-                                    const int *xmn, const int *xns, const float *wy, const int *ymn, const int *yns, int mode,
-                                    hipStream_t s)
+hipError_t pre_fused_yuv_launch(const Yuv420Src &src, f16 *out, f16 *cond, int H, int W, int Ho, int Wo, const AaTables &t, int mode, hipStream_t s)
 {
-    if (ycc10_check(src.y, src.y_pitch, src.u, src.v, src.c_pitch, src.fmt, H, W) || Ho != H / 4 || Wo != W / 4 || Ho < 1 || Wo < 1) return hipErrorInvalidValue;
-    const dim3 grid((Wo + PF_OW - 1) / PF_OW, (Ho + PF_OH - 1) / PF_OH);
-    hipLaunchKernelGGL(pre_fused_kernel<Ycc10Src>, grid, dim3(256), 0, s, src, out, cond, H, W, Ho, Wo, wx, xmn, xns, wy, ymn, yns,
-                       mode);
-    return hipGetLastError();
+    if ((H & 1) || (W & 1)) return hipErrorInvalidValue;
+    return pre_fused_any(src, out, cond, H, W, Ho, Wo, t, mode, s);
+}
+
+hipError_t pre_fused_ycbcr10_launch(const Ycc10Src &src, f16 *out, f16 *cond, int H, int W, int Ho, int Wo, const AaTables &t, int mode, hipStream_t s)
+{
+    if (!ycc_ok(src, H, W)) return hipErrorInvalidValue;
+    return pre_fused_any(src, out, cond, H, W, Ho, Wo, t, mode, s);
 }
 
 hipError_t post_u8_launch(const void *in, int is_f32, int H, int W, uint8_t *bgr, hipStream_t s)

@@ -5,40 +5,13 @@
 //  pre_unpack_yuv_f32  planes -> fp32 planar RGB, float(u8) * fp32(1/255): pre_unpack_f32 (fp32_ops.hip) of the converted frame,
 //                      for the fp32 preset (cond_resize_f32 follows).
 //
-// The arithmetic is yuv420.h's rule.  Both kernels work on pixel pairs (2i, 2i + 1) of one row: W is even, so a pair never
-// straddles two rows, and the pair shares its chroma column i.  Plane reads are byte loads (no pointer or pitch is aligned);
+// The arithmetic is ycc_in.h's rule at 8 bits.  Both kernels work on pixel pairs (2i, 2i + 1) of one row (ycc_pair; the fp32 unpack
+// is ycc_unpack_f32<8>, its body).  Plane reads are byte loads (no pointer or pitch is aligned);
 // neighbouring lanes read neighbouring bytes, so each wave load still touches few cache lines.  Built, as every file here except
 // fp32_ops.hip, without the SLP / loop vectorisers.
-#include "launchers.h"
-#include "yuv420.h"
+#include "ycc_in.h"
 
 namespace {
-
-// u8 R, G, B of the two pixels of pair i (luma columns 2i, 2i + 1) of row y.
-__device__ __forceinline__ void yuv_pair(const Yuv420Src &s, int H, int W, int y, int i, uint32_t (&r)[2], uint32_t (&g)[2],
-                                         uint32_t (&b)[2])
-{
-    const int Hc = H >> 1, Wc = W >> 1;
-    const int j = y >> 1, n = (y & 1) ? min(j + 1, Hc - 1) : max(j - 1, 0), i2 = min(i + 1, Wc - 1);
-    const uint8_t *yr = s.y + (size_t)y * s.y_pitch + 2 * i;
-    int u4a, u4b, v4a, v4b;
-    if (s.layout == YUV_NV12) {
-        const uint8_t *cj = s.u + (size_t)j * s.c_pitch, *cn = s.u + (size_t)n * s.c_pitch;
-        u4a = 3 * cj[2 * i] + cn[2 * i];
-        v4a = 3 * cj[2 * i + 1] + cn[2 * i + 1];
-        u4b = 3 * cj[2 * i2] + cn[2 * i2];
-        v4b = 3 * cj[2 * i2 + 1] + cn[2 * i2 + 1];
-    } else {
-        const uint8_t *uj = s.u + (size_t)j * s.c_pitch, *un = s.u + (size_t)n * s.c_pitch;
-        const uint8_t *vj = s.v + (size_t)j * s.c_pitch, *vn = s.v + (size_t)n * s.c_pitch;
-        u4a = 3 * uj[i] + un[i];
-        v4a = 3 * vj[i] + vn[i];
-        u4b = 3 * uj[i2] + un[i2];
-        v4b = 3 * vj[i2] + vn[i2];
-    }
-    yuv_rule(yr[0], 2 * u4a, 2 * v4a, s.k, r[0], g[0], b[0]);
-    yuv_rule(yr[1], u4a + u4b, v4a + v4b, s.k, r[1], g[1], b[1]);
-}
 
 // One lane = 8 consecutive pixels of the frame in raster order (four pairs; a group may span rows when W % 8 != 0).  A8: the
 // destination is 8-byte aligned, and a full group's 24 bytes go out as three 8-byte stores.
@@ -55,7 +28,7 @@ __global__ __launch_bounds__(256) void yuv420_to_bgr_kernel(const Yuv420Src src,
         for (int q = 0; q < 4; ++q) {
             if (q < np) {
                 uint32_t r[2], gg[2], b[2];
-                yuv_pair(src, H, W, y, x >> 1, r, gg, b);
+                ycc_pair(src, H, W, y, x >> 1, r, gg, b);
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int o = (2 * q + h) * 3;
@@ -81,42 +54,15 @@ __global__ __launch_bounds__(256) void yuv420_to_bgr_kernel(const Yuv420Src src,
 
 __global__ __launch_bounds__(256) void pre_unpack_yuv_f32_kernel(const Yuv420Src src, int H, int W, float *__restrict__ out)
 {
-    const float k255 = (float)(1.0 / 255.0);
-    const size_t npix = (size_t)H * W, npair = npix / 2;
-    const int Wc = W >> 1;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < npair; t += (size_t)gridDim.x * blockDim.x) {
-        const int y = (int)(t / (size_t)Wc), i = (int)(t - (size_t)y * Wc);
-        uint32_t r[2], g[2], b[2];
-        yuv_pair(src, H, W, y, i, r, g, b);
-        const size_t o = (size_t)y * W + 2 * i;
-        out[o] = __fmul_rn((float)r[0], k255);
-        out[o + 1] = __fmul_rn((float)r[1], k255);
-        out[npix + o] = __fmul_rn((float)g[0], k255);
-        out[npix + o + 1] = __fmul_rn((float)g[1], k255);
-        out[2 * npix + o] = __fmul_rn((float)b[0], k255);
-        out[2 * npix + o + 1] = __fmul_rn((float)b[1], k255);
-    }
-}
-
-inline int yuv_grid(size_t n)
-{
-    size_t g = (n + 255) / 256;
-    if (g > 2048) g = 2048;   // 256 CUs x 8 blocks, grid-stride beyond (as prepost.hip's ew_grid)
-    return (int)(g < 1 ? 1 : g);
-}
-
-bool yuv_ok(const Yuv420Src &s, int H, int W)
-{
-    return s.y && s.u && (s.layout == YUV_NV12 || s.v) && H > 0 && W > 0 && !(H & 1) && !(W & 1) && s.y_pitch >= W &&
-           s.c_pitch >= (s.layout == YUV_NV12 ? W : W / 2);
+    ycc_unpack_f32(src, H, W, out);
 }
 
 }  // namespace
 
 hipError_t yuv420_to_bgr_launch(const Yuv420Src &src, int H, int W, uint8_t *bgr, hipStream_t s)
 {
-    if (!yuv_ok(src, H, W) || !bgr) return hipErrorInvalidValue;
-    const dim3 g(yuv_grid(((size_t)H * W + 7) / 8)), b(256);
+    if (!ycc_ok(src, H, W) || !bgr) return hipErrorInvalidValue;
+    const dim3 g(ycc_grid(((size_t)H * W + 7) / 8)), b(256);
     if (((uintptr_t)bgr & 7) == 0) hipLaunchKernelGGL(yuv420_to_bgr_kernel<true>, g, b, 0, s, src, H, W, bgr);
     else hipLaunchKernelGGL(yuv420_to_bgr_kernel<false>, g, b, 0, s, src, H, W, bgr);
     return hipGetLastError();
@@ -124,7 +70,7 @@ hipError_t yuv420_to_bgr_launch(const Yuv420Src &src, int H, int W, uint8_t *bgr
 
 hipError_t pre_unpack_yuv_f32_launch(const Yuv420Src &src, int H, int W, float *rgb, hipStream_t s)
 {
-    if (!yuv_ok(src, H, W) || !rgb) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pre_unpack_yuv_f32_kernel, dim3(yuv_grid((size_t)H * W / 2)), dim3(256), 0, s, src, H, W, rgb);
+    if (!ycc_ok(src, H, W) || !rgb) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pre_unpack_yuv_f32_kernel, dim3(ycc_grid((size_t)H * W / 2)), dim3(256), 0, s, src, H, W, rgb);
     return hipGetLastError();
 }

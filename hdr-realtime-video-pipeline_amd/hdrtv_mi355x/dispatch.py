@@ -56,7 +56,7 @@ class _Mi355xWorker:
     stream (and activation workspace: a lane) per frame in flight."""
 
     depth = 2
-    input_format = ("bgr24", 709, False)     # (pix_fmt, matrix, full_range); _worker_main sets the dispatcher's
+    input_format = None                      # the lib.InputFormat of the input slots (None: bgr24); _worker_main sets the dispatcher's
     output_format = None                     # the lib.OutputFormat of the output slots; _worker_main sets the dispatcher's
 
     def __init__(self, rank, device_index, init_args):
@@ -121,14 +121,11 @@ class _Mi355xWorker:
     def begin(self, frame, out):
         torch, p = self._torch, self.proc
         # the processing size is the input slot's (a 4:2:0 slot is (h*3//2, w)), the delivered size the output slot's
-        ten = self.input_format[0] in self._L.YCBCR10_IN_FORMATS
-        if ten:
-            h, w = self._L.ycbcr10_frame_hw(frame, self.input_format[0])
-        else:
-            h, w = (frame.shape[0], frame.shape[1]) if frame.ndim == 3 else (frame.shape[0] * 2 // 3, frame.shape[1])
+        src = self.input_format or self._L.input_format("bgr24")
+        h, w = src.frame_hw(frame)
         fmt = self.output_format
         out_fmt = dict(out_hw=(fmt.h, fmt.w), out_pix_fmt=fmt.pix_fmt, out_siting=fmt.siting, cleanup=self.cleanup, **self.scale._asdict())
-        self._buffers(h, w, tuple(frame.shape) + ((2,) if ten else ()), fmt)       # _raw is bytes: a u16 sample is two
+        self._buffers(h, w, tuple(frame.shape) + ((2,) if frame.itemsize == 2 else ()), fmt)       # _raw is bytes: a u16 sample is two
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
         # frame's kernels with the next frame's (processor.enqueue_frame); one lane = the single compute stream of before
@@ -144,16 +141,7 @@ class _Mi355xWorker:
         main.wait_event(self._up_ev[k])
         if self._dn_ev[k] is not None:
             main.wait_event(self._dn_ev[k])                    # u16[k]'s previous frame has left the device
-        if self.input_format[0] == "bgr24":
-            p.enqueue_frame(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), stream=main, **out_fmt)
-        elif ten:
-            pix_fmt, matrix, full = self.input_format
-            p.enqueue_frame_ycbcr10(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), pix_fmt=pix_fmt, matrix=matrix,
-                                    full_range=full, stream=main, **out_fmt)
-        else:
-            layout, matrix, full = self.input_format
-            p.enqueue_frame_yuv420(lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), layout=layout, matrix=matrix,
-                                   full_range=full, stream=main, **out_fmt)
+        p._enqueue_planes(src, lane, self._raw[k].data_ptr(), h, w, self._u16[k].data_ptr(), stream=main, **out_fmt)
         self._comp_ev[k] = torch.cuda.Event()
         self._comp_ev[k].record(main)
         self._dn.wait_event(self._comp_ev[k])
@@ -252,10 +240,10 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, out_format, t
     code = 0
     try:
         h, w, slots = geom
-        input_format = tuple(input_format or ("bgr24", 709, False))
-        in_shape = _in_shape(h, w, input_format[0])
+        from .lib import input_format as _input_format
+        input_format = input_format or _input_format("bgr24")
+        in_shape, in_dtype = input_format.frame_shape(h, w), input_format.dtype
         out_shape = out_format.shape
-        in_dtype = _in_dtype(input_format[0])
         in_b, out_b = int(np.prod(in_shape)) * np.dtype(in_dtype).itemsize, out_format.nbytes
         # placement first: affinity, then the slots (created and first-touched HERE, on the GPU's node), then the GPU
         from . import numa
@@ -274,7 +262,7 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, out_format, t
         body = make_worker(rank, device_index, init_args)
         if not hasattr(body, "begin"):
             body = _SyncBody(body)
-        if input_format[0] != "bgr24" and hasattr(body, "input_format"):
+        if input_format.family != "bgr24" and hasattr(body, "input_format"):
             body.input_format = input_format
         if hasattr(body, "output_format"):
             body.output_format = out_format
@@ -354,21 +342,6 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, out_format, t
         raise SystemExit(code)
 
 
-def _in_shape(h, w, pix_fmt):
-    """An input slot's frame: u8 BGR (h, w, 3), the planes of an 8-bit 4:2:0 frame back to back (h*3//2, w), or the u16 planes of a
-    10-bit frame (``lib.ycbcr10_frame_shape``: (h*3//2, w), or (2*h, w) for yuv422p10le)."""
-    from . import lib as _L
-    if pix_fmt in _L.YCBCR10_IN_FORMATS:
-        return _L.ycbcr10_frame_shape(pix_fmt, h, w)
-    return (h, w, 3) if pix_fmt == "bgr24" else (h * 3 // 2, w)
-
-
-def _in_dtype(pix_fmt):
-    """u16 samples for the 10-bit formats, bytes for the others."""
-    from . import lib as _L
-    return np.uint16 if pix_fmt in _L.YCBCR10_IN_FORMATS else np.uint8
-
-
 class FrameDispatcher:
     def __init__(self, n_workers, height, width, sink, make_worker=mi355x_worker, init_args=None, devices=None, slots=3,
                  start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False, out_height=None,
@@ -402,10 +375,7 @@ class FrameDispatcher:
         from . import lib as _L
         if pix_fmt not in ("bgr24", "yuv420p", "nv12") + tuple(_L.YCBCR10_IN_FORMATS):
             raise ValueError(f"pix_fmt must be bgr24, yuv420p, nv12 or one of {sorted(_L.YCBCR10_IN_FORMATS)}")
-        if pix_fmt in ("yuv420p", "nv12") and (int(height) % 2 or int(width) % 2):
-            raise ValueError(f"{pix_fmt} frames have even sizes")
-        if int(yuv_matrix) not in (601, 709, 2020):
-            raise ValueError("yuv_matrix must be 601, 709 or 2020")
+        fmt = _L.input_format(pix_fmt, yuv_matrix, yuv_full_range)                 # raises for an unknown matrix
         self.n, self.h, self.w, self.slots = int(n_workers), int(height), int(width), int(slots)
         self.out_h, self.out_w = int(out_height or height), int(out_width or width)
         self.scale = _L.scale_options(antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
@@ -429,8 +399,7 @@ class FrameDispatcher:
         if self.downscaler is not None:
             init_args["downscaler"], init_args["down_antiring"] = self.downscaler, self.down_antiring
         self.pix_fmt = pix_fmt
-        self._in_shape, self._in_dtype = _in_shape(self.h, self.w, pix_fmt), _in_dtype(pix_fmt)     # raises for an odd 10-bit size
-        fmt = (pix_fmt, int(yuv_matrix), bool(yuv_full_range))
+        self._in_shape, self._in_dtype = fmt.frame_shape(self.h, self.w), fmt.dtype         # raises for an odd Y'CbCr size
         self._sink = sink
         ctx = mp.get_context("spawn")           # fresh interpreters: nothing GPU-related is inherited
         self._in_b, self._out_b = int(np.prod(self._in_shape)) * np.dtype(self._in_dtype).itemsize, out.nbytes

@@ -10,6 +10,8 @@ import ctypes as C
 import os
 from typing import NamedTuple
 
+import numpy as np
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_PKG), "lib", "libhdrtv_mi355x.so")
 # the A/B build (make AB=1): the same sources plus superseded kernels, for the GPU bit-identity tests only
@@ -162,31 +164,105 @@ def output_format(pix_fmt, siting, h, w):
 
 
 YCBCR10_IN_FORMATS = dict(YCC_FORMATS)      # the 10-bit input pixel formats: the names and codes of the output side
+YUV_LAYOUTS = {"i420": YUV_I420, "yuv420p": YUV_I420, "nv12": YUV_NV12}      # the 8-bit 4:2:0 input formats ("i420" = "yuv420p")
+IN_PIX_FMTS = ("bgr24",) + tuple(YUV_LAYOUTS) + tuple(YCBCR10_IN_FORMATS)
+
+
+class InputFormat(NamedTuple):
+    """What a source delivers per frame, the twin of ``OutputFormat``: the pixel format and, for Y'CbCr, the matrix (601 / 709 /
+    2020) and range it converts with.  Built by ``input_format`` (which validates); a plain tuple, so it crosses into the
+    dispatcher's worker processes as it is.  It knows its family -- ``bgr24``, ``yuv420`` (8-bit 4:2:0: i420 / yuv420p / nv12) or
+    ``ycbcr10`` (p010le / yuv420p10le / yuv422p10le) --, the array a frame is held as, and the C entry point that reads it."""
+    pix_fmt: str
+    matrix: int = 709
+    full_range: bool = False
+
+    @property
+    def family(self):
+        return "bgr24" if self.pix_fmt == "bgr24" else "yuv420" if self.pix_fmt in YUV_LAYOUTS else "ycbcr10"
+
+    @property
+    def dtype(self):
+        """u16 samples for the 10-bit formats, bytes for the others."""
+        return np.uint16 if self.family == "ycbcr10" else np.uint8
+
+    @property
+    def entry(self):
+        """The C preprocess entry point that serves the format (its ``_letterboxed`` form, where there is one, adds the suffix)."""
+        return {"bgr24": "hdrtv_preprocess", "yuv420": "hdrtv_preprocess_yuv420", "ycbcr10": "hdrtv_preprocess_ycbcr10"}[self.family]
+
+    @property
+    def kwargs(self):
+        """The keyword arguments of the family's public processor methods (``preprocess_yuv420(frame, layout=...)``,
+        ``preprocess_ycbcr10(frame, pix_fmt=...)``)."""
+        name = {"yuv420": "layout", "ycbcr10": "pix_fmt"}[self.family]
+        return {name: self.pix_fmt, "matrix": self.matrix, "full_range": self.full_range}
+
+    def _what(self):
+        c422 = self.pix_fmt == "yuv422p10le"
+        return f"a {self.pix_fmt} frame must be {np.dtype(self.dtype).name} " + \
+            ("[H, W, 3]" if self.family == "bgr24" else f"[{'2*H' if c422 else 'H*3//2'}, W]")
+
+    def frame_shape(self, h, w):
+        """The array shape of an ``h`` x ``w`` frame: BGR ``(h, w, 3)``, or the planes back to back at minimum pitch, ``(h*3//2, w)``
+        for 4:2:0 and ``(2*h, w)`` for ``yuv422p10le``.  Y'CbCr: W even; H even for 4:2:0."""
+        h, w = int(h), int(w)
+        if self.family == "bgr24":
+            return (h, w, 3)
+        c422 = self.pix_fmt == "yuv422p10le"
+        if h <= 0 or w <= 0 or w % 2 or (not c422 and h % 2):
+            raise ValueError(f"{self.pix_fmt} needs an even width{'' if c422 else ' and height'} (got {w}x{h})")
+        return (2 * h, w) if c422 else (h * 3 // 2, w)
+
+    def frame_hw(self, frame):
+        """(H, W) of a frame held as the array of ``frame_shape``."""
+        nd = 3 if self.family == "bgr24" else 2
+        if getattr(frame, "ndim", 0) != nd or str(frame.dtype) != np.dtype(self.dtype).name:
+            raise ValueError(self._what())
+        rows, w = frame.shape[0], frame.shape[1]
+        h = rows if nd == 3 else rows // 2 if self.pix_fmt == "yuv422p10le" else rows // 3 * 2
+        if tuple(frame.shape) != self.frame_shape(h, w):
+            raise ValueError(self._what())
+        return h, w
+
+    def planes(self, ptr, h, w):
+        """The leading arguments of the C entry points for a frame whose planes lie back to back at device address ``ptr`` at their
+        minimum pitches: ``(ptr,)`` for BGR, else (y, y_pitch, u, v, c_pitch, layout, matrix, full_range)."""
+        self.frame_shape(h, w)                                 # raises for a size the format does not have
+        h, w = int(h), int(w)
+        if self.family == "bgr24":
+            return (ptr,)
+        b = np.dtype(self.dtype).itemsize
+        code = YUV_LAYOUTS[self.pix_fmt] if b == 1 else YCBCR10_IN_FORMATS[self.pix_fmt]
+        u, tail = ptr + h * w * b, (code, self.matrix, int(self.full_range))
+        if self.pix_fmt in ("nv12", "p010le"):                 # CbCr interleaved in one plane
+            return (ptr, w * b, u, None, w * b) + tail
+        ch = h if self.pix_fmt == "yuv422p10le" else h // 2
+        return (ptr, w * b, u, u + ch * (w // 2) * b, (w // 2) * b) + tail
+
+
+def input_format(pix_fmt, matrix=709, full_range=False):
+    """The one constructor of ``InputFormat``: a known name and a known matrix."""
+    pix_fmt = str(pix_fmt).lower()
+    if pix_fmt not in IN_PIX_FMTS:
+        raise ValueError(f"pix_fmt must be one of {list(IN_PIX_FMTS)}")
+    if int(matrix) not in (601, 709, 2020):
+        raise ValueError("matrix must be 601, 709 or 2020")
+    return InputFormat(pix_fmt, int(matrix), bool(full_range))
 
 
 def ycbcr10_frame_shape(pix_fmt, h, w):
-    """The u16 array shape of an ``h`` x ``w`` 10-bit frame with its planes back to back at minimum pitch: ``(h*3//2, w)`` for
-    ``p010le`` / ``yuv420p10le``, ``(2*h, w)`` for ``yuv422p10le``.  W even; H even for the two 4:2:0 formats."""
+    """``InputFormat.frame_shape`` of a 10-bit ``pix_fmt``."""
     if pix_fmt not in YCBCR10_IN_FORMATS:
         raise ValueError(f"pix_fmt must be one of {sorted(YCBCR10_IN_FORMATS)}")
-    h, w = int(h), int(w)
-    c422 = pix_fmt == "yuv422p10le"
-    if h <= 0 or w <= 0 or w % 2 or (not c422 and h % 2):
-        raise ValueError(f"{pix_fmt} needs an even width{'' if c422 else ' and height'} (got {w}x{h})")
-    return (2 * h, w) if c422 else (h * 3 // 2, w)
+    return InputFormat(pix_fmt).frame_shape(h, w)
 
 
 def ycbcr10_frame_hw(frame, pix_fmt):
-    """(H, W) of a 10-bit frame held as the u16 array of ``ycbcr10_frame_shape``."""
+    """``InputFormat.frame_hw`` of a 10-bit ``pix_fmt``."""
     if pix_fmt not in YCBCR10_IN_FORMATS:
         raise ValueError(f"pix_fmt must be one of {sorted(YCBCR10_IN_FORMATS)}")
-    c422 = pix_fmt == "yuv422p10le"
-    if getattr(frame, "ndim", 0) != 2 or str(frame.dtype) != "uint16" or frame.shape[0] % (2 if c422 else 3):
-        raise ValueError(f"a {pix_fmt} frame must be uint16 [{'2*H' if c422 else 'H*3//2'}, W]")
-    h, w = (frame.shape[0] // 2 if c422 else frame.shape[0] // 3 * 2), frame.shape[1]
-    if tuple(frame.shape) != ycbcr10_frame_shape(pix_fmt, h, w):
-        raise ValueError(f"a {pix_fmt} frame must be uint16 [{'2*H' if c422 else 'H*3//2'}, W]")
-    return h, w
+    return InputFormat(pix_fmt).frame_hw(frame)
 
 
 def out_frame_bytes(pix_fmt, h, w):

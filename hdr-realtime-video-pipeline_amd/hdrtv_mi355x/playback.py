@@ -181,18 +181,9 @@ class RawVideoSource:
         self.width, self.height, self.fps = int(width), int(height), float(fps)
         if pix_fmt not in self.PIX_FMTS:
             raise ValueError(f"pix_fmt must be one of {self.PIX_FMTS}")
-        if int(yuv_matrix) not in (601, 709, 2020):
-            raise ValueError("yuv_matrix must be 601, 709 or 2020")
-        self.pix_fmt, self.yuv_matrix, self.yuv_full_range = pix_fmt, int(yuv_matrix), bool(yuv_full_range)
-        dtype = np.uint8
-        if pix_fmt == "bgr24":
-            shape = (self.height, self.width, 3)
-        elif pix_fmt in _lib.YCBCR10_IN_FORMATS:
-            shape, dtype = _lib.ycbcr10_frame_shape(pix_fmt, self.height, self.width), np.dtype("<u2")
-        else:
-            if self.width % 2 or self.height % 2:
-                raise ValueError(f"{pix_fmt} frames have even sizes (got {self.width}x{self.height})")
-            shape = (self.height * 3 // 2, self.width)
+        fmt = _lib.input_format(pix_fmt, yuv_matrix, yuv_full_range)
+        self.pix_fmt, self.yuv_matrix, self.yuv_full_range = fmt
+        shape, dtype = fmt.frame_shape(self.height, self.width), np.dtype(fmt.dtype).newbyteorder("<")
         fb = int(np.prod(shape)) * np.dtype(dtype).itemsize
         size = os.path.getsize(path)
         if size < fb or size % fb:

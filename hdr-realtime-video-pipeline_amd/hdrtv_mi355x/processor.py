@@ -433,16 +433,22 @@ class HDRTVNetMI355X:
             opts = _L.scale_options(antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
         return opts.plan(w, h, out.w, out.h)
 
-    def _enqueue(self, lane, pre, what, src, h, w, dst_ptr, stream, out, light_ptr=None, light_rect=None, cleanup=None, scale=None):
-        """The body of ``enqueue_frame*``: the preprocess entry point ``pre`` (named ``what``) on its source arguments ``src``,
-        ``hdrtv_infer_lane`` and ``_post_out``, all on the lane's buffers and ``stream`` (default: the lane's own)."""
+    def _enqueue_planes(self, fmt, lane, src_ptr, h, w, dst_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le", out_siting="left",
+                        light_ptr=None, light_rect=None, cleanup=None, antiring=0.0, cas=0.0, scaler="lanczos",
+                        fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
+        """The body of ``enqueue_frame*`` (whose arguments these are): the argument checks, then the preprocess entry point of the
+        ``lib.InputFormat`` ``fmt`` on the frame at ``src_ptr``, ``hdrtv_infer_lane`` and ``_post_out``, all on the lane's buffers
+        and ``stream`` (default: the lane's own)."""
+        out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
+        src = fmt.planes(src_ptr, h, w)
+        cleanup, plan = self._cleanup_for(cleanup, out), self._plan_for(h, w, out, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
         self._ensure_buffers(h, w)
         st = C.c_void_p((stream if stream is not None else self._lane_streams[lane]).cuda_stream)
         tin, tcond, tout, tagcm = self._lane_bufs[lane]
-        self._chk(pre(self._ctx, st, *src, h, w, tin.data_ptr(), tcond.data_ptr()), what)
+        self._chk(getattr(self._lib, fmt.entry)(self._ctx, st, *src, h, w, tin.data_ptr(), tcond.data_ptr()), fmt.entry)
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), self._out_dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, scale)
+        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, plan)
 
     def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le",
                       out_siting="left", light_ptr=None, light_rect=None, cleanup=None, antiring=0.0, cas=0.0,
@@ -462,19 +468,16 @@ class HDRTVNetMI355X:
         ``fsr_sharpness``, ``downscaler``, ``down_antiring``: how a frame with an ``out_hw`` other than the processing size is resized
         (``lib.ScaleOptions`` describes the six).  The defaults: plain Lanczos to a larger size, a smaller one is a
         ``ValueError``, and a frame at the processing size is touched by none of them."""
-        out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
-        self._enqueue(lane, self._lib.hdrtv_preprocess, "hdrtv_preprocess", (src_bgr_ptr,), h, w, dst_rgb48_ptr, stream, out,
-                      light_ptr, light_rect, self._cleanup_for(cleanup, out), self._plan_for(h, w, out, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring))
+        self._enqueue_planes(_BGR24, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream, out_hw, out_pix_fmt, out_siting,
+                             light_ptr, light_rect, cleanup, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
 
     def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None,
                              out_hw=None, out_pix_fmt="rgb48le", out_siting="left", light_ptr=None, light_rect=None, cleanup=None,
                              antiring=0.0, cas=0.0, scaler="lanczos", fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
         """``enqueue_frame`` of an 8-bit 4:2:0 frame: the planes lie back to back at the device address ``src_ptr`` (the
         ``(h*3//2, w)`` u8 array ``preprocess_yuv420`` takes) and ``hdrtv_preprocess_yuv420`` replaces ``hdrtv_preprocess``."""
-        out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
-        planes = _yuv_planes(src_ptr, int(h), int(w), layout, matrix, full_range)
-        self._enqueue(lane, self._lib.hdrtv_preprocess_yuv420, "hdrtv_preprocess_yuv420", planes, h, w, dst_rgb48_ptr, stream, out,
-                      light_ptr, light_rect, self._cleanup_for(cleanup, out), self._plan_for(h, w, out, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring))
+        self._enqueue_planes(_in_format("yuv420", layout, matrix, full_range), lane, src_ptr, h, w, dst_rgb48_ptr, stream, out_hw, out_pix_fmt,
+                             out_siting, light_ptr, light_rect, cleanup, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
 
     def enqueue_frame_ycbcr10(self, lane, src_ptr, h, w, dst_ptr, *, pix_fmt, matrix=709, full_range=False, stream=None, out_hw=None,
                               out_pix_fmt="rgb48le", out_siting="left", cleanup=None, antiring=0.0, cas=0.0, scaler="lanczos",
@@ -482,10 +485,8 @@ class HDRTVNetMI355X:
         """``enqueue_frame`` of a 10-bit Y'CbCr frame (``pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le``): the planes lie
         back to back at the device address ``src_ptr`` (the u16 array ``preprocess_ycbcr10`` takes) and
         ``hdrtv_preprocess_ycbcr10`` replaces ``hdrtv_preprocess``."""
-        out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
-        planes = _ycbcr10_planes(src_ptr, int(h), int(w), pix_fmt, matrix, full_range)
-        self._enqueue(lane, self._lib.hdrtv_preprocess_ycbcr10, "hdrtv_preprocess_ycbcr10", planes, h, w, dst_ptr, stream, out,
-                      None, None, self._cleanup_for(cleanup, out), self._plan_for(h, w, out, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring))
+        self._enqueue_planes(_in_format("ycbcr10", pix_fmt, matrix, full_range), lane, src_ptr, h, w, dst_ptr, stream, out_hw, out_pix_fmt,
+                             out_siting, None, None, cleanup, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
 
     def _upload(self, key, src, staged=None):
         """Device pointer of the host u8 array ``src``, uploaded through the staging slot kept per ``key`` in ``_staging``: a
@@ -554,85 +555,70 @@ class HDRTVNetMI355X:
                                              self._gpu_input.data_ptr(), self._gpu_cond.data_ptr()), "hdrtv_preprocess")
         return self._gpu_input, self._gpu_cond
 
-    def _yuv_upload(self, frame):
-        """Device pointer of an 8-bit 4:2:0 frame ``(H*3//2, W)`` u8, uploaded through its own staging slot (``_upload``; or the
-        prefetcher's own upload / pinned buffer, as ``preprocess`` uses them) -> (ptr, H, W)."""
-        h, w = _yuv_frame_hw(frame)
-        shape = (h * 3 // 2, w)
+    def _upload_planes(self, fmt, frame):
+        """Device pointer of a Y'CbCr frame (the array of ``fmt.frame_shape``), uploaded through the staging slot of its family
+        (``_upload``: the BGR path's buffers stay as they are), or, for an 8-bit frame, the prefetcher's own upload / pinned buffer
+        as ``preprocess`` uses them."""
+        if fmt.family == "ycbcr10":             # the upload path moves bytes: a u16 frame goes through it as the u8 view of its samples
+            return self._upload("ycbcr10", np.ascontiguousarray(frame).view(np.uint8))
         dev_copy, ready = getattr(frame, "device_tensor", None), getattr(frame, "ready_event", None)
-        if dev_copy is not None and ready is not None and dev_copy.device == self.device and tuple(dev_copy.shape) == shape:
+        if dev_copy is not None and ready is not None and dev_copy.device == self.device and tuple(dev_copy.shape) == tuple(frame.shape):
             torch.cuda.current_stream(self.device).wait_event(ready)
-            return dev_copy.data_ptr(), h, w
-        return self._upload("yuv", frame, getattr(frame, "pinned_tensor", None)), h, w       # the BGR path's buffers stay as they are
+            return dev_copy.data_ptr()
+        return self._upload("yuv", frame, getattr(frame, "pinned_tensor", None))
 
     @torch.inference_mode()
+    def _preprocess_planes(self, fmt, frame, letterbox_to=None):
+        """``preprocess`` of a Y'CbCr frame of the ``lib.InputFormat`` ``fmt``, through its C entry point; with ``letterbox_to =
+        (out_w, out_h)`` other than the frame's size, letterboxed to that size on the device: at ten bits in one launch
+        (``hdrtv_preprocess_ycbcr10_letterboxed``), at eight through BGR at the source size (``hdrtv_yuv420_to_bgr_u8``,
+        ``hdrtv_letterbox_u8``, ``hdrtv_preprocess``)."""
+        sh, sw = fmt.frame_hw(frame)
+        out_w, out_h = (sw, sh) if letterbox_to is None else (int(letterbox_to[0]), int(letterbox_to[1]))
+        planes = fmt.planes(self._upload_planes(fmt, frame), sh, sw)
+        self._ensure_buffers(out_h, out_w)
+        st, dst = self._stream(), (self._gpu_input.data_ptr(), self._gpu_cond.data_ptr())
+        if (sw, sh) == (out_w, out_h):
+            self._chk(getattr(self._lib, fmt.entry)(self._ctx, st, *planes, sh, sw, *dst), fmt.entry)
+        elif fmt.family == "ycbcr10":
+            self._chk(self._lib.hdrtv_preprocess_ycbcr10_letterboxed(self._ctx, st, *planes, sh, sw, out_h, out_w, *dst),
+                      "hdrtv_preprocess_ycbcr10_letterboxed")
+        else:
+            if getattr(self, "_yuv_bgr_shape", None) != (sh, sw):
+                self._yuv_bgr = torch.empty((sh, sw, 3), dtype=torch.uint8, device=self.device)
+                self._yuv_bgr_shape = (sh, sw)
+            self._chk(self._lib.hdrtv_yuv420_to_bgr_u8(self._ctx, st, *planes, sh, sw, self._yuv_bgr.data_ptr()), "hdrtv_yuv420_to_bgr_u8")
+            self._chk(self._lib.hdrtv_letterbox_u8(self._ctx, st, self._yuv_bgr.data_ptr(), sh, sw, self._gpu_raw.data_ptr(), out_h, out_w),
+                      "hdrtv_letterbox_u8")
+            self._chk(self._lib.hdrtv_preprocess(self._ctx, st, self._gpu_raw.data_ptr(), out_h, out_w, *dst), "hdrtv_preprocess")
+        return self._gpu_input, self._gpu_cond
+
     def preprocess_yuv420(self, frame, *, layout="i420", matrix=709, full_range=False):
         """``preprocess`` of an 8-bit 4:2:0 frame: ``frame`` is u8 ``(H*3//2, W)``, the planes back to back as ``ffmpeg -f
         rawvideo -pix_fmt yuv420p`` (``layout="i420"``) or ``nv12`` writes them.  The conversion to RGB (include/hdrtv_mi355x.h:
         ``matrix`` 601 / 709 / 2020, limited or ``full_range``) runs inside the preprocess kernel; the result equals
         ``preprocess`` of the converted BGR frame bit for bit.  Returns the same processor-owned ``(tensor, cond)``."""
-        ptr, h, w = self._yuv_upload(frame)
-        planes = _yuv_planes(ptr, h, w, layout, matrix, full_range)
-        self._ensure_buffers(h, w)
-        self._chk(self._lib.hdrtv_preprocess_yuv420(self._ctx, self._stream(), *planes, h, w, self._gpu_input.data_ptr(),
-                                                    self._gpu_cond.data_ptr()), "hdrtv_preprocess_yuv420")
-        return self._gpu_input, self._gpu_cond
+        return self._preprocess_planes(_in_format("yuv420", layout, matrix, full_range), frame)
 
-    @torch.inference_mode()
     def preprocess_yuv420_letterboxed(self, frame, out_w, out_h, *, layout="i420", matrix=709, full_range=False):
         """``preprocess_letterboxed`` of an 8-bit 4:2:0 frame: converted to BGR on the device at the source size
-        (``hdrtv_yuv420_to_bgr_u8``), then ``hdrtv_letterbox_u8`` and ``hdrtv_preprocess``."""
-        sh, sw = _yuv_frame_hw(frame)
-        out_w, out_h = int(out_w), int(out_h)
-        if (sw, sh) == (out_w, out_h):
-            return self.preprocess_yuv420(frame, layout=layout, matrix=matrix, full_range=full_range)
-        ptr, _, _ = self._yuv_upload(frame)
-        planes = _yuv_planes(ptr, sh, sw, layout, matrix, full_range)
-        self._ensure_buffers(out_h, out_w)
-        if getattr(self, "_yuv_bgr_shape", None) != (sh, sw):
-            self._yuv_bgr = torch.empty((sh, sw, 3), dtype=torch.uint8, device=self.device)
-            self._yuv_bgr_shape = (sh, sw)
-        st = self._stream()
-        self._chk(self._lib.hdrtv_yuv420_to_bgr_u8(self._ctx, st, *planes, sh, sw, self._yuv_bgr.data_ptr()), "hdrtv_yuv420_to_bgr_u8")
-        self._chk(self._lib.hdrtv_letterbox_u8(self._ctx, st, self._yuv_bgr.data_ptr(), sh, sw, self._gpu_raw.data_ptr(), out_h, out_w),
-                  "hdrtv_letterbox_u8")
-        self._chk(self._lib.hdrtv_preprocess(self._ctx, st, self._gpu_raw.data_ptr(), out_h, out_w, self._gpu_input.data_ptr(),
-                                             self._gpu_cond.data_ptr()), "hdrtv_preprocess")
-        return self._gpu_input, self._gpu_cond
+        (``hdrtv_yuv420_to_bgr_u8``), then ``hdrtv_letterbox_u8`` and ``hdrtv_preprocess``.  Equal sizes: ``preprocess_yuv420``."""
+        return self._preprocess_planes(_in_format("yuv420", layout, matrix, full_range), frame, (out_w, out_h))
 
-    @torch.inference_mode()
     def preprocess_ycbcr10(self, frame, *, pix_fmt, matrix=709, full_range=False):
         """``preprocess`` of a 10-bit Y'CbCr frame: ``frame`` is u16, the planes back to back at their minimum pitches as ``ffmpeg
         -f rawvideo -pix_fmt <pix_fmt>`` writes them -- ``(H*3//2, W)`` for ``p010le`` and ``yuv420p10le``, ``(2*H, W)`` for
         ``yuv422p10le``.  The conversion to RGB (include/hdrtv_mi355x.h: ``matrix`` 601 / 709 / 2020, limited or ``full_range``)
         runs inside the preprocess kernel and keeps the ten bits: the tensor holds ``fp16(code / 1023)``.  Returns the same
         processor-owned ``(tensor, cond)``."""
-        h, w = ycbcr10_frame_hw(frame, pix_fmt)
-        # the upload path moves bytes: the frame goes through it as the u8 view of its little-endian samples
-        ptr = self._upload("ycbcr10", np.ascontiguousarray(frame).view(np.uint8))
-        planes = _ycbcr10_planes(ptr, h, w, pix_fmt, matrix, full_range)
-        self._ensure_buffers(h, w)
-        self._chk(self._lib.hdrtv_preprocess_ycbcr10(self._ctx, self._stream(), *planes, h, w, self._gpu_input.data_ptr(),
-                                                     self._gpu_cond.data_ptr()), "hdrtv_preprocess_ycbcr10")
-        return self._gpu_input, self._gpu_cond
+        return self._preprocess_planes(_in_format("ycbcr10", pix_fmt, matrix, full_range), frame)
 
-    @torch.inference_mode()
     def preprocess_ycbcr10_letterboxed(self, frame, out_w, out_h, *, pix_fmt, matrix=709, full_range=False):
         """``preprocess_letterboxed`` of a 10-bit Y'CbCr frame, at ten bits: the planes are uploaded at THEIR size and one kernel
         (``hdrtv_preprocess_ycbcr10_letterboxed``) converts, resizes and pastes them into the ``out_h x out_w`` tensor, which holds
         ``fp16(code / 1023)`` of the letterboxed codes (include/hdrtv_mi355x.h states the rule; a shrink beyond 4x on an axis is
         refused).  Equal sizes: ``preprocess_ycbcr10``."""
-        sh, sw = ycbcr10_frame_hw(frame, pix_fmt)
-        out_w, out_h = int(out_w), int(out_h)
-        if (sw, sh) == (out_w, out_h):
-            return self.preprocess_ycbcr10(frame, pix_fmt=pix_fmt, matrix=matrix, full_range=full_range)
-        ptr = self._upload("ycbcr10", np.ascontiguousarray(frame).view(np.uint8))
-        planes = _ycbcr10_planes(ptr, sh, sw, pix_fmt, matrix, full_range)
-        self._ensure_buffers(out_h, out_w)
-        self._chk(self._lib.hdrtv_preprocess_ycbcr10_letterboxed(self._ctx, self._stream(), *planes, sh, sw, out_h, out_w,
-                                                                 self._gpu_input.data_ptr(), self._gpu_cond.data_ptr()),
-                  "hdrtv_preprocess_ycbcr10_letterboxed")
-        return self._gpu_input, self._gpu_cond
+        return self._preprocess_planes(_in_format("ycbcr10", pix_fmt, matrix, full_range), frame, (out_w, out_h))
 
     @torch.inference_mode()
     def infer(self, input_cond):
@@ -1040,46 +1026,17 @@ def _arch_hr():
 _hip = None
 
 
-YUV_LAYOUTS = {"i420": _L.YUV_I420, "yuv420p": _L.YUV_I420, "nv12": _L.YUV_NV12}
+YUV_LAYOUTS, YCBCR10_IN_FORMATS, ycbcr10_frame_shape, ycbcr10_frame_hw = _L.YUV_LAYOUTS, _L.YCBCR10_IN_FORMATS, _L.ycbcr10_frame_shape, _L.ycbcr10_frame_hw
+
+_BGR24 = _L.input_format("bgr24")
 
 
-def _yuv_frame_hw(frame):
-    """(H, W) of an 8-bit 4:2:0 frame held as a u8 ``(H*3//2, W)`` array; H and W even."""
-    if frame.ndim != 2 or frame.dtype != np.uint8 or frame.shape[0] % 3:
-        raise ValueError("a 4:2:0 frame must be uint8 [H*3//2, W]")
-    h, w = frame.shape[0] // 3 * 2, frame.shape[1]
-    if h % 2 or w % 2 or h <= 0:
-        raise ValueError(f"4:2:0 frames have even sizes (got {w}x{h})")
-    return h, w
-
-
-def _yuv_planes(ptr, h, w, layout, matrix, full_range):
-    """The plane arguments of hdrtv_yuv420_to_bgr_u8 / hdrtv_preprocess_yuv420 for a frame whose planes lie back to back at
-    device address ``ptr``: (y, y_pitch, u, v, c_pitch, layout, matrix, full_range)."""
-    code = YUV_LAYOUTS.get(str(layout).lower())
-    if code is None:
-        raise ValueError(f"layout must be one of {sorted(YUV_LAYOUTS)}")
-    u = ptr + h * w
-    if code == _L.YUV_NV12:
-        return ptr, w, u, None, w, code, int(matrix), int(bool(full_range))
-    return ptr, w, u, u + (h // 2) * (w // 2), w // 2, code, int(matrix), int(bool(full_range))
-
-
-YCBCR10_IN_FORMATS, ycbcr10_frame_shape, ycbcr10_frame_hw = _L.YCBCR10_IN_FORMATS, _L.ycbcr10_frame_shape, _L.ycbcr10_frame_hw
-
-
-def _ycbcr10_planes(ptr, h, w, pix_fmt, matrix, full_range):
-    """The plane arguments of hdrtv_ycbcr10_to_rgb10 / hdrtv_preprocess_ycbcr10 for a frame whose planes lie back to back at
-    device address ``ptr`` at their minimum pitches: (y, y_pitch, u, v, c_pitch, fmt, matrix, full_range)."""
-    ycbcr10_frame_shape(pix_fmt, h, w)
-    if int(matrix) not in (601, 709, 2020):
-        raise ValueError("matrix must be 601, 709 or 2020")
-    fmt = YCBCR10_IN_FORMATS[pix_fmt]
-    u = ptr + h * w * 2
-    if fmt == _L.YCC_P010:
-        return ptr, 2 * w, u, None, 2 * w, fmt, int(matrix), int(bool(full_range))
-    ch = h if fmt == _L.YCC_YUV422P10 else h // 2
-    return ptr, 2 * w, u, u + ch * w, w, fmt, int(matrix), int(bool(full_range))
+def _in_format(family, name, matrix, full_range):
+    """The ``lib.InputFormat`` behind the ``layout=`` / ``pix_fmt=`` argument of the ``*_yuv420`` / ``*_ycbcr10`` methods."""
+    names = YUV_LAYOUTS if family == "yuv420" else YCBCR10_IN_FORMATS
+    if str(name).lower() not in names:
+        raise ValueError(f"{'layout' if family == 'yuv420' else 'pix_fmt'} must be one of {sorted(names)}")
+    return _L.input_format(name, matrix, full_range)
 
 
 def _hip_memcpy_d2d(dst, src, nbytes):

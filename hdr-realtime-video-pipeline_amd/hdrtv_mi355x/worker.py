@@ -26,7 +26,7 @@ import torch
 
 from . import lib as _L
 from .lightlevel import ContentLightLevel
-from .lib import YCBCR10_IN_FORMATS, ycbcr10_frame_hw
+from .lib import YCBCR10_IN_FORMATS, input_format
 from .processor import HDRTVNetMI355X, _dtype_code
 
 _RING_FRAMES = max(2, min(8, int(os.environ.get("HDRTVNET_FEEDER_GPU_RGB48_RING_FRAMES", "3") or 3)))
@@ -176,7 +176,7 @@ class HeadlessPipelineWorker:
         self._hdr_error = None             # exception that ended the feeder thread, re-raised by _process_frame
         self._fallback = None              # (pinned host u16 tensor, device u16 tensor) of the ring-exhaustion fallback
         self.ring_fallbacks = 0
-        self._yuv_format = dict(layout="i420", matrix=709, full_range=False)     # how 2-D (4:2:0) frames convert
+        self._input_format = input_format("i420")      # the lib.InputFormat of 2-D (Y'CbCr) frames: set_input_format
         self._letterbox10 = False          # set_input_format(letterbox=True): 10-bit frames of another size are letterboxed on the device
 
     def set_input_format(self, pix_fmt, yuv_matrix=709, yuv_full_range=False, *, letterbox=False):
@@ -186,12 +186,14 @@ class HeadlessPipelineWorker:
         another size is letterboxed to the processing size on the device, at ten bits (``preprocess_ycbcr10_letterboxed``; 8-bit
         frames are letterboxed whatever the flag says).  3-D frames are BGR whatever is set here."""
         self._letterbox10 = bool(letterbox)
-        if pix_fmt in YCBCR10_IN_FORMATS:      # 2-D u16 frames: HDRTVNetMI355X.preprocess_ycbcr10
-            self._yuv_format = dict(pix_fmt=pix_fmt, matrix=int(yuv_matrix), full_range=bool(yuv_full_range))
-            return
-        if pix_fmt not in ("yuv420p", "nv12"):
+        if pix_fmt not in ("yuv420p", "nv12") + tuple(YCBCR10_IN_FORMATS):
             raise ValueError(f"pix_fmt must be yuv420p, nv12 or one of {sorted(YCBCR10_IN_FORMATS)}")
-        self._yuv_format = dict(layout=pix_fmt, matrix=int(yuv_matrix), full_range=bool(yuv_full_range))
+        self._input_format = input_format(pix_fmt, yuv_matrix, yuv_full_range)
+
+    @property
+    def _yuv_format(self):
+        """The input format as the keyword arguments of the processor's ``preprocess_yuv420`` / ``preprocess_ycbcr10`` methods."""
+        return self._input_format.kwargs
 
     # ---------------------------------------------------------------- status
     def _emit(self, msg):
@@ -311,15 +313,15 @@ class HeadlessPipelineWorker:
             if frame.ndim == 2 and frame.dtype == np.uint16:
                 # 10-bit Y'CbCr planes (set_input_format): converted inside the preprocess kernel; letterboxed there, at ten bits,
                 # only where set_input_format(letterbox=True) asked for it
-                if "pix_fmt" not in self._yuv_format:
+                if self._input_format.family != "ycbcr10":
                     raise ValueError("a uint16 frame needs set_input_format('p010le' | 'yuv420p10le' | 'yuv422p10le')")
-                fh, fw = ycbcr10_frame_hw(frame, self._yuv_format["pix_fmt"])
+                fh, fw = self._input_format.frame_hw(frame)
                 if fw == pw and fh == ph:
                     tensor, cond = self._processor.preprocess_ycbcr10(frame, **self._yuv_format)
                 elif self._letterbox10:
                     tensor, cond = self._processor.preprocess_ycbcr10_letterboxed(frame, pw, ph, **self._yuv_format)
                 else:
-                    raise ValueError(f"a {self._yuv_format['pix_fmt']} source of {fw}x{fh} differs from the processing size {pw}x{ph}: "
+                    raise ValueError(f"a {self._input_format.pix_fmt} source of {fw}x{fh} differs from the processing size {pw}x{ph}: "
                                      "the 10-bit letterbox is off, ask for it with set_input_format(..., letterbox=True) or feed the "
                                      "frame at the processing size")
             elif frame.ndim == 2:

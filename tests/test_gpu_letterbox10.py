@@ -207,7 +207,7 @@ def test_estate_before_reserve_and_einval_leave_the_destinations(golden_dir):
         assert pre(a, 128, 192, DH, DW, None, cond.data_ptr()) == L.EINVAL
         assert pre(a, 128, 192, DH, DW, rgb.data_ptr(), None) == L.EINVAL
         assert pre((None,) + a[1:], 128, 192, DH, DW, rgb.data_ptr(), cond.data_ptr()) == L.EINVAL            # NULL luma plane
-        assert pre(a, 128, 191, DH, DW, rgb.data_ptr(), cond.data_ptr()) == L.EINVAL                          # what ycc10_check refuses
+        assert pre(a, 128, 191, DH, DW, rgb.data_ptr(), cond.data_ptr()) == L.EINVAL                          # what ycc_check refuses
         assert pre(a, 0, 192, DH, DW, rgb.data_ptr(), cond.data_ptr()) == L.EINVAL
         assert pre(a, 128, 192, 0, DW, rgb.data_ptr(), cond.data_ptr()) == L.EINVAL
         assert pre(a, 128, 192, DH, -4, rgb.data_ptr(), cond.data_ptr()) == L.EINVAL

@@ -127,6 +127,22 @@ def test_device_codes_equal_the_rule_every_fmt_matrix_and_range(proc, h, w, fmt)
     assert planes.unchanged()
 
 
+# The smallest frames the chroma walk of csrc/ycc_in.h can still go wrong at: Hc = 1 or Wc = 1 puts the j - 1, j + 1 and i + 1 clamps on
+# the same sample, and the odd-height 4:2:2 frames are legal by the argument rule.  The stand-alone converter needs no hdrtv_reserve.
+TINY = [(2, 2), (2, 6), (6, 2)]
+TINY_CASES = [(h, w, fmt) for fmt in R.PIX_FMTS for h, w in TINY] + [(1, 2, "yuv422p10le"), (3, 4, "yuv422p10le")]
+
+
+@pytest.mark.parametrize("h,w,fmt", TINY_CASES)
+def test_device_codes_smallest_frames(proc, h, w, fmt):
+    """Tight pitches; luma and chroma pitches padded by one dword; the plane bases offset by one sample (two bytes); both."""
+    want = _codes(h, w, fmt)
+    for off, extra in ((0, 0), (0, 4), (2, 0), (2, 4)):
+        planes = Planes(_frame(h, w, fmt), fmt, off=off, extra=extra, seed=off + extra)
+        assert np.array_equal(_to_rgb10(proc, planes, guard=16), want), (off, extra)
+        assert planes.unchanged()
+
+
 # ---- 2. two-byte alignment, padded pitches, guard words, the six unused bits ------------------------------------------------------
 @pytest.mark.parametrize("extra", [2, 6])
 def test_device_codes_offset_planes_padded_pitches_and_guard_words(proc, extra):

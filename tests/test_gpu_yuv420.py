@@ -111,6 +111,23 @@ def test_device_conversion_pitched_misaligned_planes_and_guard_bytes(proc, off):
         assert np.array_equal(_to_bgr(proc, planes, guard=64), R.to_bgr(f, layout)), (layout, h, w)
 
 
+# The smallest frames the chroma walk of csrc/ycc_in.h can still go wrong at: Hc = 1 or Wc = 1 puts the j - 1, j + 1 and i + 1 clamps on
+# the same sample.  The stand-alone converter needs no hdrtv_reserve (whose minimum is 8 x 8).
+TINY = [(2, 2), (2, 6), (6, 2)]
+
+
+@pytest.mark.parametrize("layout", ["i420", "nv12"])
+@pytest.mark.parametrize("h,w", TINY)
+def test_device_conversion_smallest_frames(proc, h, w, layout):
+    """Tight pitches; luma and chroma pitches padded by one dword; the plane bases offset by one sample (one byte); both."""
+    f = R.random_frame(h, w, seed=10 * h + w, layout=layout)
+    want = R.to_bgr(f, layout)
+    cw = w if layout == "nv12" else w // 2
+    for off, pad in ((0, 0), (0, 4), (1, 0), (1, 4)):
+        planes = Planes(f, layout, off=off, yp=w + pad, cp=cw + pad, seed=off + pad)
+        assert np.array_equal(_to_bgr(proc, planes, guard=16), want), (off, pad)
+
+
 def _both(p, planes, h, w):
     """(fused YUV preprocess, BGR preprocess of the device-converted frame) as host arrays."""
     import torch

@@ -8,6 +8,7 @@ alternated round by round so that clocks and cache state are shared (the method 
   8-bit route                             I420                                 hdrtv_yuv420_to_bgr_u8 at the source size, hdrtv_letterbox_u8,
                                                                                hdrtv_preprocess: three launches (preprocess_yuv420_letterboxed)
   hdrtv_preprocess_ycbcr10                the three, at the DESTINATION size   what a frame decoded at the processing size costs
+  hdrtv_letterbox_u8                      BGR                                  the second launch of the 8-bit route on its own
 
 Three geometries, source -> destination: 3840x2160 -> 1920x1080 (2x2 box), 3840x2160 -> 2560x1440 (fractional area),
 1920x1080 -> 3840x2160 (cubic).  MB: the algorithmic bytes of the call (every plane, intermediate and output once).  Each figure:
@@ -30,7 +31,7 @@ GEOMETRIES = [((3840, 2160), (1920, 1080), "2x2 box"), ((3840, 2160), (2560, 144
 def measure(p, src_wh, dst_wh, kind, calls, warmup):
     import torch
     from hdrtv_mi355x import lib as L
-    from hdrtv_mi355x.processor import _ycbcr10_planes, _yuv_planes
+    from hdrtv_mi355x.lib import input_format
     lib, ctx = p._lib, p._ctx
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     (sw, sh), (w, h) = src_wh, dst_wh
@@ -44,7 +45,7 @@ def measure(p, src_wh, dst_wh, kind, calls, warmup):
     i420 = torch.from_numpy(rng.integers(0, 256, (sh * 3 // 2, sw), dtype=np.uint8)).cuda()
     bgr_src = torch.empty((sh, sw, 3), dtype=torch.uint8, device="cuda")
     bgr_dst = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
-    a8 = _yuv_planes(i420.data_ptr(), sh, sw, "i420", 709, False)
+    a8 = input_format("i420").planes(i420.data_ptr(), sh, sw)
 
     def route8():
         rc = lib.hdrtv_yuv420_to_bgr_u8(ctx, st, *a8, sh, sw, bgr_src.data_ptr())
@@ -53,6 +54,8 @@ def measure(p, src_wh, dst_wh, kind, calls, warmup):
 
     # planes in, BGR out and in again at the source size, BGR out and in again at the destination size, tensor and map out
     cases = {"8-bit route i420 (3 launches)": (route8, spx * 3 // 2 + 2 * spx * 3 + 2 * px * 3 + px * 6 + cond_b)}
+    # the u8 letterbox on its own (route8's second launch; its source is the frame route8's first launch left)
+    cases["letterbox_u8 alone"] = (lambda: lib.hdrtv_letterbox_u8(ctx, st, bgr_src.data_ptr(), sh, sw, bgr_dst.data_ptr(), h, w), spx * 3 + px * 3)
     keep = [i420, bgr_src, bgr_dst]
     for fmt in L.YCBCR10_IN_FORMATS:
         def frame(hh, ww):
@@ -61,8 +64,8 @@ def measure(p, src_wh, dst_wh, kind, calls, warmup):
             keep.append(f)
             return f
         fs, fd = frame(sh, sw), frame(h, w)
-        a = _ycbcr10_planes(fs.data_ptr(), sh, sw, fmt, 709, False)
-        ad = _ycbcr10_planes(fd.data_ptr(), h, w, fmt, 709, False)
+        a = input_format(fmt).planes(fs.data_ptr(), sh, sw)
+        ad = input_format(fmt).planes(fd.data_ptr(), h, w)
         rd, rdd = fs.numel() * 2, fd.numel() * 2
         cases[f"letterbox_ycbcr10 {fmt}"] = (lambda a=a: lib.hdrtv_letterbox_ycbcr10(ctx, st, *a, sh, sw, codes.data_ptr(), h, w), rd + px * 6)
         cases[f"preprocess_ycbcr10_letterboxed {fmt}"] = (

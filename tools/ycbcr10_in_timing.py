@@ -28,7 +28,7 @@ MODEL = {"p010le": (3 + 6.375) / 7.875, "yuv420p10le": (3 + 6.375) / 7.875, "yuv
 def measure(p, h, w, calls, warmup):
     import torch
     from hdrtv_mi355x import lib as L
-    from hdrtv_mi355x.processor import _ycbcr10_planes, _yuv_planes
+    from hdrtv_mi355x.lib import input_format
     lib, ctx = p._lib, p._ctx
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     assert lib.hdrtv_reserve(ctx, h, w) == 0, lib.hdrtv_last_error(ctx)
@@ -42,7 +42,7 @@ def measure(p, h, w, calls, warmup):
     i420 = torch.from_numpy(rng.integers(0, 256, (h * 3 // 2, w), dtype=np.uint8)).cuda()
     cases = {
         "preprocess bgr24": (lambda: lib.hdrtv_preprocess(ctx, st, bgr.data_ptr(), h, w, out.data_ptr(), cond.data_ptr()), px * 3 + wr),
-        "preprocess_yuv420 i420": (lambda a=_yuv_planes(i420.data_ptr(), h, w, "i420", 709, False):
+        "preprocess_yuv420 i420": (lambda a=input_format("i420").planes(i420.data_ptr(), h, w):
                                    lib.hdrtv_preprocess_yuv420(ctx, st, *a, h, w, out.data_ptr(), cond.data_ptr()), px * 3 // 2 + wr),
     }
     keep = [bgr, i420]
@@ -51,7 +51,7 @@ def measure(p, h, w, calls, warmup):
         v = rng.integers(0, 1024, shape, dtype=np.uint16)
         f = torch.from_numpy((v << 6) if fmt == "p010le" else v).cuda()
         keep.append(f)
-        a = _ycbcr10_planes(f.data_ptr(), h, w, fmt, 709, False)
+        a = input_format(fmt).planes(f.data_ptr(), h, w)
         rd = shape[0] * shape[1] * 2
         cases[f"preprocess_ycbcr10 {fmt}"] = (lambda a=a: lib.hdrtv_preprocess_ycbcr10(ctx, st, *a, h, w, out.data_ptr(), cond.data_ptr()),
                                               rd + wr)
