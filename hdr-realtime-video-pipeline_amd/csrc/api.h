@@ -1,5 +1,5 @@
 // api.h -- the host side of libhdrtv_mi355x.so: what its translation units share.
-//   hdrtv_api.hip        the exported C ABI (include/hdrtv_mi355x.h), rings, letterbox / metrics / PQ tables
+//   hdrtv_api.hip        the exported C ABI (include/hdrtv_mi355x.h), rings, the device copies of scale_tables.h / resample_tables.h
 //   api_util.hip         fail(), the developer-variant table
 //   api_pack.hip         state_dict -> MFMA operand layouts (build_weights); nothing else of it is visible outside
 //   api_workspace.hip    per-resolution workspace (do_reserve), shapes
@@ -11,7 +11,6 @@
 
 #include <algorithm>
 #include <array>
-#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -22,9 +21,11 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "launchers.h"
+#include "resample_tables.h"
 #include "scale_tables.h"
 
 namespace hdrtv_host {
@@ -146,6 +147,26 @@ struct Arena {
     }
 };
 
+// A device allocation its holder owns (the context's tables and scratch buffers): it only grows; release(), a move into it and the
+// destructor free it, with the context's device current.
+struct DevBuf {
+    void *dev = nullptr; size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(dev, o.dev); std::swap(cap, o.cap); return *this; }      // the old one leaves with o
+    ~DevBuf() { release(); }
+    void release() { if (dev) (void)hipFree(dev); dev = nullptr; cap = 0; }
+    bool ensure(size_t bytes)       // large enough: nothing happens (hipFree waits for kernels in flight); else freed, allocated anew; false: empty
+    {
+        if (bytes <= cap) return true;
+        release();
+        if (hipMalloc(&dev, bytes) != hipSuccess) { dev = nullptr; return false; }
+        cap = bytes; return true;
+    }
+    template <class T>
+    T *at(size_t bytes = 0) const { return reinterpret_cast<T *>(static_cast<char *>(dev) + bytes); }     // what lies at a byte offset
+};
+
 struct ConvLayer {
     size_t wpk = 0, scale = 0, shift = 0;   // weight-arena offsets
     int cin = 0, cout = 0, coutPad = 0, ks = 0, stride = 1, cin_t = 0, bn = 0;
@@ -257,30 +278,21 @@ struct hdrtv_ctx {
     bool taps_partial = false, taps_replayable = false;
     hipStream_t taps_stream = nullptr;
     std::vector<ProfEntry> prof;
-    // letterbox tables (hdrtv_letterbox_u8): device copy for the last geometry
-    int lb_key[4] = {0, 0, 0, 0};
+    std::array<int, 4> lb_key{};          // letterbox tables (hdrtv_letterbox_u8): the last geometry's, their device copy in bufs.lb
     LetterboxParams lb{};
-    void *lb_dev = nullptr;
-    size_t lb_cap = 0;
-    float *pq_bnd = nullptr;              // hdrtv_post_pq_rgb48: the 65536 code boundaries of the PQ quantiser (built on first use)
-    // the RGB48 scalers' device tables, per kind (scale_tables::Kind) and per geometry (H, W, dH, dW): one allocation in the kind's
-    // layout (scale_tables.h) and the downscaler's taps per index; built on first use of a geometry
-    struct ScaleTab {
-        char *dev;
-        int ntx, nty;
-        template <class T>
-        const T *at(size_t bytes = 0) const { return reinterpret_cast<const T *>(dev + bytes); }     // a table at a byte offset of the layout
-    };
-    std::array<std::map<std::array<int, 4>, ScaleTab>, scale_tables::NKINDS> scale_tabs;
-    // objective metrics partial sums
-    double *mt_dev = nullptr;
-    size_t mt_cap = 0;
-    // the full-reference chain (hdrtv_full_reference_metrics and its pieces), allocated on first use: the border counts, the six
-    // histograms, the two evaluation frames, and the area tables per (sh, sw, nh, nw)
-    struct FrBuf { void *dev = nullptr; size_t cap = 0; } fr_counts, fr_hist, fr_eval;
+    // Every device buffer of the entry points beside the workspace and the ring, each allocated on first use; hdrtv_destroy releases
+    // them all by assigning an empty Bufs.  lb: the letterbox tables of lb_key.  pq: the PQ quantiser's 65536 code boundaries and the
+    // kernel's first-guess table.  mt: the metrics' partial sums.  fr_*: the full-reference chain's border counts, six histograms, two
+    // evaluation frames, area tables per (sh, sw, nh, nw).  scale_tabs: the RGB48 scalers' per scale_tables::Kind and (H, W, dH, dW).
+    struct ScaleTab : hdrtv_host::DevBuf { int ntx, nty; };
+    struct AreaTab : hdrtv_host::DevBuf { resample_tables::Layout at; };
+    struct Bufs {
+        hdrtv_host::DevBuf lb, pq, mt, fr_counts, fr_hist, fr_eval;
+        std::map<std::array<int, 4>, AreaTab> fr_tabs;
+        std::array<std::map<std::array<int, 4>, ScaleTab>, scale_tables::NKINDS> scale_tabs;
+    } bufs;
+    const float *pq_bnd() const { return bufs.pq.at<const float>(); }      // null until the first PQ call of the context
     uint32_t *fr_hist_host = nullptr;     // pinned: the histograms' landing place on the host
-    struct AreaTab { char *dev; size_t o_xbeg, o_ybeg, o_xsrc, o_ysrc, o_xw, o_yw; };
-    std::map<std::array<int, 4>, AreaTab> fr_tabs;
     // ring
     std::vector<hdrtv_host::RingSlot> ring;
     int ring_next = 0, ring_H = 0, ring_W = 0, ring_waiters = 0;   // ring_waiters: threads blocked on a slot's event outside ring_mu
@@ -304,6 +316,16 @@ void variants_init(hdrtv_ctx *c);              // defaults, then HDRTV_VARIANTS 
         hipError_t e_ = (expr);                                                                 \
         if (e_ != hipSuccess) return hdrtv_host::fail(c, HDRTV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// `bytes` of host memory into b, grown if need be.  The caller's `what` names the failure: "<what>: table allocation failed"
+// (HDRTV_ENOMEM), "<what>: table upload failed" (HDRTV_EHIP; the buffer is released, not left with half a table).
+inline int upload(hdrtv_ctx *c, DevBuf &b, const char *what, const void *src, size_t bytes)
+{
+    if (!b.ensure(bytes)) return fail(c, HDRTV_ENOMEM, "%s: table allocation failed", what);
+    if (hipMemcpy(b.dev, src, bytes, hipMemcpyHostToDevice) == hipSuccess) return HDRTV_OK;
+    b.release();
+    return fail(c, HDRTV_EHIP, "%s: table upload failed", what);
+}
 
 // ---- api_pack.hip / fp32_graph.hip: the reference's state_dict -> operand layouts in c->wts (hdrtv_create)
 bool build_weights(hdrtv_ctx *c, const Pack &hr, const Pack *hg);

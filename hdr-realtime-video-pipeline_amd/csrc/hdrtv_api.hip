@@ -56,6 +56,16 @@ static int preprocess_planes(hdrtv_ctx *c, void *stream, const Src &src, int H, 
     });
 }
 
+// resample_tables.h on the device: the run tables of params P (LetterboxParams | AreaReduceParams) in the copy of a Built's words
+namespace rt = resample_tables;
+template <class P>
+static void area_slice(P &p, const DevBuf &b, const rt::Layout &o)
+{
+    const int *w = b.at<const int>();
+    p.xbeg = w + o.xbeg; p.ybeg = w + o.ybeg; p.xsrc = w + o.xsrc; p.ysrc = w + o.ysrc;
+    p.xw = (const float *)w + o.xw; p.yw = (const float *)w + o.yw;
+}
+
 // =========================================================================== exported C ABI
 extern "C" {
 
@@ -123,14 +133,7 @@ int hdrtv_destroy(hdrtv_ctx *c)
     (void)hipDeviceSynchronize();
     hdrtv_ring_destroy(c);
     for (hipEvent_t ev : c->prof_ev) (void)hipEventDestroy(ev);
-    if (c->pq_bnd) (void)hipFree(c->pq_bnd);
-    if (c->lb_dev) (void)hipFree(c->lb_dev);
-    for (auto &tabs : c->scale_tabs)
-        for (auto &kv : tabs) (void)hipFree(kv.second.dev);
-    if (c->mt_dev) (void)hipFree(c->mt_dev);
-    for (hdrtv_ctx::FrBuf *b : {&c->fr_counts, &c->fr_hist, &c->fr_eval})
-        if (b->dev) (void)hipFree(b->dev);
-    for (auto &kv : c->fr_tabs) (void)hipFree(kv.second.dev);
+    c->bufs = hdrtv_ctx::Bufs{};           // every DevBuf of the context is released here, with its device current
     if (c->fr_hist_host) (void)hipHostFree(c->fr_hist_host);
     free_workspaces(c);
     if (c->wts.dev) (void)hipFree(c->wts.dev);
@@ -317,47 +320,13 @@ int hdrtv_post_rgb48(hdrtv_ctx *c, void *stream, const void *in, int dtype, int 
     return launched(c, "post_rgb48", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, 0, 0.f, (hipStream_t)stream));
 }
 
-// ST.2084 OETF in double precision (constants gui_objective_metrics.py:63-67) -> u16 code, floor(pq * 65535 + 0.5): the
-// definition the oracle's orc_pq_code states.  bnd[v] = the smallest fp32 y in [0, 1] with code(y) >= v.
-static int pq_code64(float y)
-{
-    const double yp = std::pow((double)y, 0.1593017578125);
-    const double v = std::pow((0.8359375 + 18.8515625 * yp) / (1.0 + 18.6875 * yp), 78.84375);
-    const double q = std::floor(v * 65535.0 + 0.5);
-    return (int)(q < 0.0 ? 0.0 : (q > 65535.0 ? 65535.0 : q));
-}
-static void pq_boundaries(std::vector<float> &bnd)
-{
-    bnd.assign(65536, 0.f);
-    for (int v = 1; v <= 65535; ++v) {
-        // analytic inverse (EOTF) as the first guess, then walk the fp32 grid to the exact boundary
-        const double p = ((double)v - 0.5) / 65535.0, t = std::pow(p, 1.0 / 78.84375);
-        const double num = std::max(t - 0.8359375, 0.0), den = 18.8515625 - 18.6875 * t;
-        float f = (float)std::min(1.0, std::max(0.0, std::pow(num / den, 1.0 / 0.1593017578125)));
-        while (f > 0.f && pq_code64(std::nextafterf(f, -1.f)) >= v) f = std::nextafterf(f, -1.f);
-        while (f < 1.f && pq_code64(f) < v) f = std::nextafterf(f, 2.f);
-        bnd[v] = f;
-    }
-    // first-guess table of the kernel (prepost.hip pq_code): exact codes at the fp32 values ((127 - 27) * 64 + i) << 17
-    const int base = (127 - 27) << 6, n = 27 * 64 + 2;
-    bnd.resize(65536 + n);
-    for (int i = 0; i < n; ++i) {
-        const uint32_t bits = (uint32_t)(base + i) << 17;
-        float y;
-        memcpy(&y, &bits, 4);
-        bnd[65536 + i] = (float)pq_code64(y > 1.f ? 1.f : y);
-    }
-}
-
-// the table of pq_code (post_quant.h) in device memory: built and uploaded by the first PQ call of a context
+// the table of pq_code (post_quant.h), resample_tables.h pq_boundaries: built and uploaded by the first PQ call of a context, then kept
 static int ensure_pq_table(hdrtv_ctx *c, const char *what)
 {
-    if (c->pq_bnd) return HDRTV_OK;
+    if (c->pq_bnd()) return HDRTV_OK;
     std::vector<float> bnd;
-    pq_boundaries(bnd);
-    if (hipMalloc((void **)&c->pq_bnd, bnd.size() * 4) != hipSuccess) { c->pq_bnd = nullptr; return fail(c, HDRTV_ENOMEM, "%s: table allocation failed", what); }
-    HIPCHK(c, hipMemcpy(c->pq_bnd, bnd.data(), bnd.size() * 4, hipMemcpyHostToDevice));
-    return HDRTV_OK;
+    rt::pq_boundaries(bnd);
+    return upload(c, c->bufs.pq, what, bnd.data(), bnd.size() * sizeof(float));
 }
 
 int hdrtv_post_pq_rgb48(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, float peak_nits, uint16_t *dst)
@@ -365,7 +334,7 @@ int hdrtv_post_pq_rgb48(hdrtv_ctx *c, void *stream, const void *in, int dtype, i
     if (!c || !in || !dst || H <= 0 || W <= 0 || !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "bad argument");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = ensure_pq_table(c, "post_pq_rgb48")) return rc;
-    return launched(c, "post_pq_rgb48", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, 1, peak_nits, (hipStream_t)stream, c->pq_bnd));
+    return launched(c, "post_pq_rgb48", post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, 1, peak_nits, (hipStream_t)stream, c->pq_bnd()));
 }
 
 // ------------------------------------------------------------------- 10-bit Y'CbCr output
@@ -395,8 +364,7 @@ int hdrtv_post_ycbcr10(hdrtv_ctx *c, void *stream, const void *in, int dtype, in
     if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_ycbcr10: pq needs peak_nits > 0");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = pq ? ensure_pq_table(c, "post_ycbcr10") : HDRTV_OK) return rc;
-    p.pq_bnd = c->pq_bnd;
-    p.peak = pq ? peak_nits : 0.f;
+    p.pq_bnd = c->pq_bnd(); p.peak = pq ? peak_nits : 0.f;
     return launched(c, "post_ycbcr10", post_ycbcr10_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
@@ -421,8 +389,7 @@ int hdrtv_post_ycbcr10_ex(hdrtv_ctx *c, void *stream, const void *in, int dtype,
     if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_ycbcr10_ex: pq needs peak_nits > 0");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = pq ? ensure_pq_table(c, "post_ycbcr10_ex") : HDRTV_OK) return rc;
-    p.pq_bnd = c->pq_bnd;
-    p.peak = pq ? peak_nits : 0.f;
+    p.pq_bnd = c->pq_bnd(); p.peak = pq ? peak_nits : 0.f;
     return launched(c, "post_ycbcr10_ex", post_ycbcr10_dither_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
@@ -480,8 +447,7 @@ int hdrtv_light_stats(hdrtv_ctx *c, void *stream, const void *in, int dtype, int
     if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "light_stats: pq needs peak_nits > 0");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = pq ? ensure_pq_table(c, "light_stats") : HDRTV_OK) return rc;
-    p.pq_bnd = c->pq_bnd;
-    p.peak = pq ? peak_nits : 0.f;
+    p.pq_bnd = c->pq_bnd(); p.peak = pq ? peak_nits : 0.f;
     return launched(c, "light_stats", light_stats_launch(p, dtype == HDRTV_F32, pq != 0, c->var.at("light_wgs") * c->n_cu, (hipStream_t)stream));
 }
 
@@ -520,7 +486,7 @@ static int scale_begin(hdrtv_ctx *c, const char *what, void *stream, const void 
     if (int rc = pq ? ensure_pq_table(c, what) : HDRTV_OK) return rc;
     *done = dH == H && dW == W;
     if (!*done) return HDRTV_OK;
-    return launched(c, what, post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd));
+    return launched(c, what, post_rgb48_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, (hipStream_t)stream, c->pq_bnd()));
 }
 
 // The device tables of a geometry: first use builds them (allocates, copies), every later call finds them and only launches.  A
@@ -529,23 +495,16 @@ static int scale_begin(hdrtv_ctx *c, const char *what, void *stream, const void 
 static int scale_tables_for(hdrtv_ctx *c, st::Kind kind, const char *what, int H, int W, int dH, int dW,
                             bool (*build)(int, int, int, int, st::Built &), const hdrtv_ctx::ScaleTab **out)
 {
-    auto &tabs = c->scale_tabs[kind];
+    auto &tabs = c->bufs.scale_tabs[kind];
     const std::array<int, 4> key{H, W, dH, dW};
     auto it = tabs.find(key);
     if (it == tabs.end()) {
         st::Built b;
         if (!build(H, W, dH, dW, b)) return fail(c, HDRTV_EINVAL, "%s: the tables of %dx%d -> %dx%d leave the kernel's tile bounds", what, W, H, dW, dH);
-        if (tabs.size() >= 16) {
-            for (auto &kv : tabs) (void)hipFree(kv.second.dev);
-            tabs.clear();
-        }
-        char *dev = nullptr;
-        if (hipMalloc((void **)&dev, b.blob.size()) != hipSuccess) return fail(c, HDRTV_ENOMEM, "%s: table allocation failed", what);
-        if (hipMemcpy(dev, b.blob.data(), b.blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(dev);
-            return fail(c, HDRTV_EHIP, "%s: table upload failed", what);
-        }
-        it = tabs.emplace(key, hdrtv_ctx::ScaleTab{dev, b.ntx, b.nty}).first;
+        if (tabs.size() >= 16) tabs.clear();
+        DevBuf dev;
+        if (int rc = upload(c, dev, what, b.blob.data(), b.blob.size())) return rc;
+        it = tabs.emplace(key, hdrtv_ctx::ScaleTab{{std::move(dev)}, b.ntx, b.nty}).first;
     }
     *out = &it->second;
     return HDRTV_OK;
@@ -566,7 +525,7 @@ static int post_rgb48_scaled(hdrtv_ctx *c, void *stream, const void *in, int dty
     if (int rc = scale_begin(c, what, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, &done); rc || done) return rc;
     const hdrtv_ctx::ScaleTab *t;
     if (int rc = scale_tables_for(c, st::LANCZOS, what, H, W, dH, dW, st::build_lanczos, &t)) return rc;
-    PostScaleParams p{in, dst, t->at<int4>(), t->at<int4>(st::lanczos_ytab(dW)), c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
+    PostScaleParams p{in, dst, t->at<int4>(), t->at<int4>(st::lanczos_ytab(dW)), c->pq_bnd(), pq ? peak_nits : 0.f, H, W, dH, dW};
     if (cas) return launched(c, "post_rgb48_scaled_cas", post_scale_cas_launch(p, antiring, cas, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
     if (antiring) return launched(c, "post_rgb48_scaled_ex", post_scale_ar_launch(p, antiring, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
     return launched(c, what, post_scale_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
@@ -605,7 +564,7 @@ int hdrtv_post_rgb48_fsr(hdrtv_ctx *c, void *stream, const void *in, int dtype, 
     if (int rc = scale_begin(c, what, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, &done); rc || done) return rc;
     const hdrtv_ctx::ScaleTab *t;
     if (int rc = scale_tables_for(c, st::FSR, what, H, W, dH, dW, st::build_fsr, &t)) return rc;
-    PostFsrParams p{in, dst, t->at<int2>(), t->at<int2>(st::fsr_ytab(dW)), c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
+    PostFsrParams p{in, dst, t->at<int2>(), t->at<int2>(st::fsr_ytab(dW)), c->pq_bnd(), pq ? peak_nits : 0.f, H, W, dH, dW};
     const float sharp = rcas ? (float)std::exp2(-(double)sharpness) : 0.f;
     return launched(c, what, post_fsr_launch(p, rcas, sharp, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
@@ -626,7 +585,7 @@ int hdrtv_post_rgb48_down(hdrtv_ctx *c, void *stream, const void *in, int dtype,
     if (int rc = scale_tables_for(c, st::DOWN, what, H, W, dH, dW, st::build_down, &t)) return rc;
     const st::DownLayout l = st::down_layout(dH, dW, t->ntx, t->nty);
     PostDownParams p{in, dst, t->at<int4>(), t->at<int4>(l.yinfo), t->at<int>(l.xq), t->at<int>(l.yq), t->at<float>(l.xw),
-                     t->at<float>(l.yw), c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW, t->ntx, t->nty};
+                     t->at<float>(l.yw), c->pq_bnd(), pq ? peak_nits : 0.f, H, W, dH, dW, t->ntx, t->nty};
     return launched(c, what, post_down_launch(p, antiring, ssim, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
@@ -645,107 +604,40 @@ int hdrtv_post_rgb48_ssimsr(hdrtv_ctx *c, void *stream, const void *in, int dtyp
     if (int rc = scale_tables_for(c, st::SSIMSR, what, H, W, dH, dW, st::build_ssimsr, &t)) return rc;
     const st::SsimsrLayout l = st::ssimsr_layout(H, W, dH, dW);
     PostSsimsrParams p{in, dst, t->at<int4>(), t->at<int4>(l.ysp), t->at<int4>(l.xfin), t->at<int4>(l.yfin), t->at<int4>(l.xlow),
-                       t->at<int4>(l.ylow), t->at<float>(l.xw), t->at<float>(l.yw), c->pq_bnd, pq ? peak_nits : 0.f, H, W, dH, dW};
+                       t->at<int4>(l.ylow), t->at<float>(l.xw), t->at<float>(l.yw), c->pq_bnd(), pq ? peak_nits : 0.f, H, W, dH, dW};
     return launched(c, what, post_ssimsr_launch(p, ssim, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
 // ------------------------------------------------------------------------------- letterbox
-// Geometry and tables of _letterbox_bgr (gui_scaling.py:228-244) as restated in oracle/letterbox_oracle.py.
-static bool letterbox_setup(hdrtv_ctx *c, int sh, int sw, int dh, int dw)
+// Geometry and tables of a letterbox (resample_tables.h).  One geometry is cached, its tables in bufs.lb, which only grows; the key is
+// clear until the new geometry's tables are in place.
+static_assert(rt::COPY == LB_COPY && rt::AREA_INT == LB_AREA_INT && rt::AREA_FRAC == LB_AREA_FRAC && rt::CUBIC == LB_CUBIC, "resample_tables.h's modes are common.h's");
+static int letterbox_setup(hdrtv_ctx *c, const char *what, int sh, int sw, int dh, int dw)
 {
-    if (c->lb_key[0] == sh && c->lb_key[1] == sw && c->lb_key[2] == dh && c->lb_key[3] == dw) return true;
+    const std::array<int, 4> key{sh, sw, dh, dw};
+    if (c->lb_key == key) return HDRTV_OK;
+    c->lb_key = {};
+    const rt::Geometry g = rt::letterbox_geometry(sh, sw, dh, dw);
+    const rt::Built b = g.mode == LB_AREA_FRAC ? rt::pack(rt::area_axis(sw, g.new_w), rt::area_axis(sh, g.new_h))
+                        : g.mode == LB_CUBIC   ? rt::pack(rt::cubic_axis(sw, g.new_w), rt::cubic_axis(sh, g.new_h))
+                                               : rt::Built{};                 // copy, integer area: no tables
+    DevBuf &dev = c->bufs.lb;
+    if (!dev.ensure(b.bytes() + 16) || (!b.words.empty() && hipMemcpy(dev.dev, b.words.data(), b.bytes(), hipMemcpyHostToDevice) != hipSuccess))
+        return fail(c, HDRTV_ENOMEM, "%s: table allocation failed", what);
     LetterboxParams &L = c->lb;
-    memset(&L, 0, sizeof L);
-    L.sh = sh; L.sw = sw; L.dh = dh; L.dw = dw;
-    const double scale = std::min(dw / (double)std::max(sw, 1), dh / (double)std::max(sh, 1));
-    L.new_w = std::max(1, (int)std::nearbyint(sw * scale));          // Python round(): half to even
-    L.new_h = std::max(1, (int)std::nearbyint(sh * scale));
-    L.x0 = (dw - L.new_w) / 2; L.y0 = (dh - L.new_h) / 2;
-    std::vector<int> ints;
-    std::vector<float> flts;
-    size_t o_xbeg = 0, o_ybeg = 0, o_xsrc = 0, o_ysrc = 0, o_xc = 0, o_yc = 0, o_xw = 0, o_yw = 0;
-    if (L.new_w == sw && L.new_h == sh) {
-        L.mode = LB_COPY;
-    } else if (scale < 1.0) {
-        const double sx = sw / (double)L.new_w, sy = sh / (double)L.new_h;
-        const int ix = (int)std::nearbyint(sx), iy = (int)std::nearbyint(sy);
-        if (std::fabs(sx - ix) < DBL_EPSILON && std::fabs(sy - iy) < DBL_EPSILON) {
-            L.mode = LB_AREA_INT; L.ix = ix; L.iy = iy;
-        } else {
-            L.mode = LB_AREA_FRAC;
-            auto tab = [&](int ssize, int dsize, size_t &o_beg, size_t &o_src, size_t &o_w) {
-                const double sc = ssize / (double)dsize;
-                std::vector<int> beg(dsize + 1), src;
-                std::vector<float> w;
-                for (int dx = 0; dx < dsize; ++dx) {
-                    beg[dx] = (int)src.size();
-                    const double f1 = dx * sc, f2 = f1 + sc, cell = std::min(sc, ssize - f1);
-                    int s1 = (int)std::ceil(f1), s2 = (int)std::floor(f2);
-                    s2 = std::min(s2, ssize - 1); s1 = std::min(s1, s2);
-                    if (s1 - f1 > 1e-3) { src.push_back(s1 - 1); w.push_back((float)((s1 - f1) / cell)); }
-                    for (int q = s1; q < s2; ++q) { src.push_back(q); w.push_back((float)(1.0 / cell)); }
-                    if (f2 - s2 > 1e-3) { src.push_back(s2); w.push_back((float)(std::min(std::min(f2 - s2, 1.0), cell) / cell)); }
-                }
-                beg[dsize] = (int)src.size();
-                o_beg = ints.size(); ints.insert(ints.end(), beg.begin(), beg.end());
-                o_src = ints.size(); ints.insert(ints.end(), src.begin(), src.end());
-                o_w = flts.size(); flts.insert(flts.end(), w.begin(), w.end());
-            };
-            tab(sw, L.new_w, o_xbeg, o_xsrc, o_xw);
-            tab(sh, L.new_h, o_ybeg, o_ysrc, o_yw);
-        }
-    } else {
-        L.mode = LB_CUBIC;
-        auto tab = [&](int ssize, int dsize, size_t &o_src, size_t &o_c) {
-            const double sc = ssize / (double)dsize;
-            std::vector<int> src(dsize), co(4 * (size_t)dsize);
-            const float A = -0.75f;
-            for (int d = 0; d < dsize; ++d) {
-                float fx = (float)((d + 0.5) * sc - 0.5);
-                const int s0 = (int)std::floor(fx);
-                fx = fx - (float)s0;
-                src[d] = s0 - 1;
-                volatile float c0 = ((A * (fx + 1.f) - 5.f * A) * (fx + 1.f) + 8.f * A) * (fx + 1.f) - 4.f * A;
-                volatile float c1 = ((A + 2.f) * fx - (A + 3.f)) * fx * fx + 1.f;
-                volatile float c2 = ((A + 2.f) * (1.f - fx) - (A + 3.f)) * (1.f - fx) * (1.f - fx) + 1.f;
-                volatile float c3 = 1.f - c0 - c1 - c2;
-                const float cs[4] = {c0, c1, c2, c3};
-                for (int k = 0; k < 4; ++k) {
-                    const float r = std::nearbyint(cs[k] * 2048.f);
-                    co[4 * (size_t)d + k] = (int)std::max(-32768.f, std::min(32767.f, r));
-                }
-            }
-            o_src = ints.size(); ints.insert(ints.end(), src.begin(), src.end());
-            o_c = ints.size(); ints.insert(ints.end(), co.begin(), co.end());
-        };
-        tab(sw, L.new_w, o_xsrc, o_xc);
-        tab(sh, L.new_h, o_ysrc, o_yc);
-    }
-    const size_t bytes = ints.size() * 4 + flts.size() * 4 + 16;
-    if (bytes > c->lb_cap) {
-        if (c->lb_dev) (void)hipFree(c->lb_dev);
-        c->lb_dev = nullptr; c->lb_cap = 0;
-        if (hipMalloc(&c->lb_dev, bytes) != hipSuccess) { c->lb_dev = nullptr; return false; }
-        c->lb_cap = bytes;
-    }
-    int *di = (int *)c->lb_dev;
-    float *df = (float *)(di + ints.size());
-    if (!ints.empty() && hipMemcpy(di, ints.data(), ints.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
-    if (!flts.empty() && hipMemcpy(df, flts.data(), flts.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
-    L.xbeg = di + o_xbeg; L.ybeg = di + o_ybeg; L.xsrc = di + o_xsrc; L.ysrc = di + o_ysrc;
-    L.xc = di + o_xc; L.yc = di + o_yc; L.xw = df + o_xw; L.yw = df + o_yw;
-    c->lb_key[0] = sh; c->lb_key[1] = sw; c->lb_key[2] = dh; c->lb_key[3] = dw;
-    return true;
+    memset(&L, 0, sizeof L); L.sh = sh; L.sw = sw; L.dh = dh; L.dw = dw;
+    L.new_w = g.new_w; L.new_h = g.new_h; L.x0 = g.x0; L.y0 = g.y0; L.mode = g.mode; L.ix = g.ix; L.iy = g.iy;
+    area_slice(L, dev, b);
+    L.xc = dev.at<const int>() + b.xc; L.yc = dev.at<const int>() + b.yc;
+    c->lb_key = key;
+    return HDRTV_OK;
 }
 
 int hdrtv_letterbox_u8(hdrtv_ctx *c, void *stream, const uint8_t *src_bgr, int sh, int sw, uint8_t *dst_bgr, int dh, int dw)
 {
     if (!c || !src_bgr || !dst_bgr || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0) return fail(c, HDRTV_EINVAL, "letterbox: bad argument");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!letterbox_setup(c, sh, sw, dh, dw)) {
-        c->lb_key[0] = 0;
-        return fail(c, HDRTV_ENOMEM, "letterbox: table allocation failed");
-    }
+    if (int rc = letterbox_setup(c, "letterbox", sh, sw, dh, dw)) return rc;
     LetterboxParams p = c->lb;
     p.src = src_bgr; p.dst = dst_bgr;
     return launched(c, "letterbox", letterbox_launch(p, (hipStream_t)stream));
@@ -764,10 +656,7 @@ static int letterbox10_args(hdrtv_ctx *c, const char *what, const uint16_t *y, i
 
 static int letterbox10_tables(hdrtv_ctx *c, const char *what, int sh, int sw, int dh, int dw)
 {
-    if (!letterbox_setup(c, sh, sw, dh, dw)) {
-        c->lb_key[0] = 0;
-        return fail(c, HDRTV_ENOMEM, "%s: table allocation failed", what);
-    }
+    if (int rc = letterbox_setup(c, what, sh, sw, dh, dw)) return rc;
     if (!letterbox10_size_ok(c->lb))
         return fail(c, HDRTV_EINVAL, "%s: %dx%d -> %dx%d shrinks by more than %dx on an axis", what, sw, sh, c->lb.new_w, c->lb.new_h, LB10_MAX_SHRINK);
     return HDRTV_OK;
@@ -805,20 +694,12 @@ int hdrtv_preprocess_ycbcr10_letterboxed(hdrtv_ctx *c, void *stream, const uint1
 static int metrics_run(hdrtv_ctx *c, MetricsParams &p, bool u16, hipStream_t s, double *out3)
 {
     const size_t nblk = (size_t)metrics_blocks(p.H, p.W);
-    if (nblk > c->mt_cap) {
-        if (c->mt_dev) (void)hipFree(c->mt_dev);
-        c->mt_dev = nullptr; c->mt_cap = 0;
-        if (hipMalloc((void **)&c->mt_dev, nblk * 3 * sizeof(double)) != hipSuccess) {
-            c->mt_dev = nullptr;
-            return fail(c, HDRTV_ENOMEM, "metrics: allocation failed");
-        }
-        c->mt_cap = nblk;
-    }
-    p.partials = c->mt_dev;
+    if (!c->bufs.mt.ensure(nblk * 3 * sizeof(double))) return fail(c, HDRTV_ENOMEM, "metrics: allocation failed");
+    p.partials = c->bufs.mt.at<double>();
     hipError_t e = u16 ? metrics_u16_launch(p, s) : metrics_launch(p, s);
     if (e != hipSuccess) return fail(c, HDRTV_EHIP, "metrics: %s", hipGetErrorString(e));
     std::vector<double> host(nblk * 3);
-    HIPCHK(c, hipMemcpyAsync(host.data(), c->mt_dev, host.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(host.data(), p.partials, host.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     double se = 0.0, ss = 0.0, de = 0.0;
     for (size_t i = 0; i < nblk; ++i) { se += host[3 * i]; ss += host[3 * i + 1]; de += host[3 * i + 2]; }
@@ -841,18 +722,7 @@ int hdrtv_metrics(hdrtv_ctx *c, void *stream, const void *a, const void *b, int 
 }
 
 // ------------------------------------------------------------------- full-reference metrics (include/hdrtv_mi355x.h, R1 .. R6)
-static bool fr_ensure(hdrtv_ctx::FrBuf &b, size_t bytes)
-{
-    if (bytes <= b.cap) return true;
-    if (b.dev) (void)hipFree(b.dev);
-    b.dev = nullptr; b.cap = 0;
-    if (hipMalloc(&b.dev, bytes) != hipSuccess) { b.dev = nullptr; return false; }
-    b.cap = bytes;
-    return true;
-}
-
-// R3's case and, for the table path, computeResizeAreaTab's tables (built in double as oracle/letterbox_oracle.area_tab does, kept
-// per geometry); the sizes have passed area_reduce_size_ok
+// R3's case and, for the table path, resample_tables.h's area tables, kept per geometry; the sizes have passed area_reduce_size_ok
 static int fr_area_setup(hdrtv_ctx *c, const char *what, int sh, int sw, int nh, int nw, AreaReduceParams &p)
 {
     p.sh = sh; p.sw = sw; p.nh = nh; p.nw = nw; p.ix = p.iy = 0;
@@ -863,56 +733,17 @@ static int fr_area_setup(hdrtv_ctx *c, const char *what, int sh, int sw, int nh,
     }
     p.mode = FR_AREA_TAB;
     const std::array<int, 4> key{sh, sw, nh, nw};
-    auto it = c->fr_tabs.find(key);
-    if (it == c->fr_tabs.end()) {
-        std::vector<int> ints;
-        std::vector<float> flts;
-        hdrtv_ctx::AreaTab t{};
-        auto tab = [&](int ssize, int dsize, size_t &o_beg, size_t &o_src, size_t &o_w) {
-            const double sc = ssize / (double)dsize;
-            std::vector<int> beg(dsize + 1), src;
-            std::vector<float> w;
-            for (int dx = 0; dx < dsize; ++dx) {
-                beg[dx] = (int)src.size();
-                const double f1 = dx * sc, f2 = f1 + sc, cell = std::min(sc, ssize - f1);
-                int s1 = (int)std::ceil(f1), s2 = (int)std::floor(f2);
-                s2 = std::min(s2, ssize - 1); s1 = std::min(s1, s2);
-                if (s1 - f1 > 1e-3) { src.push_back(s1 - 1); w.push_back((float)((s1 - f1) / cell)); }
-                for (int q = s1; q < s2; ++q) { src.push_back(q); w.push_back((float)(1.0 / cell)); }
-                if (f2 - s2 > 1e-3) { src.push_back(s2); w.push_back((float)(std::min(std::min(f2 - s2, 1.0), cell) / cell)); }
-            }
-            beg[dsize] = (int)src.size();
-            o_beg = ints.size(); ints.insert(ints.end(), beg.begin(), beg.end());
-            o_src = ints.size(); ints.insert(ints.end(), src.begin(), src.end());
-            o_w = flts.size(); flts.insert(flts.end(), w.begin(), w.end());
-        };
-        tab(sw, nw, t.o_xbeg, t.o_xsrc, t.o_xw);
-        tab(sh, nh, t.o_ybeg, t.o_ysrc, t.o_yw);
-        // a run that is empty or leaves the source would send the kernel outside its segment: refuse the geometry instead
-        for (int axis = 0; axis < 2; ++axis) {
-            const int d = axis ? nh : nw, n = axis ? sh : sw;
-            const int *beg = ints.data() + (axis ? t.o_ybeg : t.o_xbeg), *src = ints.data() + (axis ? t.o_ysrc : t.o_xsrc);
-            for (int i = 0; i < d; ++i) {
-                if (beg[i + 1] <= beg[i]) return fail(c, HDRTV_EINVAL, "%s: empty area run", what);
-                for (int k = beg[i]; k < beg[i + 1]; ++k)
-                    if (src[k] < 0 || src[k] >= n || (k > 0 && k > beg[0] && src[k] < src[k - 1]))
-                        return fail(c, HDRTV_EINVAL, "%s: area run leaves the source", what);
-            }
-        }
-        const size_t bytes = (ints.size() + flts.size()) * 4;
-        if (hipMalloc((void **)&t.dev, bytes) != hipSuccess) return fail(c, HDRTV_ENOMEM, "%s: table allocation failed", what);
-        if (hipMemcpy(t.dev, ints.data(), ints.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(t.dev + ints.size() * 4, flts.data(), flts.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(t.dev);
-            return fail(c, HDRTV_EHIP, "%s: table upload failed", what);
-        }
-        t.o_xw += ints.size(); t.o_yw += ints.size();         // word offsets into the one allocation
-        it = c->fr_tabs.emplace(key, t).first;
+    auto it = c->bufs.fr_tabs.find(key);
+    if (it == c->bufs.fr_tabs.end()) {
+        const rt::Axis x = rt::area_axis(sw, nw), y = rt::area_axis(sh, nh);
+        for (const char *why : {rt::area_runs_err(x, sw), rt::area_runs_err(y, sh)})
+            if (why) return fail(c, HDRTV_EINVAL, "%s: %s", what, why);         // refused before anything is allocated
+        const rt::Built b = rt::pack(x, y);
+        DevBuf dev;
+        if (int rc = upload(c, dev, what, b.words.data(), b.bytes())) return rc;
+        it = c->bufs.fr_tabs.emplace(key, hdrtv_ctx::AreaTab{{std::move(dev)}, b}).first;
     }
-    const hdrtv_ctx::AreaTab &t = it->second;
-    const int *di = (const int *)t.dev;
-    p.xbeg = di + t.o_xbeg; p.ybeg = di + t.o_ybeg; p.xsrc = di + t.o_xsrc; p.ysrc = di + t.o_ysrc;
-    p.xw = (const float *)di + t.o_xw; p.yw = (const float *)di + t.o_yw;
+    area_slice(p, it->second, it->second.at);
     return HDRTV_OK;
 }
 
@@ -945,14 +776,14 @@ static int fr_grade_match(hdrtv_ctx *c, const char *what, hipStream_t s, const u
                           float peak_nits, float *out12)
 {
     const size_t bytes = (size_t)6 * 65536 * sizeof(uint32_t);
-    if (!fr_ensure(c->fr_hist, bytes)) return fail(c, HDRTV_ENOMEM, "%s: histogram allocation failed", what);
-    ChannelHistParams p{{pred, ref}, (uint32_t *)c->fr_hist.dev, H, W, pitch};
+    if (!c->bufs.fr_hist.ensure(bytes)) return fail(c, HDRTV_ENOMEM, "%s: histogram allocation failed", what);
+    ChannelHistParams p{{pred, ref}, c->bufs.fr_hist.at<uint32_t>(), H, W, pitch};
     if (int rc = launched(c, what, channel_hist_launch(p, s))) return rc;
     if (!c->fr_hist_host && hipHostMalloc((void **)&c->fr_hist_host, bytes, hipHostMallocDefault) != hipSuccess) {
         c->fr_hist_host = nullptr;
         return fail(c, HDRTV_ENOMEM, "%s: pinned histogram allocation failed", what);
     }
-    HIPCHK(c, hipMemcpyAsync(c->fr_hist_host, c->fr_hist.dev, bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->fr_hist_host, c->bufs.fr_hist.dev, bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     grade_match_host(c->fr_hist_host, (double)H * W, peak_nits, out12);
     return HDRTV_OK;
@@ -993,11 +824,11 @@ int hdrtv_full_reference_metrics(hdrtv_ctx *c, void *stream, const uint16_t *pre
     int b[4] = {0, H, 0, W};
     if (flags & HDRTV_FR_CROP) {
         const size_t words = (size_t)2 * (H + W);
-        if (!fr_ensure(c->fr_counts, words * sizeof(uint32_t))) return fail(c, HDRTV_ENOMEM, "%s: allocation failed", what);
-        BorderCountsParams bp{{pred, ref}, (uint32_t *)c->fr_counts.dev, H, W};
+        if (!c->bufs.fr_counts.ensure(words * sizeof(uint32_t))) return fail(c, HDRTV_ENOMEM, "%s: allocation failed", what);
+        BorderCountsParams bp{{pred, ref}, c->bufs.fr_counts.at<uint32_t>(), H, W};
         if (int rc = launched(c, what, border_counts_launch(bp, s))) return rc;
         std::vector<uint32_t> cnt(words);
-        HIPCHK(c, hipMemcpyAsync(cnt.data(), c->fr_counts.dev, words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(cnt.data(), c->bufs.fr_counts.dev, words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         int bp_[4], br_[4], r[4];
         const bool hp = fr_bounds(cnt.data(), H, W, bp_), hr = fr_bounds(cnt.data() + H + W, H, W, br_);
@@ -1021,11 +852,11 @@ int hdrtv_full_reference_metrics(hdrtv_ctx *c, void *stream, const uint16_t *pre
         if (!area_reduce_size_ok(h, w, nh, nw))
             return fail(c, HDRTV_EINVAL, "%s: %dx%d -> %dx%d is not a shrink of at most %dx per axis", what, w, h, nw, nh, FR_MAX_SHRINK);
         const size_t frame = ((size_t)nh * nw * 3 * sizeof(uint16_t) + 255) & ~(size_t)255;
-        if (!fr_ensure(c->fr_eval, 2 * frame)) return fail(c, HDRTV_ENOMEM, "%s: allocation failed", what);
+        if (!c->bufs.fr_eval.ensure(2 * frame)) return fail(c, HDRTV_ENOMEM, "%s: allocation failed", what);
         AreaReduceParams ap{};
         if (int rc = fr_area_setup(c, what, h, w, nh, nw, ap)) return rc;
         ap.src[0] = ep; ap.src[1] = er; ap.pitch = pitch;
-        ap.dst[0] = (uint16_t *)c->fr_eval.dev; ap.dst[1] = (uint16_t *)((char *)c->fr_eval.dev + frame);
+        ap.dst[0] = c->bufs.fr_eval.at<uint16_t>(); ap.dst[1] = c->bufs.fr_eval.at<uint16_t>(frame);
         if (int rc = launched(c, what, area_reduce_launch(ap, s))) return rc;
         ep = ap.dst[0]; er = ap.dst[1]; pitch = 3 * nw;
     }

@@ -273,6 +273,90 @@ def test_pq_table_survives_letterbox_growth(golden_dir):
         p.close()
 
 
+def test_device_buffers_grow_while_the_others_are_live(golden_dir):
+    """One context, every entry point that owns a device buffer, interleaved twice, the second time with larger geometries: the PQ
+    table, the letterbox tables (fractional area, then cubic: each call's tables are larger than the last), the metric partial sums,
+    the full-reference chain's counts / evaluation frames / area tables, a scaler's tables.  Each buffer grows (or is built) while the
+    others hold live data; every result is held to the yardstick of the entry point's own test, and what round 1 computed is
+    computed again, equal, after round 2; then close()."""
+    import ctypes as C
+    import torch
+    import metrics_full_ref as R
+    import rgb48_scale_ref as S
+    from hdrtv_mi355x import lib as L
+    from oracle import hdrtvnet_oracle as O
+    from oracle import letterbox_oracle as LB
+    from oracle import metrics_oracle as M
+    p = _hr(golden_dir)
+    try:
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        x = np.random.default_rng(9).uniform(-0.05, 1.05, (3, 72, 128)).astype(np.float32)
+        xin = torch.from_numpy(x).cuda()
+        pq_want = O.post_pq_rgb48(x, 1000.0)
+
+        def pq():
+            u16 = torch.zeros((72, 128, 3), dtype=torch.uint16, device="cuda")
+            p._chk(p._lib.hdrtv_post_pq_rgb48(p._ctx, st, xin.data_ptr(), L.F32, 72, 128, C.c_float(1000.0), u16.data_ptr()), "hdrtv_post_pq_rgb48")
+            return u16.cpu().numpy()
+
+        def letterbox(sh, sw, dh, dw, interp):
+            new_w, new_h, _, _, got_interp = LB.geometry(sw, sh, dw, dh)
+            assert got_interp == interp and (new_w, new_h) != (sw, sh)
+            if interp == LB.AREA:                                  # the table path: not an integer ratio
+                assert sw % new_w and sh % new_h
+            f = np.random.default_rng(sh).integers(0, 256, (sh, sw, 3), dtype=np.uint8)
+            src = torch.from_numpy(f).cuda()
+            dst = torch.empty((dh, dw, 3), dtype=torch.uint8, device="cuda")
+            p._chk(p._lib.hdrtv_letterbox_u8(p._ctx, st, src.data_ptr(), sh, sw, dst.data_ptr(), dh, dw), "hdrtv_letterbox_u8")
+            assert np.array_equal(dst.cpu().numpy(), LB.letterbox_bgr(f, dw, dh)), (sh, sw, dh, dw)
+
+        def metrics(h, w):                                         # tests/test_metrics.py's inputs and tolerances
+            rng = np.random.default_rng(h)
+            a = rng.random((3, h, w), dtype=np.float32)
+            b = np.clip(a + rng.normal(0, 0.03, a.shape).astype(np.float32), -0.05, 1.1).astype(np.float32)
+            got, want = p.objective_metrics(torch.from_numpy(a).cuda()[None], torch.from_numpy(b).cuda()[None]), M.metrics(a, b)
+            assert abs(got["psnr_db"] - want["psnr_db"]) < 1e-3 and abs(got["sssim"] - want["sssim"]) < 2e-5
+            assert abs(got["delta_e_itp"] - want["delta_e_itp"]) < 2e-3 * max(1.0, want["delta_e_itp"])
+
+        def full_reference(h, w, max_side):                        # tests/test_gpu_metrics_full.py's frames and tolerances
+            pred, ref = R.ramp_pair(h, w, h)
+            got, want = p.full_reference_metrics(pred, ref, max_side=max_side), R.full_reference(pred, ref, max_side=max_side)
+            nh, nw = want["eval_size"]
+            assert got["eval_size"] == want["eval_size"] and got["crop_rect"] == want["crop_rect"] == (0, h, 0, w)
+            assert h % nh and w % nw                               # sizes the targets do not divide: the reduction's table path
+            for k in ("psnr_db", "psnr_norm_db"):
+                assert abs(got[k] - want[k]) < 1e-3, k
+            for k in ("sssim", "sssim_norm"):
+                assert abs(got[k] - want[k]) < 2e-5, k
+            for k in ("delta_e_itp", "delta_e_itp_norm"):
+                assert abs(got[k] - want[k]) < 2e-3 * max(1.0, want[k]), k
+            return got
+
+        def scaled(h, w, dh, dw):                                  # tests/test_gpu_rgb48_table_cache.py's composition, exact
+            t = torch.from_numpy(np.random.default_rng(100 * h + w).uniform(-0.25, 1.25, (3, h, w)).astype(np.float32)).cuda()
+            codes = torch.zeros((h, w, 3), dtype=torch.uint16, device="cuda")
+            out = torch.zeros((dh, dw, 3), dtype=torch.uint16, device="cuda")
+            p._chk(p._lib.hdrtv_post_rgb48(p._ctx, st, t.data_ptr(), L.F32, h, w, codes.data_ptr()), "hdrtv_post_rgb48")
+            p._chk(p._lib.hdrtv_post_rgb48_scaled(p._ctx, st, t.data_ptr(), L.F32, h, w, 0, C.c_float(0.0), out.data_ptr(), dh, dw), "hdrtv_post_rgb48_scaled")
+            assert np.array_equal(out.cpu().numpy(), S.scale(codes.cpu().numpy(), dh, dw)), (h, w, dh, dw)
+            return out.cpu().numpy()
+
+        first = {}
+        for rnd, (area, cubic, mt, fr, sc) in enumerate((
+                ((70, 100, 48, 64), (57, 76, 96, 96), (64, 96), (57, 83, 24), (20, 24, 30, 36)),
+                ((200, 250, 128, 160), (120, 160, 256, 256), (128, 200), (150, 199, 80), (40, 48, 60, 72)))):
+            assert np.array_equal(pq(), pq_want), rnd
+            letterbox(*area, LB.AREA)
+            letterbox(*cubic, LB.CUBIC)
+            metrics(*mt)
+            got = {"fr": full_reference(*fr), "sc": scaled(*sc)}
+            first = first or got
+        assert np.array_equal(pq(), pq_want)
+        assert full_reference(57, 83, 24) == first["fr"] and np.array_equal(scaled(20, 24, 30, 36), first["sc"])
+    finally:
+        p.close()
+
+
 def test_hip_graph_follows_mask_r_and_profiling(golden_dir):
     """set_hg_mask_r() after a capture must take effect on the next infer (the captured graph baked the old threshold in),
     and profile_enable() must time real launches, not a replay that records nothing."""
