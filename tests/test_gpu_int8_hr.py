@@ -101,7 +101,9 @@ def test_mixed_w8a8_vs_reference_run(proc_mixed, golden_dir):
 
 
 def test_mixed_w8a8_layers_given_device_inputs(proc_mixed, sd_mixed, golden_dir):
-    """Every W8A8 kernel family against the oracle's fake-quant layer fed the DEVICE's input tensor."""
+    """Every W8A8 kernel family against the oracle's fake-quant layer fed the DEVICE's input tensor.
+    (Subsumed launch by launch, at six sizes and against a derived bound instead of these bars, by tests/test_gpu_le_i8_layers.py;
+    kept as the comparison with the fp32 oracle itself.)"""
     from oracle import hdrtvnet_oracle as O
     d = np.load(os.path.join(golden_dir, "int8_mixed_qat_w8a8_64x96_gradient_s6.npz"))
     sd = sd_mixed
