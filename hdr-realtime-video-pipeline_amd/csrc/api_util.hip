@@ -45,6 +45,8 @@ const std::pair<const char *, int> k_variants[] = {
     {"light_wgs", 2},        // hdrtv_light_stats / hdrtv_rgb48_light_stats: workgroups per CU the grid is capped at, 1 .. 8 (the record does not depend on it;
                              // more workgroups = more loads in flight, but every workgroup ends in global atomics on the one record: 2 is the
                              // fastest of 1 / 2 / 4 / 8 on all three inputs of profiles/light_stats_timing.txt)
+    {"fs_passes", 3},        // hdrtv_post_ycbcr10_fs / hdrtv_rgb48_to_ycbcr10_fs: bit 0 the samples launch, bit 1 the diffusion launch; 1 and 2 exist to
+                             // time the two launches apart (tools/fs_dither_timing.py) and do not give the conversion
     {"f32_narrow_below", 0}, // precision="fp32": workgroups per CU below which conv_f32 runs 8 channels per lane (0 = 3)
     {"f32_mfma", 1},         // precision="fp32": 3x3 / stride-1 layers on v_mfma_f32_32x32x2_f32 (conv_f32_mfma); 0 = every layer on the vector-FMA kernel
 };

@@ -467,6 +467,20 @@ struct Ycbcr10Params {
     int H, W, y_pitch, c_pitch, fmt, siting;
 };
 
+// Floyd-Steinberg error diffusion of the 10-bit Y'CbCr output (post_ycbcr_fs.hip; include/hdrtv_mi355x.h states the integer rule):
+// one workgroup per plane keeps FS_ROWS rows in flight (a lane owns a row) and stages samples in and out in chunks of FS_CHUNK columns.
+constexpr int FS_ROWS = 256, FS_CHUNK = 32;
+struct FsPlane {
+    const int32_t *u;                // the samples in 1/4096 code, [h][w]
+    int32_t *carry;                  // [w]: the error the last row of a row group leaves to the first row of the next
+    uint16_t *dst;                   // sample (i, j) at dst[j * pitch + i * xstride]
+    int h, w, pitch, xstride;        // P010's Cb / Cr: xstride 2 into the one interleaved plane
+    int lo, hi, base, shl;           // k is clamped to [lo, hi]; the sample is (base + k) << shl
+};
+struct FsParams {
+    FsPlane pl[3];                   // Y', Cb, Cr: one workgroup each
+};
+
 // Debanding of RGB48 codes (post_deband.hip; include/hdrtv_mi355x.h states the integer rule): a workgroup owns DB_TH x DB_TW pixels
 // and stages them with a halo of DB_HALO = the largest range on every side.
 constexpr int DB_TW = 128, DB_TH = 32, DB_HALO = 16;

@@ -161,6 +161,7 @@ int hdrtv_set_variant(hdrtv_ctx *c, const char *name, int value)
     // the row kernels take any segment height >= 1 (tests/test_gpu_le_rows.py: test_short_segments_*); 0 or less is a typo
     if (n == "le_rows_min" && (value < 1 || value > 4096)) return fail(c, HDRTV_EINVAL, "variant le_rows_min must be 1 .. 4096");
     if (n == "light_wgs" && (value < 1 || value > 8)) return fail(c, HDRTV_EINVAL, "variant light_wgs must be 1 .. 8");
+    if (n == "fs_passes" && (value < 1 || value > 3)) return fail(c, HDRTV_EINVAL, "variant fs_passes must be 1 .. 3");
     if (n == "force_ncu") {                 // sizes grids at launch time only (no workspace depends on it): takes effect at once
         if (value < 0) return fail(c, HDRTV_EINVAL, "variant force_ncu must be >= 0");
         c->n_cu = value > 0 ? value : c->dev_ncu;
@@ -402,6 +403,44 @@ int hdrtv_rgb48_to_ycbcr10_ex(hdrtv_ctx *c, void *stream, const uint16_t *src, i
     if (int rc = ycbcr10_args(c, "rgb48_to_ycbcr10_ex", src, H, W, fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch, p)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     return launched(c, "rgb48_to_ycbcr10_ex", rgb48_to_ycbcr10_dither_launch(p, (hipStream_t)stream));
+}
+
+// Floyd-Steinberg error diffusion: the argument rules of the plain entry points, and the caller's scratch
+int64_t hdrtv_ycbcr10_fs_scratch_bytes(int fmt, int H, int W)
+{
+    const int64_t n = ycbcr10_fs_scratch_bytes(fmt, H, W);
+    return n < 0 ? HDRTV_EINVAL : n;
+}
+
+static int fs_scratch_arg(hdrtv_ctx *c, const char *what, const void *scratch)
+{
+    if (!scratch) return fail(c, HDRTV_EINVAL, "%s: scratch is NULL", what);
+    if (reinterpret_cast<uintptr_t>(scratch) & 3) return fail(c, HDRTV_EINVAL, "%s: scratch must be 4-byte aligned", what);
+    return HDRTV_OK;
+}
+
+int hdrtv_post_ycbcr10_fs(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits, int fmt, int siting,
+                          uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch, void *scratch)
+{
+    Ycbcr10Params p;
+    if (int rc = ycbcr10_args(c, "post_ycbcr10_fs", in, H, W, fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch, p)) return rc;
+    if (int rc = fs_scratch_arg(c, "post_ycbcr10_fs", scratch)) return rc;
+    if (dtype != HDRTV_F16 && dtype != HDRTV_F32) return fail(c, HDRTV_EINVAL, "post_ycbcr10_fs: bad dtype %d", dtype);
+    if (pq && !(peak_nits > 0.f)) return fail(c, HDRTV_EINVAL, "post_ycbcr10_fs: pq needs peak_nits > 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = pq ? ensure_pq_table(c, "post_ycbcr10_fs") : HDRTV_OK) return rc;
+    p.pq_bnd = c->pq_bnd(); p.peak = pq ? peak_nits : 0.f;
+    return launched(c, "post_ycbcr10_fs", post_ycbcr10_fs_launch(p, dtype == HDRTV_F32, pq != 0, scratch, c->var.at("fs_passes"), (hipStream_t)stream));
+}
+
+int hdrtv_rgb48_to_ycbcr10_fs(hdrtv_ctx *c, void *stream, const uint16_t *src, int H, int W, int fmt, int siting, uint16_t *dst_y,
+                              int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch, void *scratch)
+{
+    Ycbcr10Params p;
+    if (int rc = ycbcr10_args(c, "rgb48_to_ycbcr10_fs", src, H, W, fmt, siting, dst_y, y_pitch, dst_u, dst_v, c_pitch, p)) return rc;
+    if (int rc = fs_scratch_arg(c, "rgb48_to_ycbcr10_fs", scratch)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return launched(c, "rgb48_to_ycbcr10_fs", rgb48_to_ycbcr10_fs_launch(p, scratch, c->var.at("fs_passes"), (hipStream_t)stream));
 }
 
 // ------------------------------------------------------------------- debanding of RGB48 codes

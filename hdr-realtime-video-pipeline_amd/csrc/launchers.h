@@ -171,6 +171,11 @@ hipError_t rgb48_to_ycbcr10_launch(const Ycbcr10Params &p, hipStream_t s);
 // the same two with the ordered dither of include/hdrtv_mi355x.h (post_ycbcr_dither.hip)
 hipError_t post_ycbcr10_dither_launch(const Ycbcr10Params &p, int is_f32, int pq, hipStream_t s);
 hipError_t rgb48_to_ycbcr10_dither_launch(const Ycbcr10Params &p, hipStream_t s);
+// the same two with Floyd-Steinberg error diffusion (post_ycbcr_fs.hip): a samples launch into `scratch` (ycbcr10_fs_scratch_bytes
+// bytes, 4-byte aligned), then the diffusion launch; passes: bit 0 the samples launch, bit 1 the diffusion launch (3 = the conversion)
+int64_t ycbcr10_fs_scratch_bytes(int fmt, int H, int W);       // negative for a bad argument
+hipError_t post_ycbcr10_fs_launch(const Ycbcr10Params &p, int is_f32, int pq, void *scratch, int passes, hipStream_t s);
+hipError_t rgb48_to_ycbcr10_fs_launch(const Ycbcr10Params &p, void *scratch, int passes, hipStream_t s);
 // hipErrorInvalidValue, nothing enqueued, unless H, W >= 1, range in 1 .. DB_HALO, threshold in 1 .. 65535 and src != dst
 hipError_t rgb48_deband_launch(const DebandParams &p, hipStream_t s);
 // zero the record on `s`, then one kernel over the rectangle on at most max_wgs workgroups (the record does not depend on the grid);

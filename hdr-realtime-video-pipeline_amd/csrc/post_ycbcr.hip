@@ -29,14 +29,14 @@ template <typename T, bool PQ, int FMT>
 __global__ __launch_bounds__(256) void post_ycbcr10_kernel(Ycbcr10Params p)
 {
     const TensorSrc<T, PQ> src{static_cast<const T *>(p.in), (size_t)p.H * p.W, p.W, p.peak, p.pq_bnd};
-    ycbcr_tile<TensorSrc<T, PQ>, FMT, false>(src, p);
+    ycbcr_tile<TensorSrc<T, PQ>, FMT, YC_ROUND>(src, p);
 }
 
 template <int FMT>
 __global__ __launch_bounds__(256) void rgb48_ycbcr10_kernel(Ycbcr10Params p)
 {
     const Rgb48Src src{static_cast<const uint16_t *>(p.in), p.W};
-    ycbcr_tile<Rgb48Src, FMT, false>(src, p);
+    ycbcr_tile<Rgb48Src, FMT, YC_ROUND>(src, p);
 }
 
 template <typename T, bool PQ>

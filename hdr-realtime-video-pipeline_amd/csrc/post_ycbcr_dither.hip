@@ -1,6 +1,6 @@
 // post_ycbcr_dither.hip -- the 10-bit Y'CbCr conversions of post_ycbcr.hip with the ordered dither of include/hdrtv_mi355x.h
 // (hdrtv_post_ycbcr10_ex / hdrtv_rgb48_to_ycbcr10_ex with dither = HDRTV_DITHER_ORDERED) on the device (gfx950).  The same tile code
-// (post_ycbcr_tile.h: tile, lanes' jobs, LDS layout and bank reasoning as post_ycbcr.hip describes them) with DITHER = true: the
+// (post_ycbcr_tile.h: tile, lanes' jobs, LDS layout and bank reasoning as post_ycbcr.hip describes them) with MODE = YC_ORDERED: the
 // rounding constant of every luma and chroma sample is (2 M + 1) scaled to the sample's shift, M the 16 x 16 Bayer index computed
 // from the sample's own coordinates -- a bit reverse, two shifts and masks per nibble, no table and no memory access.
 // The instances live in their own file, under their own names, so that post_ycbcr.hip keeps exactly the kernels it had.
@@ -12,14 +12,14 @@ template <typename T, bool PQ, int FMT>
 __global__ __launch_bounds__(256) void post_ycc10_dither_kernel(Ycbcr10Params p)
 {
     const TensorSrc<T, PQ> src{static_cast<const T *>(p.in), (size_t)p.H * p.W, p.W, p.peak, p.pq_bnd};
-    ycbcr_tile<TensorSrc<T, PQ>, FMT, true>(src, p);
+    ycbcr_tile<TensorSrc<T, PQ>, FMT, YC_ORDERED>(src, p);
 }
 
 template <int FMT>
 __global__ __launch_bounds__(256) void rgb48_ycc10_dither_kernel(Ycbcr10Params p)
 {
     const Rgb48Src src{static_cast<const uint16_t *>(p.in), p.W};
-    ycbcr_tile<Rgb48Src, FMT, true>(src, p);
+    ycbcr_tile<Rgb48Src, FMT, YC_ORDERED>(src, p);
 }
 
 template <typename T, bool PQ>

@@ -1,6 +1,7 @@
 // post_ycbcr_tile.h -- the tile code of the 10-bit Y'CbCr conversion (include/hdrtv_mi355x.h states the integer rule), shared by
-// post_ycbcr.hip (the rule's own rounding constants) and post_ycbcr_dither.hip (DITHER = true: the 16 x 16 Bayer threshold in their
-// place): the two sources, the luma / staging pass and the chroma pass.  post_ycbcr.hip's header comment describes the tile, the
+// post_ycbcr.hip (MODE = YC_ROUND: the rule's own rounding constants), post_ycbcr_dither.hip (YC_ORDERED: the 16 x 16 Bayer threshold
+// in their place) and post_ycbcr_fs.hip (YC_FS_SAMPLES: the samples in 1/4096 code as int32, for the error diffusion that follows):
+// the two sources, the luma / staging pass and the chroma pass.  post_ycbcr.hip's header comment describes the tile, the
 // lanes' jobs and the LDS layout; the dither adds a handful of integer operations per sample and no memory access.
 #pragma once
 #include "launchers.h"
@@ -16,6 +17,11 @@ constexpr int YC_GW = YC_TW / 8;        // eight-pixel groups per tile row
 static_assert(YC_GW == 16 && YC_TH * YC_GW == 256 && YC_LR <= 64, "one stage job per lane; the halo column fits one wave");
 
 // rnd(K * 2^20 * 876 / 65535) and rnd(K' * 2^20 * 896 / 65535), green the remainder (the header derives them)
+// what a sample becomes: rounded to ten bits, rounded against the Bayer threshold, or kept in 1/4096 code (u of the header's
+// Floyd-Steinberg rule) and written as int32 -- then p.dst_y / dst_u / dst_v are int32 planes (Y', Cb, Cr; P010 is not interleaved
+// here) and the pitches count int32 elements
+constexpr int YC_ROUND = 0, YC_ORDERED = 1, YC_FS_SAMPLES = 2;
+
 constexpr int YC_YR = 3682, YC_YG = 9503, YC_YB = 831;
 constexpr int YC_UR = -2002, YC_UG = -5166, YC_UB = 7168;
 constexpr int YC_VR = 7168, YC_VG = -6591, YC_VB = -577;
@@ -122,8 +128,9 @@ __device__ __forceinline__ uint32_t bayer16(int x, int y) { return (bayer_spread
 
 // Four chroma samples of chroma row `crow` of the tile, first luma column 8 * g.  VM = the vertical taps: 0 one row (4:2:2),
 // 1 rows 2j, 2j + 1 (left siting, Wt 8), 2 rows 2j - 1, 2j, 2j + 1 with weights 1 2 1 (top-left siting, Wt 16); Wt = 4 << VM.
-// DITHER: (ci, cj) = column and row of the first sample in the chroma plane; the rounding constant becomes (2 M + 1) << (SH - 9).
-template <int VM, bool DITHER>
+// YC_ORDERED: (ci, cj) = column and row of the first sample in the chroma plane; the rounding constant becomes (2 M + 1) << (SH - 9).
+// YC_FS_SAMPLES: cb / cr hold the signed samples (sum + (1 << (SH - 13))) >> (SH - 12), without the 512.
+template <int VM, int MODE>
 __device__ __forceinline__ void chroma4(const uint16_t (*codes)[YC_LR][YC_RS], int crow, int g, int ci, int cj, uint32_t (&cb)[4],
                                         uint32_t (&cr)[4])
 {
@@ -150,15 +157,20 @@ __device__ __forceinline__ void chroma4(const uint16_t (*codes)[YC_LR][YC_RS], i
     constexpr int SH = 22 + VM;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const long long rnd = DITHER ? (long long)(2 * bayer16(ci + j, cj) + 1) << (SH - 9) : HALF;
+        const long long rnd = MODE == YC_FS_SAMPLES ? 1ll << (SH - 13) : MODE == YC_ORDERED ? (long long)(2 * bayer16(ci + j, cj) + 1) << (SH - 9) : HALF;
         const long long u = (long long)YC_UR * h[0][j] + (long long)YC_UG * h[1][j] + (long long)YC_UB * h[2][j] + rnd;
         const long long v = (long long)YC_VR * h[0][j] + (long long)YC_VG * h[1][j] + (long long)YC_VB * h[2][j] + rnd;
-        cb[j] = (uint32_t)(512 + (int)(u >> SH));
-        cr[j] = (uint32_t)(512 + (int)(v >> SH));
+        if (MODE == YC_FS_SAMPLES) {
+            cb[j] = (uint32_t)(int)(u >> (SH - 12));
+            cr[j] = (uint32_t)(int)(v >> (SH - 12));
+        } else {
+            cb[j] = (uint32_t)(512 + (int)(u >> SH));
+            cr[j] = (uint32_t)(512 + (int)(v >> SH));
+        }
     }
 }
 
-template <typename SRC, int FMT, bool DITHER>
+template <typename SRC, int FMT, int MODE>
 __device__ __forceinline__ void ycbcr_tile(const SRC &src, const Ycbcr10Params &p)
 {
     __shared__ __attribute__((aligned(16))) uint16_t codes[3][YC_LR][YC_RS];
@@ -177,13 +189,27 @@ __device__ __forceinline__ void ycbcr_tile(const SRC &src, const Ycbcr10Params &
             src.px8(y, x, n, q);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const int rnd = DITHER ? (int)((2 * bayer16(x + i, y) + 1) << 11) : 1 << 19;
-                yy[i] = (uint32_t)(64 + ((YC_YR * (int)q[0][i] + YC_YG * (int)q[1][i] + YC_YB * (int)q[2][i] + rnd) >> 20)) << SHL;
+                if (MODE == YC_FS_SAMPLES) {
+                    yy[i] = (uint32_t)((YC_YR * (int)q[0][i] + YC_YG * (int)q[1][i] + YC_YB * (int)q[2][i] + (1 << 7)) >> 8);
+                } else {
+                    const int rnd = MODE == YC_ORDERED ? (int)((2 * bayer16(x + i, y) + 1) << 11) : 1 << 19;
+                    yy[i] = (uint32_t)(64 + ((YC_YR * (int)q[0][i] + YC_YG * (int)q[1][i] + YC_YB * (int)q[2][i] + rnd) >> 20)) << SHL;
+                }
             }
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) *reinterpret_cast<uint4 *>(&codes[ch][r + 1][YC_C0 + 8 * g]) = pack8(q[ch]);
             uint16_t *d = p.dst_y + (size_t)y * p.y_pitch + x;
-            if (n == 8 && aligned_to(d, 16)) {
+            if (MODE == YC_FS_SAMPLES) {
+                uint32_t *d32 = reinterpret_cast<uint32_t *>(p.dst_y) + (size_t)y * p.y_pitch + x;
+                if (n == 8 && aligned_to(d32, 16)) {
+                    reinterpret_cast<uint4 *>(d32)[0] = make_uint4(yy[0], yy[1], yy[2], yy[3]);
+                    reinterpret_cast<uint4 *>(d32)[1] = make_uint4(yy[4], yy[5], yy[6], yy[7]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i)
+                        if (i < n) d32[i] = yy[i];
+                }
+            } else if (n == 8 && aligned_to(d, 16)) {
                 *reinterpret_cast<uint4 *>(d) = pack8(yy);
             } else {
 #pragma unroll
@@ -222,10 +248,25 @@ __device__ __forceinline__ void ycbcr_tile(const SRC &src, const Ycbcr10Params &
         if (y >= p.H || x >= p.W) continue;
         uint32_t cb[4], cr[4];
         const int nc = min(4, (p.W - x) >> 1), cy = V422 ? y : y >> 1;
-        if (V422) chroma4<0, DITHER>(codes, crow, g, x >> 1, cy, cb, cr);
-        else if (topleft) chroma4<2, DITHER>(codes, crow, g, x >> 1, cy, cb, cr);
-        else chroma4<1, DITHER>(codes, crow, g, x >> 1, cy, cb, cr);
-        if (FMT == HDRTV_YCC_P010) {
+        if (V422) chroma4<0, MODE>(codes, crow, g, x >> 1, cy, cb, cr);
+        else if (topleft) chroma4<2, MODE>(codes, crow, g, x >> 1, cy, cb, cr);
+        else chroma4<1, MODE>(codes, crow, g, x >> 1, cy, cb, cr);
+        if (MODE == YC_FS_SAMPLES) {
+            uint32_t *du = reinterpret_cast<uint32_t *>(p.dst_u) + (size_t)cy * p.c_pitch + (x >> 1);
+            uint32_t *dv = reinterpret_cast<uint32_t *>(p.dst_v) + (size_t)cy * p.c_pitch + (x >> 1);
+            if (nc == 4 && aligned_to(du, 16) && aligned_to(dv, 16)) {
+                *reinterpret_cast<uint4 *>(du) = make_uint4(cb[0], cb[1], cb[2], cb[3]);
+                *reinterpret_cast<uint4 *>(dv) = make_uint4(cr[0], cr[1], cr[2], cr[3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (j < nc) {
+                        du[j] = cb[j];
+                        dv[j] = cr[j];
+                    }
+                }
+            }
+        } else if (FMT == HDRTV_YCC_P010) {
             uint16_t *d = p.dst_u + (size_t)cy * p.c_pitch + x;
             if (nc == 4 && aligned_to(d, 16)) {
                 *reinterpret_cast<uint4 *>(d) = make_uint4((cb[0] | (cr[0] << 16)) << 6, (cb[1] | (cr[1] << 16)) << 6,

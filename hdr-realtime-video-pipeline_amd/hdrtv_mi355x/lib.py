@@ -24,6 +24,8 @@ YUV_I420, YUV_NV12 = 0, 1                  # hdrtv_yuv420_to_bgr_u8 / hdrtv_prep
 YCC_P010, YCC_YUV420P10, YCC_YUV422P10 = 0, 1, 2   # hdrtv_post_ycbcr10 / hdrtv_rgb48_to_ycbcr10 / hdrtv_preprocess_ycbcr10 layouts
 SITING_LEFT, SITING_TOPLEFT = 0, 1
 DITHER_NONE, DITHER_ORDERED = 0, 1         # hdrtv_post_ycbcr10_ex / hdrtv_rgb48_to_ycbcr10_ex
+DITHER_FS = 2                              # Floyd-Steinberg error diffusion: never an argument of the _ex entry points (hdrtv_*_fs instead)
+FS_ROWS, FS_CHUNK = 256, 32                # csrc/common.h: the rows the diffusion kernel keeps in flight, its staging chunk in columns
 DEBAND_RANGE_MAX, DEBAND_RANGE, DEBAND_THRESHOLD = 16, 16, 1311     # hdrtv_rgb48_deband: the largest range and the defaults
 LIGHT_BINS, LIGHT_WORDS = 4096, 4104       # hdrtv_light_stats / hdrtv_rgb48_light_stats: the record, u32 words (lightlevel.py reads it)
 FR_CROP, FR_NORMALIZED = 1, 2              # hdrtv_full_reference_metrics flags
@@ -63,6 +65,9 @@ SYMBOLS = [
     ("hdrtv_rgb48_deband", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_uint32, _VP]),
     ("hdrtv_post_ycbcr10_ex", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I, _I]),
     ("hdrtv_rgb48_to_ycbcr10_ex", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I, _I]),
+    ("hdrtv_ycbcr10_fs_scratch_bytes", C.c_int64, [_I, _I, _I]),
+    ("hdrtv_post_ycbcr10_fs", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I, _VP]),
+    ("hdrtv_rgb48_to_ycbcr10_fs", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I, _VP]),
     ("hdrtv_light_stats", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _I, _I, _VP]),
     ("hdrtv_rgb48_light_stats", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     ("hdrtv_letterbox_u8", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I]),
@@ -275,13 +280,13 @@ def ycbcr10_planes(ptr, h, w, pix_fmt, siting="left"):
     return output_format(pix_fmt, siting, h, w).planes(ptr)
 
 
-DITHERS = {"none": DITHER_NONE, "ordered": DITHER_ORDERED}
+DITHERS = {"none": DITHER_NONE, "ordered": DITHER_ORDERED, "floyd_steinberg": DITHER_FS}
 
 
 class OutputCleanup(NamedTuple):
     """The picture-quality steps of the output stage, off by default: debanding of the RGB48 codes
-    (``hdrtv_rgb48_deband`` with ``deband_range`` / ``deband_threshold``) and the dither of the 10-bit Y'CbCr conversion (``"none"``
-    or ``"ordered"``).  Built by ``output_cleanup`` (which validates); it travels beside ``OutputFormat``, a plain tuple that
+    (``hdrtv_rgb48_deband`` with ``deband_range`` / ``deband_threshold``) and the dither of the 10-bit Y'CbCr conversion (``"none"``,
+    ``"ordered"`` or ``"floyd_steinberg"``).  Built by ``output_cleanup`` (which validates); it travels beside ``OutputFormat``, a plain tuple that
     crosses into the dispatcher's worker processes as it is."""
     deband: bool
     deband_range: int
@@ -296,6 +301,11 @@ class OutputCleanup(NamedTuple):
     def dither_code(self):
         return DITHERS[self.dither]
 
+    @property
+    def error_diffusion(self):
+        """The dither is Floyd-Steinberg error diffusion: the ``hdrtv_*_fs`` entry points and their scratch, not the ``_ex`` ones."""
+        return self.dither == "floyd_steinberg"
+
 
 def _int_in(name, v, lo, hi):
     if isinstance(v, bool) or not hasattr(v, "__index__"):          # an integer type (numpy's included), not a float or a string
@@ -308,8 +318,8 @@ def _int_in(name, v, lo, hi):
 
 def output_cleanup(deband=False, deband_range=DEBAND_RANGE, deband_threshold=DEBAND_THRESHOLD, dither="none", pix_fmt=None):
     """The one constructor of ``OutputCleanup``: ``deband_range`` 1 .. 16 pixels, ``deband_threshold`` 1 .. 65535 u16 code units,
-    ``dither`` ``"none"`` or ``"ordered"``.  ``pix_fmt`` (when given): the output format the cleanup goes with -- 16-bit codes are
-    not dithered, so ``"ordered"`` with ``rgb48le`` is refused."""
+    ``dither`` ``"none"``, ``"ordered"`` (a 16 x 16 Bayer threshold) or ``"floyd_steinberg"`` (error diffusion).  ``pix_fmt`` (when
+    given): the output format the cleanup goes with -- 16-bit codes are not dithered, so a dither with ``rgb48le`` is refused."""
     if not isinstance(deband, (bool, int)) or deband not in (0, 1):
         raise ValueError(f"deband must be True or False (got {deband!r})")
     dither = str(dither).lower() if isinstance(dither, str) else dither

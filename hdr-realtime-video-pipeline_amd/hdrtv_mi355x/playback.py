@@ -650,7 +650,8 @@ def parse_args(argv=None):
     ap.add_argument("--deband-threshold", type=int, default=_lib.DEBAND_THRESHOLD, help="largest difference a deband reference may "
                     "have, in u16 code units, 1 .. 65535 (1311 = 2 %% of the range)")
     ap.add_argument("--dither", choices=sorted(_lib.DITHERS), default="none", help="dither of the 16 -> 10 bit rounding of a Y'CbCr "
-                    "--out-pix-fmt: ordered = a 16x16 Bayer threshold (hdrtv_post_ycbcr10_ex); not for rgb48le")
+                    "--out-pix-fmt: ordered = a 16x16 Bayer threshold (hdrtv_post_ycbcr10_ex), floyd_steinberg = error diffusion "
+                    "(hdrtv_post_ycbcr10_fs; INTEGRATION.md 5f); not for rgb48le")
     ap.add_argument("--antiring", default=None, metavar="{auto|0..1}", help="anti-ringing of the --out-size upscale "
                     "(hdrtv_post_rgb48_scaled_ex; INTEGRATION.md 5c): a strength in 0 .. 1, or auto = the reference's schedule by "
                     "processing size (0.30 up to 960x540, 0.22 up to 1280x720, 0.10 above); default: off")

@@ -334,12 +334,21 @@ class HDRTVNetMI355X:
         ``_ensure_buffers``)."""
         return self._lane_streams[lane]
 
-    def _scratch(self, key, out):
-        """The RGB48 scratch at the output size kept per ``key``."""
+    def _scratch(self, key, out, nbytes=None):
+        """The RGB48 scratch at the output size kept per ``key``; with ``nbytes``, a scratch of that many bytes instead."""
+        shape, dtype = ((out.h, out.w, 3), torch.uint16) if nbytes is None else ((int(nbytes),), torch.uint8)
         scratch = self._ycc_scratch.get(key)
-        if scratch is None or tuple(scratch.shape) != (out.h, out.w, 3):
-            scratch = self._ycc_scratch[key] = torch.empty((out.h, out.w, 3), dtype=torch.uint16, device=self.device)
+        if scratch is None or tuple(scratch.shape) != shape or scratch.dtype != dtype:
+            scratch = self._ycc_scratch[key] = torch.empty(shape, dtype=dtype, device=self.device)
         return scratch.data_ptr()
+
+    def _fs_scratch(self, key, out):
+        """The scratch of the error-diffusion conversions (``hdrtv_ycbcr10_fs_scratch_bytes``) for ``out``, kept per ``key``: one
+        per lane / caller, so that two lanes never share one."""
+        nbytes = self._lib.hdrtv_ycbcr10_fs_scratch_bytes(_L.YCC_FORMATS[out.pix_fmt], out.h, out.w)
+        if nbytes < 0:
+            raise ValueError(f"no error-diffusion scratch for {out.pix_fmt} at {out.w}x{out.h}")
+        return self._scratch((key, "fs"), out, nbytes)
 
     def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None, scale=None):
         """The output conversion of a frame whose planar tensor lies at ``src_ptr``, to the ``lib.OutputFormat`` ``out`` at
@@ -355,6 +364,8 @@ class HDRTVNetMI355X:
         (``rgb48le``), or into a second scratch and through the conversion from codes; the light level record is then taken from
         the debanded codes, which are what is delivered.  Dither alone: ``hdrtv_post_ycbcr10_ex`` at the processing size, the
         ``_ex`` conversion behind the scaled codes otherwise; it does not enter the record, which is defined on RGB48 codes.
+        ``dither="floyd_steinberg"`` takes the same two places through ``hdrtv_post_ycbcr10_fs`` / ``hdrtv_rgb48_to_ycbcr10_fs``
+        and a scratch of ``hdrtv_ycbcr10_fs_scratch_bytes`` bytes kept per ``scratch_key``; the ``_ex`` entry points never see its code.
         ``scale``: the ``lib.ScalePlan`` of a frame delivered at another size (``lib.ScaleOptions.plan`` of the two sizes, which is
         the one place that chooses among the six entry points): its entry point replaces
         ``hdrtv_post_rgb48_scaled``, and everything behind it -- deband, the conversion from codes, the record -- sees its codes.
@@ -369,7 +380,10 @@ class HDRTVNetMI355X:
         if light_ptr is not None and not codes:
             self._chk(self._lib.hdrtv_light_stats(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *rect, light_ptr), "hdrtv_light_stats")
         if not out.is_rgb48 and not codes:
-            if dither:
+            if dither and cleanup.error_diffusion:
+                self._chk(self._lib.hdrtv_post_ycbcr10_fs(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *out.planes(dst_ptr),
+                                                          self._fs_scratch(scratch_key, out)), "hdrtv_post_ycbcr10_fs")
+            elif dither:
                 self._chk(self._lib.hdrtv_post_ycbcr10_ex(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *out.planes(dst_ptr), cleanup.dither_code),
                           "hdrtv_post_ycbcr10_ex")
             else:
@@ -388,7 +402,10 @@ class HDRTVNetMI355X:
             self._chk(self._lib.hdrtv_rgb48_light_stats(self._ctx, st, rgb_ptr, out.h, out.w, *rect, light_ptr), "hdrtv_rgb48_light_stats")
         if out.is_rgb48:
             return
-        if dither:
+        if dither and cleanup.error_diffusion:
+            self._chk(self._lib.hdrtv_rgb48_to_ycbcr10_fs(self._ctx, st, rgb_ptr, out.h, out.w, *out.planes(dst_ptr),
+                                                          self._fs_scratch(scratch_key, out)), "hdrtv_rgb48_to_ycbcr10_fs")
+        elif dither:
             self._chk(self._lib.hdrtv_rgb48_to_ycbcr10_ex(self._ctx, st, rgb_ptr, out.h, out.w, *out.planes(dst_ptr), cleanup.dither_code),
                       "hdrtv_rgb48_to_ycbcr10_ex")
         else:
@@ -831,21 +848,24 @@ class HDRTVNetMI355X:
         intermediate.  ``pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le``; ``siting`` of 4:2:0 chroma ``left`` (MPEG-2 /
         H.264, ffmpeg's default) or ``topleft`` (BT.2100 / HDR10).  Returns a new contiguous 1-D device u16 tensor, the planes back
         to back (``lib.out_frame_bytes`` bytes); stream-ordered on the current stream, no synchronisation.  ``dither="ordered"``:
-        the ordered dither of INTEGRATION.md 5f (``hdrtv_post_ycbcr10_ex``); ``"none"``: the bytes of before."""
+        the ordered dither of INTEGRATION.md 5f (``hdrtv_post_ycbcr10_ex``); ``"floyd_steinberg"``: its error diffusion
+        (``hdrtv_post_ycbcr10_fs``, through a scratch kept by the processor); ``"none"``: the bytes of before."""
         if isinstance(output, (tuple, list)):
             output = output[0]
         if output.dtype not in (torch.float16, torch.float32):
             raise ValueError("postprocess_ycbcr10 expects an fp16 or fp32 tensor")
-        dither = _L.output_cleanup(dither=dither).dither_code
+        cleanup = _L.output_cleanup(dither=dither)
         out = _L.output_format(pix_fmt, siting, int(output.shape[-2]), int(output.shape[-1]))
         if out.is_rgb48:
             raise ValueError("postprocess_ycbcr10 writes p010le, yuv420p10le or yuv422p10le")
         output = output.contiguous()
         dst = torch.empty(out.shape, dtype=torch.uint16, device=self.device)
-        self._chk(self._lib.hdrtv_post_ycbcr10_ex(self._ctx, self._stream(), output.data_ptr(),
-                                                  _dtype_code(output), out.h, out.w, 1 if pq else 0,
-                                                  float(peak_nits), *out.planes(dst.data_ptr()), dither),
-                  "hdrtv_post_ycbcr10_ex")
+        args = (self._ctx, self._stream(), output.data_ptr(), _dtype_code(output), out.h, out.w, 1 if pq else 0, float(peak_nits),
+                *out.planes(dst.data_ptr()))
+        if cleanup.error_diffusion:
+            self._chk(self._lib.hdrtv_post_ycbcr10_fs(*args, self._fs_scratch("postprocess_ycbcr10", out)), "hdrtv_post_ycbcr10_fs")
+        else:
+            self._chk(self._lib.hdrtv_post_ycbcr10_ex(*args, cleanup.dither_code), "hdrtv_post_ycbcr10_ex")
         return dst
 
     @torch.inference_mode()

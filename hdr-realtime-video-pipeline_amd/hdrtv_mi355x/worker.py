@@ -140,7 +140,7 @@ class HeadlessPipelineWorker:
         # what the sink receives, one lib.OutputFormat: "rgb48le", or 10-bit Y'CbCr ("p010le", "yuv420p10le",
         # "yuv422p10le") with the 4:2:0 chroma siting "left" / "topleft"; then a frame is a 1-D u16 view of its planes, back to back
         self._out = _L.output_format(out_pix_fmt, out_siting, self._out_h or self._proc_h, self._out_w or self._proc_w)
-        # deband / ordered dither of the delivered frames, one lib.OutputCleanup; off: nothing more is launched
+        # deband / dither (ordered or error diffusion) of the delivered frames, one lib.OutputCleanup; off: nothing more is launched
         # or allocated and the bytes are those of before.  With light_stats the record describes the debanded codes.
         self._cleanup = _L.output_cleanup(deband, deband_range, deband_threshold, dither, pix_fmt=self._out.pix_fmt)
         # how a frame delivered at another size than the processing size is resized: one lib.ScaleOptions, which

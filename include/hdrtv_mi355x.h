@@ -402,8 +402,8 @@ int hdrtv_post_rgb48_ssimsr(hdrtv_ctx *ctx, void *stream, const void *dev_out, i
  * hdrtv_post_ycbcr10 goes from the model's planar tensor to the planes in one kernel, without an RGB48 intermediate.
  * hdrtv_rgb48_to_ycbcr10 applies the same rule to RGB48 codes already in device memory ([H][W][3]): a scaled frame becomes Y'CbCr in
  * two launches, hdrtv_post_rgb48_scaled and this one.  hdrtv_ycbcr10_bytes: the bytes of a frame with its planes back to back at their
- * minimum pitches (3 H W, 4:2:2: 4 H W), or a negative value for a bad argument.  Out of scope: error-diffusion dithering (sequential; the
- * ordered dither of the _ex entry points below takes its place), full range, 12 bits, 4:4:4, bitstream / SEI writing (hdrtv_light_stats measures the content light level an HDR10 SEI carries), and fusing the Lanczos pass with the conversion.
+ * minimum pitches (3 H W, 4:2:2: 4 H W), or a negative value for a bad argument.  Dithering is the business of the entry points
+ * below (ordered: _ex; Floyd-Steinberg error diffusion: _fs).  Out of scope: full range, 12 bits, 4:4:4, bitstream / SEI writing (hdrtv_light_stats measures the content light level an HDR10 SEI carries), and fusing the Lanczos pass with the conversion.
  * Stream-ordered, no reservation needed.  HDRTV_EINVAL, with dst untouched, for a NULL pointer, a non-positive size, an odd W, an odd H
  * with 4:2:0, a short or odd pitch, an unknown fmt, siting or dtype, P010 with a non-NULL dst_v, a siting other than LEFT with 4:2:2, or
  * pq with peak_nits <= 0. */
@@ -418,12 +418,14 @@ int hdrtv_rgb48_to_ycbcr10(hdrtv_ctx *ctx, void *stream, const uint16_t *src_rgb
                            uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch);
 int64_t hdrtv_ycbcr10_bytes(int fmt, int H, int W);
 
-/* Output cleanup: debanding of the RGB48 codes and ordered dither of the 10-bit Y'CbCr conversion.  The reference's export never
- * hands its encoder a bare 16 -> 10 bit rounding: its ffmpeg chain is deband, zscale=...:dither=error_diffusion, format=yuv422p10le
- * (gui_export.py:948-962), on the CPU.  Error diffusion is sequential; zscale's dither=ordered and a debanding gather are per-pixel
- * integer rules.  Parity with ffmpeg's deband and zscale's ordered dither is UNPINNED (ffmpeg is not part of the reference tree);
- * both steps are the integer rules below, restated in tests/cleanup_ref.py, which the GPU tests hold every entry point to bit for
- * bit.  Both are off unless asked for, and each can be used alone.
+/* Output cleanup: debanding of the RGB48 codes and dither of the 10-bit Y'CbCr conversion, ordered or by error diffusion.  The
+ * reference's export never hands its encoder a bare 16 -> 10 bit rounding: its ffmpeg chain is deband,
+ * zscale=...:dither=error_diffusion, format=yuv422p10le (gui_export.py:948-962), on the CPU.  zscale's dither=ordered and a debanding
+ * gather are per-pixel integer rules; error diffusion is a chain through the whole plane, run here as a skewed wavefront (the
+ * Floyd-Steinberg rule further below).  Parity with ffmpeg's deband and zscale's dithers is UNPINNED (ffmpeg is not part of the
+ * reference tree; zimg diffuses in float); all three steps are the integer rules below, restated in tests/cleanup_ref.py (deband,
+ * ordered dither) and tests/fs_ref.py (error diffusion), which the GPU tests hold every entry point to bit for bit.  All are off
+ * unless asked for, and deband can be used with either dither or alone.
  *
  * Deband rule (hdrtv_rgb48_deband): u16 RGB48 codes [H][W][3] in, [H][W][3] out, never in place.  range R in 1..16 (default 16),
  * threshold T in 1..65535 u16 code units (default 1311 = rnd(0.02 * 65535), the share ffmpeg's deband defaults to), seed S any u32
@@ -448,7 +450,7 @@ int64_t hdrtv_ycbcr10_bytes(int fmt, int H, int W);
  * widths of the undithered rule; over an aligned 16 x 16 block of one colour the mean of Y is within 1/512 code of the unrounded
  * value.  P010 shifts left by 6 as before.  dither = HDRTV_DITHER_NONE launches the kernels of hdrtv_post_ycbcr10 /
  * hdrtv_rgb48_to_ycbcr10 and writes their bytes; any other value of dither is HDRTV_EINVAL, as is everything those refuse.
- * Out of scope: error diffusion, random or blue-noise dither, temporal variation of either pattern, dithering the u8 or RGB48
+ * Out of scope: random or blue-noise dither, temporal variation of either pattern, dithering the u8 or RGB48
  * outputs, debanding the model's float tensor, grain synthesis, and fusing deband with the conversion or the Lanczos pass. */
 #define HDRTV_DITHER_NONE 0
 #define HDRTV_DITHER_ORDERED 1
@@ -459,6 +461,46 @@ int hdrtv_post_ycbcr10_ex(hdrtv_ctx *ctx, void *stream, const void *dev_out, int
                           int dither);
 int hdrtv_rgb48_to_ycbcr10_ex(hdrtv_ctx *ctx, void *stream, const uint16_t *src_rgb48, int H, int W, int fmt, int siting,
                               uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch, int dither);
+
+/* Floyd-Steinberg error diffusion of the 10-bit Y'CbCr conversion (hdrtv_post_ycbcr10_fs / hdrtv_rgb48_to_ycbcr10_fs): what the
+ * reference's export asks zscale for (dither=error_diffusion), as an integer rule of this library's own -- parity with zimg, which
+ * diffuses in float, is UNPINNED.  tests/fs_ref.py restates the rule in numpy, twice (a raster loop and a skewed wavefront); the GPU
+ * tests hold both entry points to it bit for bit.  The rule works on the RGB48 codes of step 1 of the Y'CbCr rule above and on each
+ * of the three planes (Y', Cb, Cr) alone; P010's interleaved plane is two chains.
+ *   For a plane of w x h samples, S(i, j) is the integer sum the Y'CbCr rule forms for that sample, before its rounding constant:
+ *     luma    S = YR R + YG G + YB B,          SH = 20, base 64,  k in [0, 876]
+ *     chroma  S = sum(w u) of the siting,      SH = 20 + log2 Wt (22, 23 or 24), base 512, k in [-448, 448]
+ *   The sample in 1/4096 code:  u = (S + (1 << (SH - 13))) >> (SH - 12), an arithmetic shift.
+ *   Then in raster order (rows top to bottom, each left to right, not serpentine), with E = 0 everywhere at the start:
+ *     v = u(i, j) + E(i, j)
+ *     k = clamp((v + 2048) >> 12, lo, hi)
+ *     r = clamp(v - 4096 k, -2048, 2047)
+ *     a = (7 r) >> 4;  b = (3 r) >> 4;  c = (5 r) >> 4;  d = r - a - b - c          (arithmetic shifts)
+ *     E(i+1, j) += a;  E(i-1, j+1) += b;  E(i, j+1) += c;  E(i+1, j+1) += d        (terms outside the plane are dropped)
+ *     sample = base + k                                                            (P010: << 6)
+ * Everything fits 32-bit integers; |E| stays within 2047 + 3, luma in [64, 940], chroma in [64, 960].  (u + 2048) >> 12 is not
+ * the undithered rule's rounding -- it rounds twice, once to 1/4096 code and once to the code --: this is a rule of its own, and
+ * a frame converted with it differs from the undithered one even where no error has arrived yet.  Over a flat plane the mean of
+ * k is within 32/4096 code of u (the loss is what falls off the right and bottom edges).
+ * `scratch`: device memory of hdrtv_ycbcr10_fs_scratch_bytes(fmt, H, W) bytes (4 (H W + 2 ch cw + W + 2 cw), ch x cw the chroma
+ * plane; negative for a bad argument), 4-byte aligned, the caller's: its contents on entry do not matter and nothing is kept in
+ * it between calls.  A call is two launches on `stream` -- the samples u of all three planes into the scratch, fully parallel, then
+ * one workgroup per plane that runs the chain as a wavefront of HDRTV_FS_ROWS rows (a lane per row), staging HDRTV_FS_CHUNK columns
+ * at a time -- so the calls are stream-ordered, need no reservation, and are safe on two lanes (two streams) with two scratches;
+ * two calls in flight must not share one.  The cost is the chain's latency, not bandwidth: measured 6.7 ms at 3840x2160 and
+ * 2.1 ms at 1920x1080 on one MI355X, for 4:2:0 and 4:2:2 alike (profiles/fs_dither_timing.txt), against 20 us
+ * for the ordered dither.
+ * The argument rules are those of hdrtv_post_ycbcr10 / hdrtv_rgb48_to_ycbcr10, plus HDRTV_EINVAL for a NULL or misaligned scratch;
+ * on refusal nothing is written.  hdrtv_*_ex(..., dither = 2) stays HDRTV_EINVAL: error diffusion is reached through these entry
+ * points only.  Out of scope: serpentine scanning, other kernels (Sierra, Stucki), spreading one chain over several CUs. */
+#define HDRTV_FS_ROWS 256
+#define HDRTV_FS_CHUNK 32
+int64_t hdrtv_ycbcr10_fs_scratch_bytes(int fmt, int H, int W);
+int hdrtv_post_ycbcr10_fs(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
+                          int fmt, int siting, uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch,
+                          void *scratch);
+int hdrtv_rgb48_to_ycbcr10_fs(hdrtv_ctx *ctx, void *stream, const uint16_t *src_rgb48, int H, int W, int fmt, int siting,
+                              uint16_t *dst_y, int y_pitch, uint16_t *dst_u, uint16_t *dst_v, int c_pitch, void *scratch);
 
 /* HDR10 content light level (CTA-861.3 MaxCLL / MaxFALL; x265 max-cll=, HEVC SEI 144): the per-frame record those two numbers are
  * made from, measured on the device from exactly the codes the sink receives.  The reference has no counterpart: its export tags the
