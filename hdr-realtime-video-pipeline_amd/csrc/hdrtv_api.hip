@@ -552,19 +552,35 @@ static int scale_tables_for(hdrtv_ctx *c, st::Kind kind, const char *what, int H
 // The three entry points: antiring 0 = the plain rule (post_scale.hip's kernels), 1 .. 256 = post_scale_ar.hip's; cas 0 = those,
 // 1032 .. 4096 = post_scale_cas.hip's with either kind of pass; one tap-table cache.  Anti-ringing leaves an identity alone (the sum
 // lies between its inner taps) and sharpening belongs to an upscale (the reference's chain): equal sizes are not sharpened.
-static int post_rgb48_scaled(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
-                             uint16_t *dst, int dH, int dW, int antiring, int cas)
+static int scaled_args(hdrtv_ctx *c, const char *what, const void *in, int dtype, int H, int W, int pq, float peak_nits, const uint16_t *dst,
+                       int dH, int dW, int antiring, int cas)
 {
-    const char *what = "post_rgb48_scaled";
     const char *ratio = dH < H || dW < W ? "shrinks (enlarging only)" : nullptr;
     if (int rc = scale_common_args(c, what, in, dtype, H, W, pq, peak_nits, dst, dH, dW, ratio)) return rc;
     if (antiring < 0 || antiring > 256) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled_ex: antiring %d is outside 0 .. 256", antiring);
     if (cas != 0 && (cas < 1032 || cas > 4096)) return fail(c, HDRTV_EINVAL, "post_rgb48_scaled_cas: cas %d is neither 0 nor in 1032 .. 4096", cas);
-    bool done;
-    if (int rc = scale_begin(c, what, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, &done); rc || done) return rc;
+    return HDRTV_OK;
+}
+
+// the launch parameters of a geometry, its tap tables found or built
+static int scaled_params(hdrtv_ctx *c, const char *what, const void *in, int H, int W, int pq, float peak_nits, uint16_t *dst, int dH, int dW,
+                         PostScaleParams &p)
+{
     const hdrtv_ctx::ScaleTab *t;
     if (int rc = scale_tables_for(c, st::LANCZOS, what, H, W, dH, dW, st::build_lanczos, &t)) return rc;
-    PostScaleParams p{in, dst, t->at<int4>(), t->at<int4>(st::lanczos_ytab(dW)), c->pq_bnd(), pq ? peak_nits : 0.f, H, W, dH, dW};
+    p = PostScaleParams{in, dst, t->at<int4>(), t->at<int4>(st::lanczos_ytab(dW)), c->pq_bnd(), pq ? peak_nits : 0.f, H, W, dH, dW};
+    return HDRTV_OK;
+}
+
+static int post_rgb48_scaled(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
+                             uint16_t *dst, int dH, int dW, int antiring, int cas)
+{
+    const char *what = "post_rgb48_scaled";
+    if (int rc = scaled_args(c, what, in, dtype, H, W, pq, peak_nits, dst, dH, dW, antiring, cas)) return rc;
+    bool done;
+    if (int rc = scale_begin(c, what, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, &done); rc || done) return rc;
+    PostScaleParams p;
+    if (int rc = scaled_params(c, what, in, H, W, pq, peak_nits, dst, dH, dW, p)) return rc;
     if (cas) return launched(c, "post_rgb48_scaled_cas", post_scale_cas_launch(p, antiring, cas, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
     if (antiring) return launched(c, "post_rgb48_scaled_ex", post_scale_ar_launch(p, antiring, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
     return launched(c, what, post_scale_launch(p, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
@@ -588,10 +604,9 @@ int hdrtv_post_rgb48_scaled_cas(hdrtv_ctx *c, void *stream, const void *in, int 
     return post_rgb48_scaled(c, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, antiring, cas);
 }
 
-int hdrtv_post_rgb48_fsr(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
-                         uint16_t *dst, int dH, int dW, int rcas, float sharpness)
+static int fsr_args(hdrtv_ctx *c, const char *what, const void *in, int dtype, int H, int W, int pq, float peak_nits, const uint16_t *dst,
+                    int dH, int dW, int rcas, float sharpness)
 {
-    const char *what = "post_rgb48_fsr";
     const char *ratio = dH < H || dW < W                             ? "shrinks (enlarging only)"
                         : dH > 2 * (long long)H || dW > 2 * (long long)W ? "is more than 2x on an axis"
                                                                          : nullptr;
@@ -599,13 +614,108 @@ int hdrtv_post_rgb48_fsr(hdrtv_ctx *c, void *stream, const void *in, int dtype, 
     if (rcas != 0 && rcas != 1) return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: rcas %d is neither 0 nor 1", rcas);
     if (rcas && !(sharpness >= 0.f && sharpness <= 2.f))          // NaN fails both comparisons
         return fail(c, HDRTV_EINVAL, "post_rgb48_fsr: sharpness %g is outside 0 .. 2", (double)sharpness);
-    bool done;
-    if (int rc = scale_begin(c, what, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, &done); rc || done) return rc;
+    return HDRTV_OK;
+}
+
+// the launch parameters of a geometry, its position tables found or built; *sharp = float32(2^-sharpness) where rcas
+static int fsr_params(hdrtv_ctx *c, const char *what, const void *in, int H, int W, int pq, float peak_nits, uint16_t *dst, int dH, int dW,
+                      int rcas, float sharpness, PostFsrParams &p, float *sharp)
+{
     const hdrtv_ctx::ScaleTab *t;
     if (int rc = scale_tables_for(c, st::FSR, what, H, W, dH, dW, st::build_fsr, &t)) return rc;
-    PostFsrParams p{in, dst, t->at<int2>(), t->at<int2>(st::fsr_ytab(dW)), c->pq_bnd(), pq ? peak_nits : 0.f, H, W, dH, dW};
-    const float sharp = rcas ? (float)std::exp2(-(double)sharpness) : 0.f;
+    p = PostFsrParams{in, dst, t->at<int2>(), t->at<int2>(st::fsr_ytab(dW)), c->pq_bnd(), pq ? peak_nits : 0.f, H, W, dH, dW};
+    *sharp = rcas ? (float)std::exp2(-(double)sharpness) : 0.f;
+    return HDRTV_OK;
+}
+
+int hdrtv_post_rgb48_fsr(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
+                         uint16_t *dst, int dH, int dW, int rcas, float sharpness)
+{
+    const char *what = "post_rgb48_fsr";
+    if (int rc = fsr_args(c, what, in, dtype, H, W, pq, peak_nits, dst, dH, dW, rcas, sharpness)) return rc;
+    bool done;
+    if (int rc = scale_begin(c, what, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, &done); rc || done) return rc;
+    PostFsrParams p;
+    float sharp;
+    if (int rc = fsr_params(c, what, in, H, W, pq, peak_nits, dst, dH, dW, rcas, sharpness, p, &sharp)) return rc;
     return launched(c, what, post_fsr_launch(p, rcas, sharp, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
+}
+
+// ------------------------------------------------------------------- film grain (include/hdrtv_mi355x.h states the rule)
+float hdrtv_film_grain_seed(uint32_t stream_seed, uint32_t frame_index)
+{
+    uint32_t h = frame_index * 0x9E3779B1u + stream_seed * 0x85EBCA77u;
+    h ^= h >> 16; h *= 0x21F0AAADu;
+    h ^= h >> 15; h *= 0x735A2D97u;
+    h ^= h >> 15;
+    return (float)(h >> 8) * (1.f / 16777216.f);                  // 24 bits: exact
+}
+
+// intensity in [0, 0.1], seed in [0, 1)
+static int grain_args(hdrtv_ctx *c, const char *what, float intensity, float seed)
+{
+    if (!(intensity >= 0.f && intensity <= 0.1f))                 // NaN fails both comparisons
+        return fail(c, HDRTV_EINVAL, "%s: intensity %g is outside 0 .. 0.1", what, (double)intensity);
+    if (!(seed >= 0.f && seed < 1.f)) return fail(c, HDRTV_EINVAL, "%s: seed %g is outside [0, 1)", what, (double)seed);
+    return HDRTV_OK;
+}
+
+int hdrtv_rgb48_film_grain(hdrtv_ctx *c, void *stream, const uint16_t *src, int H, int W, float intensity, float seed, uint16_t *dst)
+{
+    const char *what = "rgb48_film_grain";
+    if (!c || !src || !dst || H < 1 || W < 1) return fail(c, HDRTV_EINVAL, "%s: bad argument", what);
+    if (int rc = grain_args(c, what, intensity, seed)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (intensity == 0.f) {                                       // the codes, copied
+        if (dst != src) HIPCHK(c, hipMemcpyAsync(dst, src, (size_t)H * W * 6, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return HDRTV_OK;
+    }
+    return launched(c, what, film_grain_launch(src, dst, H, W, intensity, seed, (hipStream_t)stream));
+}
+
+int hdrtv_post_rgb48_grain(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits, uint16_t *dst,
+                           float intensity, float seed)
+{
+    const char *what = "post_rgb48_grain";
+    if (int rc = scale_common_args(c, what, in, dtype, H, W, pq, peak_nits, dst, H, W, nullptr)) return rc;
+    if (int rc = grain_args(c, what, intensity, seed)) return rc;
+    if (intensity == 0.f)
+        return pq ? hdrtv_post_pq_rgb48(c, stream, in, dtype, H, W, peak_nits, dst) : hdrtv_post_rgb48(c, stream, in, dtype, H, W, dst);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = pq ? ensure_pq_table(c, what) : HDRTV_OK) return rc;
+    return launched(c, what, post_rgb48_grain_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, c->pq_bnd(), intensity, seed,
+                                                     (hipStream_t)stream));
+}
+
+int hdrtv_post_rgb48_scaled_grain(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
+                                  uint16_t *dst, int dH, int dW, int antiring, int cas, float intensity, float seed)
+{
+    const char *what = "post_rgb48_scaled_grain";
+    if (int rc = scaled_args(c, what, in, dtype, H, W, pq, peak_nits, dst, dH, dW, antiring, cas)) return rc;
+    if (int rc = grain_args(c, what, intensity, seed)) return rc;
+    if (intensity == 0.f) return post_rgb48_scaled(c, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, antiring, cas);
+    if (dH == H && dW == W) return hdrtv_post_rgb48_grain(c, stream, in, dtype, H, W, pq, peak_nits, dst, intensity, seed);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = pq ? ensure_pq_table(c, what) : HDRTV_OK) return rc;
+    PostScaleParams p;
+    if (int rc = scaled_params(c, what, in, H, W, pq, peak_nits, dst, dH, dW, p)) return rc;
+    return launched(c, what, post_scale_grain_launch(p, antiring, cas, intensity, seed, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
+}
+
+int hdrtv_post_rgb48_fsr_grain(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
+                               uint16_t *dst, int dH, int dW, int rcas, float sharpness, float intensity, float seed)
+{
+    const char *what = "post_rgb48_fsr_grain";
+    if (int rc = fsr_args(c, what, in, dtype, H, W, pq, peak_nits, dst, dH, dW, rcas, sharpness)) return rc;
+    if (int rc = grain_args(c, what, intensity, seed)) return rc;
+    if (intensity == 0.f) return hdrtv_post_rgb48_fsr(c, stream, in, dtype, H, W, pq, peak_nits, dst, dH, dW, rcas, sharpness);
+    if (dH == H && dW == W) return hdrtv_post_rgb48_grain(c, stream, in, dtype, H, W, pq, peak_nits, dst, intensity, seed);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = pq ? ensure_pq_table(c, what) : HDRTV_OK) return rc;
+    PostFsrParams p;
+    float sharp;
+    if (int rc = fsr_params(c, what, in, H, W, pq, peak_nits, dst, dH, dW, rcas, sharpness, p, &sharp)) return rc;
+    return launched(c, what, post_fsr_grain_launch(p, rcas, sharp, intensity, seed, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
 int hdrtv_post_rgb48_down(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,

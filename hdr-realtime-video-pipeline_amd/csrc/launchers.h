@@ -159,6 +159,17 @@ hipError_t post_scale_cas_launch(const PostScaleParams &p, int antiring, int cas
 // quantise + FSR upscale (post_fsr.hip): EASU alone (rcas = 0) or EASU + RCAS with sharp = float32(2^-sharpness), 0.25 .. 1;
 // hipErrorInvalidValue, nothing enqueued, unless 1 <= H <= dH <= 2H and 1 <= W <= dW <= 2W; pq != 0 needs p.pq_bnd
 hipError_t post_fsr_launch(const PostFsrParams &p, int rcas, float sharp, int is_f32, int pq, hipStream_t s);
+// the film grain of include/hdrtv_mi355x.h, 0 < intensity <= 0.1 and 0 <= seed < 1 (film_grain.h has the pixel rule); each returns
+// hipErrorInvalidValue with nothing enqueued otherwise, and under its twin's conditions.  film_grain.hip: codes -> grained codes
+// (dst == src allowed), and tensor -> quant_rgb -> grained codes in one launch
+hipError_t film_grain_launch(const uint16_t *src, uint16_t *dst, int H, int W, float intensity, float seed, hipStream_t s);
+hipError_t post_rgb48_grain_launch(const void *in, int is_f32, int H, int W, uint16_t *rgb, int pq, float peak, const float *pq_bnd,
+                                   float intensity, float seed, hipStream_t s);
+// post_scale_grain.hip: the Lanczos tile with the staged (antiring 0 .. 256; cas 0 or 1032 .. 4096: sharpened) codes grained over H x W
+hipError_t post_scale_grain_launch(const PostScaleParams &p, int antiring, int cas, float intensity, float seed, int is_f32, int pq,
+                                   hipStream_t s);
+// post_fsr_grain.hip: the FSR tile with the final codes grained over dH x dW
+hipError_t post_fsr_grain_launch(const PostFsrParams &p, int rcas, float sharp, float intensity, float seed, int is_f32, int pq, hipStream_t s);
 // quantise + Mitchell shrink (post_down.hip) with anti-ringing 0 .. 256, and with ssim != 0 the SSimDownscaler correction behind it;
 // hipErrorInvalidValue, nothing enqueued, unless 1 <= dH <= H <= 4 dH, 1 <= dW <= W <= 4 dW and 1 <= ntx, nty <= 17; pq != 0 needs p.pq_bnd
 hipError_t post_down_launch(const PostDownParams &p, int antiring, int ssim, int is_f32, int pq, hipStream_t s);

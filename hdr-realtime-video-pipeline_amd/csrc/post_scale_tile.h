@@ -38,9 +38,14 @@
 // A lane takes one pixel and its three channels; consecutive lanes take consecutive columns, so the nine u16 reads of a wave are
 // 64 consecutive u16 = 32 consecutive dwords (two lanes per dword broadcast), split over two rows 36 dwords apart at a row's end.
 // The two floor divisions and the root are a float reciprocal / root and one exact integer correction step each (ps_cas below).
+// Film grain (GRAIN, post_scale_grain.hip: hdrtv_post_rgb48_scaled_grain) replaces each code written to `codes` -- step 1's, or step
+// 1b's sharpened one -- by its grained code (film_grain.h) at the FRAME pixel it belongs to, the clamped (sy, sx) / (cy, cx) over
+// H x W: in the reference's chain the grain hooks MAIN at the processing size, behind ffmpeg's cas and in front of mpv's scaler, so a
+// tap outside the frame reads the grained edge pixel.  One g per staged pixel, three grain_code; vector ALU only, the LDS of the twin.
 #pragma once
 #include "common.h"
 #include "post_quant.h"
+#include "film_grain.h"
 
 constexpr int PS_SR = PS_TH + 6, PS_SC = PS_TW + 6, PS_SCP = PS_SC + 2;
 
@@ -97,9 +102,11 @@ __device__ __forceinline__ uint32_t ps_cas(int a, int b, int c, int d, int e, in
 
 constexpr int PS_RR = PS_SR + 2, PS_RC = PS_SC + 2;        // the raw codes of the CAS form: the footprint and its halo
 
-// a = the anti-ringing strength, 1 .. 256 (read only where AR); cas = the CAS code, 1032 .. 4096 (read only where CAS)
-template <typename T, bool PQ, bool AR, bool CAS = false>
-__device__ __forceinline__ void post_scale_tile(const PostScaleParams p, const int a, const int cas = 0)
+// a = the anti-ringing strength, 1 .. 256 (read only where AR); cas = the CAS code, 1032 .. 4096 (read only where CAS); intensity, seed
+// = the film grain's (read only where GRAIN)
+template <typename T, bool PQ, bool AR, bool CAS = false, bool GRAIN = false>
+__device__ __forceinline__ void post_scale_tile(const PostScaleParams p, const int a, const int cas = 0, const float intensity = 0.f,
+                                                const float seed = 0.f)
 {
     __shared__ uint16_t codes[3][PS_SR][PS_SCP];
     __shared__ __attribute__((aligned(16))) int hor[3][PS_SR][PS_TW];
@@ -133,10 +140,14 @@ __device__ __forceinline__ void post_scale_tile(const PostScaleParams p, const i
             const int cy = min(max(ys0 + r, 0), p.H - 1), cx = min(max(xs0 + c, 0), p.W - 1);
             const int r1 = cy - (ys0 - 1), r0 = max(cy - 1, 0) - (ys0 - 1), r2 = min(cy + 1, p.H - 1) - (ys0 - 1);
             const int c1 = cx - (xs0 - 1), c0 = max(cx - 1, 0) - (xs0 - 1), c2 = min(cx + 1, p.W - 1) - (xs0 - 1);
+            [[maybe_unused]] float Ig = 0.f;
+            if constexpr (GRAIN) Ig = grain_term(intensity, cx, cy, p.W, p.H, seed);
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
                 const uint16_t *t = raw[ch][r0], *m = raw[ch][r1], *b = raw[ch][r2];
-                codes[ch][r][c] = (uint16_t)ps_cas(t[c0], t[c1], t[c2], m[c0], m[c1], m[c2], b[c0], b[c1], b[c2], cas);
+                const uint32_t v = ps_cas(t[c0], t[c1], t[c2], m[c0], m[c1], m[c2], b[c0], b[c1], b[c2], cas);
+                if constexpr (GRAIN) codes[ch][r][c] = (uint16_t)grain_code(v, Ig);
+                else codes[ch][r][c] = (uint16_t)v;
             }
         }
     } else {
@@ -149,6 +160,12 @@ __device__ __forceinline__ void post_scale_tile(const PostScaleParams p, const i
             const float cr = (float)in[o], cg = (float)in[plane + o], cb = (float)in[2 * plane + o];
             uint32_t q0, q1, q2;
             quant_rgb<PQ>(cr, cg, cb, p.peak, p.pq_bnd, q0, q1, q2);
+            if constexpr (GRAIN) {                   // the grain of the frame pixel (sy, sx), not of the tap's own position
+                const float Ig = grain_term(intensity, sx, sy, p.W, p.H, seed);
+                q0 = grain_code(q0, Ig);
+                q1 = grain_code(q1, Ig);
+                q2 = grain_code(q2, Ig);
+            }
             codes[0][r][c] = (uint16_t)q0;
             codes[1][r][c] = (uint16_t)q1;
             codes[2][r][c] = (uint16_t)q2;

@@ -57,6 +57,7 @@ class _Mi355xWorker:
 
     depth = 2
     input_format = None                      # the lib.InputFormat of the input slots (None: bgr24); _worker_main sets the dispatcher's
+    frame_index = 0                          # the stream index of the frame the next begin() takes; _worker_main sets it (the film grain's seed)
     output_format = None                     # the lib.OutputFormat of the output slots; _worker_main sets the dispatcher's
 
     def __init__(self, rank, device_index, init_args):
@@ -80,6 +81,9 @@ class _Mi355xWorker:
         # how frames of another size than the processing size are resized (lib.ScaleOptions; validated by the dispatcher, which hands
         # on what is not the default): enqueue_frame's six keywords
         self.scale = L.scale_options(**{name: kw.pop(name) for name in L.ScaleOptions._fields if name in kw})
+        # the film grain of the delivered frames (validated by the dispatcher, which hands it on only when it is on): the intensity and
+        # the stream's seed; a frame's own seed comes from its index in the stream (frame_index), whichever worker or lane takes it
+        self.film_grain, self.grain_stream_seed = L.check_film_grain(kw.pop("film_grain", 0.0)), int(kw.pop("grain_stream_seed", 0))
         torch.cuda.set_device(device_index)
         with contextlib.redirect_stdout(sys.stderr):   # a worker's banner must not land on the parent's stdout (bench.py's one JSON line)
             self.proc = HDRTVNetMI355X(model, device=f"cuda:{device_index}", warmup_passes=0, **kw)
@@ -125,6 +129,8 @@ class _Mi355xWorker:
         h, w = src.frame_hw(frame)
         fmt = self.output_format
         out_fmt = dict(out_hw=(fmt.h, fmt.w), out_pix_fmt=fmt.pix_fmt, out_siting=fmt.siting, cleanup=self.cleanup, **self.scale._asdict())
+        if self.film_grain:
+            out_fmt.update(film_grain=self.film_grain, grain_seed=self._L.film_grain_seed(self.grain_stream_seed, self.frame_index))
         self._buffers(h, w, tuple(frame.shape) + ((2,) if frame.itemsize == 2 else ()), fmt)       # _raw is bytes: a u16 sample is two
         k = self._n % self.depth
         # frame n runs on lane n mod lanes: its own workspace and compute stream, so that the device overlaps the tail of one
@@ -308,6 +314,8 @@ def _worker_main(rank, device_index, make_worker, init_args, geom, out_format, t
             while backlog and free_out and len(inflight) < depth:
                 _, idx, in_slot = backlog.popleft()
                 out_slot = free_out.pop(0)
+                if hasattr(body, "frame_index"):
+                    body.frame_index = idx                 # the frame's index in the stream, not in this worker's share of it
                 t_b = time.perf_counter()
                 inflight.append((body.begin(ins[in_slot], outs[out_slot]), idx, in_slot, out_slot))
                 stats["begin_s"] += time.perf_counter() - t_b
@@ -347,7 +355,7 @@ class FrameDispatcher:
                  start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False, out_height=None,
                  out_width=None, out_pix_fmt="rgb48le", out_siting="left", deband=False, deband_range=16, deband_threshold=1311,
                  dither="none", antiring=0.0, cas=0.0, scaler="lanczos", fsr_sharpness=0.2, downscaler=None,
-                 down_antiring=0.0):
+                 down_antiring=0.0, film_grain=False, grain_stream_seed=0):
         """``sink(index, rgb48_view)`` is called in index order from the reorder thread; the view is only valid during the
         call (the slot goes back to its worker afterwards).  ``numa``: workers pin themselves to their GPU's NUMA node
         (False: report only).  ``pix_fmt``: ``bgr24`` input frames are u8 (H, W, 3); ``yuv420p`` / ``nv12`` frames are u8
@@ -369,7 +377,10 @@ class FrameDispatcher:
         too (``ValueError``), and kept under these names (``"auto"`` of ``down_antiring`` resolved) and as ``.scale``.  Each travels
         in ``init_args`` under its name only when it is not the default -- ``fsr_sharpness`` with ``scaler="fsr"``,
         ``down_antiring`` with a downscaler -- and the product's worker hands them to ``enqueue_frame``; stand-in workers fill
-        slots of the output size."""
+        slots of the output size.  ``film_grain`` (``lib.check_film_grain``: True = the reference's 0.01, or an intensity up to 0.1)
+        / ``grain_stream_seed`` (a u32): the reference's film grain on the delivered frames; the chains without
+        grain are refused here (``lib.check_grain_chain``).  When on, both travel in ``init_args``, and frame ``i`` of the stream gets
+        ``lib.film_grain_seed(grain_stream_seed, i)`` whichever worker, device or lane computes it."""
         if n_workers < 1 or slots < 2:
             raise ValueError("n_workers >= 1 and slots >= 2")
         from . import lib as _L
@@ -384,7 +395,11 @@ class FrameDispatcher:
         out = _L.output_format(out_pix_fmt, out_siting, self.out_h, self.out_w)    # raises for an odd size of a Y'CbCr layout
         self.out_pix_fmt, self.out_siting, self._out_shape = out.pix_fmt, out.siting, out.shape
         self.cleanup = _L.output_cleanup(deband, deband_range, deband_threshold, dither, pix_fmt=out.pix_fmt)
+        self.film_grain = _L.check_grain_chain(film_grain, self.scaler, self.downscaler, self.cleanup.deband)
+        self.grain_stream_seed = _L.check_grain_stream_seed(grain_stream_seed)
         init_args = dict(init_args or {})
+        if self.film_grain:
+            init_args["film_grain"], init_args["grain_stream_seed"] = self.film_grain, self.grain_stream_seed
         if self.cleanup.active:
             init_args["cleanup"] = tuple(self.cleanup)
         # an option travels only when it is not the default: otherwise the init_args of before

@@ -59,6 +59,11 @@ SYMBOLS = [
     ("hdrtv_post_rgb48_fsr", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, C.c_float]),
     ("hdrtv_post_rgb48_down", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, _I]),
     ("hdrtv_post_rgb48_ssimsr", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I]),
+    ("hdrtv_film_grain_seed", C.c_float, [C.c_uint32, C.c_uint32]),
+    ("hdrtv_rgb48_film_grain", _I, [_VP, _VP, _VP, _I, _I, C.c_float, C.c_float, _VP]),
+    ("hdrtv_post_rgb48_grain", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, C.c_float, C.c_float]),
+    ("hdrtv_post_rgb48_scaled_grain", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, _I, C.c_float, C.c_float]),
+    ("hdrtv_post_rgb48_fsr_grain", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, C.c_float, C.c_float, C.c_float]),
     ("hdrtv_post_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_rgb48_to_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_ycbcr10_bytes", C.c_int64, [_I, _I, _I]),
@@ -560,9 +565,71 @@ def down_options(downscaler, down_antiring, proc_w, proc_h, out_w, out_h, scaler
     return antiring_code(strength), 1 if downscaler == "ssim" else 0
 
 
+FILM_GRAIN_INTENSITY = 0.01                # the reference's INTENSITY (assets/shaders/filmgrain.glsl)
+FILM_GRAIN_MAX = 0.1                       # the largest intensity the ``_grain`` entry points take
+
+
+def check_film_grain(value=False):
+    """A ``film_grain`` option as the processor, the worker, the dispatcher and the command line take it -> the intensity as a float:
+    ``False`` / ``0`` -> 0.0 (off), ``True`` -> the reference's ``FILM_GRAIN_INTENSITY``, a float in [0, ``FILM_GRAIN_MAX``] -> itself;
+    ``ValueError`` for anything else (a string, None, NaN, a value outside the range)."""
+    if isinstance(value, (bool, np.bool_)):
+        return FILM_GRAIN_INTENSITY if value else 0.0
+    if isinstance(value, (str, bytes)) or value is None:
+        raise ValueError(f"film_grain must be True, False or an intensity in [0, {FILM_GRAIN_MAX}] (got {value!r})")
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"film_grain must be True, False or an intensity in [0, {FILM_GRAIN_MAX}] (got {value!r})") from None
+    if not 0.0 <= v <= FILM_GRAIN_MAX:        # NaN fails both comparisons
+        raise ValueError(f"film_grain must be in [0, {FILM_GRAIN_MAX}] (got {value!r})")
+    return v
+
+
+def check_grain_seed(value=0.0):
+    """A per-frame ``grain_seed`` (``film_grain_seed`` of the stream's seed and the frame index) -> a float in [0, 1)."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"grain_seed must be a number in [0, 1) (got {value!r})") from None
+    if isinstance(value, bool) or not 0.0 <= v < 1.0:
+        raise ValueError(f"grain_seed must be in [0, 1) (got {value!r})")
+    return v
+
+
+def check_grain_stream_seed(value=0):
+    """A ``grain_stream_seed`` option: an integer in 0 .. 2^32 - 1 (``film_grain_seed`` hashes it with the frame index)."""
+    return _int_in("grain_stream_seed", value, 0, 0xFFFFFFFF)
+
+
+def film_grain_seed(stream_seed, frame_index):
+    """The seed of frame ``frame_index`` (taken mod 2^32) of the stream ``stream_seed``: ``hdrtv_film_grain_seed``, the integer hash
+    of include/hdrtv_mi355x.h -- a function of the frame index, not of the order frames complete in, so two lanes or two devices
+    give a frame the grain one lane would.  Host only: needs the built library, no device."""
+    return float(load().hdrtv_film_grain_seed(check_grain_stream_seed(stream_seed), int(frame_index) & 0xFFFFFFFF))
+
+
+def check_grain_chain(film_grain, scaler="lanczos", downscaler=None, deband=False):
+    """``ValueError`` for the chains the film grain is not provided in, whatever the sizes: ``scaler``
+    ``"spline36"`` / ``"ssim_superres"`` and any ``downscaler`` -- in the reference the grain sits in front of those scalers, inside
+    kernels that do not take it --, and ``deband``, which behind the grain would average it away.  Returns the intensity."""
+    intensity = check_film_grain(film_grain)
+    if intensity == 0:
+        return 0.0
+    if downscaler is not None:
+        raise ValueError(f"film_grain does not go with downscaler {downscaler!r}: the grain in front of the shrinking chain is not provided")
+    if scaler in SSIMSR_SCALERS:
+        raise ValueError(f"film_grain does not go with scaler {scaler!r}: the grain in front of spline36 / SSimSuperRes is not provided "
+                         f"(scalers {list(SCALERS)} take it)")
+    if deband:
+        raise ValueError("film_grain does not go with deband: a deband behind the grain would average the grain away")
+    return intensity
+
+
 class ScalePlan(NamedTuple):
     """How one frame geometry is resized: ``entry``, the C symbol (one of the six ``hdrtv_post_rgb48_scaled*`` / ``_fsr`` / ``_down`` /
-    ``_ssimsr``), and ``args``, the tuple that follows ``dH, dW`` in its signature."""
+    ``_ssimsr``, or with film grain ``hdrtv_post_rgb48_scaled_grain`` / ``_fsr_grain``), and ``args``, the tuple that follows
+    ``dH, dW`` in its signature."""
     entry: str
     args: tuple
 
@@ -591,9 +658,15 @@ class ScaleOptions(NamedTuple):
     downscaler: object
     down_antiring: float
 
-    def plan(self, proc_w, proc_h, out_w, out_h):
+    def plan(self, proc_w, proc_h, out_w, out_h, film_grain=0.0, grain_seed=0.0):
         """The ``ScalePlan`` of a frame processed at ``proc_w`` x ``proc_h`` and delivered at ``out_w`` x ``out_h``, or None when
-        nothing is scaled; everything that depends on the sizes is checked (``ValueError``) and ``"auto"`` resolved here."""
+        nothing is scaled; everything that depends on the sizes is checked (``ValueError``) and ``"auto"`` resolved here.
+        ``film_grain`` (``check_film_grain``) nonzero: the plan's entry is the scaler's ``_grain`` form -- ``"lanczos"``:
+        ``hdrtv_post_rgb48_scaled_grain`` with ``(antiring, cas, intensity, seed)``, ``"fsr"``: ``hdrtv_post_rgb48_fsr_grain`` with
+        ``(rcas, sharpness, intensity, seed)`` --, ``grain_seed`` the frame's seed; the chains without grain are refused
+        (``check_grain_chain``).  At 0 the plan is the one of before."""
+        intensity = check_grain_chain(film_grain, self.scaler, self.downscaler) if film_grain else 0.0
+        grain = (intensity, check_grain_seed(grain_seed)) if intensity else None
         if self.downscaler is not None:
             return ScalePlan("hdrtv_post_rgb48_down", down_options(self.downscaler, self.down_antiring, proc_w, proc_h, out_w, out_h,
                                                                    self.scaler, self.antiring, self.cas))
@@ -603,12 +676,15 @@ class ScaleOptions(NamedTuple):
             raise ValueError(f"output size {out_w}x{out_h} is below the processing size {proc_w}x{proc_h} (enlarging only)")
         if self.scaler == "fsr":
             check_fsr_size(proc_w, proc_h, out_w, out_h)
-            return ScalePlan("hdrtv_post_rgb48_fsr", (0, 0.0) if self.fsr_sharpness is None else (1, self.fsr_sharpness))
+            args = (0, 0.0) if self.fsr_sharpness is None else (1, self.fsr_sharpness)
+            return ScalePlan("hdrtv_post_rgb48_fsr_grain", args + grain) if grain else ScalePlan("hdrtv_post_rgb48_fsr", args)
         if self.scaler in SSIMSR_SCALERS:
             check_ssimsr_size(proc_w, proc_h, out_w, out_h)
             return ScalePlan("hdrtv_post_rgb48_ssimsr", (1 if self.scaler == "ssim_superres" else 0,))
         antiring = antiring_code(resolve_antiring(self.antiring, proc_w, proc_h, out_w, out_h))
         cas = cas_code(resolve_cas(self.cas, proc_w, proc_h, out_w, out_h))
+        if grain:
+            return ScalePlan("hdrtv_post_rgb48_scaled_grain", (antiring, cas) + grain)
         if cas:
             return ScalePlan("hdrtv_post_rgb48_scaled_cas", (antiring, cas))
         return ScalePlan("hdrtv_post_rgb48_scaled_ex", (antiring,)) if antiring else ScalePlan("hdrtv_post_rgb48_scaled", ())

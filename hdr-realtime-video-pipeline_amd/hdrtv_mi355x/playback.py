@@ -617,7 +617,8 @@ def parse_args(argv=None):
     ``.src_wh`` hold the three sizes as ``(w, h)``, ``.cleanup`` the ``lib.OutputCleanup`` of --deband / --dither, ``.antiring`` and ``.cas`` ``"auto"`` or the
     strength as a float (0.0: off; both 0.0 under any ``--scaler`` but lanczos), ``.scaler`` one of ``lib.UPSCALERS``, ``.fsr_sharpness`` the RCAS
     sharpness as a float or None (EASU alone), ``.downscaler`` None, ``"mitchell"`` or ``"ssim"``, ``.down_antiring`` its anti-ringing
-    strength as a float (``auto`` resolved to the reference's 0.20)."""
+    strength as a float (``auto`` resolved to the reference's 0.20), ``.film_grain`` the film grain's intensity as a float (0.0: off)
+    and ``.film_grain_seed`` the stream's seed."""
     import argparse
 
     ap = argparse.ArgumentParser(description=main.__doc__)
@@ -670,6 +671,13 @@ def parse_args(argv=None):
                     "and its SSimDownscaler shader; default: none, a smaller --out-size is refused")
     ap.add_argument("--down-antiring", default=None, metavar="{auto|0..1}", help="anti-ringing of --downscaler: a strength in 0 .. 1, or "
                     "auto = the reference's 0.20; default: off")
+    ap.add_argument("--film-grain", type=int, choices=(0, 1), default=0, help="the reference's flag: 1 = its film grain shader on the "
+                    "delivered frames at its intensity 0.01, on the device and placed as its shader chain places it (hdrtv_post_rgb48_grain "
+                    "and the _grain scalers; INTEGRATION.md 5c); with --scaler lanczos or fsr, without --downscaler and --deband")
+    ap.add_argument("--film-grain-intensity", type=float, default=None, metavar="{0..0.1}", help="intensity of --film-grain 1 instead of "
+                    "the reference's 0.01")
+    ap.add_argument("--film-grain-seed", type=int, default=0, help="the stream's grain seed, 0 .. 2^32 - 1: frame n is grained with "
+                    "hdrtv_film_grain_seed(seed, n)")
     ap.add_argument("--no-hg", action="store_true")
     ap.add_argument("--hg-weights", default=None, help="HG weight file, or seeded:<n>")
     ap.add_argument("--max-throughput", action="store_true", help="do not pace to the source clock")
@@ -759,6 +767,15 @@ def parse_args(argv=None):
         _lib.down_options(a.downscaler, a.down_antiring, wd, ht, owd, oht, a.scaler, a.antiring, a.cas)
     except ValueError as exc:
         ap.error(f"--downscaler: {exc}")
+    if a.film_grain_intensity is not None and not a.film_grain:
+        ap.error("--film-grain-intensity applies to --film-grain 1")
+    try:
+        # a bool is the flag itself; an intensity is a float (never True / False, which check_film_grain reads as the flag)
+        a.film_grain = _lib.check_grain_chain(bool(a.film_grain) if a.film_grain_intensity is None else float(a.film_grain_intensity),
+                                              a.scaler, a.downscaler, a.cleanup.deband)
+        a.film_grain_seed = _lib.check_grain_stream_seed(a.film_grain_seed)
+    except ValueError as exc:
+        ap.error(f"--film-grain: {exc}")
     a.proc_wh, a.out_wh, a.src_wh = (wd, ht), (owd, oht), (swd, sht)
     return a
 
@@ -783,7 +800,7 @@ def main(argv=None):
                                     deband=a.cleanup.deband, deband_range=a.cleanup.deband_range,
                                     deband_threshold=a.cleanup.deband_threshold, dither=a.cleanup.dither, antiring=a.antiring,
                                     cas=a.cas, scaler=a.scaler, fsr_sharpness=a.fsr_sharpness, downscaler=a.downscaler,
-                                    down_antiring=a.down_antiring)
+                                    down_antiring=a.down_antiring, film_grain=a.film_grain, grain_stream_seed=a.film_grain_seed)
     if not worker._load_model(a.precision):
         return 1
     sink = None
@@ -823,6 +840,8 @@ def main(argv=None):
         res["scaler"], res["fsr_sharpness"] = a.scaler, a.fsr_sharpness
     if a.downscaler is not None:
         res["downscaler"], res["down_antiring"] = a.downscaler, a.down_antiring
+    if a.film_grain:
+        res["film_grain"], res["film_grain_seed"] = a.film_grain, a.film_grain_seed
     if cll is not None:
         res["max_cll"], res["max_fall"], res["light_frames"] = cll.max_cll, cll.max_fall, cll.frames
         if a.light_level_json:

@@ -350,7 +350,8 @@ class HDRTVNetMI355X:
             raise ValueError(f"no error-diffusion scratch for {out.pix_fmt} at {out.w}x{out.h}")
         return self._scratch((key, "fs"), out, nbytes)
 
-    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None, scale=None):
+    def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None, scale=None,
+                  film_grain=0.0, grain_seed=0.0):
         """The output conversion of a frame whose planar tensor lies at ``src_ptr``, to the ``lib.OutputFormat`` ``out`` at
         ``dst_ptr``: ``rgb48le`` at the processing size (``hdrtv_post_rgb48``) or enlarged to ``out.h`` x ``out.w``
         (``hdrtv_post_rgb48_scaled``); a 10-bit Y'CbCr layout in one kernel at the processing size (``hdrtv_post_ycbcr10``), or,
@@ -369,14 +370,24 @@ class HDRTVNetMI355X:
         ``scale``: the ``lib.ScalePlan`` of a frame delivered at another size (``lib.ScaleOptions.plan`` of the two sizes, which is
         the one place that chooses among the six entry points): its entry point replaces
         ``hdrtv_post_rgb48_scaled``, and everything behind it -- deband, the conversion from codes, the record -- sees its codes.
-        A frame delivered at the processing size has none."""
+        A frame delivered at the processing size has none.
+        ``film_grain`` (an intensity, ``lib.check_film_grain``; 0: every path above as it is, no new launch, no new scratch) with
+        the frame's ``grain_seed``: the frame passes through RGB48 codes -- ``hdrtv_post_rgb48_grain`` at the processing size, the
+        ``_grain`` entry of ``scale`` (``lib.ScaleOptions.plan(..., film_grain, grain_seed)``) otherwise --, a Y'CbCr layout is
+        converted from those codes through the scratch, and the light level record is taken from the grained codes, which are
+        what the sink receives.  Deband with grain is a ``ValueError`` (``lib.check_grain_chain``)."""
         scaled = (out.h, out.w) != (h, w)
+        grain = film_grain != 0
         rect = (0, 0, out.w, out.h) if light_rect is None else tuple(int(v) for v in light_rect)
         active = cleanup is not None and cleanup.active
         deband, dither = active and cleanup.deband, active and cleanup.dither != "none"
         if dither and out.is_rgb48:
             raise ValueError("dither applies to the 10-bit Y'CbCr formats: rgb48le (16-bit codes) is not dithered")
-        codes = scaled or deband                     # the frame passes through RGB48 codes in device memory
+        if grain:
+            _L.check_grain_chain(film_grain, deband=deband)
+            if scaled and not scale.entry.endswith("_grain"):
+                raise ValueError(f"film_grain needs the _grain form of {scale.entry} (lib.ScaleOptions.plan(..., film_grain, grain_seed))")
+        codes = scaled or deband or grain            # the frame passes through RGB48 codes in device memory
         if light_ptr is not None and not codes:
             self._chk(self._lib.hdrtv_light_stats(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *rect, light_ptr), "hdrtv_light_stats")
         if not out.is_rgb48 and not codes:
@@ -393,6 +404,9 @@ class HDRTVNetMI355X:
         raw_ptr = self._scratch((scratch_key, "raw"), out) if deband else rgb_ptr       # deband never works in place
         if scaled:
             self._chk(getattr(self._lib, scale.entry)(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, out.h, out.w, *scale.args), scale.entry)
+        elif grain:
+            self._chk(self._lib.hdrtv_post_rgb48_grain(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, film_grain, grain_seed),
+                      "hdrtv_post_rgb48_grain")
         else:
             self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, src_ptr, dt, h, w, raw_ptr), "hdrtv_post_rgb48")
         if deband:
@@ -440,36 +454,42 @@ class HDRTVNetMI355X:
         return _L.output_cleanup(*cleanup, pix_fmt=out.pix_fmt)
 
     @staticmethod
-    def _plan_for(h, w, out, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring):
-        """The six scaler arguments of ``enqueue_frame*`` (``lib.ScaleOptions``) -> the ``lib.ScalePlan`` of the frame, or None."""
+    def _plan_for(h, w, out, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring, film_grain=0.0, grain_seed=0.0):
+        """The six scaler arguments of ``enqueue_frame*`` (``lib.ScaleOptions``) and the film grain's two -> the ``lib.ScalePlan`` of
+        the frame, or None."""
         def off(v):
             return type(v) in (float, int) and v == 0
         if scaler == "lanczos" and downscaler is None and off(antiring) and off(cas) and off(down_antiring):
             opts = _L.SCALE_OFF                                       # the default: nothing to check on the hot path
         else:
             opts = _L.scale_options(antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
-        return opts.plan(w, h, out.w, out.h)
+        return opts.plan(w, h, out.w, out.h, film_grain, grain_seed) if film_grain else opts.plan(w, h, out.w, out.h)
 
     def _enqueue_planes(self, fmt, lane, src_ptr, h, w, dst_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le", out_siting="left",
                         light_ptr=None, light_rect=None, cleanup=None, antiring=0.0, cas=0.0, scaler="lanczos",
-                        fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
+                        fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0, film_grain=0.0, grain_seed=0.0):
         """The body of ``enqueue_frame*`` (whose arguments these are): the argument checks, then the preprocess entry point of the
         ``lib.InputFormat`` ``fmt`` on the frame at ``src_ptr``, ``hdrtv_infer_lane`` and ``_post_out``, all on the lane's buffers
         and ``stream`` (default: the lane's own)."""
         out = self._frame_out(lane, h, w, out_hw, out_pix_fmt, out_siting)
         src = fmt.planes(src_ptr, h, w)
-        cleanup, plan = self._cleanup_for(cleanup, out), self._plan_for(h, w, out, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
+        if film_grain:                         # 0.0 / False: the path of before, nothing checked
+            film_grain, grain_seed = _L.check_grain_chain(film_grain, scaler, downscaler), _L.check_grain_seed(grain_seed)
+        cleanup = self._cleanup_for(cleanup, out)
+        plan = self._plan_for(h, w, out, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring, film_grain, grain_seed)
         self._ensure_buffers(h, w)
         st = C.c_void_p((stream if stream is not None else self._lane_streams[lane]).cuda_stream)
         tin, tcond, tout, tagcm = self._lane_bufs[lane]
         self._chk(getattr(self._lib, fmt.entry)(self._ctx, st, *src, h, w, tin.data_ptr(), tcond.data_ptr()), fmt.entry)
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), self._out_dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
-        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, plan)
+        self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, plan,
+                       film_grain, grain_seed)
 
     def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le",
                       out_siting="left", light_ptr=None, light_rect=None, cleanup=None, antiring=0.0, cas=0.0,
-                      scaler="lanczos", fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
+                      scaler="lanczos", fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0, film_grain=0.0,
+                      grain_seed=0.0):
         """One frame of the hot path on lane ``lane``, stream-ordered and without any host synchronisation: u8 BGR frame in
         device memory at ``src_bgr_ptr`` -> hdrtv_preprocess -> hdrtv_infer_lane -> hdrtv_post_rgb48 -> u16 RGB48 at the device
         address ``dst_rgb48_ptr``.  ``stream``: a ``torch.cuda.Stream`` (default: the lane's own).  Frames enqueued on different
@@ -484,26 +504,33 @@ class HDRTVNetMI355X:
         (``_post_out``); None: neither, and the bytes of before.  ``antiring``, ``cas``, ``scaler``,
         ``fsr_sharpness``, ``downscaler``, ``down_antiring``: how a frame with an ``out_hw`` other than the processing size is resized
         (``lib.ScaleOptions`` describes the six).  The defaults: plain Lanczos to a larger size, a smaller one is a
-        ``ValueError``, and a frame at the processing size is touched by none of them."""
+        ``ValueError``, and a frame at the processing size is touched by none of them.  ``film_grain`` (``lib.check_film_grain``:
+        True = the reference's 0.01, or an intensity up to 0.1) with ``grain_seed`` = ``lib.film_grain_seed(stream_seed, frame
+        index)``: the reference's film grain on the delivered frame, placed as its shader chain places it (``_post_out``;
+        INTEGRATION.md 5c); 0: every path exactly as before."""
         self._enqueue_planes(_BGR24, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream, out_hw, out_pix_fmt, out_siting,
-                             light_ptr, light_rect, cleanup, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
+                             light_ptr, light_rect, cleanup, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring,
+                             film_grain, grain_seed)
 
     def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None,
                              out_hw=None, out_pix_fmt="rgb48le", out_siting="left", light_ptr=None, light_rect=None, cleanup=None,
-                             antiring=0.0, cas=0.0, scaler="lanczos", fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
+                             antiring=0.0, cas=0.0, scaler="lanczos", fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0,
+                             film_grain=0.0, grain_seed=0.0):
         """``enqueue_frame`` of an 8-bit 4:2:0 frame: the planes lie back to back at the device address ``src_ptr`` (the
         ``(h*3//2, w)`` u8 array ``preprocess_yuv420`` takes) and ``hdrtv_preprocess_yuv420`` replaces ``hdrtv_preprocess``."""
         self._enqueue_planes(_in_format("yuv420", layout, matrix, full_range), lane, src_ptr, h, w, dst_rgb48_ptr, stream, out_hw, out_pix_fmt,
-                             out_siting, light_ptr, light_rect, cleanup, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
+                             out_siting, light_ptr, light_rect, cleanup, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring,
+                             film_grain, grain_seed)
 
     def enqueue_frame_ycbcr10(self, lane, src_ptr, h, w, dst_ptr, *, pix_fmt, matrix=709, full_range=False, stream=None, out_hw=None,
                               out_pix_fmt="rgb48le", out_siting="left", cleanup=None, antiring=0.0, cas=0.0, scaler="lanczos",
-                              fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
+                              fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0, film_grain=0.0, grain_seed=0.0):
         """``enqueue_frame`` of a 10-bit Y'CbCr frame (``pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le``): the planes lie
         back to back at the device address ``src_ptr`` (the u16 array ``preprocess_ycbcr10`` takes) and
         ``hdrtv_preprocess_ycbcr10`` replaces ``hdrtv_preprocess``."""
         self._enqueue_planes(_in_format("ycbcr10", pix_fmt, matrix, full_range), lane, src_ptr, h, w, dst_ptr, stream, out_hw, out_pix_fmt,
-                             out_siting, None, None, cleanup, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
+                             out_siting, None, None, cleanup, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring,
+                             film_grain, grain_seed)
 
     def _upload(self, key, src, staged=None):
         """Device pointer of the host u8 array ``src``, uploaded through the staging slot kept per ``key`` in ``_staging``: a
@@ -801,12 +828,14 @@ class HDRTVNetMI355X:
 
     @torch.inference_mode()
     def postprocess_rgb48_scaled(self, output, out_w, out_h, pq=False, peak_nits=1000.0, antiring=0.0, cas=0.0, scaler="lanczos",
-                                 fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
+                                 fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0, film_grain=0.0, grain_seed=0.0):
         """RGB48 at the display size: the u16 codes of ``hdrtv_post_rgb48`` (``pq=True``: of
         ``hdrtv_post_pq_rgb48`` at ``peak_nits``) upscaled to ``out_h`` x ``out_w`` by ``hdrtv_post_rgb48_scaled`` in one kernel.
         The six options after ``peak_nits`` choose another scaler, or one for a size below the processing size (``lib.ScaleOptions``
-        describes them; its ``plan`` has the refusals, each a ``ValueError``).  Returns a new device u16 ``(out_h, out_w, 3)``
-        tensor; stream-ordered on the current stream, no synchronisation."""
+        describes them; its ``plan`` has the refusals, each a ``ValueError``).  ``film_grain`` / ``grain_seed``: the reference's film
+        grain in the chain (``lib.check_film_grain``, ``lib.film_grain_seed``; the ``_grain`` entry points, ``hdrtv_post_rgb48_grain``
+        at equal sizes).  Returns a new device u16 ``(out_h, out_w, 3)`` tensor; stream-ordered on the current stream, no
+        synchronisation."""
         if isinstance(output, (tuple, list)):
             output = output[0]
         if output.dtype not in (torch.float16, torch.float32):
@@ -815,11 +844,33 @@ class HDRTVNetMI355X:
         out_w, out_h = int(out_w), int(out_h)
         opts = _L.scale_options(antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
         # equal sizes: the entry point itself writes the unscaled kernel's bytes (and takes pq, which hdrtv_post_rgb48 does not)
-        plan = opts.plan(w, h, out_w, out_h) or _L.ScalePlan("hdrtv_post_rgb48_scaled", ())
+        intensity = _L.check_grain_chain(film_grain, opts.scaler, opts.downscaler)
+        if intensity:
+            seed = _L.check_grain_seed(grain_seed)
+            plan = opts.plan(w, h, out_w, out_h, intensity, seed) or _L.ScalePlan("hdrtv_post_rgb48_scaled_grain", (0, 0, intensity, seed))
+        else:
+            plan = opts.plan(w, h, out_w, out_h) or _L.ScalePlan("hdrtv_post_rgb48_scaled", ())
         output = output.contiguous()
         dst = torch.empty((out_h, out_w, 3), dtype=torch.uint16, device=self.device)
         self._chk(getattr(self._lib, plan.entry)(self._ctx, self._stream(), output.data_ptr(), _dtype_code(output), h, w, 1 if pq else 0,
                                                  float(peak_nits), dst.data_ptr(), out_h, out_w, *plan.args), plan.entry)
+        return dst
+
+    @torch.inference_mode()
+    def postprocess_film_grain(self, rgb48, intensity=_L.FILM_GRAIN_INTENSITY, seed=0.0):
+        """Grained RGB48 codes: ``hdrtv_rgb48_film_grain`` on a device u16 ``(H, W, 3)`` tensor of codes (what
+        ``hdrtv_post_rgb48`` / ``postprocess_rgb48_scaled`` write), grain positions over its ``H`` x ``W``, ``seed`` =
+        ``lib.film_grain_seed(stream_seed, frame_index)``.  Returns a new device tensor of the same shape; the source is not
+        touched.  Stream-ordered on the current stream, no synchronisation."""
+        if not isinstance(rgb48, torch.Tensor) or rgb48.dtype != torch.uint16 or rgb48.ndim != 3 or rgb48.shape[2] != 3 or not rgb48.is_cuda:
+            raise ValueError("postprocess_film_grain expects a device uint16 (H, W, 3) tensor of RGB48 codes")
+        if rgb48.shape[0] < 1 or rgb48.shape[1] < 1:
+            raise ValueError("postprocess_film_grain expects a non-empty frame")
+        intensity, seed = _L.check_film_grain(intensity), _L.check_grain_seed(seed)
+        src = rgb48.contiguous()
+        dst = torch.empty_like(src)
+        self._chk(self._lib.hdrtv_rgb48_film_grain(self._ctx, self._stream(), src.data_ptr(), int(src.shape[0]), int(src.shape[1]),
+                                                   intensity, seed, dst.data_ptr()), "hdrtv_rgb48_film_grain")
         return dst
 
     @torch.inference_mode()

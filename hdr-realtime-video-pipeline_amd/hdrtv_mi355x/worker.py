@@ -129,7 +129,7 @@ class HeadlessPipelineWorker:
                  status_cb=None, buffer_frames=1, out_w=None, out_h=None, out_pix_fmt="rgb48le", out_siting="left",
                  light_stats=False, light_rect=None, deband=False, deband_range=_L.DEBAND_RANGE,
                  deband_threshold=_L.DEBAND_THRESHOLD, dither="none", antiring=0.0, cas=0.0, scaler="lanczos",
-                 fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0):
+                 fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0, film_grain=False, grain_stream_seed=0):
         self._weights_dir = weights_dir
         self._use_hg = bool(use_hg)
         self._hg_override = hg_weights
@@ -150,6 +150,13 @@ class HeadlessPipelineWorker:
         self._scale = _L.scale_options(antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring)
         if self._scale.scaler != "lanczos" or self._scale.downscaler is not None:
             self._scale.plan(self._proc_w, self._proc_h, self._out.w, self._out.h)
+        # the reference's film grain on the delivered frames, placed as its shader chain places it: True = its
+        # 0.01, or an intensity up to 0.1; off: nothing more is launched and the bytes are those of before.  Frame n of the stream
+        # gets lib.film_grain_seed(grain_stream_seed, n), n = the frame_idx of _process_frame: a function of the index, so another
+        # sink of the same stream (a second worker, the dispatcher's lanes) gives the frame the same grain.  With light_stats the
+        # record describes the grained codes.  The chains without grain are refused here (lib.check_grain_chain).
+        self._film_grain = _L.check_grain_chain(film_grain, self._scale.scaler, self._scale.downscaler, self._cleanup.deband)
+        self._grain_stream_seed = _L.check_grain_stream_seed(grain_stream_seed)
         # HDR10 content light level: every delivered frame carries its record (``.light``), measured on the
         # device from the codes the sink receives over ``light_rect = (x0, y0, rw, rh)`` in delivered-frame coordinates (None: the
         # whole frame), and ``content_light`` accumulates MaxCLL / MaxFALL in delivery order.  Off: nothing is launched or allocated.
@@ -346,7 +353,7 @@ class HeadlessPipelineWorker:
             staged = self._stage_hdr_display_tensor(prepared_out, use_cuda)
             ready = torch.cuda.Event(enable_timing=False)
             ready.record(torch.cuda.current_stream())
-            self._queue_display_item(self._hdr_queue, (present_t, staged, ready, (oh, ow)))
+            self._queue_display_item(self._hdr_queue, (present_t, staged, ready, (oh, ow), int(frame_idx)))
         need_hdr_cpu = not mpv_w
         output = self._processor.postprocess(prepared_out) if need_hdr_cpu else frame
         return None, output, prepared_out, need_hdr_cpu, model_latency_ms
@@ -363,7 +370,7 @@ class HeadlessPipelineWorker:
             q.put_nowait(item)
 
     # ---------------------------------------------------------------- RGB48 ring + feeder
-    def _tensor_to_rgb48_bytes(self, tensor, stream=None, out_hw=None):
+    def _tensor_to_rgb48_bytes(self, tensor, stream=None, out_hw=None, frame_idx=0):
         """feeders.py:193-249, GPU branch: quantise to RGB48 directly into a pinned ring slot and
         return a ``PinnedFrame`` guarded by the slot's ready event.  Ring exhaustion (no slot free
         within 250 ms, feeders.py:166-167) falls back to one blocking pinned buffer as the reference
@@ -371,7 +378,8 @@ class HeadlessPipelineWorker:
         ring, the fallback buffer and the frame are at that size and the conversion is the ``lib.ScalePlan`` of the worker's scaler
         options for the tensor's and the delivered size (``hdrtv_post_rgb48_scaled`` by default).  With a
         Y'CbCr ``out_pix_fmt`` the slot (an RGB48 slot holds any of the layouts) receives the planes, only the frame's bytes are
-        committed (``hdrtv_ring_commit_bytes``) and the frame is a 1-D u16 view of them."""
+        committed (``hdrtv_ring_commit_bytes``) and the frame is a 1-D u16 view of them.  ``frame_idx``: the frame's index in the
+        stream, which with ``film_grain`` on gives its grain seed (``lib.film_grain_seed``)."""
         p = self._processor
         t = tensor[0] if isinstance(tensor, (tuple, list)) else tensor
         th, tw = int(t.shape[-2]), int(t.shape[-1])
@@ -385,20 +393,23 @@ class HeadlessPipelineWorker:
         out = self._out.at(h, w)
         shape = out.shape
         # a hot-swap of the processing resolution may have moved the ratio past a scaler's limit: checked again here
-        scale = self._scale.plan(tw, th, w, h) if (h, w) != (th, tw) else None
+        grain = self._film_grain
+        seed = _L.film_grain_seed(self._grain_stream_seed, frame_idx) if grain else 0.0
+        scale = self._scale.plan(tw, th, w, h, grain, seed) if (h, w) != (th, tw) else None
 
         def convert(dst, key):
             """The frame into ``dst`` and, when measured, its light level record into the pinned record kept per ``key``, all on
             ``st``: whatever is recorded on ``st`` afterwards (the slot's ready event) covers both.  Returns that record."""
             if not self._light:
-                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, scale=scale)
+                p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, scale=scale,
+                            film_grain=grain, grain_seed=seed)
                 return None
             bufs = self._light_bufs.get(key)
             if bufs is None:
                 bufs = self._light_bufs[key] = (torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, device=p.device),
                                                 torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, pin_memory=True))
             p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", bufs[0].data_ptr(), self._light_rect,
-                        self._cleanup, scale)
+                        self._cleanup, scale, grain, seed)
             with torch.cuda.stream(st):
                 bufs[1].copy_(bufs[0], non_blocking=True)
             return bufs[1].numpy()
@@ -454,10 +465,10 @@ class HeadlessPipelineWorker:
                         continue
                     if item is None:
                         break
-                    present_t, tensor, ready, out_hw = item
+                    present_t, tensor, ready, out_hw, frame_idx = item
                     ready.synchronize()                      # cross-thread device sync (feeders.py:469-473)
                     with torch.cuda.stream(side):
-                        payload = self._tensor_to_rgb48_bytes(tensor, side, out_hw)
+                        payload = self._tensor_to_rgb48_bytes(tensor, side, out_hw, frame_idx)
                     if present_t is not None:
                         delay = present_t - time.perf_counter()
                         if delay > 0:

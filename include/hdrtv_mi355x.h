@@ -369,6 +369,56 @@ int hdrtv_post_rgb48_down(hdrtv_ctx *ctx, void *stream, const void *dev_out, int
 int hdrtv_post_rgb48_ssimsr(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
                             uint16_t *dst, int dH, int dW, int ssim);
 
+/* Film grain, the last shader of every chain the reference builds (assets/shaders/filmgrain.glsl: its "Film grain" checkbox,
+ * --film-grain 1, _build_shader_paths), as a rule on u16 RGB48 codes: a sink that takes these frames is not mpv and runs no GLSL
+ * hook.  The rule is this project's restatement of the shader, operation by operation in float32: every multiply, add, subtract and
+ * divide is rounded on its own (no fused multiply-add; GLSL parses x * 1.0/289.0 as (x * 1.0) / 289.0, a division, and likewise by
+ * 41), fract(v) = v - floor(v).  tests/film_grain_ref.py restates it in NumPy and the GPU tests hold every entry point below to
+ * it bit for bit.  For H x W grain positions, the position (x, y) and a per-frame seed in [0, 1) (the shader's `random`):
+ *       px = (float32(x) + 0.5) / float32(W);  py = (float32(y) + 0.5) / float32(H);  mx = px + 1;  my = py + 1;  mz = seed + 1
+ *       permute(v):  t = (34 v + 1) v;  return fract(t / 289) * 289
+ *       state = permute(permute(mx) + my) + mz;  state = permute(state);  rnd = fract(state / 41)
+ *       p = 0.95 rnd + 0.025;  q = p - 0.5;  r = q q;  num = a1 r + a0;  den = (r r + b1 r) + b0
+ *       g = q (a2 + num / den);  g = g * 0.255121822830526
+ *   with a0 = 0.151015505647689, a1 = -0.5303572634357367, a2 = 1.365020122861334, b0 = 0.132089632343748, b1 = -0.7607324991323768,
+ *   each rounded once to float32.  |g| <= 0.50000006; no intermediate is denormal and den >= 0.011, so a flush-to-zero mode does not
+ *   enter.  The grained code G of a code c, with the same g for the three channels of a pixel and the intensity I:
+ *       s = float32(c) / 65535;  v = sat(s + I * g);  G = (int)(v * 65535 + 0.5)        (the quantiser of the unscaled entry point)
+ *   The reference's I is 0.01 (a code moves by at most +-328); I * g = 0 returns c for every code.
+ * The seed of frame `frame_index` of a stream is an integer hash, so that two sinks (two lanes, two devices) agree on a frame:
+ *       h = (frame_index * 0x9E3779B1 + stream_seed * 0x85EBCA77) mod 2^32;  h ^= h >> 16;  h = h * 0x21F0AAAD mod 2^32;
+ *       h ^= h >> 15;  h = h * 0x735A2D97 mod 2^32;  h ^= h >> 15;  seed = float32((h >> 8) * 2^-24)
+ *   hdrtv_film_grain_seed computes it on the host (no context, no device).
+ * UNPINNED: mpv's own `random` sequence; the texture format mpv keeps a hooked MAIN in (this rule requantises to u16); what the
+ * GLSL compiler of a display makes of the divisions.
+ * Where the grain sits, as _build_shader_paths orders the chain:
+ *   hdrtv_rgb48_film_grain        G of the codes at src_rgb48, positions over H x W.  dst == src is allowed (a pixel depends on itself
+ *                                 only); any other overlap is the caller's error.
+ *   hdrtv_post_rgb48_grain        the codes hdrtv_post_rgb48 (pq = 0; peak_nits ignored) / hdrtv_post_pq_rgb48 (pq != 0) would write,
+ *                                 grained, in one launch: a frame delivered at the processing size.
+ *   hdrtv_post_rgb48_scaled_grain the Lanczos chain of hdrtv_post_rgb48_scaled_cas (antiring 0 .. 256, cas 0 or 1032 .. 4096): cas is
+ *                                 an ffmpeg filter in front of mpv, the grain hooks MAIN at the processing size, mpv scales last.  So:
+ *                                 codes, CAS where asked, G with positions over H x W, then the integer passes on the grained codes.
+ *                                 A tap outside the frame reads the grained edge pixel: G at the clamped position.
+ *   hdrtv_post_rgb48_fsr_grain    EASU and RCAS hook MAIN first and enlarge it, the grain comes after: G of the codes
+ *                                 hdrtv_post_rgb48_fsr would write, positions over dH x dW.
+ *   Every fused result is thus its twin's rule composed with this one; the three fused forms keep no codes in device memory in
+ *   between.  The grain in front of the spline36 / SSimSuperRes and Mitchell / SSimDownscaler scalers is not provided.
+ * intensity == 0 delegates to the twin without grain and writes its bytes (hdrtv_rgb48_film_grain copies the codes); equal sizes
+ * (dH == H && dW == W) in the two scaled forms delegate to hdrtv_post_rgb48_grain.  Stream-ordered; no reservation beyond the
+ * twin's tables.  HDRTV_EINVAL, before any device call and with dst untouched, for everything the twin refuses (hdrtv_post_rgb48 /
+ * hdrtv_post_pq_rgb48, hdrtv_post_rgb48_scaled_cas, hdrtv_post_rgb48_fsr; for hdrtv_rgb48_film_grain a NULL pointer or H, W < 1), for
+ * an intensity that is NaN, infinite or outside [0, 0.1], and for a seed that is NaN or outside [0, 1). */
+float hdrtv_film_grain_seed(uint32_t stream_seed, uint32_t frame_index);
+int hdrtv_rgb48_film_grain(hdrtv_ctx *ctx, void *stream, const uint16_t *src_rgb48, int H, int W, float intensity, float seed,
+                           uint16_t *dst);
+int hdrtv_post_rgb48_grain(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
+                           uint16_t *dst, float intensity, float seed);
+int hdrtv_post_rgb48_scaled_grain(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
+                                  uint16_t *dst, int dH, int dW, int antiring, int cas, float intensity, float seed);
+int hdrtv_post_rgb48_fsr_grain(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
+                               uint16_t *dst, int dH, int dW, int rcas, float sharpness, float intensity, float seed);
+
 /* 10-bit limited-range Y'CbCr for an encoder (HEVC Main10, hardware encoders, ProRes): P010 and yuv420p10le are 3 bytes per pixel,
  * yuv422p10le 4, against the 6 of RGB48.  The reference's export converts on the CPU: it pipes rgb48le into ffmpeg, zscale goes to
  * BT.2020nc limited range and format=yuv422p10le feeds prores_ks (gui_export.py:948-1005).  The network's output is PQ-encoded BT.2020
