@@ -72,8 +72,8 @@ is W8A8 where the checkpoint says so; every other layer is R's fp16 primitive of
 `plan(profile, P)` merges what R.plan merges (rt1a+rt1b, rt2a+rt2b, rt30a..rt32b: the intermediate is overwritten later in the
 frame), checks every kernel tag and fails on an LE launch no check claims.
 
-NOT held this way (they stay on the cumulative bars of tests/test_gpu_int8_hr.py / test_gpu_int8_hg.py): the fake-quant row form
-le_rows<fq> that the mixed recipe's default path takes, agcm_fold<q8> / agcm_mlp<q8>, the HG int8 head.  The int8 row kernels
+NOT held this way (they stay on the cumulative bars of tests/test_gpu_int8_hr.py): le_rows<fq>, agcm_fold<q8> / agcm_mlp<q8>.  (The HG
+int8 head: tests/hg_i8_layer_ref.py.)  The int8 row kernels
 (le_rows_i8.hip) are reached through bit-identity with these launches (tests/test_gpu_le_i8_layers.py `default` form).
 """
 from __future__ import annotations
