@@ -282,16 +282,17 @@ struct hdrtv_ctx {
     LetterboxParams lb{};
     // Every device buffer of the entry points beside the workspace and the ring, each allocated on first use; hdrtv_destroy releases
     // them all by assigning an empty Bufs.  lb: the letterbox tables of lb_key.  pq: the PQ quantiser's 65536 code boundaries and the
-    // kernel's first-guess table.  mt: the metrics' partial sums.  fr_*: the full-reference chain's border counts, six histograms, two
-    // evaluation frames, area tables per (sh, sw, nh, nw).  scale_tabs: the RGB48 scalers' per scale_tables::Kind and (H, W, dH, dW).
+    // kernel's first-guess table.  lin: the tone map's 65536 levels of the PQ codes (resample_tables.h pq_eotf_table).  mt: the
+    // metrics' partial sums.  fr_*: the full-reference chain's border counts, six histograms, two evaluation frames, area tables per (sh, sw, nh, nw).  scale_tabs: the RGB48 scalers' per scale_tables::Kind and (H, W, dH, dW).
     struct ScaleTab : hdrtv_host::DevBuf { int ntx, nty; };
     struct AreaTab : hdrtv_host::DevBuf { resample_tables::Layout at; };
     struct Bufs {
-        hdrtv_host::DevBuf lb, pq, mt, fr_counts, fr_hist, fr_eval;
+        hdrtv_host::DevBuf lb, pq, lin, mt, fr_counts, fr_hist, fr_eval;
         std::map<std::array<int, 4>, AreaTab> fr_tabs;
         std::array<std::map<std::array<int, 4>, ScaleTab>, scale_tables::NKINDS> scale_tabs;
     } bufs;
     const float *pq_bnd() const { return bufs.pq.at<const float>(); }      // null until the first PQ call of the context
+    const float *pq_lin() const { return bufs.lin.at<const float>(); }     // null until the first tone-map call of the context
     uint32_t *fr_hist_host = nullptr;     // pinned: the histograms' landing place on the host
     // ring
     std::vector<hdrtv_host::RingSlot> ring;

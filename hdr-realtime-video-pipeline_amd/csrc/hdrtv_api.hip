@@ -718,6 +718,49 @@ int hdrtv_post_rgb48_fsr_grain(hdrtv_ctx *c, void *stream, const void *in, int d
     return launched(c, what, post_fsr_grain_launch(p, rcas, sharp, intensity, seed, dtype == HDRTV_F32, pq != 0, (hipStream_t)stream));
 }
 
+// ------------------------------------------------------------------- tone map (include/hdrtv_mi355x.h states the rule)
+static const std::vector<float> &pq_eotf_levels()
+{
+    static const std::vector<float> lin = [] { std::vector<float> v; rt::pq_eotf_table(v); return v; }();
+    return lin;
+}
+
+int hdrtv_pq_eotf_table(float *dst65536)
+{
+    if (!dst65536) return HDRTV_EINVAL;
+    memcpy(dst65536, pq_eotf_levels().data(), 65536 * sizeof(float));
+    return HDRTV_OK;
+}
+
+// the walk's boundaries and the levels of the codes: built and uploaded by the first tone-map call of a context, then kept
+static int ensure_tone_tables(hdrtv_ctx *c, const char *what)
+{
+    if (int rc = ensure_pq_table(c, what)) return rc;
+    if (c->pq_lin()) return HDRTV_OK;
+    return upload(c, c->bufs.lin, what, pq_eotf_levels().data(), 65536 * sizeof(float));
+}
+
+int hdrtv_rgb48_tonemap(hdrtv_ctx *c, void *stream, const uint16_t *src, int H, int W, const float *dev_gain, uint16_t *dst)
+{
+    const char *what = "rgb48_tonemap";
+    if (!c || !src || !dst || !dev_gain || H < 1 || W < 1) return fail(c, HDRTV_EINVAL, "%s: bad argument", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_tone_tables(c, what)) return rc;
+    return launched(c, what, rgb48_tonemap_launch(src, dst, H, W, dev_gain, c->pq_lin(), c->pq_bnd(), (hipStream_t)stream));
+}
+
+int hdrtv_post_rgb48_tonemap(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
+                             const float *dev_gain, uint16_t *dst)
+{
+    const char *what = "post_rgb48_tonemap";
+    if (int rc = scale_common_args(c, what, in, dtype, H, W, pq, peak_nits, dst, H, W, nullptr)) return rc;
+    if (!dev_gain) return fail(c, HDRTV_EINVAL, "%s: bad argument", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_tone_tables(c, what)) return rc;
+    return launched(c, what, post_rgb48_tonemap_launch(in, dtype == HDRTV_F32, H, W, dst, pq != 0, peak_nits, dev_gain, c->pq_lin(),
+                                                       c->pq_bnd(), (hipStream_t)stream));
+}
+
 int hdrtv_post_rgb48_down(hdrtv_ctx *c, void *stream, const void *in, int dtype, int H, int W, int pq, float peak_nits,
                           uint16_t *dst, int dH, int dW, int antiring, int ssim)
 {

@@ -165,6 +165,13 @@ hipError_t post_fsr_launch(const PostFsrParams &p, int rcas, float sharp, int is
 hipError_t film_grain_launch(const uint16_t *src, uint16_t *dst, int H, int W, float intensity, float seed, hipStream_t s);
 hipError_t post_rgb48_grain_launch(const void *in, int is_f32, int H, int W, uint16_t *rgb, int pq, float peak, const float *pq_bnd,
                                    float intensity, float seed, hipStream_t s);
+// the tone map of include/hdrtv_mi355x.h (post_tonemap.hip): codes -> tone-mapped codes (dst == src allowed), and tensor -> quant_rgb
+// -> tone-mapped codes in one launch.  gain: the caller's 65536 floats; lin: resample_tables.h pq_eotf_table; pq_bnd: the PQ code
+// boundaries, needed whatever pq is.  hipErrorInvalidValue, nothing enqueued, for a null pointer or H, W < 1
+hipError_t rgb48_tonemap_launch(const uint16_t *src, uint16_t *dst, int H, int W, const float *gain, const float *lin, const float *pq_bnd,
+                                hipStream_t s);
+hipError_t post_rgb48_tonemap_launch(const void *in, int is_f32, int H, int W, uint16_t *rgb, int pq, float peak, const float *gain,
+                                     const float *lin, const float *pq_bnd, hipStream_t s);
 // post_scale_grain.hip: the Lanczos tile with the staged (antiring 0 .. 256; cas 0 or 1032 .. 4096: sharpened) codes grained over H x W
 hipError_t post_scale_grain_launch(const PostScaleParams &p, int antiring, int cas, float intensity, float seed, int is_f32, int pq,
                                    hipStream_t s);

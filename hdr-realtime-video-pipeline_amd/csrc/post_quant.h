@@ -26,9 +26,10 @@ __device__ __forceinline__ uint32_t quant_u16(float x)
 // bit pattern is (PQ_LUT_BASE + i) << 17 -- 64 steps per binary octave from 2^-27 to 1, the curve's own near-logarithmic
 // spacing -- and the code in between is interpolated on the low 17 mantissa bits (within 2 codes of the truth everywhere).
 constexpr int PQ_LUT_BASE = (127 - 27) << 6, PQ_LUT_N = 27 * 64 + 2, PQ_LUT_OFF = 65536;
-__device__ __forceinline__ uint32_t pq_code(float lin, float peak, const float *__restrict__ bnd)
+// pq_code_level: the code of a level y with 1.0 = 10000 nits, clamped to [0, 1] here (the oracle's orc_pq_code; post_tonemap.hip
+// calls it on a scaled table entry).  pq_code: the code of a linear value with 1.0 = `peak` nits -- the same walk behind its scaling.
+__device__ __forceinline__ uint32_t pq_code_level(float y, const float *__restrict__ bnd)
 {
-    float y = __fdiv_rn(__fmul_rn(lin, peak), 10000.f);
     y = fminf(fmaxf(y, 0.f), 1.f);
     const uint32_t bits = __float_as_uint(y);
     int c = 0;
@@ -40,6 +41,10 @@ __device__ __forceinline__ uint32_t pq_code(float lin, float peak, const float *
     while (c < 65535 && y >= bnd[c + 1]) ++c;
     while (c > 0 && y < bnd[c]) --c;
     return (uint32_t)c;
+}
+__device__ __forceinline__ uint32_t pq_code(float lin, float peak, const float *__restrict__ bnd)
+{
+    return pq_code_level(__fdiv_rn(__fmul_rn(lin, peak), 10000.f), bnd);
 }
 __device__ __forceinline__ float gamut_row(float m0, float m1, float m2, float r, float g, float b)
 {

@@ -144,4 +144,20 @@ inline void pq_boundaries(std::vector<float> &bnd)
     }
 }
 
+// ---- the way back, for the tone map (post_tonemap.hip): lin[c] = the fp32 nearest to the ST.2084 EOTF of c / 65535 (1.0 = 10000
+// nits), then moved along the fp32 grid until pq_code64(lin[c]) == c.  So the round trip code -> level -> code is the identity on
+// all 65536 codes, and a level scaled by exactly 1.0f comes back as the code it was read from.
+inline void pq_eotf_table(std::vector<float> &lin)
+{
+    lin.assign(65536, 0.f);
+    for (int c = 1; c <= 65535; ++c) {
+        const double t = std::pow((double)c / 65535.0, 1.0 / 78.84375);
+        const double num = std::max(t - 0.8359375, 0.0), den = 18.8515625 - 18.6875 * t;
+        float f = (float)std::min(1.0, std::max(0.0, std::pow(num / den, 1.0 / 0.1593017578125)));
+        while (f < 1.f && pq_code64(f) < c) f = std::nextafterf(f, 2.f);
+        while (f > 0.f && pq_code64(f) > c) f = std::nextafterf(f, -1.f);
+        lin[c] = f;
+    }
+}
+
 }  // namespace resample_tables

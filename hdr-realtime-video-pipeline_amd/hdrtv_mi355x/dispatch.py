@@ -84,6 +84,9 @@ class _Mi355xWorker:
         # the film grain of the delivered frames (validated by the dispatcher, which hands it on only when it is on): the intensity and
         # the stream's seed; a frame's own seed comes from its index in the stream (frame_index), whichever worker or lane takes it
         self.film_grain, self.grain_stream_seed = L.check_film_grain(kw.pop("film_grain", 0.0)), int(kw.pop("grain_stream_seed", 0))
+        # the tone map of the delivered frames (validated by the dispatcher, which hands its four options on only when it is on)
+        self.tone = L.tone_mapping(kw.pop("tone_mapping", None), kw.pop("target_peak", None), kw.pop("source_peak", L.TONE_SOURCE_PEAK),
+                                   param=kw.pop("tone_param", None))
         torch.cuda.set_device(device_index)
         with contextlib.redirect_stdout(sys.stderr):   # a worker's banner must not land on the parent's stdout (bench.py's one JSON line)
             self.proc = HDRTVNetMI355X(model, device=f"cuda:{device_index}", warmup_passes=0, **kw)
@@ -129,6 +132,8 @@ class _Mi355xWorker:
         h, w = src.frame_hw(frame)
         fmt = self.output_format
         out_fmt = dict(out_hw=(fmt.h, fmt.w), out_pix_fmt=fmt.pix_fmt, out_siting=fmt.siting, cleanup=self.cleanup, **self.scale._asdict())
+        if self.tone is not None:
+            out_fmt["tone"] = self.tone
         if self.film_grain:
             out_fmt.update(film_grain=self.film_grain, grain_seed=self._L.film_grain_seed(self.grain_stream_seed, self.frame_index))
         self._buffers(h, w, tuple(frame.shape) + ((2,) if frame.itemsize == 2 else ()), fmt)       # _raw is bytes: a u16 sample is two
@@ -355,7 +360,8 @@ class FrameDispatcher:
                  start_timeout=600.0, numa=True, pix_fmt="bgr24", yuv_matrix=709, yuv_full_range=False, out_height=None,
                  out_width=None, out_pix_fmt="rgb48le", out_siting="left", deband=False, deband_range=16, deband_threshold=1311,
                  dither="none", antiring=0.0, cas=0.0, scaler="lanczos", fsr_sharpness=0.2, downscaler=None,
-                 down_antiring=0.0, film_grain=False, grain_stream_seed=0):
+                 down_antiring=0.0, film_grain=False, grain_stream_seed=0, tone_mapping=None, target_peak=None, source_peak=1000.0,
+                 tone_param=None):
         """``sink(index, rgb48_view)`` is called in index order from the reorder thread; the view is only valid during the
         call (the slot goes back to its worker afterwards).  ``numa``: workers pin themselves to their GPU's NUMA node
         (False: report only).  ``pix_fmt``: ``bgr24`` input frames are u8 (H, W, 3); ``yuv420p`` / ``nv12`` frames are u8
@@ -380,7 +386,12 @@ class FrameDispatcher:
         slots of the output size.  ``film_grain`` (``lib.check_film_grain``: True = the reference's 0.01, or an intensity up to 0.1)
         / ``grain_stream_seed`` (a u32): the reference's film grain on the delivered frames; the chains without
         grain are refused here (``lib.check_grain_chain``).  When on, both travel in ``init_args``, and frame ``i`` of the stream gets
-        ``lib.film_grain_seed(grain_stream_seed, i)`` whichever worker, device or lane computes it."""
+        ``lib.film_grain_seed(grain_stream_seed, i)`` whichever worker, device or lane computes it.  ``tone_mapping`` (``"spline"``,
+        ``"bt.2390"``, ``"clip"``; None / ``"none"``: off) / ``target_peak`` / ``source_peak`` / ``tone_param``: the delivered frames
+        rolled off to the sink's peak (``lib.tone_mapping`` validates), kept as ``.tone`` (a ``lib.ToneMapping`` or
+        None).  Only when on, the four travel in ``init_args`` under these names and the product's worker hands the record to
+        ``enqueue_frame(..., tone=)``; a curve is a function of the record alone, so every worker, device and lane rolls a frame
+        off to the same bytes."""
         if n_workers < 1 or slots < 2:
             raise ValueError("n_workers >= 1 and slots >= 2")
         from . import lib as _L
@@ -397,7 +408,11 @@ class FrameDispatcher:
         self.cleanup = _L.output_cleanup(deband, deband_range, deband_threshold, dither, pix_fmt=out.pix_fmt)
         self.film_grain = _L.check_grain_chain(film_grain, self.scaler, self.downscaler, self.cleanup.deband)
         self.grain_stream_seed = _L.check_grain_stream_seed(grain_stream_seed)
+        self.tone = _L.tone_mapping(tone_mapping, target_peak, source_peak, param=tone_param)
         init_args = dict(init_args or {})
+        if self.tone is not None:
+            init_args.update(tone_mapping=self.tone.kind, target_peak=self.tone.target_peak, source_peak=self.tone.source_peak,
+                             tone_param=self.tone.param)
         if self.film_grain:
             init_args["film_grain"], init_args["grain_stream_seed"] = self.film_grain, self.grain_stream_seed
         if self.cleanup.active:

@@ -64,6 +64,9 @@ SYMBOLS = [
     ("hdrtv_post_rgb48_grain", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, C.c_float, C.c_float]),
     ("hdrtv_post_rgb48_scaled_grain", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, _I, C.c_float, C.c_float]),
     ("hdrtv_post_rgb48_fsr_grain", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _I, _I, _I, C.c_float, C.c_float, C.c_float]),
+    ("hdrtv_pq_eotf_table", _I, [_VP]),
+    ("hdrtv_rgb48_tonemap", _I, [_VP, _VP, _VP, _I, _I, _VP, _VP]),
+    ("hdrtv_post_rgb48_tonemap", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _VP, _VP]),
     ("hdrtv_post_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_rgb48_to_ycbcr10", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _I]),
     ("hdrtv_ycbcr10_bytes", C.c_int64, [_I, _I, _I]),
@@ -624,6 +627,55 @@ def check_grain_chain(film_grain, scaler="lanczos", downscaler=None, deband=Fals
     if deband:
         raise ValueError("film_grain does not go with deband: a deband behind the grain would average the grain away")
     return intensity
+
+
+TONE_CURVES = ("spline", "bt.2390", "clip")          # tonemap.KINDS; "spline" is the reference's (mpv tone-mapping=spline)
+TONE_SOURCE_PEAK = 1000.0                  # the reference's expectation of the model's output, in nits
+
+
+class ToneMapping(NamedTuple):
+    """The tone map of the delivered frames: the arguments of ``tonemap.tone_curve``, validated.  Built by
+    ``tone_mapping``; a plain tuple that crosses into the dispatcher's worker processes as it is, like ``OutputCleanup``, and the
+    key under which a processor keeps the curve's device gain table."""
+    kind: str
+    target_peak: float
+    source_peak: float
+    target_min: float
+    source_min: float
+    source_avg: object
+    param: object
+
+    def curve(self):
+        from . import tonemap
+        return tonemap.tone_curve(*self)
+
+    def gain_table(self):
+        """The curve's ``gain[65536]`` as float32 (``hdrtv_rgb48_tonemap``'s ``dev_gain``, once uploaded)."""
+        return self.curve().gain_table()
+
+
+def tone_mapping(kind=None, target_peak=None, source_peak=TONE_SOURCE_PEAK, target_min=0.0, source_min=0.0, source_avg=None, param=None):
+    """The one constructor of ``ToneMapping``, as the processor, the worker, the dispatcher and the command line take the option:
+    ``kind`` None / ``"none"`` -> None (off: nothing else is looked at); one of ``TONE_CURVES`` with a ``target_peak`` in nits ->
+    the record, or None when ``target_peak >= source_peak`` (nothing to roll off; mpv does not tone-map then either).
+    ``ValueError`` for everything ``tonemap.tone_curve`` refuses and for a curve without ``target_peak``."""
+    if kind is None or (isinstance(kind, str) and kind.lower() == "none"):
+        return None
+    if target_peak is None:
+        raise ValueError(f"tone mapping {kind!r} needs target_peak, the sink's peak in nits")
+    from . import tonemap
+    c = tonemap.tone_curve(kind, target_peak, source_peak, target_min, source_min, source_avg, param)
+    return None if c.off else ToneMapping(c.kind, c.target_peak, c.source_peak, c.target_min, c.source_min, c.source_avg, c.param)
+
+
+def pq_eotf_table():
+    """``hdrtv_pq_eotf_table``: the tone map's ``lin[65536]`` as float32 -- the level (1.0 = 10000 nits) of every u16 PQ code, with
+    ``code(lin[c]) == c``.  Host only: needs the built library, no device."""
+    lin = np.empty(65536, dtype=np.float32)
+    rc = load().hdrtv_pq_eotf_table(lin.ctypes.data)
+    if rc != OK:
+        raise RuntimeError(f"hdrtv_pq_eotf_table failed ({rc})")
+    return lin
 
 
 class ScalePlan(NamedTuple):

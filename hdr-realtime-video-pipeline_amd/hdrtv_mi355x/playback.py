@@ -618,7 +618,8 @@ def parse_args(argv=None):
     strength as a float (0.0: off; both 0.0 under any ``--scaler`` but lanczos), ``.scaler`` one of ``lib.UPSCALERS``, ``.fsr_sharpness`` the RCAS
     sharpness as a float or None (EASU alone), ``.downscaler`` None, ``"mitchell"`` or ``"ssim"``, ``.down_antiring`` its anti-ringing
     strength as a float (``auto`` resolved to the reference's 0.20), ``.film_grain`` the film grain's intensity as a float (0.0: off)
-    and ``.film_grain_seed`` the stream's seed."""
+    and ``.film_grain_seed`` the stream's seed, ``.tone`` the ``lib.ToneMapping`` of --tone-mapping / --target-peak / --source-peak /
+    --tone-mapping-param, or None when off."""
     import argparse
 
     ap = argparse.ArgumentParser(description=main.__doc__)
@@ -678,6 +679,15 @@ def parse_args(argv=None):
                     "the reference's 0.01")
     ap.add_argument("--film-grain-seed", type=int, default=0, help="the stream's grain seed, 0 .. 2^32 - 1: frame n is grained with "
                     "hdrtv_film_grain_seed(seed, n)")
+    ap.add_argument("--tone-mapping", choices=("none",) + tuple(_lib.TONE_CURVES), default="none", help="roll the delivered frames off to "
+                    "--target-peak on the device (hdrtv_rgb48_tonemap / hdrtv_post_rgb48_tonemap; INTEGRATION.md 5i): spline = the "
+                    "reference's mpv setting (this library's restatement of it), bt.2390 = the Report's EETF, clip; default: none")
+    ap.add_argument("--target-peak", type=float, default=None, metavar="NITS", help="the sink's peak in nits, needed with --tone-mapping; at "
+                    "or above --source-peak nothing is tone-mapped")
+    ap.add_argument("--source-peak", type=float, default=_lib.TONE_SOURCE_PEAK, metavar="NITS", help="the peak the frames are mastered at; "
+                    "default: the model's 1000 nits")
+    ap.add_argument("--tone-mapping-param", type=float, default=None, metavar="{0..1}", help="contrast of --tone-mapping spline; default: "
+                    "the reference's 0.45")
     ap.add_argument("--no-hg", action="store_true")
     ap.add_argument("--hg-weights", default=None, help="HG weight file, or seeded:<n>")
     ap.add_argument("--max-throughput", action="store_true", help="do not pace to the source clock")
@@ -776,6 +786,12 @@ def parse_args(argv=None):
         a.film_grain_seed = _lib.check_grain_stream_seed(a.film_grain_seed)
     except ValueError as exc:
         ap.error(f"--film-grain: {exc}")
+    if a.tone_mapping == "none" and (a.target_peak is not None or a.tone_mapping_param is not None):
+        ap.error("--target-peak and --tone-mapping-param apply to --tone-mapping spline, bt.2390 or clip")
+    try:
+        a.tone = _lib.tone_mapping(a.tone_mapping, a.target_peak, a.source_peak, param=a.tone_mapping_param)
+    except ValueError as exc:
+        ap.error(f"--tone-mapping: {exc}")
     a.proc_wh, a.out_wh, a.src_wh = (wd, ht), (owd, oht), (swd, sht)
     return a
 
@@ -800,7 +816,9 @@ def main(argv=None):
                                     deband=a.cleanup.deband, deband_range=a.cleanup.deband_range,
                                     deband_threshold=a.cleanup.deband_threshold, dither=a.cleanup.dither, antiring=a.antiring,
                                     cas=a.cas, scaler=a.scaler, fsr_sharpness=a.fsr_sharpness, downscaler=a.downscaler,
-                                    down_antiring=a.down_antiring, film_grain=a.film_grain, grain_stream_seed=a.film_grain_seed)
+                                    down_antiring=a.down_antiring, film_grain=a.film_grain, grain_stream_seed=a.film_grain_seed,
+                                    tone_mapping=a.tone_mapping, target_peak=a.target_peak, source_peak=a.source_peak,
+                                    tone_param=a.tone_mapping_param)
     if not worker._load_model(a.precision):
         return 1
     sink = None
@@ -842,6 +860,8 @@ def main(argv=None):
         res["downscaler"], res["down_antiring"] = a.downscaler, a.down_antiring
     if a.film_grain:
         res["film_grain"], res["film_grain_seed"] = a.film_grain, a.film_grain_seed
+    if a.tone is not None:
+        res["tone_mapping"], res["target_peak"], res["source_peak"] = a.tone.kind, a.tone.target_peak, a.tone.source_peak
     if cll is not None:
         res["max_cll"], res["max_fall"], res["light_frames"] = cll.max_cll, cll.max_fall, cll.frames
         if a.light_level_json:

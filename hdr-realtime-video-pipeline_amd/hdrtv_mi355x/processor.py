@@ -228,6 +228,7 @@ class HDRTVNetMI355X:
                 self._ctx = C.c_void_p()
                 raise
         self._lane_bufs, self._lane_streams = [], []
+        self._tone_tables = {}                 # _tone_gain: lib.ToneMapping -> its device gain table, at most TONE_TABLES_MAX of them
         self._ycc_scratch = {}                 # _post_out: RGB48 at the output size per lane / caller (the two-launch Y'CbCr path)
         if self._fast_zero_condition or self._fast_condition_resize:
             self._chk(self._lib.hdrtv_set_cond_mode(self._ctx, 2 if self._fast_zero_condition else 1), "hdrtv_set_cond_mode")
@@ -351,7 +352,7 @@ class HDRTVNetMI355X:
         return self._scratch((key, "fs"), out, nbytes)
 
     def _post_out(self, st, src_ptr, dt, h, w, dst_ptr, out, scratch_key, light_ptr=None, light_rect=None, cleanup=None, scale=None,
-                  film_grain=0.0, grain_seed=0.0):
+                  film_grain=0.0, grain_seed=0.0, tone=None):
         """The output conversion of a frame whose planar tensor lies at ``src_ptr``, to the ``lib.OutputFormat`` ``out`` at
         ``dst_ptr``: ``rgb48le`` at the processing size (``hdrtv_post_rgb48``) or enlarged to ``out.h`` x ``out.w``
         (``hdrtv_post_rgb48_scaled``); a 10-bit Y'CbCr layout in one kernel at the processing size (``hdrtv_post_ycbcr10``), or,
@@ -375,9 +376,16 @@ class HDRTVNetMI355X:
         the frame's ``grain_seed``: the frame passes through RGB48 codes -- ``hdrtv_post_rgb48_grain`` at the processing size, the
         ``_grain`` entry of ``scale`` (``lib.ScaleOptions.plan(..., film_grain, grain_seed)``) otherwise --, a Y'CbCr layout is
         converted from those codes through the scratch, and the light level record is taken from the grained codes, which are
-        what the sink receives.  Deband with grain is a ``ValueError`` (``lib.check_grain_chain``)."""
+        what the sink receives.  Deband with grain is a ``ValueError`` (``lib.check_grain_chain``).
+        ``tone`` (a ``lib.ToneMapping``; None: every path above as it is, no new launch, no new scratch): the frame is rolled off to
+        the sink's peak behind scale, grain and deband and in front of the record and the conversion from
+        codes.  A frame at the processing size without grain and deband takes ``hdrtv_post_rgb48_tonemap`` in place of
+        ``hdrtv_post_rgb48`` (a Y'CbCr layout into the codes scratch it is then converted from); every other path runs
+        ``hdrtv_rgb48_tonemap`` in place on the RGB48 codes it already holds.  The record is always taken from the tone-mapped
+        codes (``hdrtv_rgb48_light_stats``), so MaxCLL describes what is delivered."""
         scaled = (out.h, out.w) != (h, w)
         grain = film_grain != 0
+        gain_ptr = None if tone is None else self._tone_gain(tone)
         rect = (0, 0, out.w, out.h) if light_rect is None else tuple(int(v) for v in light_rect)
         active = cleanup is not None and cleanup.active
         deband, dither = active and cleanup.deband, active and cleanup.dither != "none"
@@ -387,7 +395,7 @@ class HDRTVNetMI355X:
             _L.check_grain_chain(film_grain, deband=deband)
             if scaled and not scale.entry.endswith("_grain"):
                 raise ValueError(f"film_grain needs the _grain form of {scale.entry} (lib.ScaleOptions.plan(..., film_grain, grain_seed))")
-        codes = scaled or deband or grain            # the frame passes through RGB48 codes in device memory
+        codes = scaled or deband or grain or gain_ptr is not None      # the frame passes through RGB48 codes in device memory
         if light_ptr is not None and not codes:
             self._chk(self._lib.hdrtv_light_stats(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, *rect, light_ptr), "hdrtv_light_stats")
         if not out.is_rgb48 and not codes:
@@ -407,11 +415,16 @@ class HDRTVNetMI355X:
         elif grain:
             self._chk(self._lib.hdrtv_post_rgb48_grain(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, raw_ptr, film_grain, grain_seed),
                       "hdrtv_post_rgb48_grain")
+        elif gain_ptr is not None and not deband:
+            self._chk(self._lib.hdrtv_post_rgb48_tonemap(self._ctx, st, src_ptr, dt, h, w, 0, 0.0, gain_ptr, rgb_ptr), "hdrtv_post_rgb48_tonemap")
+            gain_ptr = None                          # done
         else:
             self._chk(self._lib.hdrtv_post_rgb48(self._ctx, st, src_ptr, dt, h, w, raw_ptr), "hdrtv_post_rgb48")
         if deband:
             self._chk(self._lib.hdrtv_rgb48_deband(self._ctx, st, raw_ptr, out.h, out.w, cleanup.deband_range, cleanup.deband_threshold, 0,
                                                    rgb_ptr), "hdrtv_rgb48_deband")
+        if gain_ptr is not None:
+            self._chk(self._lib.hdrtv_rgb48_tonemap(self._ctx, st, rgb_ptr, out.h, out.w, gain_ptr, rgb_ptr), "hdrtv_rgb48_tonemap")
         if light_ptr is not None and codes:
             self._chk(self._lib.hdrtv_rgb48_light_stats(self._ctx, st, rgb_ptr, out.h, out.w, *rect, light_ptr), "hdrtv_rgb48_light_stats")
         if out.is_rgb48:
@@ -424,6 +437,28 @@ class HDRTVNetMI355X:
                       "hdrtv_rgb48_to_ycbcr10_ex")
         else:
             self._chk(self._lib.hdrtv_rgb48_to_ycbcr10(self._ctx, st, rgb_ptr, out.h, out.w, *out.planes(dst_ptr)), "hdrtv_rgb48_to_ycbcr10")
+
+    TONE_TABLES_MAX = 16                       # gain tables a processor keeps (256 KiB each): one per lib.ToneMapping it has been given
+
+    def _tone_gain(self, tone):
+        """Device address of the float32 ``gain[65536]`` of the ``lib.ToneMapping`` ``tone``: built (``tonemap.py``, on the host) and
+        uploaded on first use, then kept for as long as the processor lives -- frames in flight on any lane may read it, so no
+        entry is ever replaced.  The cache is bounded instead: a processor serves a few sinks, and record number
+        ``TONE_TABLES_MAX`` + 1 is a ``ValueError``."""
+        if not isinstance(tone, _L.ToneMapping):
+            raise ValueError("tone must be a lib.ToneMapping (lib.tone_mapping builds one) or None")
+        table = self._tone_tables.get(tone)
+        if table is None:
+            if len(self._tone_tables) >= self.TONE_TABLES_MAX:
+                raise ValueError(f"this processor already keeps {self.TONE_TABLES_MAX} tone curves (their tables live as long as it does)")
+            tone = _L.tone_mapping(*tone)          # validated again: the record may have crossed a process boundary
+            if tone is None:
+                raise ValueError("tone resolves to off (target_peak >= source_peak): pass None")
+            with torch.cuda.device(self.device):
+                table = torch.from_numpy(tone.gain_table()).to(self.device)
+                torch.cuda.current_stream().synchronize()      # uploaded before any lane's stream reads it
+            self._tone_tables[tone] = table
+        return table.data_ptr()
 
     def light_stats(self, tensor, rect=None):
         """The content light level record (``lib.LIGHT_WORDS`` u32, a device tensor; ``lightlevel.FrameLight.from_record`` reads
@@ -467,7 +502,7 @@ class HDRTVNetMI355X:
 
     def _enqueue_planes(self, fmt, lane, src_ptr, h, w, dst_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le", out_siting="left",
                         light_ptr=None, light_rect=None, cleanup=None, antiring=0.0, cas=0.0, scaler="lanczos",
-                        fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0, film_grain=0.0, grain_seed=0.0):
+                        fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0, film_grain=0.0, grain_seed=0.0, tone=None):
         """The body of ``enqueue_frame*`` (whose arguments these are): the argument checks, then the preprocess entry point of the
         ``lib.InputFormat`` ``fmt`` on the frame at ``src_ptr``, ``hdrtv_infer_lane`` and ``_post_out``, all on the lane's buffers
         and ``stream`` (default: the lane's own)."""
@@ -484,12 +519,12 @@ class HDRTVNetMI355X:
         self._chk(self._lib.hdrtv_infer_lane(self._ctx, lane, st, tin.data_ptr(), tcond.data_ptr(), h, w, tout.data_ptr(), self._out_dt,
                                              tagcm.data_ptr()), "hdrtv_infer_lane")
         self._post_out(st, tout.data_ptr(), self._out_dt, h, w, dst_ptr, out, ("lane", lane), light_ptr, light_rect, cleanup, plan,
-                       film_grain, grain_seed)
+                       film_grain, grain_seed, tone)
 
     def enqueue_frame(self, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream=None, out_hw=None, out_pix_fmt="rgb48le",
                       out_siting="left", light_ptr=None, light_rect=None, cleanup=None, antiring=0.0, cas=0.0,
                       scaler="lanczos", fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0, film_grain=0.0,
-                      grain_seed=0.0):
+                      grain_seed=0.0, tone=None):
         """One frame of the hot path on lane ``lane``, stream-ordered and without any host synchronisation: u8 BGR frame in
         device memory at ``src_bgr_ptr`` -> hdrtv_preprocess -> hdrtv_infer_lane -> hdrtv_post_rgb48 -> u16 RGB48 at the device
         address ``dst_rgb48_ptr``.  ``stream``: a ``torch.cuda.Stream`` (default: the lane's own).  Frames enqueued on different
@@ -507,30 +542,33 @@ class HDRTVNetMI355X:
         ``ValueError``, and a frame at the processing size is touched by none of them.  ``film_grain`` (``lib.check_film_grain``:
         True = the reference's 0.01, or an intensity up to 0.1) with ``grain_seed`` = ``lib.film_grain_seed(stream_seed, frame
         index)``: the reference's film grain on the delivered frame, placed as its shader chain places it (``_post_out``;
-        INTEGRATION.md 5c); 0: every path exactly as before."""
+        INTEGRATION.md 5c); 0: every path exactly as before.  ``tone`` (a ``lib.ToneMapping``, ``lib.tone_mapping``): the delivered
+        frame rolled off to the sink's peak, behind scale, grain and deband and in front of the record (``_post_out``;
+        INTEGRATION.md 5i); None: every path exactly as before."""
         self._enqueue_planes(_BGR24, lane, src_bgr_ptr, h, w, dst_rgb48_ptr, stream, out_hw, out_pix_fmt, out_siting,
                              light_ptr, light_rect, cleanup, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring,
-                             film_grain, grain_seed)
+                             film_grain, grain_seed, tone)
 
     def enqueue_frame_yuv420(self, lane, src_ptr, h, w, dst_rgb48_ptr, *, layout="i420", matrix=709, full_range=False, stream=None,
                              out_hw=None, out_pix_fmt="rgb48le", out_siting="left", light_ptr=None, light_rect=None, cleanup=None,
                              antiring=0.0, cas=0.0, scaler="lanczos", fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0,
-                             film_grain=0.0, grain_seed=0.0):
+                             film_grain=0.0, grain_seed=0.0, tone=None):
         """``enqueue_frame`` of an 8-bit 4:2:0 frame: the planes lie back to back at the device address ``src_ptr`` (the
         ``(h*3//2, w)`` u8 array ``preprocess_yuv420`` takes) and ``hdrtv_preprocess_yuv420`` replaces ``hdrtv_preprocess``."""
         self._enqueue_planes(_in_format("yuv420", layout, matrix, full_range), lane, src_ptr, h, w, dst_rgb48_ptr, stream, out_hw, out_pix_fmt,
                              out_siting, light_ptr, light_rect, cleanup, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring,
-                             film_grain, grain_seed)
+                             film_grain, grain_seed, tone)
 
     def enqueue_frame_ycbcr10(self, lane, src_ptr, h, w, dst_ptr, *, pix_fmt, matrix=709, full_range=False, stream=None, out_hw=None,
                               out_pix_fmt="rgb48le", out_siting="left", cleanup=None, antiring=0.0, cas=0.0, scaler="lanczos",
-                              fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0, film_grain=0.0, grain_seed=0.0):
+                              fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0, film_grain=0.0, grain_seed=0.0,
+                              tone=None):
         """``enqueue_frame`` of a 10-bit Y'CbCr frame (``pix_fmt`` ``p010le`` / ``yuv420p10le`` / ``yuv422p10le``): the planes lie
         back to back at the device address ``src_ptr`` (the u16 array ``preprocess_ycbcr10`` takes) and
         ``hdrtv_preprocess_ycbcr10`` replaces ``hdrtv_preprocess``."""
         self._enqueue_planes(_in_format("ycbcr10", pix_fmt, matrix, full_range), lane, src_ptr, h, w, dst_ptr, stream, out_hw, out_pix_fmt,
                              out_siting, None, None, cleanup, antiring, cas, scaler, fsr_sharpness, downscaler, down_antiring,
-                             film_grain, grain_seed)
+                             film_grain, grain_seed, tone)
 
     def _upload(self, key, src, staged=None):
         """Device pointer of the host u8 array ``src``, uploaded through the staging slot kept per ``key`` in ``_staging``: a
@@ -871,6 +909,27 @@ class HDRTVNetMI355X:
         dst = torch.empty_like(src)
         self._chk(self._lib.hdrtv_rgb48_film_grain(self._ctx, self._stream(), src.data_ptr(), int(src.shape[0]), int(src.shape[1]),
                                                    intensity, seed, dst.data_ptr()), "hdrtv_rgb48_film_grain")
+        return dst
+
+    @torch.inference_mode()
+    def postprocess_tonemap(self, rgb48, tone):
+        """Tone-mapped RGB48 codes: ``hdrtv_rgb48_tonemap`` on a device u16 ``(H, W, 3)`` tensor of BT.2020 PQ
+        codes (what ``hdrtv_post_rgb48`` / ``postprocess_rgb48_scaled`` write for the model's output) with the curve of the
+        ``lib.ToneMapping`` ``tone`` (``lib.tone_mapping``; None: a copy of the codes).  Returns a new device tensor of the same
+        shape; the source is not touched.  Stream-ordered on the current stream; the first use of a curve uploads its table and
+        waits for that, later calls do not synchronise."""
+        if not isinstance(rgb48, torch.Tensor) or rgb48.dtype != torch.uint16 or rgb48.ndim != 3 or rgb48.shape[2] != 3 or not rgb48.is_cuda:
+            raise ValueError("postprocess_tonemap expects a device uint16 (H, W, 3) tensor of RGB48 codes")
+        if rgb48.shape[0] < 1 or rgb48.shape[1] < 1:
+            raise ValueError("postprocess_tonemap expects a non-empty frame")
+        src = rgb48.contiguous()
+        if tone is None:
+            return src.clone()
+        gain = self._tone_gain(tone)
+        dst = torch.empty_like(src)
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.hdrtv_rgb48_tonemap(self._ctx, self._stream(), src.data_ptr(), int(src.shape[0]), int(src.shape[1]), gain,
+                                                    dst.data_ptr()), "hdrtv_rgb48_tonemap")
         return dst
 
     @torch.inference_mode()

@@ -129,7 +129,8 @@ class HeadlessPipelineWorker:
                  status_cb=None, buffer_frames=1, out_w=None, out_h=None, out_pix_fmt="rgb48le", out_siting="left",
                  light_stats=False, light_rect=None, deband=False, deband_range=_L.DEBAND_RANGE,
                  deband_threshold=_L.DEBAND_THRESHOLD, dither="none", antiring=0.0, cas=0.0, scaler="lanczos",
-                 fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0, film_grain=False, grain_stream_seed=0):
+                 fsr_sharpness=_L.FSR_SHARPNESS, downscaler=None, down_antiring=0.0, film_grain=False, grain_stream_seed=0,
+                 tone_mapping=None, target_peak=None, source_peak=_L.TONE_SOURCE_PEAK, tone_param=None):
         self._weights_dir = weights_dir
         self._use_hg = bool(use_hg)
         self._hg_override = hg_weights
@@ -157,6 +158,11 @@ class HeadlessPipelineWorker:
         # record describes the grained codes.  The chains without grain are refused here (lib.check_grain_chain).
         self._film_grain = _L.check_grain_chain(film_grain, self._scale.scaler, self._scale.downscaler, self._cleanup.deband)
         self._grain_stream_seed = _L.check_grain_stream_seed(grain_stream_seed)
+        # the delivered frames rolled off to the sink's peak, one lib.ToneMapping or None: tone_mapping "spline"
+        # (the reference's mpv setting; tone_param = its contrast, default 0.45), "bt.2390" or "clip" from source_peak (the model's
+        # 1000 nits) to target_peak nits, behind scale, grain and deband.  None / "none", or a target_peak at or above source_peak:
+        # nothing more is launched and the bytes are those of before.  With light_stats the record describes the tone-mapped codes.
+        self._tone = _L.tone_mapping(tone_mapping, target_peak, source_peak, param=tone_param)
         # HDR10 content light level: every delivered frame carries its record (``.light``), measured on the
         # device from the codes the sink receives over ``light_rect = (x0, y0, rw, rh)`` in delivered-frame coordinates (None: the
         # whole frame), and ``content_light`` accumulates MaxCLL / MaxFALL in delivery order.  Off: nothing is launched or allocated.
@@ -402,14 +408,14 @@ class HeadlessPipelineWorker:
             ``st``: whatever is recorded on ``st`` afterwards (the slot's ready event) covers both.  Returns that record."""
             if not self._light:
                 p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", cleanup=self._cleanup, scale=scale,
-                            film_grain=grain, grain_seed=seed)
+                            film_grain=grain, grain_seed=seed, tone=self._tone)
                 return None
             bufs = self._light_bufs.get(key)
             if bufs is None:
                 bufs = self._light_bufs[key] = (torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, device=p.device),
                                                 torch.empty(_L.LIGHT_WORDS, dtype=torch.uint32, pin_memory=True))
             p._post_out(sp, t.contiguous().data_ptr(), _dtype_code(t), th, tw, dst, out, "worker", bufs[0].data_ptr(), self._light_rect,
-                        self._cleanup, scale, grain, seed)
+                        self._cleanup, scale, grain, seed, self._tone)
             with torch.cuda.stream(st):
                 bufs[1].copy_(bufs[0], non_blocking=True)
             return bufs[1].numpy()

@@ -419,6 +419,38 @@ int hdrtv_post_rgb48_scaled_grain(hdrtv_ctx *ctx, void *stream, const void *dev_
 int hdrtv_post_rgb48_fsr_grain(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
                                uint16_t *dst, int dH, int dW, int rcas, float sharpness, float intensity, float seed);
 
+/* Tone mapping of the delivered frames to the sink's peak, the last step of the reference's display chain (gui_mpv_widget.py
+ * _MPV_TONE_MAPPING: mpv's tone-mapping=spline, tone-mapping-param=0.45), as a rule on full-range u16 RGB48 codes of BT.2020 PQ -- what
+ * hdrtv_post_rgb48 writes for the model's output.  The curve reaches the device as one table, gain[65536] of float32, built on the
+ * host (hdrtv_mi355x/tonemap.py has clip, BT.2390 and a spline); the device is held bit for bit to this pixel rule
+ * (tests/tonemap_ref.py restates it in NumPy):
+ *       m = max(R, G, B)                         (u16 codes)
+ *       g = gain[m]
+ *       for c in (R, G, B):   y = lin[c] * g     one float32 multiply, rounded to nearest: no FMA, no reassociation
+ *                             y = min(max(y, 0), 1)
+ *                             out = code(y)
+ *   code(y) = floor(pq(y) * 65535 + 0.5) with the ST.2084 OETF in double precision and 1.0 = 10000 nits: the exact code
+ *   hdrtv_post_pq_rgb48 is defined by, without its lin * peak / 10000 in front.  lin[c] = the float32 nearest to the ST.2084 EOTF of
+ *   c / 65535 (1.0 = 10000 nits), then moved along the float32 grid until code(lin[c]) == c.  That round trip holds for all 65536
+ *   codes and is part of the rule: a gain of exactly 1.0f is the identity on every byte.  hdrtv_pq_eotf_table writes lin (host
+ *   only: no context, no device), so that a caller or a test reads the rule's table instead of deriving it with another libm.
+ *   The maximum channel carries the curve and the other two are scaled by the same linear-light factor: hue is kept and, for a
+ *   non-increasing gain-times-level, no channel exceeds the target (mpv's "max" tone-mapping mode).  A NaN product counts as 0.
+ * Out of scope: desaturation, gamut mapping, an SDR (BT.709 / gamma) target, and a measured per-scene source peak (mpv's
+ * hdr-compute-peak).  UNPINNED: parity with mpv / libplacebo's own curves and its peak detection; the rule above is this library's.
+ *   hdrtv_rgb48_tonemap       the rule on the codes at src_rgb48.  dst == src is allowed (a pixel depends on itself only); any other
+ *                             overlap is the caller's error.
+ *   hdrtv_post_rgb48_tonemap  the codes hdrtv_post_rgb48 (pq = 0; peak_nits ignored) / hdrtv_post_pq_rgb48 (pq != 0) would write,
+ *                             tone-mapped, in one launch; no codes go to device memory in between.
+ * dev_gain: 65536 floats in device memory, owned by the caller and read by the launch (keep it until the stream has passed it).
+ * Stream-ordered; no reservation (the context keeps lin and the code boundaries, uploaded by its first tone-map call).
+ * HDRTV_EINVAL, before any device call and with dst untouched, for a NULL pointer, for H or W < 1 and, in the fused form, for
+ * everything the twin refuses (a dtype that is neither HDRTV_F16 nor HDRTV_F32, pq without peak_nits > 0). */
+int hdrtv_pq_eotf_table(float *dst65536);
+int hdrtv_rgb48_tonemap(hdrtv_ctx *ctx, void *stream, const uint16_t *src_rgb48, int H, int W, const float *dev_gain, uint16_t *dst);
+int hdrtv_post_rgb48_tonemap(hdrtv_ctx *ctx, void *stream, const void *dev_out, int dtype, int H, int W, int pq, float peak_nits,
+                             const float *dev_gain, uint16_t *dst);
+
 /* 10-bit limited-range Y'CbCr for an encoder (HEVC Main10, hardware encoders, ProRes): P010 and yuv420p10le are 3 bytes per pixel,
  * yuv422p10le 4, against the 6 of RGB48.  The reference's export converts on the CPU: it pipes rgb48le into ffmpeg, zscale goes to
  * BT.2020nc limited range and format=yuv422p10le feeds prores_ks (gui_export.py:948-1005).  The network's output is PQ-encoded BT.2020
